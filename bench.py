@@ -2,6 +2,7 @@
 """bench.py -- throughput of the MI355X message-passing path on BASELINE.json's headline workload.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--nodes 256] [--graphs 1] [--L 4] [--mode auto|eager|graph|graphk|graphs]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one MOTMPNet.forward (encoder + L message-passing steps + the classifier on the last 3 steps, eval
 mode, no grad) over one batch of synthetic input already resident in HBM: `--graphs` independent fully-connected
@@ -13,23 +14,27 @@ the environment) or -- when WORLD_SIZE is unset -- by this script itself: the pa
 children of itself with those variables set, waits for them and exits non-zero if any of them does.  Every rank runs
 the same per-GPU workload on its own graphs (weak scaling; independent graphs, no cross-GPU edges, no data-path
 collective); rank 0 packs the weights and broadcasts the blob over RCCL.  value = edges processed by all ranks /
-max-over-ranks time.  The line also carries `config4_sharded`: BASELINE config 4 (512 independent dense128 graphs)
+max-over-ranks time.  With `--full` the line also carries `config4_sharded`: BASELINE config 4 (512 independent dense128 graphs)
 sharded 512/N per rank through gnn_cca_amd.sharding.forward_sharded, timed the same way (total work fixed: strong).
 
-Timing: >= 10 blocks of exactly `--steps` steps, each block bracketed by barrier + synchronize on both sides and reduced
-with MAX over ranks; the MEDIAN block is reported (ms_per_step = median block / steps), so a short `--steps` run is not
-one sub-millisecond sample.  How the K steps of a block are issued is `--mode`, each form through the package API a caller of the
-reference's per-frame loop (inference.py:173-283) would use: K eager calls of MOTMPNet.forward; K replays of
-gnn_cca_amd.inference.GraphedForward's one-forward HIP graph; ONE replay of GraphedForward.block -- the K forwards, every launch of
-each, nothing cached or skipped, captured back to back in one HIP graph; or the same K forwards as HIP graphs of four frames round
-robin on `--streams` streams (GraphedForward.block(chains=S): independent frames in flight).  `auto` times every form with the same
-block protocol and lists each in `config.ms_per_step_by_mode`; `value` / `ms_per_step` / `config.gpu_over_cpu` are the fastest form that
-runs ONE forward at a time (eager, graph, graph_block: SURVEY 8d's E / t_forward, the definition of rounds 1-3), named in
-`config.mode`; the frames-in-flight figure lives in `pipelined` only (`--mode graphs` selects it by name for experiments).
+How the K steps of a block are issued is `--mode`, each form through the package API a caller of the reference's per-frame loop
+(inference.py:173-283) would use: K eager calls of MOTMPNet.forward; K replays of gnn_cca_amd.inference.GraphedForward's one-forward
+HIP graph; ONE replay of GraphedForward.block -- the K forwards, every launch of each, nothing cached or skipped, captured back to back
+in one HIP graph; or the same K forwards as HIP graphs of four frames round robin on `--streams` streams (GraphedForward.block(chains=S):
+independent frames in flight).  `value` / `ms_per_step` are the fastest form that runs ONE forward at a time (eager, graph, graph_block:
+SURVEY 8d's E / t_forward, the definition of rounds 1-3), named in `config.mode`; `--mode graphs` selects the frames-in-flight form by name.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (dominant kernel mpn_step_kernel, per-launch
-algorithmic bytes / HIP-event duration) and `cpu_baseline` (the reference-shaped torch CPU
-restatement in oracle/, timed on this box's host cores; N = 1 only).
+Timing: W warm-up steps, then ONE block of exactly `--steps` steps of the chosen form, bracketed by barrier + synchronize on both sides
+and reduced with MAX over ranks (ms_per_step = block / steps).  With `--mode auto` the form is chosen first by short probes of each
+(W warm-up steps, then three blocks of min(K, 50) steps; the block forms replay their K-forward graph) listed in
+`config.selection_ms_per_step_by_mode`.  `--dump-outputs DIR` then writes the logits of the timed block's last step as
+DIR/classified_edges_<i>.npy (float32; a seeded sample of rows above 60 MB in all).
+
+A plain run stops there and prints ONE JSON line (rank 0).  `--full` adds everything else, as one run: every form timed with the block
+protocol (>= `--min-blocks` blocks of K steps, the median, in `config.ms_per_step_by_mode`; the form picked from these), `pipelined`,
+`config4_sharded`, `roofline` (dominant kernel mpn_step_kernel, per-launch algorithmic bytes / HIP-event duration)
+and `kernels_us`, `roofline_at_scale`, `terrace_pipeline`, `configs`, `dynamic_range`, `train_step` and `cpu_baseline` (the
+reference-shaped torch CPU restatement in oracle/, timed on the host's cores; N = 1 only).
 """
 import argparse
 import json
@@ -318,7 +323,7 @@ def flat_evidence(res):
     """The scalars the line's claims rest on, copied into `config` / `roofline` under short flat keys: the driver's record
     keeps the scalar entries of those two objects and only the NAMES of the nested legs, so rows (d), (e), N1-N3 could not be checked from
     BENCH_rNN.json alone.  Every value here is a copy of a figure of the nested objects of the same line, nothing is computed twice."""
-    c, r = res["config"], res["roofline"]
+    c, r = res["config"], res.get("roofline", {})
 
     def put(dst, key, val):
         if val is not None and not isinstance(val, (dict, list)):
@@ -402,6 +407,28 @@ def flat_evidence(res):
                 notes[f"{name}.{k}"] = v
                 d_[k] = v[:96] + " ..."
     return res
+
+
+DUMP_BYTES_MAX = 60_000_000   # under 64 MB (of 10^6 or 2^20 bytes) with the .npy headers
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """`arrays` (name -> host array, all of the same length) as <outdir>/<name>.npy in float32 (float64 stays float64).  Above
+    DUMP_BYTES_MAX in all, the same seeded sample of rows of every array, in row order, and the sampled row numbers as
+    sample_rows.npy (float64): the files of two runs with the same arguments compare element for element."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v.itemsize * (v.size // max(n, 1)) for v in arrays.values())
+    if n * row_bytes > DUMP_BYTES_MAX:
+        keep = DUMP_BYTES_MAX // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def state_hash(model):
@@ -947,6 +974,11 @@ def main():
     ap.add_argument("--launch-timeout", type=float, default=900.0, help="launcher: seconds before the rank processes are stopped")
     ap.add_argument("--fail-capture-rank", type=int, default=-1,
                     help="(diagnostic) HIP-graph capture 'fails' on this rank: every rank must then time the same remaining forms (eager) and exit 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the timed block's last step as DIR/classified_edges_<i>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (block protocol per form, config 4, roofline / per-kernel times, scale probe, Terrace "
+                         "pipeline, configs 2 / 3 / 5, dynamic range, training iteration, CPU baselines); off: the headline alone")
     args = ap.parse_args()
 
     if args.train_leg_only:
@@ -1046,7 +1078,7 @@ def main():
             # complete with its own outputs -- the throughput form of the per-frame loop.  (Measured on the way: S parallel branches
             # inside ONE graph 25.8 us, one big graph per stream 26.1 us -- the host-side launch of a 400-kernel graph takes a third
             # of its run --, one-forward graphs round robin 15.9-26 us depending on how the streams land on the hardware queues.)
-            if "graph_block" in forms and args.streams > 1 and args.mode in ("graphs", "auto"):
+            if "graph_block" in forms and args.streams > 1 and (args.mode == "graphs" or (args.mode == "auto" and args.full)):
                 try:
                     # frames per graph: four on long blocks; two / one on short ones so that every stream gets the same number of groups
                     depth_s = 4 if args.steps >= 16 * args.streams else (2 if args.steps >= 4 * args.streams else 1)
@@ -1062,27 +1094,40 @@ def main():
         agreed = agree_forms(forms, dist, device, args.backend)
         if rank == 0 and sorted(agreed) != sorted(forms):
             print(f"[bench] forms dropped because a rank could not capture them: {sorted(set(forms) - set(agreed))}", file=sys.stderr)
-        timed = {}
-        for name in want:
-            if name not in agreed:
-                continue
-            run_f, run_b = forms[name]
-            timed[name] = timed_blocks(run_f, args.steps, args.warmup, dist, device, args.backend, min_blocks=args.min_blocks,
-                                       run_block=run_b)
-        if not timed:   # the requested graph form could not be captured
-            timed["eager"] = timed_blocks(eager_run, args.steps, args.warmup, dist, device, args.backend, min_blocks=args.min_blocks)
-        by_mode = {k: v[0][len(v[0]) // 2] / args.steps * 1e3 for k, v in timed.items()}
+        cands = [name for name in want if name in agreed] or ["eager"]    # ["eager"]: the requested graph form could not be captured
+        timed, by_mode, probe_ms = {}, {}, {}
+        if args.full:      # every form with the block protocol: >= --min-blocks blocks of K steps, the median
+            for name in cands:
+                run_f, run_b = forms[name]
+                timed[name] = timed_blocks(run_f, args.steps, args.warmup, dist, device, args.backend, min_blocks=args.min_blocks,
+                                           run_block=run_b)
+            by_mode = {k: v[0][len(v[0]) // 2] / args.steps * 1e3 for k, v in timed.items()}
+        elif len(cands) > 1:   # a short probe of each form chooses (a block form's probe is its K-forward graph: <= 1 GB of outputs)
+            probe = min(args.steps, 50)
+            for name in cands:
+                run_f, run_b = forms[name]
+                blocks_p, _ = timed_blocks(run_f, probe, args.warmup, dist, device, args.backend, min_blocks=3, min_total_s=0.0,
+                                           run_block=run_b)
+                probe_ms[name] = blocks_p[len(blocks_p) // 2] / (args.steps if run_b else probe) * 1e3
         # `value` = one forward at a time; frames in flight only when that form was asked for by name (--mode graphs)
-        one_at_a_time = {k: v for k, v in by_mode.items() if k != "graph_block_chains"} or by_mode
-        best = min(one_at_a_time, key=one_at_a_time.get)
-        blocks, out = timed[best]
+        ranked = by_mode or probe_ms
+        one_at_a_time = {k: v for k, v in ranked.items() if k != "graph_block_chains"} or ranked
+        best = min(one_at_a_time, key=one_at_a_time.get) if ranked else cands[0]
+        # the headline: ONE block of exactly K steps of that form (its warm-up already done when it was timed or probed above)
+        blocks, out = timed_blocks(forms[best][0], args.steps, 0 if ranked else args.warmup, dist, device, args.backend, min_blocks=1,
+                                   min_total_s=0.0, run_block=forms[best][1])
+        t = blocks[0]
         api = {"eager": "eager: MOTMPNet.forward, one call per step",
                "graph": "graph: GraphedForward.__call__, one HIP-graph replay per step",
                "graph_block": f"graph_block: GraphedForward.block, one HIP graph of {args.steps} forwards",
                "graph_block_chains": f"graph_block_chains: GraphedForward.block(chains={args.streams}), {args.streams} frames in flight"}
         mode_used = api[best] + (" (auto: fastest one-at-a-time form)" if args.mode == "auto" else "")
         run = forms[best][0] or eager_run
-        t = blocks[len(blocks) // 2]      # median block of K steps (max over ranks inside every block)
+        ok = all(torch.isfinite(o).all().item() for o in out["classified_edges"])
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {f"classified_edges_{i}": o.detach().cpu().numpy()
+                                                      for i, o in enumerate(out["classified_edges"])})
         # one frame at a time vs frames in flight, side by side (both are in ms_per_step_by_mode; `value` is the one-at-a-time form)
         pipelined = None
         if "graph_block_chains" in by_mode and "graph_block" in by_mode:
@@ -1094,7 +1139,7 @@ def main():
                                  "independent frames (every forward complete, its own outputs, a workspace per stream)"}
         # every rank's OWN time per step (no barrier inside), gathered: how evenly the ranks run
         rank_ms = None
-        if world > 1:
+        if world > 1 and args.full:
             torch.cuda.synchronize()
             dist.barrier()
             t0 = time.perf_counter()
@@ -1106,13 +1151,12 @@ def main():
             all_ms = [torch.zeros(1, dtype=torch.float64, device=dev_) for _ in range(world)]
             dist.all_gather(all_ms, torch.tensor([own], dtype=torch.float64, device=dev_))
             rank_ms = [float(v.item()) for v in all_ms]
-        ok = all(torch.isfinite(o).all().item() for o in out["classified_edges"])
 
         # ---- BASELINE config 4: 512 independent dense128 graphs, sharded 512/N per rank (forward_sharded) ----------
         cfg4, share = None, None
         # (the leg's timed blocks are collective: every rank must enter it or none -- eligibility is a pure function of the arguments, and
         # is all-reduced anyway so that a rank with a different command line cannot desynchronise the job)
-        if agree_flag(not args.no_config4 and args.config4_graphs >= 1, dist, device, args.backend):
+        if agree_flag(args.full and not args.no_config4 and args.config4_graphs >= 1, dist, device, args.backend):
             from gnn_cca_amd.sharding import forward_sharded, shard_batch
             m4 = build_model(graph_net_params(L=4), 128, seed=rank).to(device)
             m4.edge_state_dtype = args.edge_state
@@ -1223,7 +1267,7 @@ def main():
 
         # per-kernel durations (HIP events attached to every dispatch; separate pass so the timed region is undisturbed)
         kernel_ms = {}
-        for _ in range(args.profile_reps):
+        for _ in range(args.profile_reps if args.full else 0):
             for _q in range(4):  # a warm queue, as in the timed region
                 model(data)
             _, times = model.forward_profiled(data)
@@ -1231,6 +1275,38 @@ def main():
                 kernel_ms.setdefault(kind, []).append(ms)
 
     if rank == 0:
+        shape = f"{args.nodes}-node dense graph" if args.graphs == 1 else f"{args.graphs} x {args.nodes}-node dense graphs"
+        res = {
+            "metric": f"processed edges/sec (L={args.L} MPN steps), {shape}",
+            "value": world * E * args.steps / t,
+            "unit": "edges/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": t / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",   # the arithmetic type of the path (every product and sum is fp32-accurate; see config.edge_state for storage)
+            "data": "synthetic",
+            "config": {"workload": f"{args.graphs} x dense{args.nodes} per GPU per step (N={N}, E={E}), feat 2048, L={args.L}, 3 cls steps, "
+                                   f"fp32, {args.edge_state} state, eval",
+                       "mode": mode_used,
+                       "frames_in_flight": args.streams if best == "graph_block_chains" else 1, "edge_state": args.edge_state, "edge_state_storage": "bf16" if args.edge_state == "bf16" else "f32",
+                       "encoder_products": args.enc_products, "encoder_unsplit": args.enc_unsplit,
+                       "outputs_finite": bool(ok), "outputs_dumped": dumped,
+                       "edge_steps_per_s": world * E * args.L * args.steps / t,
+                       "timing": f"one block of exactly {args.steps} steps after {args.warmup} warm-up steps (barrier + sync both sides, MAX over ranks)",
+                       "launcher": "single process" if world == 1 else "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ
+                       else "bench.py (self-launched rank processes)", "backend": args.backend if world > 1 else None,
+                       "ranks_seen": dist.get_world_size() if dist else 1, "broadcast_ms": broadcast_ms,
+                       "weights_hash": f"{weights_hash & 0xFFFFFFFFFFFFFFFF:016x}" if weights_hash is not None else None},
+        }
+        if not args.full:
+            res["config"]["selection_ms_per_step_by_mode"] = probe_ms
+    if rank == 0 and args.full:
+        res["config"]["ms_per_step_by_mode"] = by_mode
+        res["config"]["rank_ms_per_step"] = {"min": min(rank_ms), "max": max(rank_ms), "all": rank_ms} if rank_ms else None
         e_bytes = 12 if args.edge_state == "bf16" else 24
         per_launch = step_algorithmic_bytes(E, args.L, 3, e_bytes=e_bytes)
         step_ms = float(np.mean(kernel_ms["step"])) if "step" in kernel_ms else float("nan")
@@ -1250,48 +1326,19 @@ def main():
         # the edge state of one step (read + write) against the 8 x 4 MB of L2: below that the launch is bounded by its
         # dependent round trips after the kernel boundary, not by HBM; the HBM fraction is still reported
         cache_resident = E * 2 * e_bytes < 32e6
-        shape = f"{args.nodes}-node dense graph" if args.graphs == 1 else f"{args.graphs} x {args.nodes}-node dense graphs"
-        res = {
-            "metric": f"processed edges/sec (L={args.L} MPN steps), {shape}",
-            "value": world * E * args.steps / t,
-            "unit": "edges/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": t / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",   # the arithmetic type of the path (every product and sum is fp32-accurate; see config.edge_state for storage)
-            "data": "synthetic",
-            "config": {"workload": f"{args.graphs} x dense{args.nodes} per GPU per step (N={N}, E={E}), feat 2048, L={args.L}, 3 cls steps, "
-                                   f"fp32, {args.edge_state} state, eval",
-                       "mode": mode_used, "ms_per_step_by_mode": by_mode,
-                       "frames_in_flight": args.streams if best == "graph_block_chains" else 1, "edge_state": args.edge_state, "edge_state_storage": "bf16" if args.edge_state == "bf16" else "f32",
-                       "encoder_products": args.enc_products, "encoder_unsplit": args.enc_unsplit,
-                       "outputs_finite": bool(ok),
-                       "edge_steps_per_s": world * E * args.L * args.steps / t,
-                       "timing": f"median of {len(blocks)} blocks of {args.steps} steps (barrier + sync both sides, MAX over ranks)",
-                       "block_ms": {"min": blocks[0] * 1e3, "median": t * 1e3, "max": blocks[-1] * 1e3},
-                       "launcher": "single process" if world == 1 else "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ
-                       else "bench.py (self-launched rank processes)", "backend": args.backend if world > 1 else None,
-                       "ranks_seen": dist.get_world_size() if dist else 1, "broadcast_ms": broadcast_ms,
-                       "weights_hash": f"{weights_hash & 0xFFFFFFFFFFFFFFFF:016x}" if weights_hash is not None else None,
-                       "rank_ms_per_step": ({"min": min(rank_ms), "max": max(rank_ms), "all": rank_ms} if rank_ms else None)},
-            "roofline": {"bound": "latency" if cache_resident else "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                         "kernel": ("mpn_step_fast_kernel" if N <= 512 else "mpn_step_pipe_kernel") + "<FIRST|CLS, MSG>: message step, L-1 launches/forward",
-                         "avg_launch_us": step_ms * 1e3, "rocprof_avg_launch_us": rocprof_us,
-                         "algorithmic_bytes_per_launch": alg,
-                         "note": "edge state is L2/Infinity-Cache resident at this size: the launch is bounded by its dependent "
-                                 "round trips (latency), `frac` is still algorithmic bytes / time / HBM peak; "
-                                 "`roofline_at_scale` is the same kernel where HBM is the bound" if cache_resident else ""},
-            "kernels_us": {k: float(np.mean(v)) * 1e3 for k, v in kernel_ms.items()},
-            "kernels_us_note": "per-kernel times of a SEPARATE eager pass with start / stop events attached to each dispatch "
-                               "(gnncca_mpn_forward_profiled); a dispatch's span includes its own launch latency, which consecutive "
-                               "kernels of a HIP-graph block overlap -- with config.mode = 'graph of K forwards per block' ms_per_step "
-                               "can therefore be below the sum of these",
-        }
+        res["roofline"] = {"bound": "latency" if cache_resident else "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                           "kernel": ("mpn_step_fast_kernel" if N <= 512 else "mpn_step_pipe_kernel") + "<FIRST|CLS, MSG>: message step, L-1 launches/forward",
+                           "avg_launch_us": step_ms * 1e3, "rocprof_avg_launch_us": rocprof_us,
+                           "algorithmic_bytes_per_launch": alg,
+                           "note": "edge state is L2/Infinity-Cache resident at this size: the launch is bounded by its dependent "
+                                   "round trips (latency), `frac` is still algorithmic bytes / time / HBM peak; "
+                                   "`roofline_at_scale` is the same kernel where HBM is the bound" if cache_resident else ""}
+        res["kernels_us"] = {k: float(np.mean(v)) * 1e3 for k, v in kernel_ms.items()}
+        res["kernels_us_note"] = ("per-kernel times of a SEPARATE eager pass with start / stop events attached to each dispatch "
+                                 "(gnncca_mpn_forward_profiled); a dispatch's span includes its own launch latency, which consecutive "
+                                 "kernels of a HIP-graph block overlap -- with config.mode = 'graph of K forwards per block' ms_per_step "
+                                 "can therefore be below the sum of these")
         if pipelined is not None:
             res["pipelined"] = pipelined
         if cfg4 is not None:
@@ -1341,7 +1388,8 @@ def main():
                 res["cpu_baseline_fused"] = cpu_baseline_fused(params, model, args.nodes, args.graphs)
             except Exception as exc:  # noqa: BLE001
                 res["cpu_baseline_fused"] = {"error": f"{type(exc).__name__}: {exc}"}
-        res["config"]["forms_timed"] = ",".join(k for k in FORM_ORDER if k in by_mode)
+    if rank == 0:
+        res["config"]["forms_timed"] = ",".join(k for k in FORM_ORDER if k in (by_mode or probe_ms or {best: None}))
         flat_evidence(res)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(res) + "\n").encode())

@@ -1,6 +1,6 @@
 """bench.py's line, without a GPU: `flat_evidence` copies the scalars the claims rest on into `config` / `roofline` under short keys and keeps every
 string of the objects the driver's record keeps under 100 characters; `step_algorithmic_bytes` / `forward_algorithmic_bytes`
-are the byte counts DESIGN.md section 4 states."""
+are the byte counts DESIGN.md section 4 states; `dump_outputs` writes what `--dump-outputs` promises."""
 import bench
 
 
@@ -47,3 +47,25 @@ def test_flat_evidence_keys_and_string_lengths():
         for k, v in out[name].items():
             assert not isinstance(v, str) or len(v) <= 100, (name, k, len(v))
     assert out["notes"]["config.workload"] == long and out["notes"]["roofline.kernel"] == long      # the long forms are kept, in a nested object
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_above_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    logits = [np.arange(1000, dtype=np.float32).reshape(-1, 1) + i for i in range(3)]
+    names = bench.dump_outputs(str(tmp_path / "all"), {f"classified_edges_{i}": a for i, a in enumerate(logits)})
+    assert names == ["classified_edges_0", "classified_edges_1", "classified_edges_2"]
+    for i, a in enumerate(logits):
+        got = np.load(tmp_path / "all" / f"classified_edges_{i}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    # above the cap: the same seeded rows of every array, the row numbers beside them, the whole within the cap -- and the same files again
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2400)
+    for run in ("s1", "s2"):
+        names = bench.dump_outputs(str(tmp_path / run), {f"classified_edges_{i}": a for i, a in enumerate(logits)})
+        assert names == ["classified_edges_0", "classified_edges_1", "classified_edges_2", "sample_rows"]
+        assert sum((tmp_path / run / f"{n}.npy").stat().st_size for n in names) <= 2400 + 4 * 128    # + the .npy headers
+    rows = np.load(tmp_path / "s1" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 2400 // (3 * 4 + 8) and np.all(np.diff(rows) > 0)
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}.npy"), np.load(tmp_path / "s2" / f"{n}.npy"))
+    for i, a in enumerate(logits):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"classified_edges_{i}.npy"), a[rows.astype(np.int64)])

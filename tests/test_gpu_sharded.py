@@ -83,7 +83,7 @@ def test_bench_launches_its_own_ranks():
     with n_gpus = 2 and the sharded config-4 leg."""
     multi = torch.cuda.device_count() >= 2
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--min-blocks", "3",
-           "--no-cpu-baseline", "--no-scale-probe", "--profile-reps", "1", "--config4-graphs", "6", "--mode", "eager"]
+           "--no-cpu-baseline", "--no-scale-probe", "--profile-reps", "1", "--config4-graphs", "6", "--mode", "eager", "--full"]
     if not multi:
         cmd += ["--single-device", "--backend", "gloo"]
     r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=600)
