@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end walk through the reference's per-batch inference flow (inference.py:173-345) on synthetic frames, with
 every GPU-side step taken by this repository: graph construction + edge attributes (row N1), the MPN forward (the hot
-path), threshold / pruning / identity clusters (row N2).  Needs an MI355X.
+path), threshold / pruning / identity clusters (row N2), and the per-frame scores of inference.py:349-371 aggregated as main.py:335-348
+does (gnn_cca_amd.evaluation).  Needs an MI355X.
 
     python examples/frames_end_to_end.py [frames] [cams] [detections_per_cam]
 """
@@ -15,6 +16,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
+from gnn_cca_amd.evaluation import EvalAccumulator, evaluate_frames  # noqa: E402
 from gnn_cca_amd.graph_build import build_graph_batch  # noqa: E402
 from gnn_cca_amd.postprocess import prune_and_cluster, threshold  # noqa: E402
 
@@ -68,6 +70,9 @@ def main():
           f"({e / dt / 1e6:.1f} M edges/s end to end, host planning included)")
     print(f"active edges after pruning: {int(post['pruned'].sum())}, identity clusters: {int(post['n_clusters'].item())}, "
           f"max out-flow per node: {int(post['flow_out'].max())}")
+    # per-frame metrics against the ground truth the graph build wrote (batch.edge_labels: same person id), then main.py's aggregates
+    acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"]))
+    print("aggregates over the frames:", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))
     print("random weights / random embeddings: the cluster structure is meaningless, the plumbing is what is shown")
 
 

@@ -1,0 +1,378 @@
+// evaluate.hip -- the per-frame scoring of the reference's evaluation loop on gfx950 (inference.py:349-371): the edge confusion counts and
+// P / R / F / per-class precisions of `compute_P_R_F` (inference.py:23-68), and ARI, AMI, homogeneity, completeness and V-measure between
+// ID_GT (the components of the ground-truth-active edges, inference.py:296-299) and the predicted partition -- the numbers main.py:335-348
+// averages.  The formulas and special cases are scikit-learn 1.7.2's (metrics/cluster/_supervised.py, _expected_mutual_info_fast.pyx).
+//
+// One workgroup per frame (frames are independent), everything frame-local in LDS:
+//   1. edge counts (integers) and the GT partition in ONE pass over the edges: union-find over the edges with label 1 (the larger root
+//      hooked under the smaller by compare-and-swap, then pointer jumping; the root of a component is its smallest node);
+//   2. cluster sizes a_i (GT) and b_j (predicted) as one LDS histogram of packed 16-bit counts, and the contingency cells n_ij as runs of
+//      the sorted 24-bit keys (gt_root << 12 | pred_root) (bitonic sort in LDS);
+//   3. entropies, MI and the pair counts of ARI from the sizes and the cells;
+//   4. the expected mutual information over DISTINCT cluster sizes with their multiplicities (a term depends on the two sizes only; a
+//      frame of n nodes has at most ~sqrt(2 n) distinct sizes per side), each term table lookups into lf[k] = lgamma(k + 1) plus one
+//      log and one exp.  The table lives in the caller's workspace ((n_g + 1) doubles per frame).
+// LDS: 3 x P int32 (P = the batch's largest frame rounded up to a power of two: 48 KiB at 4096 nodes) + ~2 KiB.
+// Deterministic: integer sums through LDS atomics, fp64 sums per lane in a fixed order, then a butterfly per wave and the waves in order.
+// No fp64 atomics.  The whole file is compiled without fp contraction: the counts, P, R, F, the precisions and ARI are the reference's
+// expressions operation for operation (bit-identical), and no multiply-add may fuse them.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "internal.h"
+
+#pragma clang fp contract(off)
+
+namespace gnncca {
+
+#define HIP_TRY_EV(expr)                   \
+    do {                                   \
+        hipError_t _e = (expr);            \
+        if (_e != hipSuccess) {            \
+            g_last_hip_error = (int)_e;    \
+            return GNNCCA_ERR_HIP;         \
+        }                                  \
+    } while (0)
+
+constexpr int kEvalMaxNodes = GNNCCA_EVAL_MAX_FRAME_NODES;   // 12-bit frame-local ids in the contingency keys
+constexpr int kEvalMaxSizes = 96;   // distinct cluster sizes of one side: k (k + 1) / 2 <= 4096  ->  k <= 90
+constexpr double kEps = 2.220446049250313e-16;   // np.finfo(np.float64).eps
+
+// integer accumulators of a frame (LDS atomics: order-independent)
+enum { I_TP, I_FP, I_TN, I_FN, I_C1, I_C0, I_SSQ, I_SA2, I_SB2, I_KA, I_KB, I_NGT, I_NPRED, I_COUNT };
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);   // every lane ends with the same bits (a + b == b + a)
+    return v;
+}
+
+// sum over the block in a fixed order: butterfly per wave, then the waves in order (every thread gets the result)
+template <int BLOCK>
+__device__ __forceinline__ double block_sum(double v, double* scratch) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = scratch[0];
+#pragma unroll
+    for (int w = 1; w < BLOCK / 64; ++w) s += scratch[w];
+    __syncthreads();
+    return s;
+}
+
+__device__ __forceinline__ int lds_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// out[g][16] = P, R, F, TP, FP, FN, TN, ARI, AMI, homogeneity, completeness, V, precision0, precision1, n_clusters_gt, n_clusters_pred.
+// P_lds: ints per LDS region (a power of two >= every frame's node count, <= kEvalMaxNodes).  lf_ws: the lgamma tables, frame g's at
+// lf_ws + node_ptr[g] + g.  A frame whose ranges do not fit (node count above P_lds, ranges outside the arrays) gets a NaN row.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __restrict__ ei, long long E, const float* __restrict__ elab,
+                                                            const long long* __restrict__ pred, const int* __restrict__ labels, int N_all,
+                                                            const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int P_lds,
+                                                            int* __restrict__ gt_out, double* __restrict__ out, double* __restrict__ lf_ws) {
+    extern __shared__ int s_dyn[];
+    __shared__ unsigned long long s_int[I_COUNT];
+    __shared__ double s_red[BLOCK / 64];
+    __shared__ int s_sa[kEvalMaxSizes], s_ma[kEvalMaxSizes], s_sb[kEvalMaxSizes], s_mb[kEvalMaxSizes];
+    __shared__ int s_na, s_nb;
+    int* parent = s_dyn;                                             // union-find, later the histogram of cluster sizes
+    unsigned* cnt = reinterpret_cast<unsigned*>(s_dyn + P_lds);       // per local root: a (bits 0-15) | b (bits 16-31)
+    unsigned* keys = reinterpret_cast<unsigned*>(s_dyn + 2 * P_lds);  // contingency keys, sorted
+
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int v0 = node_ptr[g], v1 = node_ptr[g + 1];
+    const long long k0 = edge_ptr[g], k1 = edge_ptr[g + 1];
+    const int n = v1 - v0;
+    double* row = out + (size_t)g * 16;
+    if (v0 < 0 || n < 0 || n > P_lds || v1 > N_all || k0 < 0 || k1 < k0 || k1 > E) {
+        if (tid < 16) row[tid] = __builtin_nan("");
+        return;
+    }
+    double* lf = lf_ws + v0 + g;
+    for (int v = tid; v < n; v += BLOCK) {
+        parent[v] = v;
+        cnt[v] = 0;
+    }
+    for (int k = tid; k <= n; k += BLOCK) lf[k] = lgamma((double)k + 1.0);   // read only after the barriers below
+    if (tid < I_COUNT) s_int[tid] = 0;
+    __syncthreads();
+
+    // ---- 1. edge counts (compute_P_R_F) and the GT partition, one pass over the frame's edges ----------------------------------------
+    // Union-find over the edges with label 1: a root is hooked under the smaller root by compare-and-swap (it fails when another thread
+    // hooked that root first: find the new roots and retry), so one pass joins every GT edge's endpoints; pointer jumping then leaves
+    // parent[v] = the smallest node of v's component.
+    {
+        unsigned tp = 0, fp = 0, tn = 0, fn = 0, c1 = 0, c0 = 0;
+        for (long long k = k0 + tid; k < k1; k += BLOCK) {
+            const long long a = ei[k] - v0, b = ei[E + k] - v0;
+            if (a < 0 || a >= n || b < 0 || b >= n) continue;   // an edge that leaves its frame: ignored
+            const float l = elab[k];
+            const long long p = pred[k];
+            if (l == 1.f) {
+                ++c1;
+                tp += p == 1;
+                fn += p == 0;
+                int ra = (int)a, rb = (int)b;
+                while (true) {
+                    for (int q = lds_load(&parent[ra]); q != ra; q = lds_load(&parent[ra])) ra = q;
+                    for (int q = lds_load(&parent[rb]); q != rb; q = lds_load(&parent[rb])) rb = q;
+                    if (ra == rb) break;
+                    const int hi = max(ra, rb), lo = min(ra, rb);
+                    if (atomicCAS(&parent[hi], hi, lo) == hi) break;
+                }
+            } else if (l == 0.f) {
+                ++c0;
+                fp += p == 1;
+                tn += p == 0;
+            }
+        }
+        if (c1) {
+            atomicAdd(&s_int[I_C1], (unsigned long long)c1);
+            atomicAdd(&s_int[I_TP], (unsigned long long)tp);
+            atomicAdd(&s_int[I_FN], (unsigned long long)fn);
+        }
+        if (c0) {
+            atomicAdd(&s_int[I_C0], (unsigned long long)c0);
+            atomicAdd(&s_int[I_FP], (unsigned long long)fp);
+            atomicAdd(&s_int[I_TN], (unsigned long long)tn);
+        }
+    }
+    __syncthreads();
+    for (int v = tid; v < n; v += BLOCK) {   // pointer jumping (the forest no longer grows: every write points at an ancestor)
+        int r = v;
+        for (int q = lds_load(&parent[r]); q != r; q = lds_load(&parent[r])) r = q;
+        __hip_atomic_store(&parent[v], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+
+    // ---- 2. sizes and contingency keys ---------------------------------------------------------------------------------------------
+    int sort_n = 1;
+    while (sort_n < n) sort_n <<= 1;
+    {
+        unsigned ngt = 0, npred = 0;
+        for (int v = tid; v < n; v += BLOCK) {
+            const int r = parent[v];
+            const int lab = labels[v0 + v];
+            int lp = lab - v0;
+            if (lp < 0 || lp >= n) lp = v;   // outside the frame: the node's own cluster
+            atomicAdd(&cnt[r], 1u);
+            atomicAdd(&cnt[lp], 1u << 16);
+            keys[v] = ((unsigned)r << 12) | (unsigned)lp;
+            ngt += r == v;
+            npred += lab == v0 + v;
+            if (gt_out) gt_out[v0 + v] = v0 + r;
+        }
+        for (int v = n + tid; v < sort_n; v += BLOCK) keys[v] = 0xFFFFFFFFu;
+        if (ngt) atomicAdd(&s_int[I_NGT], (unsigned long long)ngt);
+        if (npred) atomicAdd(&s_int[I_NPRED], (unsigned long long)npred);
+    }
+    __syncthreads();
+    for (int v = tid; v < n; v += BLOCK) parent[v] = 0;   // from here on: histogram of cluster sizes (a - 1: bits 0-15, b - 1: bits 16-31)
+    for (int k = 2; k <= sort_n; k <<= 1) {               // bitonic sort of the keys
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < sort_n; i += BLOCK) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned x = keys[i], y = keys[l];
+                    if ((x > y) == ((i & k) == 0)) {
+                        keys[i] = y;
+                        keys[l] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. entropies, MI, pair counts ---------------------------------------------------------------------------------------------
+    const double dn = (double)n, logn = log(dn);
+    double hc = 0.0, hk = 0.0, mi = 0.0;
+    {
+        unsigned long long sa2 = 0, sb2 = 0, ssq = 0;
+        unsigned ka = 0, kb = 0;
+        for (int v = tid; v < n; v += BLOCK) {
+            const unsigned c = cnt[v], a = c & 0xFFFFu, b = c >> 16;
+            if (a) {   // entropy(labels_true): -sum((pi / pi_sum) * (log(pi) - log(pi_sum)))
+                sa2 += (unsigned long long)a * a;
+                hc += ((double)a / dn) * (log((double)a) - logn);
+                ++ka;
+                atomicAdd((unsigned*)&parent[a - 1], 1u);
+            }
+            if (b) {
+                sb2 += (unsigned long long)b * b;
+                hk += ((double)b / dn) * (log((double)b) - logn);
+                ++kb;
+                atomicAdd((unsigned*)&parent[b - 1], 1u << 16);
+            }
+        }
+        for (int p = tid; p < n; p += BLOCK) {   // one thread per contingency cell: the first position of its run of keys
+            const unsigned key = keys[p];
+            if (p > 0 && keys[p - 1] == key) continue;
+            int lo = p + 1, hi = n;   // end of the run
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (keys[mid] == key) lo = mid + 1;
+                else hi = mid;
+            }
+            const int nij = lo - p;
+            ssq += (unsigned long long)nij * nij;
+            const unsigned a = cnt[key >> 12] & 0xFFFFu, b = cnt[key & 0xFFFu] >> 16;
+            // mutual_info_score: cnm * (log(nij) - log(N)) + cnm * (-log(a b) + log(N) + log(N)), |term| < eps -> 0
+            const double cnm = (double)nij / dn;
+            const double log_outer = -log((double)((unsigned long long)a * b)) + logn + logn;
+            double t = cnm * (log((double)nij) - logn) + cnm * log_outer;
+            if (fabs(t) < kEps) t = 0.0;
+            mi += t;
+        }
+        if (sa2) atomicAdd(&s_int[I_SA2], sa2);
+        if (sb2) atomicAdd(&s_int[I_SB2], sb2);
+        if (ssq) atomicAdd(&s_int[I_SSQ], ssq);
+        if (ka) atomicAdd(&s_int[I_KA], (unsigned long long)ka);
+        if (kb) atomicAdd(&s_int[I_KB], (unsigned long long)kb);
+    }
+    hc = block_sum<BLOCK>(hc, s_red);   // (its barriers also publish the histograms and counters)
+    hk = block_sum<BLOCK>(hk, s_red);
+    mi = block_sum<BLOCK>(mi, s_red);
+    const unsigned ka = (unsigned)s_int[I_KA], kb = (unsigned)s_int[I_KB];
+
+    // ---- 4. expected mutual information over distinct sizes ------------------------------------------------------------------------
+    if (wave == 0) {   // compaction of the size histogram, in size order
+        int na = 0, nb = 0;
+        const unsigned long long below = (1ull << lane) - 1;
+        for (int base = 0; base < n; base += 64) {
+            const int s = base + lane;
+            const unsigned h = s < n ? (unsigned)parent[s] : 0u, ha = h & 0xFFFFu, hb = h >> 16;
+            const unsigned long long ma = __ballot(ha != 0), mb = __ballot(hb != 0);
+            const int pa = na + __popcll(ma & below), pb = nb + __popcll(mb & below);
+            if (ha && pa < kEvalMaxSizes) {
+                s_sa[pa] = s + 1;
+                s_ma[pa] = (int)ha;
+            }
+            if (hb && pb < kEvalMaxSizes) {
+                s_sb[pb] = s + 1;
+                s_mb[pb] = (int)hb;
+            }
+            na += __popcll(ma);
+            nb += __popcll(mb);
+        }
+        if (lane == 0) {
+            s_na = min(na, kEvalMaxSizes);
+            s_nb = min(nb, kEvalMaxSizes);
+        }
+    }
+    __threadfence_block();   // lf (global) and the lists (LDS) of every thread are visible after the barrier
+    __syncthreads();
+    double emi = 0.0;
+    if (ka > 1 && kb > 1) {
+        const int na = s_na, nb = s_nb;
+        const double lfn = lf[n];
+        double acc = 0.0;
+        for (int q = wave; q < na * nb; q += BLOCK / 64) {
+            const int i = q / nb, j = q - (q / nb) * nb;
+            const int a = s_sa[i], b = s_sb[j];
+            const double w = (double)s_ma[i] * (double)s_mb[j];
+            const double la = log((double)a), lb = log((double)b);
+            const double glnab = lf[a] + lf[b] + lf[n - a] + lf[n - b];
+            const int start = max(1, a - n + b), end = min(a, b) + 1;
+            for (int nij = start + lane; nij < end; nij += 64) {
+                const double term1 = (double)nij / dn;
+                const double term2 = (logn + log((double)nij)) - la - lb;
+                const double gln = glnab - (lf[nij] + lfn) - lf[a - nij] - lf[b - nij] - lf[n - a - b + nij];
+                acc += w * (term1 * term2 * exp(gln));
+            }
+        }
+        emi = block_sum<BLOCK>(acc, s_red);
+    }
+
+    // ---- the row ------------------------------------------------------------------------------------------------------------------
+    if (tid != 0) return;
+    const unsigned long long TP = s_int[I_TP], FP = s_int[I_FP], TN = s_int[I_TN], FN = s_int[I_FN], C1 = s_int[I_C1], C0 = s_int[I_C0];
+    // compute_P_R_F, expression for expression
+    const double P = (TP + FP) != 0 ? (double)TP / (double)(TP + FP) : 0.0;
+    const double R = (TP + FN) != 0 ? (double)TP / (double)(TP + FN) : 0.0;
+    const double PR = P * R;
+    const double F = (P + R) != 0.0 ? 2.0 * PR / (P + R) : 0.0;
+    const double prec1 = TP != 0 ? ((double)TP / (double)C1) * 100.0 : 0.0;
+    const double prec0 = TN != 0 ? ((double)TN / (double)C0) * 100.0 : 0.0;
+    // adjusted_rand_score from pair_confusion_matrix (all integers below 2^53 at 4096 nodes: exact)
+    const long long nn = n, ssq = (long long)s_int[I_SSQ];
+    const long long c11 = ssq - nn, c01 = (long long)s_int[I_SB2] - ssq, c10 = (long long)s_int[I_SA2] - ssq;
+    const long long c00 = nn * nn - c01 - c10 - ssq;
+    double ari = 1.0;
+    if (!(c10 == 0 && c01 == 0)) {
+        const long long num = c11 * c00 - c10 * c01;
+        const long long den = (c11 + c10) * (c10 + c00) + (c11 + c01) * (c01 + c00);
+        ari = 2.0 * (double)num / (double)den;
+    }
+    // homogeneity_completeness_v_measure (beta = 1) and adjusted_mutual_info_score (arithmetic)
+    double h = 1.0, c = 1.0, vm = 1.0, ami = 1.0;
+    if (n > 0) {
+        const double HC = ka == 1 ? 0.0 : -hc, HK = kb == 1 ? 0.0 : -hk;
+        const double MI = (ka == 1 || kb == 1) ? 0.0 : (mi > 0.0 ? mi : 0.0);
+        h = HC != 0.0 ? MI / HC : 1.0;
+        c = HK != 0.0 ? MI / HK : 1.0;
+        const double hc2 = 2.0 * h;
+        vm = h + c == 0.0 ? 0.0 : hc2 * c / (h + c);
+        if (ka == 1 && kb == 1) {
+            ami = 1.0;
+        } else if (ka == 1 || kb == 1) {
+            ami = 0.0;
+        } else {
+            const double normalizer = (HC + HK) / 2.0;
+            double den = normalizer - emi;
+            den = den < 0.0 ? fmin(den, -kEps) : fmax(den, kEps);
+            double num = MI - emi;
+            num = num < 0.0 ? fmin(num, -kEps) : fmax(num, kEps);
+            ami = num / den;
+        }
+    }
+    const double vals[16] = {P, R, F, (double)TP, (double)FP, (double)FN, (double)TN, ari, ami, h, c, vm, prec0, prec1,
+                             (double)s_int[I_NGT], (double)s_int[I_NPRED]};
+#pragma unroll
+    for (int q = 0; q < 16; ++q) row[q] = vals[q];
+}
+
+}  // namespace gnncca
+
+using namespace gnncca;
+
+extern "C" {
+
+size_t gnncca_eval_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return 0;
+    const size_t bytes = ((size_t)n_nodes + (size_t)n_frames) * sizeof(double);   // lf tables: n_g + 1 entries per frame
+    return bytes < 256 ? 256 : (bytes + 255) / 256 * 256;
+}
+
+int gnncca_eval_frames(const int64_t* edge_index, const float* edge_labels, const int64_t* predictions, const int32_t* labels,
+                       int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                       int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace, size_t workspace_bytes,
+                       gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > kEvalMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames == 0) return GNNCCA_OK;
+    if (!node_ptr_dev || !edge_ptr_dev || !out || !workspace) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes > 0 && !labels) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !edge_labels || !predictions)) return GNNCCA_ERR_INVALID_ARG;
+    if (workspace_bytes < gnncca_eval_workspace_bytes(n_nodes, n_edges, n_frames)) return GNNCCA_ERR_WORKSPACE;
+    if (n_nodes >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    int P = 1;
+    while (P < max_frame_nodes) P <<= 1;
+    const size_t lds = (size_t)3 * P * sizeof(int);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    const long long* pr = reinterpret_cast<const long long*>(predictions);
+    double* lf = static_cast<double*>(workspace);
+    if (P <= 64)   // small frames (a Terrace frame has ~20 detections): one wave per frame
+        hipLaunchKernelGGL(eval_frames_kernel<64>, dim3((unsigned)n_frames), dim3(64), lds, st, ei, (long long)n_edges, edge_labels, pr,
+                           labels, (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, gt_labels_out, out, lf);
+    else
+        hipLaunchKernelGGL(eval_frames_kernel<256>, dim3((unsigned)n_frames), dim3(256), lds, st, ei, (long long)n_edges, edge_labels, pr,
+                           labels, (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, gt_labels_out, out, lf);
+    HIP_TRY_EV(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+}  // extern "C"

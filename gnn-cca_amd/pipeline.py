@@ -90,7 +90,7 @@ class PendingFinal:
 class FrameResult:
     """Outputs of one batch; tensors are views of ONE device buffer owned by this object."""
     __slots__ = ("batch", "outputs", "probs", "preds", "pruned", "flow_out", "flow_in", "labels", "n_clusters", "triggers", "_switches", "_final", "_keep",
-                 "_pipe", "_d2h", "_pending")
+                 "_pipe", "_d2h", "_pending", "_eval")
 
     def final_async(self):
         """Hand this batch to the pipeline's pool of host threads (no synchronisation) -> PendingFinal.  Results that did not come from the
@@ -126,6 +126,23 @@ class FrameResult:
                                    "n_clusters": kv.to(dev, non_blocking=True),
                                    "frames_finalized": res["frames_finalized"], "triggers": res["triggers"]}
         return self._final
+
+    def evaluate(self, final=True):
+        """The per-frame metrics of inference.py:349-371 for this batch (gnn_cca_amd.evaluation.evaluate_frames): float64 [G, 16] on the
+        device, columns evaluation.METRICS.  final=True scores final()'s predictions / partition (which waits for this batch's host
+        heuristics), final=False the device chain's pruned predictions / labels.  Computed once per mode."""
+        from .evaluation import evaluate_frames
+        cache = getattr(self, "_eval", None)
+        if cache is None:
+            cache = self._eval = {}
+        key = bool(final)
+        if key not in cache:
+            if key:
+                f = self.final()
+                cache[key] = evaluate_frames(self.batch, f["predictions"], f["labels"])
+            else:
+                cache[key] = evaluate_frames(self.batch, self.pruned, self.labels)
+        return cache[key]
 
 
 class _Finished:

@@ -503,6 +503,27 @@ GNNCCA_API int gnncca_pad_frame(const float* x, int64_t n_nodes, const int64_t* 
                                 float* x_pad, int64_t n_real_max, int n_dummy, int64_t* edge_index_pad, float* edge_attr_pad,
                                 int64_t e_pad, int node_in, int edge_in, gnncca_stream_t stream);
 
+/* ---- Per-frame association metrics (inference.py:349-371, the scores main.py:335-348 aggregates) ---------------------------------
+ * One launch scores every frame of a batch laid out as above (node_ptr_dev / edge_ptr_dev: int32 [n_frames + 1] in DEVICE memory; edges
+ * of a frame contiguous, an edge that leaves its frame is ignored).  Inputs: edge_index int64 [2][E] (batch-global ids), edge_labels fp32
+ * [E] (0/1 ground truth, as gnncca_build_edges writes it), predictions int64 [E] (0/1), labels int32 [N] (the predicted partition: a
+ * node's label is the smallest batch-global node id of its cluster).  ID_GT is the partition into connected components of the edges
+ * with label 1 (the reference's strongly connected components of a symmetric edge set).  Output: out fp64 [n_frames][16] in the order
+ * GNNCCA_EVAL_COLUMNS lists (compute_P_R_F, inference.py:23-68, and scikit-learn's adjusted_rand_score, adjusted_mutual_info_score
+ * (arithmetic), homogeneity / completeness / v_measure; n_clusters_pred counts the nodes with labels[v] == v); gt_labels_out (nullable)
+ * int32 [N] = ID_GT in the smallest-id convention.  Frames of at most GNNCCA_EVAL_MAX_FRAME_NODES nodes: `max_frame_nodes` (the largest
+ * frame, known to the caller from its host copy of node_ptr) above that is GNNCCA_ERR_INVALID_ARG before any launch; a frame the device
+ * offsets make larger than max_frame_nodes gets a NaN row.  The workspace (gnncca_eval_workspace_bytes) holds per-frame lgamma tables;
+ * no host synchronisation, no allocation: capturable. */
+#define GNNCCA_EVAL_MAX_FRAME_NODES 4096
+#define GNNCCA_EVAL_COLUMNS "P R F TP FP FN TN rand_index mutual_index homogeneity completeness v_measure precision0 precision1 " \
+                            "n_clusters_gt n_clusters_pred"
+GNNCCA_API size_t gnncca_eval_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames);
+GNNCCA_API int gnncca_eval_frames(const int64_t* edge_index, const float* edge_labels, const int64_t* predictions, const int32_t* labels,
+                                  int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev,
+                                  int32_t n_frames, int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace,
+                                  size_t workspace_bytes, gnncca_stream_t stream);
+
 /* Synchronises `stream` and returns the flag word of the last forward that used `workspace`. */
 GNNCCA_API int gnncca_read_graph_flags(const void* workspace, uint32_t* flags_out, gnncca_stream_t stream);
 /* The same plus, in flags_out[1], the column-range verdict of that forward: 0 = every node's target ids were <= 2 contiguous runs (or
