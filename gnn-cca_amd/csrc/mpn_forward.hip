@@ -153,8 +153,9 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         static const int split_min = diag_env("GNNCCA_GEMM_SPLIT_MIN") ? std::atoi(diag_env("GNNCCA_GEMM_SPLIT_MIN")) : 384;   // diagnostics
         // round 6: below 4096 nodes the first layer runs on the fp16-split GEMM in 32-row tiles with K split over one round of workgroups
         // (enc_f16_slices.cuh): a fraction of the slabs of the two forms above (dense1024: 8 x 0.5 MB instead of 16 x 0.5 MB written and read
-        // back; dense256: 16 instead of 32) and half the matrix work of the six-product form.  nks: powers of two while one round of
-        // workgroups holds the tiles (nrt * nks <= 384), a slice stays >= 128 deep and the workspace has the slabs.
+        // back; dense256: 16 instead of 32) and half the matrix work of the six-product form.  nks: at least K / 256, then powers of two
+        // while one round of workgroups holds the tiles (nrt * nks <= 256), a slice stays >= 64 deep and the workspace has the slabs.
+        // The minimum K / 256 is taken even where nrt * nks exceeds one round (K = 2048 near N = 4095: 128 x 8 = 1024 workgroups).
         static const int slices_min = diag_env_int("GNNCCA_GEMM_SLICES_MIN", 1, 0, 0x7FFFFFFF);
         static const int slices_max = diag_env_int("GNNCCA_GEMM_SLICES_MAX", 4095, 0, 0x7FFFFFFF);
         static const bool slices_bf16 = diag_env("GNNCCA_GEMM_BF16") != nullptr;
@@ -467,11 +468,13 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
             HIP_TRY(hipGetLastError());
             PROF_MARK(split ? GNNCCA_K_PLAN_ROWS : GNNCCA_K_ENC_GEMM);
         }
+        // the slabs the GEMM that ran actually wrote: the slices and split forms pick their own count (<= ws.ksplit), the plan
+        // GEMM writes ks; the rest of the workspace's slab region holds whatever an earlier forward left there
         ks_last = (split || use_slices) ? ks_split : ks;
         if (g < n_gemm - 1) {
             float* dst = act + (size_t)(g & 1) * N * O;
             GNNCCA_LAUNCH(reduce_bias_act_kernel, grid1((size_t)N * O, 256), dim3(256), 0, st, (const float*)part,
-                               blob + hdr.enc_node_b[g], dst, N, O, ks, l.relu);
+                               blob + hdr.enc_node_b[g], dst, N, O, ks_last, l.relu);
             HIP_TRY(hipGetLastError());
             PROF_MARK(GNNCCA_K_ENC_REDUCE);
             cur_in = dst;

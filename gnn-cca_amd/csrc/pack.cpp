@@ -67,6 +67,8 @@ Family classify(const gnncca_mpn_dims* d) {
         if (d->enc_node.layers[i].out_dim > 1024) return kFamilyGeneric;
     if (d->cls_edge.n_layers > 2) return kFamilyGeneric;
     if (d->cls_edge.n_layers == 2 && d->cls_edge.layers[0].out_dim > kMaxCls) return kFamilyGeneric;
+    // the family's classifier kernels apply ReLU after the hidden layer; a hidden layer of width 1 has none (models/mlp.py:17)
+    if (d->cls_edge.n_layers == 2 && !d->cls_edge.layers[0].relu) return kFamilyGeneric;
     return kFamilyMfma32x6;
 }
 

@@ -190,11 +190,16 @@ typedef struct gnncca_dropout {
  * leading ones (x0 w0 + x0 w1 + x1 w0): ~2^-17 relative on that layer's pre-activations (encoder output 5e-6 from fp64
  * instead of 3e-7 .. 1e-6), measured logit deviation 1.5e-7 (tolerance 1e-4), GEMM 19-28 % faster.  Off by default. */
 #define GNNCCA_OPT_ENC_SPLIT3 2u
-/* GNNCCA_OPT_ENC_UNSPLIT: a forward over >= 4096 nodes never splits K in that layer.  By default mid-size batches (a few thousand
- * to a few ten thousand nodes) run it split-K (partial slabs + a tail launch) and the largest ones un-split, so a graph's logits
- * agree across batch sizes within rounding only (<= 2e-6 asserted, 6e-8 measured).  With this option the mid-size batches take an
- * un-split 32-row kernel whose per-element arithmetic is the big un-split kernel's: a graph's logits are then BIT FOR BIT
- * independent of the batch (or the shard of a sharded batch) it is computed in, as long as that batch has >= 4096 nodes.
+/* GNNCCA_OPT_ENC_UNSPLIT: a forward over >= 4096 nodes never splits K in that layer (for the encoder shapes named below).  By
+ * default mid-size batches (a few thousand to a few ten thousand nodes) run it split-K (partial slabs + a tail launch) and the
+ * largest ones un-split, so a graph's logits agree across batch sizes within rounding only (<= 2e-6 asserted, 6e-8 measured).
+ * With this option the mid-size batches take an un-split 32-row kernel whose per-element arithmetic is the big un-split
+ * kernel's: a graph's logits are then BIT FOR BIT independent of the batch (or the shard of a sharded batch) it is computed in,
+ * as long as that batch has >= 4096 nodes.
+ * This holds for fast-family node encoders of exactly two layers, the first 128 wide with node_in_dim a multiple of 256, and
+ * without reattach_initial_nodes (the shipped 2048 -> 128 -> 32 among them): the un-split kernels finish the encoder in their
+ * epilogue, which needs that shape.  Any other node encoder still runs its first layer split-K on mid-size batches (the option
+ * only keeps it on the bf16 split GEMMs), and its logits agree across batch sizes within rounding only.
  * Price: encoder 48 instead of 44 us at 8192 nodes (plan launch included), 87 instead of 70 us at 16 384.
  * Off by default. */
 #define GNNCCA_OPT_ENC_UNSPLIT 4u

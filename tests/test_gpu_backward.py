@@ -200,6 +200,60 @@ def test_random_graphs_gradients_vs_oracle(agg):
             assert err <= 3e-5 * scale, (it, n, ei.shape, k, err)
 
 
+@pytest.mark.parametrize("node_fc,edge_fc,engine", [([64], [4], "fused"), ([256], [4], "fused"), ([128], [8], "fused"),
+                                                    ([128], [1], "layerwise"), ([128], [], "fused"), ([128, 64], [4], "layerwise")])
+def test_random_graphs_other_encoder_and_classifier_shapes_gradients_vs_oracle(node_fc, edge_fc, engine):
+    """backward_ok (csrc/mpn_forward.hip) sends every fast-family model with a two-layer node encoder to the fused engine: first-layer
+    widths other than 128, classifiers with a hidden layer of 8 (BatchNorm after it) or with none.  A hidden layer of width 1 has no
+    ReLU (models/mlp.py), which the family's classifier kernels would apply: that model is on the generic family and, like a
+    three-layer encoder, trains on the layer-by-layer engine under train_engine = 'auto'.  Irregular graphs of
+    test_random_graphs_gradients_vs_oracle, the loss and every parameter gradient against torch autograd over the CPU oracle."""
+    from gnn_cca_amd import MOTMPNet
+    from oracle.mpn_oracle import load_case
+    from test_gpu_fuzz import random_graph
+    params, arch, sd0, _ = load_case(os.path.join(GOLDEN_DIR, "n8_sum.npz"))
+    params = copy.deepcopy(params)
+    params["encoder_feats_dict"]["nodes"][arch]["node_fc_dims"] = list(node_fc)
+    params["classifier_feats_dict"]["edge_fc_dims"] = list(edge_fc)
+    torch.manual_seed(len(node_fc) * 1000 + node_fc[0] + 10 * len(edge_fc) + sum(edge_fc))
+    m = MOTMPNet(copy.deepcopy(params), None, arch)
+    sd = {k: v.detach().numpy().copy() for k, v in m.state_dict().items()}
+    for k, v in sd0.items():   # the conditioned weights of n8_sum wherever the shapes agree (the MPN MLPs)
+        if k in sd and sd[k].shape == np.asarray(v).shape:
+            sd[k] = np.asarray(v).copy()
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    m = m.cuda().train()
+    assert m.train_engine == "auto"
+    orc = TorchTrainOracle(params, arch, sd)
+    cls_bn_bias = "classifier.edge_mlp.fc_layers.0.bias" if m.classifier.edge_mlp.bn_index[0] is not None else None
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(repr((node_fc, edge_fc)).encode()))
+    for it in range(8):
+        kind = ["chunks", "sparse", "unsorted", "frames"][it % 4]
+        n, ei = random_graph(rng, kind)
+        while ei.shape[1] < 2:  # train-mode BatchNorm1d (classifier) refuses a batch of one edge, in torch as here
+            n, ei = random_graph(rng, "frames")
+        x = (rng.standard_normal((n, 64)) * 0.3).astype(np.float32)
+        ea = rng.random((ei.shape[1], 4)).astype(np.float32)
+        labels = (rng.random(ei.shape[1]) < 0.3).astype(np.float32)
+        ref_loss, _, ref = orc.loss_and_grads(x, ei, ea, labels)
+        m.zero_grad(set_to_none=True)
+        out = m(Data(torch.from_numpy(x).cuda(), torch.from_numpy(ei).cuda(), torch.from_numpy(ea).cuda()))
+        assert m._train_path == engine
+        loss = loss_of(out, torch.from_numpy(labels).cuda())
+        loss.backward()
+        # (without a hidden layer the logits and the loss reach O(10): the bound scales with the loss)
+        assert abs(float(loss) - ref_loss) <= 1e-5 * max(1.0, abs(ref_loss)), (it, float(loss), ref_loss)
+        for k, p in m.named_parameters():
+            r = ref[k].numpy()
+            if k == cls_bn_bias:   # feeds a train-mode BatchNorm: analytically zero, both sides hold rounding residue
+                assert float(np.abs(p.grad.cpu().numpy()).max()) <= 5e-4 and float(np.abs(r).max()) <= 5e-4, (it, k)
+                continue
+            scale = max(1.0, float(np.abs(r).max()))
+            err = float(np.abs(p.grad.cpu().numpy() - r).max())
+            assert err <= 3e-5 * scale, (it, n, ei.shape, k, err)
+
+
 @pytest.mark.parametrize("name", ["terrace32", "terrace32_max", "terrace32_mean"])
 @pytest.mark.parametrize("which,bad", [(0, 10 ** 6), (1, -3), (0, 2 ** 40 + 1)])
 def test_out_of_range_index_in_train_mode_is_contained(name, which, bad):

@@ -186,3 +186,43 @@ def test_unsplit_option_with_long_segments_shard_of_two_dense2048_equals_union_o
             for a, b in zip(part, full):
                 assert torch.equal(a, b[lo * e_per:hi * e_per]), (lo, hi, float((a - b[lo * e_per:hi * e_per]).abs().max()))
             del share, part
+
+
+def test_unsplit_option_bitwise_shares_hold_for_the_documented_encoder_shapes():
+    """include/gnncca_mpn.h states which encoders GNNCCA_OPT_ENC_UNSPLIT makes batch-independent: two layers, the first 128 wide,
+    node_in_dim a multiple of 256, no reattach_initial_nodes -- not only the shipped 2048 -> 128 -> 32.  Here node_in_dim 512: shares
+    of 4096, 6144 and 10 240 nodes (the 32-row un-split kernel) against the 65 536-node union (the 256-row un-split kernel, one round
+    of workgroups), every logit bit for bit.  Sparse ring graphs of 256 nodes, random weights."""
+    from gnn_cca_amd import MOTMPNet
+    import bench
+    params = copy.deepcopy(bench.graph_net_params())
+    params["encoder_feats_dict"]["nodes"]["resnet50"]["node_in_dim"] = 512
+    torch.manual_seed(21)
+    model = MOTMPNet(params, None, "resnet50")
+    with torch.no_grad():
+        for p in model.MPNet.node_model.node_mlp.parameters():
+            p.mul_(1.0 / 3)
+    model = model.cuda().eval()
+    model.encoder_unsplit = True
+    n, g_all, hops = 256, 256, (1, 5, 17)
+    rng = np.random.default_rng(21)
+    x = torch.from_numpy(rng.standard_normal((n * g_all, 512)).astype(np.float32)).cuda()
+    src = np.repeat(np.arange(n), len(hops))
+    one = np.stack([src, (src + np.tile(list(hops), n)) % n])
+    e_per = one.shape[1]
+    ei = torch.from_numpy(np.concatenate([one + g * n for g in range(g_all)], axis=1).astype(np.int64)).cuda()
+    ea = torch.from_numpy(rng.random((ei.shape[1], 4)).astype(np.float32)).cuda()
+    union = bench.Data()
+    union.x, union.edge_index, union.edge_attr = x, ei, ea
+    with torch.no_grad():
+        full = [t.clone() for t in model(union)["classified_edges"]]
+    assert all(torch.isfinite(t).all() for t in full)
+    for lo, hi in ((0, 16), (100, 124), (216, 256)):
+        share = bench.Data()
+        share.x = x[lo * n:hi * n].contiguous()
+        share.edge_index = (ei[:, lo * e_per:hi * e_per] - lo * n).contiguous()
+        share.edge_attr = ea[lo * e_per:hi * e_per].contiguous()
+        with torch.no_grad():
+            part = model(share)["classified_edges"]
+        for a, b in zip(part, full):
+            assert torch.equal(a, b[lo * e_per:hi * e_per]), (lo, hi, float((a - b[lo * e_per:hi * e_per]).abs().max()))
