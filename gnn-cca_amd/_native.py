@@ -165,6 +165,12 @@ _SIGNATURES = {
     "gnncca_eval_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "gnncca_eval_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnncca_edge_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "gnncca_edge_loss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
+    "gnncca_edge_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -15,8 +15,13 @@ Semantics: every call is exactly one optimizer step on the given batch.  The fir
 (N, E) shape run eagerly (the allocator and the workspace settle), the next one is captured while it runs, later ones
 replay the graph after copying the batch into the captured input buffers.  Optimizers must be capture-safe (SGD is;
 Adam needs `capturable=True`).
+
+`EdgeLoss` (gnn_cca_amd.loss) fits the loss_fn slot: the reference's compute_loss_acc loss and statistics in three launches, with
+`TrainMeters` collecting the per-iteration statistics on the device inside the captured graph.
 """
 import torch
+
+from .loss import EdgeLoss, TrainMeters  # noqa: F401  (the loss_fn of a step, and its device-side meters)
 
 
 class _Batch:

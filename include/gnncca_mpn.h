@@ -529,6 +529,43 @@ GNNCCA_API int gnncca_eval_frames(const int64_t* edge_index, const float* edge_l
                                   int32_t n_frames, int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace,
                                   size_t workspace_bytes, gnncca_stream_t stream);
 
+/* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
+ * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).
+ * criterion: GNNCCA_LOSS_BCE, GNNCCA_LOSS_BCE_WEIGHTED (pos_weight > 0) or GNNCCA_LOSS_FOCAL (utils.FocalLoss_binary: focusing_param,
+ * balance_param; with reduction 'mean' the focal factor applies to the step's mean BCE, with 'none' to every edge's).  validate != 0
+ * uses plain BCE with logits whatever the criterion, as the reference does.  The forward writes loss_out fp32 [1] (the sum over steps of
+ * the criterion) and record fp64 [GNNCCA_LOSS_REC_LEN(n_steps)]:
+ *   loss, loss_class1, loss_class0 (sums over steps of the per-edge loss averaged over label 1 / label 0: NaN for an empty class),
+ *   precision1, precision0, precision ((hits / count) * 100.0 on the last step with sigmoid(x) >= 0.5f, 0 without a hit), n_pos, n_neg,
+ *   mean_prob [n_steps][2] (mean sigmoid over label 0, label 1; 0.5 for an empty class), coef [n_steps] (d loss / d mean BCE of step s).
+ * With history != NULL the record is also written to row cursor[0] of history fp64 [capacity][REC_LEN] and cursor[0] is incremented,
+ * on the device; past capacity cursor[1] is set to 1 and nothing is written.  n_edges = 0 gives NaN losses, zero precisions and mean
+ * probabilities of 0.5.  The backward writes grad fp32 [n_steps][n_edges] = g * coef[s] * t(x, y) / n_edges, g = grad_loss[0] (device).
+ * Deterministic (fixed-order fp64 sums, no float atomics) and capturable (workspace from the caller, no synchronisation).  Arguments are
+ * checked before any launch. */
+#define GNNCCA_LOSS_BCE 0
+#define GNNCCA_LOSS_BCE_WEIGHTED 1
+#define GNNCCA_LOSS_FOCAL 2
+#define GNNCCA_LOSS_MAX_STEPS 64
+#define GNNCCA_LOSS_REC_LOSS 0
+#define GNNCCA_LOSS_REC_LOSS1 1
+#define GNNCCA_LOSS_REC_LOSS0 2
+#define GNNCCA_LOSS_REC_PREC1 3
+#define GNNCCA_LOSS_REC_PREC0 4
+#define GNNCCA_LOSS_REC_PREC 5
+#define GNNCCA_LOSS_REC_NPOS 6
+#define GNNCCA_LOSS_REC_NNEG 7
+#define GNNCCA_LOSS_REC_MEAN_PROB 8
+#define GNNCCA_LOSS_REC_LEN(n_steps) (8 + 3 * (n_steps))
+GNNCCA_API size_t gnncca_edge_loss_workspace_bytes(int32_t n_steps, int64_t n_edges);
+GNNCCA_API int gnncca_edge_loss_forward(const float* logits, const float* labels, int32_t n_steps, int64_t n_edges, int32_t criterion,
+                                        int32_t validate, float pos_weight, float focusing_param, float balance_param, float* loss_out,
+                                        double* record, double* history, int64_t capacity, int64_t* cursor, void* workspace,
+                                        size_t workspace_bytes, gnncca_stream_t stream);
+GNNCCA_API int gnncca_edge_loss_backward(const float* logits, const float* labels, int32_t n_steps, int64_t n_edges, int32_t criterion,
+                                         int32_t validate, float pos_weight, const float* grad_loss, const double* record, float* grad,
+                                         gnncca_stream_t stream);
+
 /* Synchronises `stream` and returns the flag word of the last forward that used `workspace`. */
 GNNCCA_API int gnncca_read_graph_flags(const void* workspace, uint32_t* flags_out, gnncca_stream_t stream);
 /* The same plus, in flags_out[1], the column-range verdict of that forward: 0 = every node's target ids were <= 2 contiguous runs (or
