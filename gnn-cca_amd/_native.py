@@ -73,6 +73,8 @@ OPT_COLUMN_RANGES = 8
 BWD_GRADS_ZEROED = 1
 POST_ROUNDING, POST_PRUNING, POST_SPLITTING = 1, 2, 4        # gnncca_post_finalize_frame_host switches (config_inference.yaml:6-8)
 POST_TRIGGER_ROUNDING, POST_TRIGGER_SPLITTING = 1, 2         # trigger bits of gnncca_post_prune_cluster_frames_ex
+OPTIM_SGD, OPTIM_ADAM = 0, 1                                 # rules of gnncca_optim_set_hyper
+OPTIM_BLOCK_HYPER_OFFSET, OPTIM_BLOCK_STEPS_OFFSET = 0, 80   # byte offsets inside an optimizer block (fp64 [8]; int32 [n_slots])
 
 
 _SIGNATURES = {
@@ -171,6 +173,14 @@ _SIGNATURES = {
                                            C.c_void_p]),
     "gnncca_edge_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_optim_block_bytes": (C.c_size_t, [C.c_int32]),
+    "gnncca_optim_set_hyper": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                         C.c_void_p]),
+    "gnncca_optim_sgd_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),
+    "gnncca_optim_adam_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int32), C.c_void_p]),
 }
 
 _lib = None

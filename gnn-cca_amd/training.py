@@ -16,12 +16,21 @@ Semantics: every call is exactly one optimizer step on the given batch.  The fir
 replay the graph after copying the batch into the captured input buffers.  Optimizers must be capture-safe (SGD is;
 Adam needs `capturable=True`).
 
+Learning-rate schedules: `torch.optim` optimizers hold `lr`, `momentum`, ... as Python numbers, which a capture freezes into the graph
+-- `scheduler.step()` or `param_groups[0]['lr'] = x` after the capture change nothing a replay reads (the step warns once when it sees
+that).  `FusedSGD` / `FusedAdam` (gnn_cca_amd.optim) keep them, and Adam's step counts, in device memory: the step uploads changed
+values before the capture and before every replay (`optimizer.sync_hyperparameters()`), so one graph follows the whole schedule of
+main_training.py:220-256, 349-370.  `set_optimizer()` is the optimizer switch at the end of the reference's warm-up.
+
 `EdgeLoss` (gnn_cca_amd.loss) fits the loss_fn slot: the reference's compute_loss_acc loss and statistics in three launches, with
 `TrainMeters` collecting the per-iteration statistics on the device inside the captured graph.
 """
+import warnings
+
 import torch
 
 from .loss import EdgeLoss, TrainMeters  # noqa: F401  (the loss_fn of a step, and its device-side meters)
+from .optim import FusedAdam, FusedSGD  # noqa: F401  (optimizers whose hyperparameters a captured step reads from device memory)
 
 
 class _Batch:
@@ -33,7 +42,21 @@ class GraphedTrainStep:
         self.model, self.optimizer, self.loss_fn = model, optimizer, loss_fn
         self.warmup, self.max_graphs = int(warmup), int(max_graphs)
         self._seen = {}     # shape key -> eager calls so far
-        self._graphs = {}   # shape key -> (graph, static batch, static labels, static loss)
+        self._graphs = {}   # shape key -> (graph, static batch, static labels, static loss, the groups' lr at capture)
+        self._warned = False
+        self._sync = getattr(optimizer, "sync_hyperparameters", None)   # FusedSGD / FusedAdam: upload changed hyperparameters
+
+    def set_optimizer(self, optimizer):
+        """Installs another optimizer (main_training.py:353-363 builds a fresh one at the end of the warm-up) and drops every captured
+        graph and warm-up count: the graphs hold the old optimizer's launches."""
+        self.optimizer = optimizer
+        self._graphs.clear()
+        self._seen.clear()
+        self._warned = False
+        self._sync = getattr(optimizer, "sync_hyperparameters", None)
+
+    def _lrs(self):
+        return tuple(g.get("lr") for g in self.optimizer.param_groups)
 
     def _eager(self, data, labels):
         self.optimizer.zero_grad(set_to_none=True)
@@ -49,7 +72,18 @@ class GraphedTrainStep:
                data.x.dtype, data.edge_attr.dtype, labels.dtype)
         entry = self._graphs.get(key)
         if entry is not None:
-            graph, sb, sl, loss = entry
+            graph, sb, sl, loss, lrs = entry
+            if self._sync is not None:
+                self._sync()
+            elif not self._warned and self._lrs() != lrs:
+                for was, now in zip(lrs, self._lrs()):
+                    if isinstance(now, (int, float)) and isinstance(was, (int, float)) and now != was:
+                        self._warned = True
+                        warnings.warn(f"GraphedTrainStep: the learning rate is now {now} but the captured graph holds {was}: "
+                                      f"{type(self.optimizer).__name__} keeps it as a Python number, which the capture froze, so replays "
+                                      "ignore the change.  Use gnn_cca_amd.optim.FusedSGD / FusedAdam, whose hyperparameters are read "
+                                      "from device memory at every replay.", UserWarning, stacklevel=2)
+                        break
             sb.x.copy_(data.x, non_blocking=True)
             sb.edge_index.copy_(data.edge_index, non_blocking=True)
             sb.edge_attr.copy_(data.edge_attr, non_blocking=True)
@@ -64,11 +98,13 @@ class GraphedTrainStep:
         sb = _Batch()
         sb.x, sb.edge_index, sb.edge_attr = data.x.clone(), data.edge_index.clone(), data.edge_attr.clone()
         sl = labels.clone()
+        if self._sync is not None:
+            self._sync()
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad(set_to_none=True)
         with torch.cuda.graph(graph):
             loss = self._eager(sb, sl)
         graph.replay()   # capture records, it does not execute: this replay IS the step for this call
-        self._graphs[key] = (graph, sb, sl, loss)
+        self._graphs[key] = (graph, sb, sl, loss, self._lrs())
         return loss

@@ -566,6 +566,42 @@ GNNCCA_API int gnncca_edge_loss_backward(const float* logits, const float* label
                                          int32_t validate, float pos_weight, const float* grad_loss, const double* record, float* grad,
                                          gnncca_stream_t stream);
 
+/* ---- Optimizer step (train.py:492-494; the optimizers and schedules of main_training.py:220-256, 349-370) --------------------------
+ * torch.optim.SGD (weight_decay, momentum, dampening, nesterov; the momentum buffer of a tensor is initialised to its gradient on the
+ * tensor's first step) and torch.optim.Adam (betas, eps, L2 weight_decay, amsgrad; bias corrections in fp64 from the step count) on fp32
+ * tensors, one launch per GNNCCA_OPTIM_MAX_TENSORS_PER_LAUNCH tensors.  The launches take NO hyperparameter and NO step count as an
+ * argument: they read them from the "block", a zero-initialised device buffer of gnncca_optim_block_bytes(n_slots) bytes that belongs to
+ * one parameter group:
+ *   fp64 [8] at GNNCCA_OPTIM_BLOCK_HYPER_OFFSET   lr, weight_decay, a, b, c, flag, rule, unused (written by gnncca_optim_set_hyper:
+ *                                                 SGD a = momentum, b = dampening, flag = nesterov; Adam a = beta1, b = beta2, c = eps,
+ *                                                 flag = amsgrad)
+ *   uint32 at GNNCCA_OPTIM_BLOCK_TICKET_OFFSET    the launch's ticket word (0 between launches)
+ *   int32 [n_slots] at GNNCCA_OPTIM_BLOCK_STEPS_OFFSET   one step count per tensor slot, advanced ON THE DEVICE by the step launch itself
+ *                                                 (Adam: steps taken; SGD: steps the tensor's momentum buffer has seen).  The caller may
+ *                                                 read and write them between launches (checkpoints).
+ * so a HIP graph that captured a step follows whatever gnncca_optim_set_hyper writes between its replays.  params / grads / state are HOST
+ * arrays of n_tensors DEVICE pointers, copied into the launch arguments by value (a captured graph keeps the addresses of its capture);
+ * numel[i] elements each, slots[i] in [0, n_slots) and distinct.  SGD: momentum_bufs (or single entries of it) may be NULL, the tensor
+ * is then stepped without momentum.  Adam: exp_avg and exp_avg_sq are required, max_exp_avg_sq (or entries) may be NULL without amsgrad.
+ * A state tensor is not read on its slot's first step (count 0), so it needs no initialisation.  16-byte accesses where every pointer
+ * of a tensor is 16-byte aligned, 4-byte ones otherwise.  Every argument is checked before any launch (GNNCCA_ERR_INVALID_ARG: null
+ * pointers, negative sizes, an unknown rule, lr / weight_decay / momentum / eps negative or not finite, Nesterov without momentum or with
+ * dampening, a beta outside [0, 1)); capturable: no allocation, no synchronisation, nothing read back. */
+#define GNNCCA_OPTIM_SGD 0
+#define GNNCCA_OPTIM_ADAM 1
+#define GNNCCA_OPTIM_MAX_TENSORS_PER_LAUNCH 64
+#define GNNCCA_OPTIM_BLOCK_HYPER_OFFSET 0
+#define GNNCCA_OPTIM_BLOCK_TICKET_OFFSET 64
+#define GNNCCA_OPTIM_BLOCK_STEPS_OFFSET 80
+GNNCCA_API size_t gnncca_optim_block_bytes(int32_t n_slots);
+GNNCCA_API int gnncca_optim_set_hyper(void* block, int32_t rule, double lr, double weight_decay, double a, double b, double c, int32_t flag,
+                                      gnncca_stream_t stream);
+GNNCCA_API int gnncca_optim_sgd_step(void* block, int32_t n_slots, int32_t n_tensors, void* const* params, const void* const* grads,
+                                     void* const* momentum_bufs, const int64_t* numel, const int32_t* slots, gnncca_stream_t stream);
+GNNCCA_API int gnncca_optim_adam_step(void* block, int32_t n_slots, int32_t n_tensors, void* const* params, const void* const* grads,
+                                      void* const* exp_avg, void* const* exp_avg_sq, void* const* max_exp_avg_sq, const int64_t* numel,
+                                      const int32_t* slots, gnncca_stream_t stream);
+
 /* Synchronises `stream` and returns the flag word of the last forward that used `workspace`. */
 GNNCCA_API int gnncca_read_graph_flags(const void* workspace, uint32_t* flags_out, gnncca_stream_t stream);
 /* The same plus, in flags_out[1], the column-range verdict of that forward: 0 = every node's target ids were <= 2 contiguous runs (or
