@@ -34,12 +34,6 @@ def build_stamps(verbose=False):
     return build(force=True, verbose=verbose, out=os.path.join(LIB_DIR, "libgnncca_mpn_stamps.so"), defs=["-DGNNCCA_STAMPS"])
 
 
-def build_f16_ablations(verbose=False):
-    """Diagnostic twin (tools/ab_f16_ablations.sh): the fp16-split encoder GEMM's ablation kernels compiled in -> lib/libgnncca_mpn_f16abl.so
-    (select with GNNCCA_DIAG=1 GNNCCA_LIB=... GNNCCA_GEMM_F16_DIAG=n)."""
-    return build(force=True, verbose=verbose, out=os.path.join(LIB_DIR, "libgnncca_mpn_f16abl.so"), defs=["-DGNNCCA_F16_ABLATIONS"])
-
-
 def _deps(src_path):
     """The quoted includes of a source, transitively (csrc/ and include/): what its object file has to be newer than."""
     import re
@@ -103,7 +97,5 @@ def build(force=False, verbose=False, out=None, defs=()):
 if __name__ == "__main__":
     if "--stamps" in sys.argv:
         print(build_stamps(verbose=True))
-    elif "--f16-ablations" in sys.argv:
-        print(build_f16_ablations(verbose=True))
     else:
         print(build(force="--force" in sys.argv, verbose=True))

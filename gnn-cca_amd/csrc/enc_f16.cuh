@@ -212,15 +212,11 @@ struct EncF16Params {
     const unsigned short* w3;      // BlobHeader::enc_w3 (the bf16 arm's pieces)
     float* out;                    // split-K slabs [ks][M][128] (not FUSE)
     int M, K, kslice;
-    int k_rotate;
     int force_arm;                 // diagnostics / tests: 1 = every tile takes the bf16 arm
-    int prio_late_half;            // 1: waves 4-7 run the main loop at s_setprio 1
     int x_nt;                      // 1: the x stream's LDS-DMA requests carry the non-temporal cache policy
 };
 
-// DIAG (GNNCCA_DIAG builds of the ablation matrix, timing only -- the results are garbage): bit 0 = no MFMAs (the fragments stay used), bit 1 = every
-// workgroup streams the FIRST 256 rows of x (x from L2), bit 2 = no fp16 split (the raw bits of x feed the MFMAs)
-template <bool FUSE, int DIAG = 0>
+template <bool FUSE>
 __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const EncFuseParams fp) {
     constexpr int BK = 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -237,15 +233,11 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
     const int row0 = blockIdx.x * 256;
     const int kbeg = blockIdx.y * p.kslice;
     const int nk = min(p.kslice, K - kbeg) / BK;
-    const int rot = p.k_rotate ? (int)((blockIdx.x * 37u + blockIdx.y * 11u) % (unsigned)nk) : 0;
-    auto kchunk = [&](int kt) {
-        const int kr = kt + rot;
-        return kr >= nk ? kr - nk : kr;
-    };
+    // (every workgroup walks k from chunk 0 on -- no rotation by row block, for position independence: enc_gemm_split_lds_kernel says why)
     // ---- LDS-DMA sources: this workgroup's rows of x behind a descriptor of their own (rows beyond M read as zero: out of range),
     //      the whole fp16 W image behind another ---------------------------------------------------------------------------------------
     const int rows_here = min(256, M - row0);
-    const rsrc_t rx = make_rsrc(p.x + ((DIAG & 2) ? (size_t)0 : (size_t)row0 * K), (unsigned long long)rows_here * K * 4);
+    const rsrc_t rx = make_rsrc(p.x + (size_t)row0 * K, (unsigned long long)rows_here * K * 4);
     const rsrc_t rw = make_rsrc(p.w2h, (unsigned long long)(K / BK) * kF16WSlot);
     unsigned xoff[4];
 #pragma unroll
@@ -261,7 +253,7 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
     // (kt beyond the last chunk: a clamped duplicate into a stage nobody reads any more -- the loop stays branch-free and every iteration
     // leaves exactly six instructions in flight, which is what its one counted wait assumes)
     auto issue_one = [&](int kt, int j) {
-        const int kc = kchunk(min(kt, nk - 1));
+        const int kc = min(kt, nk - 1);
         const int st = kt % kF16Stages;
         if (j < 4) {
             if (p.x_nt)   // x is read once: the non-temporal policy keeps it from displacing what the step kernels left in the caches (and W)
@@ -291,8 +283,8 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
     const int aswz = (l32 >> 1) & 7;
     const unsigned char* abase = xring + l32 * 128;
     // two waves share every SIMD; the later-dispatched half loses every arbitration at equal priority (stamps: its compute phase took
-    // 2650 cycles per chunk against 1900, and the first half then waited for it at the barrier): one static priority for that half
-    if (p.prio_late_half && wave >= 4) __builtin_amdgcn_s_setprio(1);
+    // 2650 cycles per chunk against 1900, and the first half then waited for it at the barrier).  A static priority for that half around
+    // the main loop was measured and is not set: 122.9 vs 121 us at N = 65 536
     PHASE_T(4);   // prologue
     for (int kt = 0; kt < nk; ++kt) {
         PHASE_T(3);
@@ -320,9 +312,6 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
                 b1[c] = *reinterpret_cast<const f16x8*>(b + 8192 + (c * 2 + s) * 1024 + lane * 16);
             }
             f16x8 a0, a1;
-            if (DIAG & 4) {
-                a0 = __builtin_bit_cast(f16x8, v0), a1 = __builtin_bit_cast(f16x8, v1);
-            } else
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const f32x2 v = q < 2 ? f32x2{v0[2 * q], v0[2 * q + 1]} : f32x2{v1[2 * q - 4], v1[2 * q - 3]};
@@ -333,9 +322,6 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
                 a1[2 * q] = p1[0], a1[2 * q + 1] = p1[1];
                 amax = fmaxf(fmaxf(amax, fabsf(v[0])), fabsf(v[1]));
             }
-            if (DIAG & 1) {
-                asm volatile("" ::"v"(a0), "v"(a1), "v"(b0[0]), "v"(b0[1]), "v"(b0[2]), "v"(b0[3]), "v"(b1[0]), "v"(b1[1]), "v"(b1[2]), "v"(b1[3]));
-            } else
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 accA[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0[c], accA[c], 0, 0, 0);
@@ -351,7 +337,6 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
         }
     }
     PHASE_T(3);
-    if (p.prio_late_half && wave >= 4) __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped duplicates of the last two iterations must land before the rings are reused
     f32x16 acc[4];
 #pragma unroll
@@ -413,17 +398,6 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
 // (concrete kernels around the body: with this toolchain a __global__ TEMPLATE that issues the LDS-DMA builtin from a lambda was not emitted)
 __global__ __launch_bounds__(512) void enc_gemm_f16_fused_kernel(const EncF16Params p, const EncFuseParams fp) { enc_gemm_f16_body<true>(p, fp); }
 __global__ __launch_bounds__(512) void enc_gemm_f16_split_kernel(const EncF16Params p, const EncFuseParams fp) { enc_gemm_f16_body<false>(p, fp); }
-#ifdef GNNCCA_F16_ABLATIONS   // diagnostic twin build only (tools/ab_f16_ablations.sh)
-#define GNNCCA_F16_DIAG_KERNEL(D) \
-    __global__ __launch_bounds__(512) void enc_gemm_f16_fused_diag##D##_kernel(const EncF16Params p, const EncFuseParams fp) { enc_gemm_f16_body<true, D>(p, fp); }
-GNNCCA_F16_DIAG_KERNEL(1)
-GNNCCA_F16_DIAG_KERNEL(2)
-GNNCCA_F16_DIAG_KERNEL(3)
-GNNCCA_F16_DIAG_KERNEL(4)
-GNNCCA_F16_DIAG_KERNEL(5)
-GNNCCA_F16_DIAG_KERNEL(6)
-GNNCCA_F16_DIAG_KERNEL(7)
-#endif
 
 }  // namespace gnncca
 
@@ -478,11 +452,7 @@ __global__ __launch_bounds__(kF16R32Threads) void enc_gemm_f16_rows32_kernel(con
     const int kg = (wave >> 1) & 3, ch = wave & 1;
     const int row0 = blockIdx.x * 32;
     const int nkc = K / BK / 4;                     // chunks per k-quarter
-    const int rot = p.k_rotate ? (int)((blockIdx.x * 5u) % (unsigned)nkc) : 0;
-    auto lchunk = [&](int it) {                    // the quarter-local chunk of iteration `it` (clamped past the end: a harmless duplicate)
-        int lc = min(it, nkc - 1) + rot;
-        return lc >= nkc ? lc - nkc : lc;
-    };
+    auto lchunk = [&](int it) { return min(it, nkc - 1); };   // the quarter-local chunk of iteration `it` (clamped past the end: a harmless duplicate)
     const int rows_here = min(32, M - row0);
     const rsrc_t rx = make_rsrc(p.x + (size_t)row0 * K, (unsigned long long)rows_here * K * 4);
     const rsrc_t rw = make_rsrc(p.w2h, (unsigned long long)(K / BK) * kF16WSlot);

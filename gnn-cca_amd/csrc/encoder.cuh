@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void enc_gemm_split_direct_kernel(const float*
 //   LDS image: [stage][piece][row][32 k] bf16, 64-B rows, the 16-B granule kc of row r stored at kc ^ ((r >> 2) & 3):
 //   ds_read_b128 of 16 consecutive rows at one kc hits 64 distinct banks (no padding: 144 KB must fit 160 KB).
 // Measured (N = 65 536, counters): TCP line accesses 52.9 M -> 18.4 M, TA busy 82 M -> 32 M cycles, LDS bank
-// conflicts 0.  Time, A/B in one process on one box (GNNCCA_GEMM_DIRECT=1 selects the kernel above): 195-197 us ->
+// conflicts 0.  Time, A/B in one process on one box (against the kernel above): 195-197 us ->
 // 189-192 us at N = 65 536, 59.9 -> 57.4 us at N = 16 384 -- the L1 pressure was real but is not what bounds the
 // kernel.  Requesting the operands two chunks ahead (two register sets, 215 VGPRs) did not help either kernel (+4 %
 // here): what remains is not load latency either; the waves spend 60 % of their cycles waiting on instruction issue
@@ -277,26 +277,24 @@ struct EncFuseParams {
     unsigned* flags;
     const unsigned* blockflags;
     int E;
-    int k_rotate;      // 1: workgroup b walks its k chunks from chunk (37 b) mod nk on, wrapping (the sum is order-free; see the kernel)
-    int diag_x_rows;   // GNNCCA_DIAG experiment (0 in production): > 0 = every workgroup streams rows [0, diag_x_rows) of x instead of its
-                       // own -- the same loads, conversions and MFMAs with x served from L2 (timing only: the results are garbage)
 };
 
-// Main loop: top of iteration kt = global loads of chunk kt + 1 (x: 4 x 16 B per thread, W pieces: 3 x 16 B), middle = the
-// MFMAs of chunk kt from LDS stage kt & 1, bottom = conversion + LDS store of chunk kt + 1, one barrier.  Measured and NOT
-// kept (round 2, N = 65 536, same box): waves 4-7 running [convert][MFMA] against waves 0-3 [MFMA][convert] (the stagger of
+// The first form of the main loop (round 2, retired): top of iteration kt = global loads of chunk kt + 1 (x: 4 x 16 B per thread, W
+// pieces: 3 x 16 B), middle = the MFMAs of chunk kt from LDS stage kt & 1, bottom = conversion + LDS store of chunk kt + 1, one
+// barrier at the chunk end.  Measured on it and NOT kept (N = 65 536, same box): waves 4-7 running [convert][MFMA] against
+// waves 0-3 [MFMA][convert] (the stagger of
 // MI355X_MICROARCH's "two waves that run the same program") 202 -> 220 us; x two chunks ahead in a second register set
 // 202 -> 216 us.  Ablations of the same build: no MFMAs and no LDS reads at all 160 us; x re-read from L2 instead of HBM 183 us;
 // no conversion / LDS stores 183 us -- the kernel is bound by its x stream, not by the matrix pipe: walking a 256-row tile in
 // 128-B-per-row chunks with one workgroup per CU streams at 4.4 TB/s even in a bare copy loop (tools/ubench_rowtile.hip:
 // 122 us for these 537 MB; a linear sweep of the same bytes 86 us).
-// PIPE (round 2): the same operands, stages and MFMAs, software-pipelined by k-HALF with the chunk's one barrier BETWEEN the halves.
-// With the barrier at the chunk end (the form above) every wave of the workgroup converts / stores / reads fragments at the same
+// The loop as it is now (round 2): the same operands, stages and MFMAs, software-pipelined by k-HALF with the chunk's one barrier BETWEEN
+// the halves.  With the barrier at the chunk end (the first form) every wave of the workgroup converts / stores / reads fragments at the same
 // time and then queues for the matrix pipe at the same time -- 48 % MFMA-busy, and an LDS-DMA variant that hid ALL of the x latency
 // ran no faster.  Here, while the 24 MFMAs of one half run, the wave reads the fragments of the next half
 // (the next chunk's first half included: that chunk is published at the mid-chunk barrier) and converts + stores the chunk after
 // it; x is requested two chunks ahead in two register sets.
-template <bool FUSE, bool P3, bool PIPE = false>
+template <bool FUSE, bool P3>
 __global__ __launch_bounds__(512) void enc_gemm_split_lds_kernel(const float* __restrict__ x, const unsigned short* __restrict__ w3,
                                                                  float* __restrict__ out, int M, int K, int O, int kslice,
                                                                  const EncFuseParams fp) {
@@ -316,25 +314,19 @@ __global__ __launch_bounds__(512) void enc_gemm_split_lds_kernel(const float* __
     const int row0 = blockIdx.x * RA;
     const int kbeg = blockIdx.y * kslice;
     const int nk = min(kslice, K - kbeg) / BK;
-    // k ROTATION (round 5; an option, off by default: mpn_forward.hip says why).  Every workgroup of a round reads 128 B from each of its 256 rows (8 KB apart) per chunk, and all of them walk
-    // the same k at about the same time: the chip's 256 request streams then agree in the address bits BELOW the row stride chunk after
-    // chunk, i.e. they crowd the same memory channels (tools/ubench_xring.hip: this walk streams at 5.0 TB/s, the same walk with every
-    // workgroup STARTING at another chunk at 6.2 -- the linear-sweep rate).  A dot product does not care where its sum starts, so
-    // workgroup b takes its chunks in the order rot, rot + 1, ..., nk - 1, 0, ..., rot - 1 with rot = 37 b mod nk.  The summation ORDER
-    // then depends on the row block, which is why GNNCCA_OPT_ENC_UNSPLIT (bitwise batch independence) runs with k_rotate = 0.
-    const int rot = fp.k_rotate ? (int)((blockIdx.x * 37u + blockIdx.y * 11u) % (unsigned)nk) : 0;
-    auto kchunk = [&](int kt) {
-        const int kr = kt + rot;
-        return kr >= nk ? kr - nk : kr;
-    };
+    // Every workgroup walks its k chunks in the same order, 0 ... nk - 1.  Each reads 128 B from each of its 256 rows (8 KB apart) per chunk, and
+    // all of them walk the same k at about the same time: the chip's 256 request streams then agree in the address bits BELOW the row stride
+    // chunk after chunk, i.e. they crowd the same memory channels (tools/ubench_xring.hip: this walk streams at 5.0 TB/s, the same walk with
+    // every workgroup STARTING at another chunk at 6.2 -- the linear-sweep rate).  Rotating the start by the row block (round 5) is NOT done:
+    // a node's sum would then start at a chunk that depends on its position in the batch, and its encoder output with it -- and the kernels
+    // themselves gained 0-3 % at best (mpn_forward.hip has the figures).
     // loader roles: x chunk = 256 rows x 8 float4 -> 4 per thread; W chunk = 1536 16-B granules -> 3 per thread
     const float* xsrc[4];
     int xdst[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int q = tid + 512 * u, row = q >> 3, c4 = q & 7;
-        const int xrow = fp.diag_x_rows > 0 ? row % fp.diag_x_rows : min(row0 + row, M - 1);
-        xsrc[u] = x + (size_t)xrow * K + kbeg + c4 * 4;
+        xsrc[u] = x + (size_t)min(row0 + row, M - 1) * K + kbeg + c4 * 4;
         xdst[u] = row * BK + (((c4 >> 1) ^ ((row >> 2) & 3)) << 3) + ((c4 & 1) << 2);
     }
     int wdst[3];
@@ -344,40 +336,11 @@ __global__ __launch_bounds__(512) void enc_gemm_split_lds_kernel(const float* __
         wdst[u] = (p * RB + col) * BK + ((kc ^ ((col >> 2) & 3)) << 3);
     }
     const size_t wchunk = (size_t)3 * O * BK;  // bf16 elements per k-chunk of w3
-    f32x4 xr[4];
     bf16x8 wreg[3];
-    auto load_x = [&](int kt) {
-        const int kc = kchunk(kt);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) xr[u] = *reinterpret_cast<const f32x4*>(xsrc[u] + kc * BK);
-    };
     auto load_w = [&](int kt) {
-        const int kc = kchunk(kt);
 #pragma unroll
         for (int u = 0; u < 3; ++u)
-            wreg[u] = *reinterpret_cast<const bf16x8*>(w3 + (size_t)(kbeg / BK + kc) * wchunk + (size_t)(tid + 512 * u) * 8);
-    };
-    auto store_stage = [&](int stage) {
-        __bf16* a = sa + (size_t)stage * 3 * RA * BK;
-        __bf16* b = sb + (size_t)stage * 3 * RB * BK;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            bf16x4 p0, p1, p2;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float v = xr[u][q];
-                const __bf16 h0 = (__bf16)v;
-                const float r1 = v - (float)h0;
-                const __bf16 h1 = (__bf16)r1;
-                const float r2 = r1 - (float)h1;
-                p0[q] = h0, p1[q] = h1, p2[q] = (__bf16)r2;
-            }
-            *reinterpret_cast<bf16x4*>(a + xdst[u]) = p0;
-            *reinterpret_cast<bf16x4*>(a + RA * BK + xdst[u]) = p1;
-            *reinterpret_cast<bf16x4*>(a + 2 * RA * BK + xdst[u]) = p2;
-        }
-#pragma unroll
-        for (int u = 0; u < 3; ++u) *reinterpret_cast<bf16x8*>(b + wdst[u]) = wreg[u];
+            wreg[u] = *reinterpret_cast<const bf16x8*>(w3 + (size_t)(kbeg / BK + kt) * wchunk + (size_t)(tid + 512 * u) * 8);
     };
     f32x16 acc[2][2];
 #pragma unroll
@@ -394,178 +357,131 @@ __global__ __launch_bounds__(512) void enc_gemm_split_lds_kernel(const float* __
         arow[t] = ra * BK, aswz[t] = (ra >> 2) & 3;
         brow[t] = cb * BK, bswz[t] = (cb >> 2) & 3;
     }
-    auto mfma_chunk = [&](int stage) {
+    struct Frag {
+        bf16x8 a[2][3], b[2][3];
+    };
+    auto read_frag = [&](int stage, int ks, Frag& f) {
         const __bf16* a = sa + (size_t)stage * 3 * RA * BK;
         const __bf16* b = sb + (size_t)stage * 3 * RB * BK;
+        const int kc = 2 * ks + h;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int kc = 2 * ks + h;
-            bf16x8 af[2][3], bf[2][3];
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    af[t][p] = *reinterpret_cast<const bf16x8*>(a + p * RA * BK + arow[t] + ((kc ^ aswz[t]) << 3));
-                    bf[t][p] = *reinterpret_cast<const bf16x8*>(b + p * RB * BK + brow[t] + ((kc ^ bswz[t]) << 3));
-                }
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    // smallest terms first
-                    if (!P3) {   // the three 2^-16-order terms (GNNCCA_OPT_ENC_SPLIT3 drops them)
-                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rt][2], bf[ct][0], acc[rt][ct], 0, 0, 0);
-                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rt][1], bf[ct][1], acc[rt][ct], 0, 0, 0);
-                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rt][0], bf[ct][2], acc[rt][ct], 0, 0, 0);
-                    }
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rt][1], bf[ct][0], acc[rt][ct], 0, 0, 0);
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rt][0], bf[ct][1], acc[rt][ct], 0, 0, 0);
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rt][0], bf[ct][0], acc[rt][ct], 0, 0, 0);
-                }
-        }
-    };
-    if (!PIPE) {
-        load_w(0);
-        load_x(0);
-        store_stage(0);
-        __syncthreads();
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt + 1 < nk) {
-                load_w(kt + 1);
-                load_x(kt + 1);
+            for (int p = 0; p < 3; ++p) {
+                f.a[t][p] = *reinterpret_cast<const bf16x8*>(a + p * RA * BK + arow[t] + ((kc ^ aswz[t]) << 3));
+                f.b[t][p] = *reinterpret_cast<const bf16x8*>(b + p * RB * BK + brow[t] + ((kc ^ bswz[t]) << 3));
             }
-            mfma_chunk(kt & 1);
-            if (kt + 1 < nk) store_stage((kt + 1) & 1);
-            __syncthreads();
-        }
-    } else {
-        struct Frag {
-            bf16x8 a[2][3], b[2][3];
-        };
-        auto read_frag = [&](int stage, int ks, Frag& f) {
-            const __bf16* a = sa + (size_t)stage * 3 * RA * BK;
-            const __bf16* b = sb + (size_t)stage * 3 * RB * BK;
-            const int kc = 2 * ks + h;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    f.a[t][p] = *reinterpret_cast<const bf16x8*>(a + p * RA * BK + arow[t] + ((kc ^ aswz[t]) << 3));
-                    f.b[t][p] = *reinterpret_cast<const bf16x8*>(b + p * RB * BK + brow[t] + ((kc ^ bswz[t]) << 3));
-                }
-        };
-        auto mfma_half = [&](const Frag& f) {
+    };
+    auto mfma_half = [&](const Frag& f) {
 #ifdef GNNCCA_EXP_GEMM_NO_MFMA   // diagnostic twin build: the main loop without its MFMAs (the fragments stay used: their LDS reads remain)
-            asm volatile("" ::"v"(f.a[0][0]), "v"(f.a[1][2]), "v"(f.b[0][0]), "v"(f.b[1][2]));
-            return;
+        asm volatile("" ::"v"(f.a[0][0]), "v"(f.a[1][2]), "v"(f.b[0][0]), "v"(f.b[1][2]));
+        return;
 #endif
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
+        for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    if (!P3) {
-                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][2], f.b[ct][0], acc[rt][ct], 0, 0, 0);
-                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][1], f.b[ct][1], acc[rt][ct], 0, 0, 0);
-                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][0], f.b[ct][2], acc[rt][ct], 0, 0, 0);
-                    }
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][1], f.b[ct][0], acc[rt][ct], 0, 0, 0);
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][0], f.b[ct][1], acc[rt][ct], 0, 0, 0);
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][0], f.b[ct][0], acc[rt][ct], 0, 0, 0);
+            for (int ct = 0; ct < 2; ++ct) {
+                if (!P3) {
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][2], f.b[ct][0], acc[rt][ct], 0, 0, 0);
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][1], f.b[ct][1], acc[rt][ct], 0, 0, 0);
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][0], f.b[ct][2], acc[rt][ct], 0, 0, 0);
                 }
-        };
-        // x in two register sets (chunk k in set k & 1), W in one (its source is L2-resident)
-        f32x4 xs[1][4];
-        auto load_x2 = [&](int kt, f32x4 (&dst)[4]) {
-            const int kc = kchunk(kt);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) dst[u] = *reinterpret_cast<const f32x4*>(xsrc[u] + kc * BK);
-        };
-        auto store_stage2 = [&](int stage, const f32x4 (&src)[4], const bf16x8 (&wsrc)[3]) {
-            __bf16* a = sa + (size_t)stage * 3 * RA * BK;
-            __bf16* b = sb + (size_t)stage * 3 * RB * BK;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                // the same three roundings as store_stage, two elements at a time: v_cvt_pk_bf16_f32 rounds a pair, the pair's
-                // float images are one shift and one mask of that word, the remainders one packed subtract (exact: a value minus
-                // its own 8-bit rounding fits fp32) -- 9 VALU per pair instead of 13
-                typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-                unsigned w[3][2];
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) {
-                    f32x2 v = {src[u][2 * pr], src[u][2 * pr + 1]};
-#pragma unroll
-                    for (int lev = 0; lev < 3; ++lev) {
-                        const unsigned word = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-                        w[lev][pr] = word;
-                        if (lev < 2)
-                            v = __builtin_elementwise_fma(f32x2{-1.f, -1.f},
-                                                          f32x2{__uint_as_float(word << 16), __uint_as_float(word & 0xffff0000u)}, v);
-                    }
-                }
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                *reinterpret_cast<u32x2*>(a + xdst[u]) = u32x2{w[0][0], w[0][1]};
-                *reinterpret_cast<u32x2*>(a + RA * BK + xdst[u]) = u32x2{w[1][0], w[1][1]};
-                *reinterpret_cast<u32x2*>(a + 2 * RA * BK + xdst[u]) = u32x2{w[2][0], w[2][1]};
+                acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][1], f.b[ct][0], acc[rt][ct], 0, 0, 0);
+                acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][0], f.b[ct][1], acc[rt][ct], 0, 0, 0);
+                acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[rt][0], f.b[ct][0], acc[rt][ct], 0, 0, 0);
             }
+    };
+    // x in two register sets (chunk k in set k & 1), W in one (its source is L2-resident)
+    f32x4 xs[1][4];
+    auto load_x2 = [&](int kt, f32x4 (&dst)[4]) {
 #pragma unroll
-            for (int u = 0; u < 3; ++u) *reinterpret_cast<bf16x8*>(b + wdst[u]) = wsrc[u];
-        };
-        Frag f0, f1;
-        // chunk k lives in stage k & 1.  Phase 1 of chunk kt: MFMAs of its first half while its second half is read.  Barrier: every
-        // wave has read all of chunk kt (its stage is free) and chunk kt + 1 -- stored a chunk ago -- is visible.  Phase 2: MFMAs of
-        // the second half while chunk kt + 2 is converted and stored into the freed stage, the loads of chunk kt + 3 are issued (they
-        // have a whole chunk to land: an HBM round trip under load is about one) and the first half of chunk kt + 1 is read.
-        // (Requesting chunks 0 and 1 together, chunk 1 in a register set of its own, changes nothing: 28.3 vs 27.7-29 us at N = 8192,
-        // r3_prol1.log -- the launch's 8.5 us of fixed cost are its 128 KB of slab stores per workgroup, not the prologue's round trips.)
-        load_w(0);
-        load_x2(0, xs[0]);
-        store_stage2(0, xs[0], wreg);
-        load_w(min(1, nk - 1));
-        load_x2(min(1, nk - 1), xs[0]);
-        store_stage2(1, xs[0], wreg);
-        load_w(min(2, nk - 1));
-        load_x2(min(2, nk - 1), xs[0]);
+        for (int u = 0; u < 4; ++u) dst[u] = *reinterpret_cast<const f32x4*>(xsrc[u] + kt * BK);
+    };
+    auto store_stage2 = [&](int stage, const f32x4 (&src)[4], const bf16x8 (&wsrc)[3]) {
+        __bf16* a = sa + (size_t)stage * 3 * RA * BK;
+        __bf16* b = sb + (size_t)stage * 3 * RB * BK;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            // the three roundings v -> bf16, remainder -> bf16, remainder -> bf16, two elements at a time: v_cvt_pk_bf16_f32 rounds a pair, the pair's
+            // float images are one shift and one mask of that word, the remainders one packed subtract (exact: a value minus
+            // its own 8-bit rounding fits fp32) -- 9 VALU per pair instead of 13
+            typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+            unsigned w[3][2];
+#pragma unroll
+            for (int pr = 0; pr < 2; ++pr) {
+                f32x2 v = {src[u][2 * pr], src[u][2 * pr + 1]};
+#pragma unroll
+                for (int lev = 0; lev < 3; ++lev) {
+                    const unsigned word = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+                    w[lev][pr] = word;
+                    if (lev < 2)
+                        v = __builtin_elementwise_fma(f32x2{-1.f, -1.f},
+                                                      f32x2{__uint_as_float(word << 16), __uint_as_float(word & 0xffff0000u)}, v);
+                }
+            }
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            *reinterpret_cast<u32x2*>(a + xdst[u]) = u32x2{w[0][0], w[0][1]};
+            *reinterpret_cast<u32x2*>(a + RA * BK + xdst[u]) = u32x2{w[1][0], w[1][1]};
+            *reinterpret_cast<u32x2*>(a + 2 * RA * BK + xdst[u]) = u32x2{w[2][0], w[2][1]};
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) *reinterpret_cast<bf16x8*>(b + wdst[u]) = wsrc[u];
+    };
+    Frag f0, f1;
+    // chunk k lives in stage k & 1.  Phase 1 of chunk kt: MFMAs of its first half while its second half is read.  Barrier: every
+    // wave has read all of chunk kt (its stage is free) and chunk kt + 1 -- stored a chunk ago -- is visible.  Phase 2: MFMAs of
+    // the second half while chunk kt + 2 is converted and stored into the freed stage, the loads of chunk kt + 3 are issued (they
+    // have a whole chunk to land: an HBM round trip under load is about one) and the first half of chunk kt + 1 is read.
+    // (Requesting chunks 0 and 1 together, chunk 1 in a register set of its own, changes nothing: 28.3 vs 27.7-29 us at N = 8192,
+    // r3_prol1.log -- the launch's 8.5 us of fixed cost are its 128 KB of slab stores per workgroup, not the prologue's round trips.)
+    load_w(0);
+    load_x2(0, xs[0]);
+    store_stage2(0, xs[0], wreg);
+    load_w(min(1, nk - 1));
+    load_x2(min(1, nk - 1), xs[0]);
+    store_stage2(1, xs[0], wreg);
+    load_w(min(2, nk - 1));
+    load_x2(min(2, nk - 1), xs[0]);
+    __syncthreads();
+    read_frag(0, 0, f0);
+    PHASE_T_DECL;
+    for (int kt = 0; kt < nk - 1; ++kt) {   // every chunk but the last: straight-line phases (loads unconditional, clamped)
+        const int stage = kt & 1;
+        PHASE_T(3);
+        __builtin_amdgcn_sched_barrier(0);
+        read_frag(stage, 1, f1);
+        mfma_half(f0);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, P3 ? 1 : 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        PHASE_T(0);
         __syncthreads();
-        read_frag(0, 0, f0);
-        PHASE_T_DECL;
-        for (int kt = 0; kt < nk - 1; ++kt) {   // every chunk but the last: straight-line phases (loads unconditional, clamped)
-            const int stage = kt & 1;
-            PHASE_T(3);
-            __builtin_amdgcn_sched_barrier(0);
-            read_frag(stage, 1, f1);
-            mfma_half(f0);
+        PHASE_T(1);
+        store_stage2(stage, xs[0], wreg);            // chunk kt + 2 (for kt + 2 >= nk: a clamped duplicate nobody reads)
+        load_w(min(kt + 3, nk - 1));
+        load_x2(min(kt + 3, nk - 1), xs[0]);
+        read_frag(stage ^ 1, 0, f0);
+        mfma_half(f1);
 #pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, P3 ? 1 : 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            PHASE_T(0);
-            __syncthreads();
-            PHASE_T(1);
-            store_stage2(stage, xs[0], wreg);            // chunk kt + 2 (for kt + 2 >= nk: a clamped duplicate nobody reads)
-            load_w(min(kt + 3, nk - 1));
-            load_x2(min(kt + 3, nk - 1), xs[0]);
-            read_frag(stage ^ 1, 0, f0);
-            mfma_half(f1);
-#pragma unroll
-            for (int i = 0; i < (P3 ? 12 : 24); ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);   // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, P3 ? 10 : 5, 1);   // conversion arithmetic
-                __builtin_amdgcn_sched_group_barrier(0x080, P3 ? 3 : 2, 1);    // LDS stores / fragment reads
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 1);   // a global load
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            PHASE_T(2);
+        for (int i = 0; i < (P3 ? 12 : 24); ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);   // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, P3 ? 10 : 5, 1);   // conversion arithmetic
+            __builtin_amdgcn_sched_group_barrier(0x080, P3 ? 3 : 2, 1);    // LDS stores / fragment reads
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 1);   // a global load
         }
-        PHASE_T_FLUSH(6);
-        {   // last chunk: nothing left to stage
-            read_frag((nk - 1) & 1, 1, f1);
-            mfma_half(f0);
-            mfma_half(f1);
-        }
-        __syncthreads();   // the epilogue overwrites the stages
+        __builtin_amdgcn_sched_barrier(0);
+        PHASE_T(2);
     }
+    PHASE_T_FLUSH(6);
+    {   // last chunk: nothing left to stage
+        read_frag((nk - 1) & 1, 1, f1);
+        mfma_half(f0);
+        mfma_half(f1);
+    }
+    __syncthreads();   // the epilogue overwrites the stages
     if (!FUSE) {
         float* __restrict__ dst = out + (size_t)blockIdx.y * M * O;
 #pragma unroll

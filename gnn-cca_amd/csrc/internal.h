@@ -1,4 +1,4 @@
-// internal.h -- layouts shared by the host packer (pack.cpp) and the HIP kernels (mpn_kernels.hip).
+// internal.h -- layouts shared by the host packer (pack.cpp) and the HIP kernels (mpn_forward.hip).
 // Not part of the public ABI (include/gnncca_mpn.h is).
 #pragma once
 #include <stddef.h>

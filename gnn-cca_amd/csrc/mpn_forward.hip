@@ -1,4 +1,4 @@
-// mpn_kernels.hip -- gfx950 (MI355X / CDNA4) kernels and the C-ABI forward of the GNN-CCA message-passing path.
+// mpn_forward.hip -- gfx950 (MI355X / CDNA4) kernels and the C-ABI forward of the GNN-CCA message-passing path.
 //
 // Algebra (derived from models/mpn.py:48,68-69,97-99): with the edge-MLP weight split by the
 // cat order [x[row] | x[col] | e] and the node-MLP weight by [x[row] | e'],
@@ -16,8 +16,6 @@
 //   topology     seg_ptr: [N+1] int32 CSR offsets by source node;  col32 [E] int32 (sorted order)
 // One wave owns (a share of) one source node's contiguous edge segment, so the per-destination reduction needs
 // no atomics and is bitwise reproducible.
-#include <cstdlib>
-
 #include "common.cuh"
 #include "wave_reduce.cuh"
 #include "plan.cuh"
@@ -132,12 +130,16 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
     int ks_last = 1;
     bool fused_tail = false;   // the GEMM launch already produced h0 and the step-1 projections
     const bool split3 = (options & GNNCCA_OPT_ENC_SPLIT3) != 0;
+    const bool unsplit = (options & GNNCCA_OPT_ENC_UNSPLIT) != 0;
+    // diagnostics, read once for every encoder form below: the bf16 form as the A/B reference of the fp16-split GEMMs; every tile / wave of
+    // the fp16-split GEMMs on its fallback arm (tests)
+    static const bool gemm_bf16 = diag_env("GNNCCA_GEMM_BF16") != nullptr;
+    static const int f16_force_arm = diag_env_int("GNNCCA_GEMM_F16_ARM", 0, 0, 1);
     // graphs and batches whose GEMM ran split-K: the tail on the matrix pipe, 32 nodes per workgroup, from 2560 nodes (round 3 lowered this
     // from 6144: 8.7 -> 6.9 us at N = 4096, 10.3 -> 7.5 at 5120, 10.4 -> 7.0 at 4000, 9.2 -> 7.2 at 3000, 8.6 -> 6.4 at 3072; equal at 2048
     // (6.2), the register-resident tail ahead at 1024 (5.0 vs 7.6); profiles/r03_logs/r3_thresh1.log, r3_thresh2.log)
-    static const bool no_mfma_tail = diag_env("GNNCCA_NO_MFMA_TAIL") != nullptr;  // diagnostics: A/B the two tails
-    static const int kTailMfmaMin = diag_env("GNNCCA_TAIL_MFMA_MIN") ? std::atoi(diag_env("GNNCCA_TAIL_MFMA_MIN")) : 2560;
-    const bool tail_mfma_ok = !dropping && !no_mfma_tail && N >= kTailMfmaMin && nl == 2 && d->enc_node.layers[0].out_dim == 128 &&
+    static const int kTailMfmaMin = diag_env_int("GNNCCA_TAIL_MFMA_MIN", 2560, 0, 0x7FFFFFFF);   // diagnostics
+    const bool tail_mfma_ok = !dropping && N >= kTailMfmaMin && nl == 2 && d->enc_node.layers[0].out_dim == 128 &&
                               !d->reattach_nodes && (reinterpret_cast<uintptr_t>(part) & 15) == 0;
     for (int g = 0; g < n_gemm; ++g) {
         const gnncca_layer& l = d->enc_node.layers[g];
@@ -150,7 +152,7 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         // and 17.4 + 17.1, r3_gemm_split_min.log -- and, once the plan rode along, to 384: GEMM 11.5 / 12.1 / 17.7 / 20.8 -> 9.3 / 9.2 /
         // 10.5 / 13.2 us at 384 / 512 / 768 / 896 nodes, 3 x dense256 17.0 -> 10.0; at 256 nodes the f32 form stays ahead, 6.6 vs 7.6;
         // r3_split_min2.log)
-        static const int split_min = diag_env("GNNCCA_GEMM_SPLIT_MIN") ? std::atoi(diag_env("GNNCCA_GEMM_SPLIT_MIN")) : 384;   // diagnostics
+        static const int split_min = diag_env_int("GNNCCA_GEMM_SPLIT_MIN", 384, 0, 0x7FFFFFFF);   // diagnostics
         // round 6: below 4096 nodes the first layer runs on the fp16-split GEMM in 32-row tiles with K split over one round of workgroups
         // (enc_f16_slices.cuh): a fraction of the slabs of the two forms above (dense1024: 8 x 0.5 MB instead of 16 x 0.5 MB written and read
         // back; dense256: 16 instead of 32) and half the matrix work of the six-product form.  nks: at least K / 256, then powers of two
@@ -158,9 +160,8 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         // The minimum K / 256 is taken even where nrt * nks exceeds one round (K = 2048 near N = 4095: 128 x 8 = 1024 workgroups).
         static const int slices_min = diag_env_int("GNNCCA_GEMM_SLICES_MIN", 1, 0, 0x7FFFFFFF);
         static const int slices_max = diag_env_int("GNNCCA_GEMM_SLICES_MAX", 4095, 0, 0x7FFFFFFF);
-        static const bool slices_bf16 = diag_env("GNNCCA_GEMM_BF16") != nullptr;
         const bool use_slices = g == 0 && hdr.enc_w2h != 0 && O == 128 && K >= 64 && (K & (K - 1)) == 0 && K / kF16SlMaxKs <= ws.ksplit && N >= slices_min && N <= slices_max && !split3 &&
-                                !slices_bf16 && (options & GNNCCA_OPT_ENC_UNSPLIT) == 0 && (reinterpret_cast<uintptr_t>(cur_in) & 15) == 0;
+                                !gemm_bf16 && !unsplit && (reinterpret_cast<uintptr_t>(cur_in) & 15) == 0;
         const bool split = !use_slices && g == 0 && hdr.enc_w3 != 0 && N >= split_min && (reinterpret_cast<uintptr_t>(cur_in) & 15) == 0;
         EncPlanParams ep;
         std::memset(&ep, 0, sizeof(ep));
@@ -205,8 +206,7 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
             q.w32 = blob + hdr.enc_node_w[0];
             q.part = part;
             q.M = N, q.K = K, q.nrt = nrt, q.nks = nks, q.Ks = K / nks;
-            static const int sl_force_arm = diag_env_int("GNNCCA_GEMM_F16_ARM", 0, 0, 1);   // diagnostics / tests: every wave on the fp32 arm
-            q.force_arm = sl_force_arm;
+            q.force_arm = f16_force_arm;   // (here: every wave on the fp32 arm)
             EncPlanParams pl = ep;
             int ride = 0;
             if (plan_blocks > 0) {   // the plan rides in this launch (extra workgroups beyond the GEMM tiles)
@@ -232,20 +232,17 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         }
         if (split) {  // big batches: split-bf16 MFMA GEMM; the plan gets its own launch
             const unsigned short* w3 = reinterpret_cast<const unsigned short*>(blob + hdr.enc_w3);
-            static const bool force_direct = diag_env("GNNCCA_GEMM_DIRECT") != nullptr;  // diagnostics: A/B the GEMMs
-            static const bool no_fuse = diag_env("GNNCCA_NO_FUSE") != nullptr;             // A/B against GEMM + tail launch
-            static const int lds_min = diag_env("GNNCCA_GEMM_LDS_MIN") ? std::atoi(diag_env("GNNCCA_GEMM_LDS_MIN")) : 6144;
-            const bool fusable = !no_fuse && !dropping && nl == 2 && d->enc_node.layers[1].in_dim == 128 && d->enc_node.layers[1].out_dim == kH &&
+            static const int lds_min = diag_env_int("GNNCCA_GEMM_LDS_MIN", 6144, 0, 0x7FFFFFFF);   // diagnostics
+            const bool fusable = !dropping && nl == 2 && d->enc_node.layers[1].in_dim == 128 && d->enc_node.layers[1].out_dim == kH &&
                                  !d->reattach_nodes && hdr.proj_wT != 0;
-            const bool use_lds = N >= lds_min && O == 128 && !force_direct;
+            const bool use_lds = N >= lds_min && O == 128;
             if (use_lds) ks_split = std::min(enc_lds_ksplit(N, K), ws.ksplit);
             // mid-size batches, where the 256-row form would run split-K: 32-row workgroups, un-split, fused epilogue (enc_rows32.cuh)
             // GNNCCA_OPT_ENC_UNSPLIT: batches of >= 4096 nodes never split K -- where the 256-row form would, 32-row workgroups run
             // un-split with the same fused epilogue (enc_rows32.cuh), so a node's encoder output is bit for bit independent of the batch
             // around it (a shard of a sharded batch reproduces the union's logits exactly).  Not the default: one wave per SIMD at
             // N <= 8192 (N = 8192: 41-43.5 us against 28 + 9 for split-K + tail; enc_rows32.cuh says where the time goes)
-            static const int r32_nst = diag_env("GNNCCA_GEMM_R32_NST") ? std::atoi(diag_env("GNNCCA_GEMM_R32_NST")) : 0;
-            const bool use_r32 = (options & GNNCCA_OPT_ENC_UNSPLIT) != 0 && fusable && O == 128 && K % 256 == 0 && !force_direct && N >= 4096 &&
+            const bool use_r32 = unsplit && fusable && O == 128 && K % 256 == 0 && N >= 4096 &&
                                  !(use_lds && ks_split == 1);
             if (use_r32) ks_split = 1;
             // round 5: mid-size batches on the fp16-split form take 32-row workgroups that split K over their WAVES and finish the encoder in
@@ -255,24 +252,19 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
             // against 26.6 / 35.0 / 31.2 / 33.0 / 38.3 for the split-K forms; 47.4 against 39.2 at 9216; profiles/r05_logs/ab_r32f_2.log)
             static const int r32f_min = diag_env_int("GNNCCA_GEMM_R32F_MIN", 4096, 0, 0x7FFFFFFF);
             static const int r32f_max = diag_env_int("GNNCCA_GEMM_R32F_MAX", 8192, 0, 0x7FFFFFFF);
-            static const bool gemm_bf16_early = diag_env("GNNCCA_GEMM_BF16") != nullptr;
-            const bool use_r32f = !use_r32 && fusable && O == 128 && K % 256 == 0 && hdr.enc_w2h != 0 && !split3 && !gemm_bf16_early && !force_direct &&
-                                  (options & GNNCCA_OPT_ENC_UNSPLIT) == 0 && N >= r32f_min && N <= r32f_max && !(use_lds && ks_split == 1);
+            const bool use_r32f = !use_r32 && fusable && O == 128 && K % 256 == 0 && hdr.enc_w2h != 0 && !split3 && !gemm_bf16 &&
+                                  !unsplit && N >= r32f_min && N <= r32f_max && !(use_lds && ks_split == 1);
             if (use_r32f) ks_split = 1;
             // un-split and the shipped encoder shape (2048 -> 128 -> 32, no reattach): the rest of the encoder, the step-1
             // projections and the plan fold run in the GEMM's epilogue, on the tile while it is on chip
             fused_tail = (use_lds && fusable && ks_split == 1) || use_r32 || use_r32f;
             EncFuseParams fp;
             std::memset(&fp, 0, sizeof(fp));
-            static const int gemm_x_l2 = diag_env_int("GNNCCA_GEMM_X_L2_ROWS", 0, 1, 256);   // diagnostics: x served from L2 (timing only)
-            fp.diag_x_rows = gemm_x_l2;
-            // k rotation of the big-batch GEMMs (encoder.cuh / enc_f16.cuh): OFF.  A bare streaming loop of this access shape gains 20 % from it
-            // (tools/ubench_xring.hip: 5.0 -> 6.2 TB/s), the kernels themselves 0-3 % at N = 65 536 and LOSE 4 % at 32 768 (their waves are
+            // k rotation of the big-batch GEMMs (every workgroup starting its walk over k at another chunk): NOT done (round 5 measured it and
+            // the code is gone).  A bare streaming loop of this access shape gains 20 % from it (tools/ubench_xring.hip: 5.0 -> 6.2 TB/s), the kernels themselves 0-3 % at N = 65 536 and LOSE 4 % at 32 768 (their waves are
             // not in lockstep across CUs the way the microbenchmark's are; profiles/r05_logs/ab_krot{1,2}.log) -- and it makes a node's encoder
             // output depend on WHICH row block of the batch it sits in (the summation starts elsewhere), which the un-rotated kernels do not
-            // (tests/test_gpu_fuzz.py: 512 copies of one graph, bitwise).  Kept behind GNNCCA_GEMM_KROT=1 for the record.
-            static const bool k_rot = diag_env("GNNCCA_GEMM_KROT") != nullptr;
-            fp.k_rotate = ((options & GNNCCA_OPT_ENC_UNSPLIT) == 0 && k_rot) ? 1 : 0;
+            // (tests/test_gpu_fuzz.py: 512 copies of one graph, bitwise).
             if (fused_tail) {
                 fp.b1 = blob + hdr.enc_node_b[0];
                 fp.W2 = blob + hdr.enc_node_w[1];
@@ -306,8 +298,6 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
             // The fp16-split form (enc_f16.cuh) is the default of the 256-row regime; the bf16 form stays for GNNCCA_OPT_ENC_UNSPLIT (whose
             // bitwise batch independence is stated on the bf16 arithmetic of all three un-split kernels), for GNNCCA_OPT_ENC_SPLIT3 (an option
             // of that form) and as the A/B reference (GNNCCA_GEMM_BF16).  K / ks_split is a multiple of 32 on this path.
-            static const bool gemm_bf16 = diag_env("GNNCCA_GEMM_BF16") != nullptr;
-            static const int f16_force_arm = diag_env_int("GNNCCA_GEMM_F16_ARM", 0, 0, 1);   // diagnostics / tests: every tile on the bf16 arm
             // x stream of the fp16-split GEMMs: NON-TEMPORAL from 128 MB of x on (N >= 16 384 at K = 2048).  Inside a real forward the caches are full
             // of what the previous forward's step kernels left (dirty edge state), and a default-policy x stream fights it for every line: BASELINE
             // config 4 in situ 174 -> 137 us for this launch (0.516 -> 0.485 ms per forward), while an encoder timed alone on clean caches hides
@@ -315,8 +305,8 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
             // (profiles/r05_logs/ab_config4_nt.log).  GNNCCA_GEMM_F16_XNT = 0 / 1 forces it off / on.
             static const int f16_x_nt_force = diag_env_int("GNNCCA_GEMM_F16_XNT", -1, -1, 1);
             const int f16_x_nt = f16_x_nt_force >= 0 ? f16_x_nt_force : ((double)N * K * 4.0 >= 128.0 * 1024 * 1024 ? 1 : 0);
-            const bool use_f16 = use_lds && !use_r32 && !use_r32f && hdr.enc_w2h != 0 && !split3 && (options & GNNCCA_OPT_ENC_UNSPLIT) == 0 && !gemm_bf16 &&
-                                 gemm_x_l2 == 0 && K % 32 == 0 && (K / ks_split) % 32 == 0;
+            const bool use_f16 = use_lds && !use_r32 && !use_r32f && hdr.enc_w2h != 0 && !split3 && !unsplit && !gemm_bf16 &&
+                                 K % 32 == 0 && (K / ks_split) % 32 == 0;
             static thread_local int attr_dev = -1;  // once per device and thread: the attribute is per device
             int dev = 0;
             HIP_TRY(hipGetDevice(&dev));
@@ -324,14 +314,10 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(enc_gemm_f16_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kF16LdsBytes));
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(enc_gemm_f16_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kF16LdsBytes));
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(enc_gemm_f16_rows32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kF16R32LdsBytes));
-                const void* fns[8] = {reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<false, false>),
+                const void* fns[4] = {reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<false, false>),
                                       reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<true, false>),
                                       reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<false, true>),
-                                      reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<true, true>),
-                                      reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<false, false, true>),
-                                      reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<true, false, true>),
-                                      reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<false, true, true>),
-                                      reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<true, true, true>)};
+                                      reinterpret_cast<const void*>(enc_gemm_split_lds_kernel<true, true>)};
                 for (const void* fn : fns)
                     HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsGemmBytes));
                 attr_dev = dev;
@@ -348,13 +334,12 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
                 q.w_bad = reinterpret_cast<const unsigned*>(blob + hdr.enc_w2h_bad);
                 q.w3 = w3;
                 q.M = N, q.K = K, q.kslice = K;
-                q.k_rotate = fp.k_rotate;
-                q.force_arm = f16_force_arm;
+                q.force_arm = f16_force_arm;   // (here and in the 256-row form below: every tile on the bf16 arm)
                 q.x_nt = f16_x_nt;
                 GNNCCA_LAUNCH(enc_gemm_f16_rows32_kernel, dim3((unsigned)((N + 31) / 32) + 1), dim3(kF16R32Threads), kF16R32LdsBytes, st, q, fp);
             } else if (use_r32) {
                 const dim3 rgrid((unsigned)((N + 31) / 32) + 1);
-                const int nst = r32_nst == 4 || r32_nst == 8 ? r32_nst : ((N + 31) / 32 <= 256 ? 8 : 4);
+                const int nst = (N + 31) / 32 <= 256 ? 8 : 4;
                 if (nst == 8 && split3)
                     GNNCCA_LAUNCH((enc_gemm_rows32_fused_kernel<true, 8>), rgrid, dim3(256), 0, st, cur_in, w3, N, K, fp);
                 else if (nst == 8)
@@ -373,22 +358,9 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
                 q.w3 = w3;
                 q.out = part;
                 q.M = N, q.K = K, q.kslice = K / ks_split;
-                q.k_rotate = fp.k_rotate;
                 q.force_arm = f16_force_arm;
-                static const int f16_prio = diag_env_int("GNNCCA_GEMM_F16_PRIO", 0, 0, 1);   // diagnostics: static priority of waves 4-7 (measured: 122.9 vs 121 us at N = 65 536 -- off)
-                q.prio_late_half = f16_prio;
                 q.x_nt = f16_x_nt;
                 const dim3 fgrid((N + 255) / 256 + 1, 1), sgrid((N + 255) / 256, ks_split);
-#ifdef GNNCCA_F16_ABLATIONS
-                static const int f16_diag = diag_env_int("GNNCCA_GEMM_F16_DIAG", 0, 0, 7);
-                if (fused_tail && f16_diag) {
-                    typedef void (*kfn)(const EncF16Params, const EncFuseParams);
-                    static const kfn fns[8] = {nullptr, enc_gemm_f16_fused_diag1_kernel, enc_gemm_f16_fused_diag2_kernel, enc_gemm_f16_fused_diag3_kernel,
-                                               enc_gemm_f16_fused_diag4_kernel, enc_gemm_f16_fused_diag5_kernel, enc_gemm_f16_fused_diag6_kernel, enc_gemm_f16_fused_diag7_kernel};
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fns[f16_diag]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kF16LdsBytes));
-                    GNNCCA_LAUNCH(fns[f16_diag], fgrid, dim3(512), kF16LdsBytes, st, q, fp);
-                } else
-#endif
                 if (fused_tail)
                     GNNCCA_LAUNCH(enc_gemm_f16_fused_kernel, fgrid, dim3(512), kF16LdsBytes, st, q, fp);
                 else
@@ -410,18 +382,7 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
                 // workgroup (one address, eight L2s: 22.9 us) and the release fence in front of it ~95 ns (an L2 write-back each: 117-120 us).
                 // profiles/r04_logs/ab_tailride{1,2,3}.log)
                 const dim3 fgrid((N + 255) / 256 + 1, 1), sgrid((N + 255) / 256, ks_split);
-                static const bool gemm_pipe = diag_env("GNNCCA_GEMM_NOPIPE") == nullptr;   // diagnostics: A/B against the barrier-per-chunk form (encoder.cuh: PIPE)
-                if (gemm_pipe && fused_tail && split3)
-                    GNNCCA_LAUNCH((enc_gemm_split_lds_kernel<true, true, true>), fgrid, dim3(512), kLdsGemmBytes, st, cur_in, w3, part, N, K, O, K, fp);
-                else if (gemm_pipe && fused_tail)
-                    GNNCCA_LAUNCH((enc_gemm_split_lds_kernel<true, false, true>), fgrid, dim3(512), kLdsGemmBytes, st, cur_in, w3, part, N, K, O, K, fp);
-                else if (gemm_pipe && split3)
-                    GNNCCA_LAUNCH((enc_gemm_split_lds_kernel<false, true, true>), sgrid, dim3(512), kLdsGemmBytes, st, cur_in, w3, part, N, K, O,
-                                  K / ks_split, fp);
-                else if (gemm_pipe)
-                    GNNCCA_LAUNCH((enc_gemm_split_lds_kernel<false, false, true>), sgrid, dim3(512), kLdsGemmBytes, st, cur_in, w3, part, N, K, O,
-                                  K / ks_split, fp);
-                else if (fused_tail && split3)
+                if (fused_tail && split3)
                     GNNCCA_LAUNCH((enc_gemm_split_lds_kernel<true, true>), fgrid, dim3(512), kLdsGemmBytes, st, cur_in, w3, part, N, K, O, K, fp);
                 else if (fused_tail)
                     GNNCCA_LAUNCH((enc_gemm_split_lds_kernel<true, false>), fgrid, dim3(512), kLdsGemmBytes, st, cur_in, w3, part, N, K, O, K, fp);
@@ -433,14 +394,12 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
                                   K / ks_split, fp);
             } else {
                 // 128-row workgroups (a wave = 32 rows x 128 columns); split-K until >= 512 workgroups are in flight
-                static const int direct_wg = diag_env("GNNCCA_GEMM_DIRECT_WG") ? std::atoi(diag_env("GNNCCA_GEMM_DIRECT_WG")) : 512;   // diagnostics
-                while (ks_split < ws.ksplit && ((N + 127) / 128) * ks_split < direct_wg && (K / (ks_split * 2)) % 32 == 0) ks_split *= 2;
+                while (ks_split < ws.ksplit && ((N + 127) / 128) * ks_split < 512 && (K / (ks_split * 2)) % 32 == 0) ks_split *= 2;
                 const int rb = (N + 127) / 128;
                 // the plan rides in this launch (extra workgroups beyond the GEMM tiles)
                 EncPlanParams pl = ep;
                 int ride = 0;
-                static const bool no_ride_d = diag_env("GNNCCA_NO_RIDE") != nullptr;   // diagnostics: A/B against a plan launch of its own
-                if (plan_blocks > 0 && (N < 4096 || !no_ride_d)) {
+                if (plan_blocks > 0) {
                     pl.plan_span = plan_span(edge_index, E);   // narrow (0) or pair form by the edge count and alignment
                     ride = pl.plan_span > 1 ? (plan_blocks + pl.plan_span - 1) / pl.plan_span : plan_blocks;
                     plan_launched = true;
@@ -528,11 +487,10 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         if (fused_tail) {
             // nothing: h0, the projections and the plan's flag word all came out of the GEMM launch
         } else if (tail_fast) {
-            static const int tail_npw = diag_env("GNNCCA_TAIL_NPW") ? std::atoi(diag_env("GNNCCA_TAIL_NPW")) : 0;   // diagnostics
             // nodes per workgroup: one up to 320 nodes, two up to 640, four beyond (a block of 200 forwards in one HIP graph: dense256 28.07 ->
             // 27.4 us per forward with one, dense64 24.7 -> 24.1; dense512 39.97 -> 39.5-39.8 with two; dense1024 best with four;
             // profiles/r03_logs/r3_tailnpw1.log)
-            tp.npw = tail_npw == 1 || tail_npw == 2 || tail_npw == 4 ? tail_npw : (N <= 320 ? 1 : (N <= 640 ? 2 : 4));
+            tp.npw = N <= 320 ? 1 : (N <= 640 ? 2 : 4);
             const unsigned fblocks = (unsigned)std::min<size_t>(((size_t)N + tp.npw - 1) / tp.npw, 2048) + 1;
             GNNCCA_LAUNCH(enc_tail_fast_kernel, dim3(fblocks), dim3(256), 0, st, tp);
         }
@@ -575,9 +533,8 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
     sp.off_cb2 = hdr.cls_b2;
     sp.off_fast = hdr.fast_consts;
     sp.off_wnebf = hdr.wne_bf16;
-    static const bool step_r2 = diag_env("GNNCCA_STEP_R2") != nullptr;   // diagnostics: A/B against round 2's step kernel
     // which arithmetic the node message uses (StepParams::msg_f32): the traced (general) and the fast kernels follow ONE rule
-    sp.msg_f32 = (N <= 512 || step_r2 || !step_pipe_fits(N, E, ws.e_stride, ws.total)) ? 1 : 0;
+    sp.msg_f32 = (N <= 512 || !step_pipe_fits(N, E, ws.e_stride, ws.total)) ? 1 : 0;
     sp.cls_hidden = hdr.cls_hidden;
     sp.N = N;
     sp.E = E;
@@ -600,7 +557,7 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         // cross-wave combine sums in another order with another wave count, and `want` above depends on N (a shard of 2 x dense2048
         // would get four waves per node, the union of 8 one), so the option pins one wave per node there, the rule of every round
         // before the four-wave one (tests/test_gpu_sharded.py: dense2048 shard against its union, bitwise)
-        if ((options & GNNCCA_OPT_ENC_UNSPLIT) != 0 && N >= 4096) wps = 1;
+        if (unsplit && N >= 4096) wps = 1;
         static const int force_wps = diag_env_int("GNNCCA_WPS", 0, 1, 4);  // diagnostics
         if (force_wps == 1 || force_wps == 2 || force_wps == 4) wps = std::min(force_wps, chunks >= 4 ? 4 : (chunks >= 2 ? 2 : 1));
         sp.wps = wps;
@@ -612,16 +569,13 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         // (profiles/r04_logs/ab_npw{6,7}.log), so one threshold serves both
         static const int npw_min_n = diag_env_int("GNNCCA_NPW_MIN_N", 16384, 0, 0x7FFFFFFF);
         static const int npw_min_n_first = diag_env_int("GNNCCA_NPW_MIN_N_FIRST", 16384, 0, 0x7FFFFFFF);
-        static const int npw_max_chunks = diag_env_int("GNNCCA_NPW_MAX_CHUNKS", 2, 1, 64);   // diagnostics: average 64-edge chunks per node up to which it is used
-        npw_later = (wps == 1 && chunks <= npw_max_chunks && (force_npw == 2 || (force_npw == 0 && N >= npw_min_n))) ? 2 : 1;
+        npw_later = (wps == 1 && chunks <= 2 && (force_npw == 2 || (force_npw == 0 && N >= npw_min_n))) ? 2 : 1;
         npw_first = (npw_later == 2 && (force_npw == 2 || N >= npw_min_n_first)) ? 2 : 1;
         sp.npw = npw_later;
     }
     sp.hin = hin;
     // column ranges instead of the col32 stream on steps 2 ... L of the specialised kernels (StepParams::rng)
-    static const bool step_norange = diag_env("GNNCCA_STEP_NORANGE") != nullptr;   // diagnostics: A/B against streaming col32 on every step
-    static const int range_max_e = diag_env_int("GNNCCA_RANGE_MAX_E", 0x7FFFFFFF, 0, 0x7FFFFFFF);   // diagnostics: edge count up to which the buffer-addressed kernel uses them
-    sp.rng = (L >= 2 && !step_norange && (options & GNNCCA_OPT_COLUMN_RANGES) != 0 && (sp.msg_f32 || E <= range_max_e)) ? reinterpret_cast<int*>(base + ws.rng) : nullptr;
+    sp.rng = (L >= 2 && (options & GNNCCA_OPT_COLUMN_RANGES) != 0) ? reinterpret_cast<int*>(base + ws.rng) : nullptr;
     sp.ws_base = base;
     sp.ws_bytes = ws.total;
     sp.so_e = (unsigned)ws.e, sp.so_col = (unsigned)ws.col32, sp.so_perm = (unsigned)ws.perm;
@@ -638,10 +592,9 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
     sp.ell_S = use_ell ? ws.ell_S : 0;
     sp.drop = drop;
     {
-        static const bool no_nt = diag_env("GNNCCA_NO_NT") != nullptr;  // diagnostics: A/B the cache policy
         const double state_bytes = (double)(sp.e_bf16 ? kEF / 2 : kEF) * (double)ws.e_stride * 4.0;
-        sp.nt_store = !no_nt && state_bytes > 150e6;
-        sp.nt_load = !no_nt && state_bytes > 256e6;
+        sp.nt_store = state_bytes > 150e6;
+        sp.nt_load = state_bytes > 256e6;
         static const int force_nt = diag_env_int("GNNCCA_STEP_NT", -1, -1, 2);   // diagnostics: 0 / 1 / 2 = default policy / nt stores / nt loads too
         if (force_nt >= 0) sp.nt_store = force_nt >= 1, sp.nt_load = force_nt >= 2;
     }
@@ -661,10 +614,9 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
     // the state back does (the last step: its input and its output).  The classifying message steps then run the variant without the
     // classifier -- lighter, and eligible for two nodes per wave.  Where it pays: forwards whose message steps run two nodes per wave
     // (sp.npw == 2); fp32 edge state only (the bf16 state is rounded after its step classified it); logits bit for bit the same.
-    static const int force_defer = diag_env_int("GNNCCA_DEFER_CLS", -1, 0, 1);   // diagnostics: 0 / 1 = never / whenever possible
     const bool can_defer = hdr.fast_consts != 0 && sp.attr_vec && !trace && d->agg != GNNCCA_AGG_MAX && !sp.msg_f32 && !sp.e_bf16 && !sp.pd_lds &&
                            sp.rng == nullptr && first_cls < L && !dropping;
-    const bool defer = can_defer && (force_defer == 1 || (force_defer != 0 && npw_later == 2));
+    const bool defer = can_defer && npw_later == 2;
     for (int step = 1; step <= L; ++step) {
         const bool want_h = trace && trace->h_steps;
         const bool msg = step < L || want_h;
@@ -694,11 +646,7 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
         sp.trace_h = want_h ? trace->h_steps + (size_t)(step - 1) * N * kH : nullptr;
         hipError_t err;
         const bool fast = hdr.fast_consts != 0 && sp.attr_vec && !trace && d->agg != GNNCCA_AGG_MAX;
-        static const bool step_nomem = diag_env("GNNCCA_STEP_NOMEM") != nullptr;   // diagnostics: arithmetic-only timing of the step kernel
-        static const bool step_noepi = diag_env("GNNCCA_STEP_NOEPI") != nullptr;   // diagnostics: what the projection epilogue costs
-        static const bool step_nohook = diag_env("GNNCCA_STEP_NOHOOK") != nullptr;   // diagnostics: second round's state requested after the first round
-        static const bool step_earlybar = diag_env("GNNCCA_STEP_EARLYBAR") != nullptr;   // diagnostics: the staging barrier in front of the loop even with several waves per node
-        sp.diag = (step_nomem ? 1 : 0) | (step_noepi ? 2 : 0) | (step_nohook ? 4 : 0) | (step_earlybar ? 8 : 0);
+        sp.diag = 0;   // nothing sets its bits any more; the step kernels keep the field for their register allocation (StepParams::diag)
         const bool pipe_ok = fast && !sp.msg_f32;
         if (pipe_ok)
             err = launch_pipe_dispatch(sp, msg, st);

@@ -696,9 +696,8 @@ int64_t gnncca_post_pool_submit_copy(gnncca_post_pool* pool, const gnncca_post_b
         std::lock_guard<std::mutex> g(pool->m);
         if (!pool->free_events.empty()) j->e_copy = pool->free_events.back(), pool->free_events.pop_back();
     }
-    // (e_copy is what a pool thread waits on: GNNCCA_POOL_BLOCKING=1 under GNNCCA_DIAG makes that wait a sleep instead of a spin)
-    static const bool blocking = gnncca::diag_env("GNNCCA_POOL_BLOCKING") != nullptr;
-    if (!j->e_copy && hipEventCreateWithFlags(&j->e_copy, hipEventDisableTiming | (blocking ? hipEventBlockingSync : 0)) != hipSuccess)
+    // (e_copy is what a pool thread waits on: an event without hipEventBlockingSync, so that wait is a spin, not a sleep)
+    if (!j->e_copy && hipEventCreateWithFlags(&j->e_copy, hipEventDisableTiming) != hipSuccess)
         return -(int64_t)GNNCCA_ERR_HIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (hipMemcpyAsync(host_dst, device_src, nbytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(j->e_copy, st) != hipSuccess) {

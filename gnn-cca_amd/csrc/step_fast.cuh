@@ -348,8 +348,8 @@ __global__ __launch_bounds__(256) GNNCCA_FAST_ATTR void mpn_step_fast_kernel(con
     // s_proj or s_part, and no wave returns or skips that barrier (the BAD_INDEX return above is block-uniform and precedes the stores).
     // With several waves per node the cross-wave combine's barrier is therefore the one that publishes s_proj to the epilogue, its only
     // reader, and no early barrier is needed unless the gathers read s_pd.  A new LDS read in between, or a per-wave early exit, turns
-    // this into a silent race: GNNCCA_STEP_EARLYBAR (diag bit 3) restores the early barrier to bisect such a change.
-    if (PD_LDS || (MSG && (wps == 1 || (p.diag & 8)))) __syncthreads();   // (diag bit 3: A/B with the early barrier of rounds 1-2)
+    // this into a silent race (to bisect such a change, make the barrier below unconditional: the early barrier of rounds 1-2).
+    if (PD_LDS || (MSG && (wps == 1 || (p.diag & 8)))) __syncthreads();   // (p.diag: always 0, see StepParams)
     GNNCCA_STAMP(p.stamp_slot, 2);
     auto round_body = [&](int rb, Chunk& a, Chunk& b, bool requested = false) {
         if (!requested) {

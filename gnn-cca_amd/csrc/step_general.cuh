@@ -69,8 +69,9 @@ struct StepParams {
     unsigned long long ws_bytes;
     unsigned so_e, so_col, so_perm, so_pd;
     int npw;                 // nodes per wave of mpn_step_pipe_kernel's message steps: 1, or 2 (step_pipe.cuh: NPW)
-    int diag;                // GNNCCA_DIAG experiments (0 in production): bit 0 = timing-only run of mpn_step_pipe_kernel with
-                             // zero-record stream descriptors (no HBM traffic: what the arithmetic alone costs)
+    int diag;                // always 0.  Four bits of retired timing experiments that mpn_step_pipe_kernel (and, one of them,
+                             // mpn_step_fast_kernel) still test: without them the two-node pipe variants, which sit at the 126-128 VGPR
+                             // line, allocate more registers and scratch, and step 1 of the bf16-state fast kernel spills 20 more SGPRs
 };
 
 template <bool REATT_E, bool MSG, bool AGG_MAX>

@@ -16,7 +16,7 @@ namespace gnncca {
 //     accumulate of a finished tile); three accumulator tiles rotate.  __builtin_amdgcn_sched_barrier keeps hipcc from
 //     regrouping; the empty asm statements in `ra` pin pure arithmetic that instruction selection would otherwise sink.
 // Work split, LDS tables, prefetch of the first two rounds, cross-wave combine, projection epilogue and cache policies
-// are mpn_step_fast_kernel's of round 2 (step_fast.cuh, kept as the A/B reference behind GNNCCA_DIAG).
+// are mpn_step_fast_kernel's of round 2 (step_fast.cuh).
 // ------------------------------------------------------------------------------------------------------------
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSG ? (NPW 
     int eoff = padded ? nclamp * p.ell_S - seg_s : 0;
     const int eoff2 = (NPW == 2 && padded) ? (node + 1) * p.ell_S - seg_t : 0;   // the second node's
     const unsigned plane_b = (unsigned)p.e_stride * 4u;                       // bytes between two feature planes
-    const unsigned long long live = (p.diag & 1) ? 0ull : 1ull;               // timing-only diagnostic: every stream descriptor empty
+    const unsigned long long live = (p.diag & 1) ? 0ull : 1ull;               // (p.diag: always 0, see StepParams)
     // ONE descriptor for everything this kernel streams out of the forward's workspace -- edge state, target ids, permutation, P_dst
     // table -- with the region's byte offset as the scalar offset of each access (round 4; rounds 1-3 kept a descriptor per buffer:
     // 16 SGPRs where 4 + 3 do, in a kernel whose scalar file is full -- hipcc spills SGPRs into VGPR lanes with v_writelane /
@@ -219,8 +219,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSG ? (NPW 
     // s_proj or s_part, and no wave returns or skips that barrier (the BAD_INDEX return above is block-uniform and precedes the stores).
     // With several waves per node the cross-wave combine's barrier is therefore the one that publishes s_proj to the epilogue, its only
     // reader, and no early barrier is needed unless the gathers read s_pd.  A new LDS read in between, or a per-wave early exit, turns
-    // this into a silent race: GNNCCA_STEP_EARLYBAR (diag bit 3) restores the early barrier to bisect such a change.
-    if (PD_LDS || (MSG && (wps == 1 || (p.diag & 8)))) __syncthreads();   // (diag bit 3: A/B with the early barrier of rounds 1-2)
+    // this into a silent race (to bisect such a change, make the barrier below unconditional: the early barrier of rounds 1-2).
+    if (PD_LDS || (MSG && (wps == 1 || (p.diag & 8)))) __syncthreads();   // (p.diag: always 0, see StepParams)
     GNNCCA_STAMP(p.stamp_slot, 2);
     auto round_compute = [&](int rb, Chunk& a, Chunk& b) {
         if (rb + stride < seg_t) {
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSG ? (NPW 
             if (d_nb > 1) atomicOr(p.flags + 1, 1u);   // not two runs: every later step of this forward streams col32
         }
         GNNCCA_STAMP(p.stamp_slot, 6);
-        if (active && sub == 0 && !(p.diag & 2)) {   // (diag bit 1: timing-only run without the projection epilogue)
+        if (active && sub == 0 && !(p.diag & 2)) {   // (p.diag: always 0)
             const int deg = seg_t - seg_s;
             if (p.agg == GNNCCA_AGG_MEAN) v = v / (float)max(deg, 1);
             if (deg == 0) v = 0.f;
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSG ? (NPW 
             round_compute(seg_s, n0, n1);
             base = seg_s + 2 * stride;
         } else {
-            const bool use_hook = !PD_LDS && base2 < seg_t && base + stride < seg_t && !(p.diag & 4);   // (diag bit 2: A/B without it)
+            const bool use_hook = !PD_LDS && base2 < seg_t && base + stride < seg_t && !(p.diag & 4);   // (p.diag: always 0)
             if (!PD_LDS) {
                 load_index(base2, n0);
                 load_index(base2 + stride, n1);
