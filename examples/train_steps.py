@@ -63,6 +63,15 @@ def run(title, params, steps=30):
     print(f"{title}: engine = {model._train_path}, loss {losses[0]:.4f} -> {losses[-1]:.4f}, {(time.perf_counter() - t0) / 20 * 1e3:.2f} ms per "
           f"training step (N = {batch.x.shape[0]}, E = {batch.edge_index.shape[1]}, replayed HIP graph)")
     assert losses[-1] < losses[0]
+    # inputs that require grad receive theirs: a small projection in front of the MPN (a ReID head, say) trains through the same loss
+    # (both figures are zero when the ReLUs of the node path have died, which un-scaled 'sum' aggregation does to random weights)
+    head = torch.nn.Linear(256, 2048).cuda()
+    proj = Batch()
+    proj.x, proj.edge_index, proj.edge_attr = 0.05 * head(torch.randn(batch.x.shape[0], 256, device="cuda")), batch.edge_index, batch.edge_attr
+    model.zero_grad(set_to_none=True)
+    loss_fn(model(proj), labels).backward()
+    print(f"{title}: a projection in front of the MPN receives max|d loss / d head.weight| = {float(head.weight.grad.abs().max()):.3e} "
+          f"(first encoder layer: {float(model.encoder.node_mlp.fc_layers[0].weight.grad.abs().max()):.3e})")
 
 
 if __name__ == "__main__":

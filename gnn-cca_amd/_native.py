@@ -66,6 +66,11 @@ class Dropout(C.Structure):
     _fields_ = [("p_enc", C.c_float), ("p_edge", C.c_float), ("p_node", C.c_float), ("p_cls", C.c_float), ("seed_dev", C.c_void_p)]
 
 
+class InputGrads(C.Structure):
+    """gnncca_input_grads (include/gnncca_mpn.h): where d loss / d x and d loss / d edge_attr go; a null member is not computed."""
+    _fields_ = [("dx", C.c_void_p), ("d_edge_attr", C.c_void_p)]
+
+
 OPT_EDGE_STATE_BF16 = 1
 OPT_ENC_SPLIT3 = 2
 OPT_ENC_UNSPLIT = 4
@@ -140,6 +145,9 @@ _SIGNATURES = {
     "gnncca_mpn_backward_train": (C.c_int, [C.POINTER(MpnDims), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int64, C.c_int64, C.POINTER(Trace), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                             C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(Dropout), C.c_void_p]),
+    "gnncca_mpn_backward_inputs": (C.c_int, [C.POINTER(MpnDims), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_int64, C.POINTER(Trace), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                             C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(Dropout), C.POINTER(InputGrads), C.c_void_p]),
     "gnncca_mlp_eval_workspace_bytes": (C.c_size_t, [C.POINTER(Mlp), C.c_int64]),
     "gnncca_mlp_eval": (C.c_int, [C.POINTER(Mlp), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),
@@ -155,6 +163,9 @@ _SIGNATURES = {
     "gnncca_train_backward": (C.c_int, [C.POINTER(MpnDims), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p),
                                         C.POINTER(Dropout), C.c_void_p]),
+    "gnncca_train_backward_inputs": (C.c_int, [C.POINTER(MpnDims), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p),
+                                               C.POINTER(Dropout), C.POINTER(InputGrads), C.c_void_p]),
     "gnncca_normalize_columns2": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gnncca_frames_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "gnncca_plan_frames_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),

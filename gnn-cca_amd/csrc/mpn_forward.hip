@@ -31,6 +31,7 @@
 #include "generic.cuh"
 #include "postprocess.cuh"
 #include "backward.cuh"
+#include "input_grads.cuh"
 #include "pack_device.cuh"
 #include "train_generic.cuh"
 
@@ -761,9 +762,18 @@ int gnncca_train_forward(const gnncca_mpn_dims* d, float* const* params_dev, int
 int gnncca_train_backward(const gnncca_mpn_dims* d, float* const* params_dev, int n_params, const float* x, const int64_t* edge_index,
                           const float* edge_attr, int64_t n_nodes, int64_t n_edges, void* tape, size_t tape_bytes,
                           const float* grad_logits, float* const* grads_dev, const gnncca_dropout* dropout, gnncca_stream_t stream) {
+    return gnncca_train_backward_inputs(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, tape, tape_bytes, grad_logits,
+                                        grads_dev, dropout, nullptr, stream);
+}
+
+int gnncca_train_backward_inputs(const gnncca_mpn_dims* d, float* const* params_dev, int n_params, const float* x,
+                                 const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges, void* tape,
+                                 size_t tape_bytes, const float* grad_logits, float* const* grads_dev, const gnncca_dropout* dropout,
+                                 const gnncca_input_grads* input_grads, gnncca_stream_t stream) {
     if (!x || (n_edges > 0 && (!edge_index || !edge_attr))) return GNNCCA_ERR_INVALID_ARG;
     return train_backward_impl(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, tape, tape_bytes, grad_logits,
-                               grads_dev, dropout, static_cast<hipStream_t>(stream));
+                               grads_dev, dropout, input_grads ? input_grads->dx : nullptr,
+                               input_grads ? input_grads->d_edge_attr : nullptr, static_cast<hipStream_t>(stream));
 }
 
 int gnncca_mpn_forward_profiled(const gnncca_mpn_dims* d, const void* packed_dev, const float* x,
@@ -1165,6 +1175,17 @@ int gnncca_mpn_backward_train(const gnncca_mpn_dims* d, const float* const* para
                               const gnncca_trace* saved, const float* cls_bn_stat, const float* grad_logits,
                               float* const* grads_dev, void* workspace, size_t workspace_bytes, uint32_t options,
                               const gnncca_dropout* dropout, gnncca_stream_t stream) {
+    return gnncca_mpn_backward_inputs(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, saved, cls_bn_stat,
+                                      grad_logits, grads_dev, workspace, workspace_bytes, options, dropout, nullptr, stream);
+}
+
+int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* x,
+                               const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
+                               const gnncca_trace* saved, const float* cls_bn_stat, const float* grad_logits,
+                               float* const* grads_dev, void* workspace, size_t workspace_bytes, uint32_t options,
+                               const gnncca_dropout* dropout, const gnncca_input_grads* input_grads, gnncca_stream_t stream) {
+    float* const dx_out = input_grads ? input_grads->dx : nullptr;
+    float* const dattr_out = input_grads ? input_grads->d_edge_attr : nullptr;
     DropCfg drop;
     {
         const int ds = drop_cfg(dropout, &drop);
@@ -1193,7 +1214,10 @@ int gnncca_mpn_backward_train(const gnncca_mpn_dims* d, const float* const* para
                     for (int k = 0; k < 4; ++k) HIP_TRY(hipMemsetAsync(grads_dev[pi++], 0, (size_t)m->layers[l].out_dim * 4, st));
             }
     }
-    if (N == 0 || E == 0) return GNNCCA_OK;
+    if (N == 0 || E == 0) {   // no edge, no logit: nothing reaches either input
+        if (dx_out && N > 0) HIP_TRY(hipMemsetAsync(dx_out, 0, (size_t)N * D * 4, st));
+        return GNNCCA_OK;
+    }
     if (!x || !edge_index || !edge_attr || !saved || !saved->h_enc || !saved->e_enc || !saved->h_steps || !saved->e_steps ||
         !grad_logits || !workspace)
         return GNNCCA_ERR_INVALID_ARG;
@@ -1380,6 +1404,13 @@ int gnncca_mpn_backward_train(const gnncca_mpn_dims* d, const float* const* para
                        gz1, N, kH, F1, enc_scale);
     HIP_TRY(launch_outer(gz1, F1, x, D, gW1, D, gb1, N, F1, D, st));
     HIP_TRY(hipGetLastError());
+    // ---- inputs (only what the caller asked for) ----------------------------------------------------------------------
+    if (dattr_out) {
+        hipLaunchKernelGGL(bwd_edge_attr_kernel, grid1((size_t)E * A, 256), dim3(256), 0, st, ge_in, saved->e_enc, params_dev[4],
+                           dattr_out, A, (long long)E, enc_scale);
+        HIP_TRY(hipGetLastError());
+    }
+    if (dx_out) HIP_TRY(launch_dx(gz1, W1, dx_out, N, F1, D, st));
     return GNNCCA_OK;
 }
 

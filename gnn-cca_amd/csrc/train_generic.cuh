@@ -498,8 +498,10 @@ static int tr_mlp_forward(const TrCtx& c, const TrCall& call, const float* xin, 
 
 // backward of one MLP call.  `g` = d loss / d output ([M][out], overwritten); `gbuf` two scratch buffers of at least M x the
 // widest layer; d input goes to *dx ([M][in], one of the scratch buffers or g itself for an empty MLP) when want_dx.
+// `dx_out` (optional, [M][in]): where the first layer writes d input instead of a scratch buffer -- the encoders' inputs are
+// wider than any scratch buffer, and their gradients are the caller's (gnncca_input_grads).
 static int tr_mlp_backward(const TrCtx& c, const TrCall& call, const float* xin, float* g, float* gbuf0, float* gbuf1, bool want_dx,
-                           float** dx) {
+                           float** dx, float* dx_out = nullptr) {
     const gnncca_mlp& mlp = mlp_by_index(c.d, call.mlp);
     const long long M = call.M;
     const float p = c.p_of(call.mlp);
@@ -530,10 +532,14 @@ static int tr_mlp_backward(const TrCtx& c, const TrCall& call, const float* xin,
                 HIP_TRY(launch_outer(cur, O, X, K, c.grads[pi], K, c.grads[pi + 1], (int)M, O, K, c.st));
             }
             if (l > 0 || want_dx) {
-                float* nxt = cur == gbuf0 ? gbuf1 : gbuf0;
-                hipLaunchKernelGGL(tr_matmul_kernel, grid1((size_t)M * K, 256), dim3(256), 0, c.st, (const float*)cur,
-                                   (const float*)c.params[pi], nxt, M, O, K);
-                HIP_TRY(hipGetLastError());
+                float* nxt = (l == 0 && dx_out) ? dx_out : (cur == gbuf0 ? gbuf1 : gbuf0);
+                if (l == 0 && call.mlp == 0) {   // d x of the node encoder ([N][node_in]): the matrix pipe (input_grads.cuh)
+                    HIP_TRY(launch_dx(cur, c.params[pi], nxt, M, O, K, c.st));
+                } else {
+                    hipLaunchKernelGGL(tr_matmul_kernel, grid1((size_t)M * K, 256), dim3(256), 0, c.st, (const float*)cur,
+                                       (const float*)c.params[pi], nxt, M, O, K);
+                    HIP_TRY(hipGetLastError());
+                }
                 cur = nxt;
             }
         }
@@ -671,12 +677,16 @@ static int train_forward_impl(const gnncca_mpn_dims* d, float* const* params, in
 
 static int train_backward_impl(const gnncca_mpn_dims* d, float* const* params, int n_params, const float* x, const int64_t* edge_index,
                                const float* edge_attr, int64_t n_nodes, int64_t n_edges, void* tape, size_t tape_bytes,
-                               const float* grad_logits, float* const* grads, const gnncca_dropout* dropout, hipStream_t st) {
+                               const float* grad_logits, float* const* grads, const gnncca_dropout* dropout, float* dx_out,
+                               float* dattr_out, hipStream_t st) {
     TrPlan P;
     int s = tr_prepare(d, params, n_params, n_nodes, n_edges, tape, tape_bytes, &P);
     if (s != GNNCCA_OK) return s;
     if (!grads) return GNNCCA_ERR_INVALID_ARG;
-    if (n_edges == 0) return GNNCCA_OK;   // no edge, no logit: nothing reaches any parameter (an empty grad_logits may be a null pointer)
+    if (n_edges == 0) {   // no edge, no logit: nothing reaches any parameter or input (an empty grad_logits may be a null pointer)
+        if (dx_out && n_nodes > 0) HIP_TRY(hipMemsetAsync(dx_out, 0, (size_t)n_nodes * d->node_in * 4, st));
+        return GNNCCA_OK;
+    }
     if (!grad_logits) return GNNCCA_ERR_INVALID_ARG;
     TrCtx c;
     c.d = d, c.P = &P, c.base = static_cast<char*>(tape), c.params = params, c.grads = grads, c.drop = tr_dropcfg(dropout), c.st = st;
@@ -784,18 +794,22 @@ static int train_backward_impl(const gnncca_mpn_dims* d, float* const* params, i
     hipLaunchKernelGGL(bwd_add_kernel, grid1((size_t)N * H, 256), dim3(256), 0, st, dh, (const float*)dh0, (long long)N * H);
     hipLaunchKernelGGL(bwd_add_kernel, grid1((size_t)E * EF, 256), dim3(256), 0, st, de, (const float*)de0, (long long)E * EF);
     HIP_TRY(hipGetLastError());
-    // encoders (no gradient flows into x / edge_attr)
+    // encoders; d x / d edge_attr only where the caller asked (a configuration without an encoder passes the latent gradient through)
     if (d->enc_edge.n_layers > 0) {
         float* g = gE0;
         HIP_TRY(hipMemcpyAsync(g, de, (size_t)E * EF * 4, hipMemcpyDeviceToDevice, st));
-        s = tr_mlp_backward(c, P.enc_edge, edge_attr, g, gE0, gE1, false, nullptr);
+        s = tr_mlp_backward(c, P.enc_edge, edge_attr, g, gE0, gE1, dattr_out != nullptr, nullptr, dattr_out);
         if (s != GNNCCA_OK) return s;
+    } else if (dattr_out) {
+        HIP_TRY(hipMemcpyAsync(dattr_out, de, (size_t)E * EF * 4, hipMemcpyDeviceToDevice, st));
     }
     if (d->enc_node.n_layers > 0) {
         float* g = gN0;
         HIP_TRY(hipMemcpyAsync(g, dh, (size_t)N * H * 4, hipMemcpyDeviceToDevice, st));
-        s = tr_mlp_backward(c, P.enc_node, x, g, gN0, gN1, false, nullptr);
+        s = tr_mlp_backward(c, P.enc_node, x, g, gN0, gN1, dx_out != nullptr, nullptr, dx_out);
         if (s != GNNCCA_OK) return s;
+    } else if (dx_out) {
+        HIP_TRY(hipMemcpyAsync(dx_out, dh, (size_t)N * H * 4, hipMemcpyDeviceToDevice, st));
     }
     return GNNCCA_OK;
 }

@@ -13,6 +13,7 @@ import ctypes as C
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .mlp import MLP
@@ -200,8 +201,11 @@ class _HotState:
 
 class _MPNTrainFunction(torch.autograd.Function):
     """Autograd bridge for train mode: forward = the traced HIP forward (it saves the latents the
-    backward needs), backward = gnncca_mpn_backward.  Gradients flow to the module's parameters only (the reference
-    computes the node features under torch.no_grad(), train.py:248-253, so d/dx is never asked for)."""
+    backward needs), backward = gnncca_mpn_backward_inputs.  Gradients flow to the module's parameters and, where the caller's
+    tensors require grad, to ``x`` and ``edge_attr`` as on the reference (its own training loop computes the node features under
+    torch.no_grad(), train.py:248-253, and so never asks; a ReID head or a learned edge feature in front of the module does).
+    Nothing is allocated or launched for an input that does not require grad; ``edge_index`` has no gradient; the backward is
+    differentiable once (double backward raises torch's error)."""
 
     @staticmethod
     def forward(ctx, module, x, edge_index, edge_attr, *params):
@@ -235,6 +239,7 @@ class _MPNTrainFunction(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_out):
         x, edge_index, edge_attr, h_enc, e_enc, h_steps, e_steps, bn_stat = ctx.saved_tensors[:8]
         params = ctx.saved_tensors[8:]
@@ -242,7 +247,7 @@ class _MPNTrainFunction(torch.autograd.Function):
         lib, d = nat.lib(), module.native_dims()
         dev = x.device
         n, e = x.shape[0], edge_index.shape[1]
-        g = grad_out.reshape(grad_out.shape[0], -1).float().contiguous()
+        g = grad_out.reshape(grad_out.shape[0], e).float().contiguous()   # [n_out][E] (E may be 0)
         # every gradient is a view of ONE flat buffer cleared by a single fill (GNNCCA_BWD_GRADS_ZEROED)
         offs, total = [], 0
         for p in params:
@@ -254,20 +259,34 @@ class _MPNTrainFunction(torch.autograd.Function):
         gp = (C.c_void_p * len(params))(*[t.data_ptr() for t in grads])
         ws = torch.empty(lib.gnncca_backward_workspace_bytes(C.byref(d), n, e) + 256, dtype=torch.uint8, device=dev)
         saved = nat.Trace(h_enc.data_ptr(), e_enc.data_ptr(), h_steps.data_ptr(), e_steps.data_ptr())
+        dx, dea, ig = _input_grad_buffers(ctx, x, edge_attr)
         with torch.cuda.device(dev):
-            st = lib.gnncca_mpn_backward_train(C.byref(d), pp, len(params), x.data_ptr(), edge_index.data_ptr(),
-                                               edge_attr.data_ptr(), n, e, C.byref(saved),
-                                               bn_stat.data_ptr() if ctx.has_bn else None, g.data_ptr(), gp, ws.data_ptr(),
-                                               ws.numel(), nat.BWD_GRADS_ZEROED,
-                                               C.byref(ctx.drop) if ctx.drop is not None else None, _raw_stream(dev))
+            st = lib.gnncca_mpn_backward_inputs(C.byref(d), pp, len(params), x.data_ptr(), edge_index.data_ptr(),
+                                                edge_attr.data_ptr(), n, e, C.byref(saved),
+                                                bn_stat.data_ptr() if ctx.has_bn else None, g.data_ptr(), gp, ws.data_ptr(),
+                                                ws.numel(), nat.BWD_GRADS_ZEROED,
+                                                C.byref(ctx.drop) if ctx.drop is not None else None, ig, _raw_stream(dev))
         nat.check(st, "gnncca_mpn_backward")
-        return (None, None, None, None, *[gr if p.requires_grad else None for gr, p in zip(grads, params)])
+        return (None, dx, None, dea, *[gr if p.requires_grad else None for gr, p in zip(grads, params)])
+
+
+def _input_grad_buffers(ctx, x, edge_attr):
+    """(dx, d_edge_attr, gnncca_input_grads or None) of one backward: a buffer only for an input that requires grad (slots 1 and 3 of
+    the bridges' forward).  The native call overwrites them: zeros when the graph has no edge (no path from an input to a logit)."""
+    want_x, want_ea = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+    if not (want_x or want_ea):
+        return None, None, None
+    dx = torch.empty_like(x) if want_x else None
+    dea = torch.empty_like(edge_attr) if want_ea else None
+    ig = nat.InputGrads(dx.data_ptr() if want_x else None, dea.data_ptr() if want_ea else None)
+    return dx, dea, C.byref(ig)
 
 
 class _LayerwiseTrainFunction(torch.autograd.Function):
-    """Autograd bridge to the layer-by-layer training engine (gnncca_train_forward / gnncca_train_backward, csrc/train_generic.cuh):
-    every legal GRAPH_NET_PARAMS in train mode -- BatchNorm with batch statistics in any MLP, Dropout, the generic family.  The tape
-    (what autograd would keep) is one device buffer owned by this call."""
+    """Autograd bridge to the layer-by-layer training engine (gnncca_train_forward / gnncca_train_backward_inputs,
+    csrc/train_generic.cuh): every legal GRAPH_NET_PARAMS in train mode -- BatchNorm with batch statistics in any MLP, Dropout, the
+    generic family.  The tape (what autograd would keep) is one device buffer owned by this call.  Input gradients as in
+    _MPNTrainFunction."""
 
     @staticmethod
     def forward(ctx, module, x, edge_index, edge_attr, *params):
@@ -302,13 +321,14 @@ class _LayerwiseTrainFunction(torch.autograd.Function):
         return logits
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_out):
         x, edge_index, edge_attr = ctx.saved_tensors[:3]
         params = ctx.saved_tensors[3:]
         lib, d = nat.lib(), ctx.module.native_dims()
         dev = x.device
         n, e = x.shape[0], edge_index.shape[1]
-        g = grad_out.reshape(grad_out.shape[0], -1).float().contiguous()
+        g = grad_out.reshape(grad_out.shape[0], e).float().contiguous()   # [n_out][E] (E may be 0)
         offs, total = [], 0
         for p in params:
             offs.append(total)
@@ -317,12 +337,13 @@ class _LayerwiseTrainFunction(torch.autograd.Function):
         grads = [flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
         pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
         gp = (C.c_void_p * len(params))(*[t.data_ptr() for t in grads])
+        dx, dea, ig = _input_grad_buffers(ctx, x, edge_attr)
         with torch.cuda.device(dev):
-            st = lib.gnncca_train_backward(C.byref(d), pp, len(params), x.data_ptr(), edge_index.data_ptr(), edge_attr.data_ptr(),
-                                           n, e, ctx.tape.data_ptr(), ctx.tape.numel(), g.data_ptr(), gp,
-                                           C.byref(ctx.drop) if ctx.drop is not None else None, _raw_stream(dev))
+            st = lib.gnncca_train_backward_inputs(C.byref(d), pp, len(params), x.data_ptr(), edge_index.data_ptr(), edge_attr.data_ptr(),
+                                                  n, e, ctx.tape.data_ptr(), ctx.tape.numel(), g.data_ptr(), gp,
+                                                  C.byref(ctx.drop) if ctx.drop is not None else None, ig, _raw_stream(dev))
         nat.check(st, "gnncca_train_backward")
-        return (None, None, None, None, *[gr if p.requires_grad else None for gr, p in zip(grads, params)])
+        return (None, dx, None, dea, *[gr if p.requires_grad else None for gr, p in zip(grads, params)])
 
 
 def _fill_mlp(dst, mlp):
@@ -613,7 +634,8 @@ class MOTMPNet(nn.Module):
 
     def forward(self, data, trace=None):
         """See class docstring.  ``trace`` (optional dict) receives the intermediate latents for debugging.
-        In train mode the outputs carry an autograd graph to the parameters (row N3)."""
+        In train mode the outputs carry an autograd graph to the parameters and to ``data.x`` / ``data.edge_attr`` where those
+        require grad (row N3); eval-mode outputs carry none."""
         if self.training:
             return self._forward_train(data)
         if trace is None and self._containers_hooked():
@@ -766,7 +788,7 @@ class MOTMPNet(nn.Module):
         self._check_batchnorm_rows(x.shape[0], edge_index.shape[1])
         fn = _MPNTrainFunction if self._train_path == 'fused' else _LayerwiseTrainFunction
         self._train_latents = None
-        logits = fn.apply(self, x.detach(), edge_index, edge_attr.detach(), *params)
+        logits = fn.apply(self, x, edge_index, edge_attr, *params)   # x / edge_attr that require grad receive theirs (row N3)
         latents, self._train_latents = self._train_latents, None
         if latents is not None:   # forward hooks on the containers: the reference's call sequence, fed from what the forward saved
             return self._replay_containers(data, list(logits.unbind(0)), *latents)

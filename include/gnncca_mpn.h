@@ -456,6 +456,20 @@ GNNCCA_API int gnncca_mpn_backward_train(const gnncca_mpn_dims* dims, const floa
                                          size_t workspace_bytes, uint32_t options, const gnncca_dropout* dropout,
                                          gnncca_stream_t stream);
 
+/* Gradients of the INPUTS of a train-mode forward (the reference's module backpropagates to data.x / data.edge_attr; a ReID head or a
+ * learned edge feature in front of the MPN trains through this).  dx: [N][node_in], d_edge_attr: [E][edge_in], device pointers; either
+ * may be null (nothing is launched for it), and what is given is OVERWRITTEN (zero-filled when the graph has no edge: no edge, no
+ * path from an input to a logit).  Each is one product with the first encoder layer's weight -- no atomics, a deterministic function
+ * of the gradient that reaches the encoder; dx runs on the fp32 matrix pipe (exact fp32).  A null `input_grads` makes either call
+ * its plain counterpart; neither needs more workspace / tape than that counterpart. */
+typedef struct { float* dx; float* d_edge_attr; } gnncca_input_grads;
+GNNCCA_API int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* dims, const float* const* params_dev, int n_params,
+                                          const float* x, const int64_t* edge_index, const float* edge_attr, int64_t n_nodes,
+                                          int64_t n_edges, const gnncca_trace* saved, const float* cls_bn_stat,
+                                          const float* grad_logits, float* const* grads_dev, void* workspace,
+                                          size_t workspace_bytes, uint32_t options, const gnncca_dropout* dropout,
+                                          const gnncca_input_grads* input_grads, gnncca_stream_t stream);
+
 /* Layer-by-layer training engine (SURVEY.md 8f row N3 remainder; train.py:454-494 through models/mpn.py:250-299 and
  * models/mlp.py:4-28 op for op): EVERY legal GRAPH_NET_PARAMS in train mode -- BatchNorm1d with batch statistics in any MLP
  * (running_mean / running_var updated in place with momentum 0.1, as torch.nn.BatchNorm1d; the caller bumps num_batches_tracked),
@@ -481,6 +495,13 @@ GNNCCA_API int gnncca_train_backward(const gnncca_mpn_dims* dims, float* const* 
                                      const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
                                      void* tape, size_t tape_bytes, const float* grad_logits, float* const* grads_dev,
                                      const gnncca_dropout* dropout, gnncca_stream_t stream);
+/* gnncca_train_backward that also writes the input gradients asked for in `input_grads` (see gnncca_input_grads above): any depth,
+ * BatchNorm or Dropout in the two encoders; a configuration without a node / edge encoder passes the latent gradient through. */
+GNNCCA_API int gnncca_train_backward_inputs(const gnncca_mpn_dims* dims, float* const* params_dev, int n_params, const float* x,
+                                            const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
+                                            void* tape, size_t tape_bytes, const float* grad_logits, float* const* grads_dev,
+                                            const gnncca_dropout* dropout, const gnncca_input_grads* input_grads,
+                                            gnncca_stream_t stream);
 
 /* Stand-alone calls of the sub-modules, which the reference allows (models/mlp.py:26-28 MLP.forward; models/mpn.py:128-142
  * MLPGraphIndependent.forward, :59-69 EdgeModel.forward, :71-101 NodeModel.forward, :32-54 MetaLayer.forward): eval semantics
