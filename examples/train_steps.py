@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Training through the HIP path (train.py:454-494 of the reference: forward, BCE over the classified steps, backward, SGD) on
 synthetic frames -- once with the shipped training configuration (fused training kernels, the whole iteration replayed as one HIP
-graph) and once with BatchNorm + Dropout switched on in every MLP (the layer-by-layer engine).  GPU box:
+graph) and once with BatchNorm + Dropout switched on in every MLP (the layer-by-layer engine); before them, a short leg that trains a ReID
+head THROUGH the GPU graph build (build_graph_batch is differentiable with respect to the raw embeddings).  GPU box:
     python examples/train_steps.py
 """
 import copy
@@ -74,7 +75,40 @@ def run(title, params, steps=30):
           f"(first encoder layer: {float(model.encoder.node_mlp.fc_layers[0].weight.grad.abs().max()):.3e})")
 
 
+def head_through_graph_build(params, steps=20):
+    """A ReID head trained through the association loss: nn.Linear head -> build_graph_batch (differentiable: the gradients of x and
+    edge_attr reach the raw embeddings through the normalisation and the edge attributes) -> MOTMPNet.train() -> EdgeLoss -> backward ->
+    an optimizer step on the head alone."""
+    from gnn_cca_amd.graph_build import build_graph_batch
+    from gnn_cca_amd.loss import EdgeLoss
+    torch.manual_seed(0)
+    rng = np.random.default_rng(1)
+    model = MOTMPNet(copy.deepcopy(params), None, "resnet50").cuda().train()
+    head = torch.nn.Linear(128, 2048).cuda()
+    opt = torch.optim.SGD(head.parameters(), lr=0.5)
+    loss_fn = EdgeLoss("BCE")
+    n_frames, cams, per = 8, 4, 5
+    n = n_frames * cams * per
+    id_cam = np.tile(np.repeat(np.arange(cams), per), n_frames)
+    ids = np.concatenate([rng.permutation(per)[np.arange(cams * per) % per] for _ in range(n_frames)])   # every person once per camera
+    crops = torch.from_numpy((np.eye(per, 128)[ids] + 0.3 * rng.standard_normal((n, 128))).astype(np.float32)).cuda()   # stand-in for the CNN input
+    xw, yw = rng.uniform(-10, 10, n), rng.uniform(-10, 10, n)
+    losses = []
+    for _ in range(steps):
+        emb = head(crops)
+        batch = build_graph_batch(xw, yw, ids, id_cam, [cams * per] * n_frames, [40.0] * n_frames, emb, emb)
+        loss = loss_fn(model(batch), batch.edge_labels)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        losses.append(float(loss))
+    print(f"ReID head through the graph build: loss {losses[0]:.4f} -> {losses[-1]:.4f} over {steps} steps on the head alone "
+          f"(max|d loss / d head.weight| = {float(head.weight.grad.abs().max()):.3e})")
+    assert head.weight.grad is not None and np.isfinite(losses).all()
+
+
 if __name__ == "__main__":
+    head_through_graph_build(bench.graph_net_params(cls_bn=False))
     run("shipped training configuration", bench.graph_net_params(cls_bn=False))
     p = bench.graph_net_params(cls_bn=True)
     p["encoder_feats_dict"]["nodes"]["resnet50"].update(use_batchnorm=True, dropout_p=0.1)

@@ -403,6 +403,8 @@ __global__ __launch_bounds__(256) void colnorm_fused_lds_kernel(const ColnormJob
 
 }  // namespace gnncca
 
+#include "graph_grads.cuh"
+
 using namespace gnncca;
 
 extern "C" {
@@ -460,6 +462,91 @@ int gnncca_normalize_columns(const float* x, int64_t n_rows, int64_t n_cols, flo
     const long long total = (long long)n_rows * n_cols;
     hipLaunchKernelGGL(colnorm_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x,
                        (const float*)(scratch + chunks * n_cols), total, (long long)n_cols, out);
+    HIP_TRY_GB(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- backward of row N1 (graph_grads.cuh) ----
+size_t gnncca_build_edges_backward_bytes(int64_t n_nodes) { return n_nodes > 0 ? (size_t)n_nodes * sizeof(NodeAux) : 0; }
+
+int gnncca_build_edges_backward(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                                const float* edge_attr, const float* grad_edge_attr, void* workspace, size_t workspace_bytes,
+                                float* grad_reid_out, gnncca_stream_t stream) {
+    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes == 0 || reid_dim == 0) return GNNCCA_OK;
+    if (!grad_reid_out) return GNNCCA_ERR_INVALID_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_edges == 0 || mode == GNNCCA_EDGE_ATTR_ONLY_DIST) {   // no edge attribute depends on the reid table: zeros, nothing launched
+        HIP_TRY_GB(hipMemsetAsync(grad_reid_out, 0, (size_t)n_nodes * (size_t)reid_dim * sizeof(float), st));
+        return GNNCCA_OK;
+    }
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (!fr->cam || !fr->graph_of || !fr->graph_ptr || !fr->src_order || !fr->edge_ptr || !reid || !edge_attr || !grad_edge_attr || !workspace)
+        return GNNCCA_ERR_INVALID_ARG;
+    if (workspace_bytes < gnncca_build_edges_backward_bytes(n_nodes)) return GNNCCA_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return GNNCCA_ERR_INVALID_ARG;
+    NodeAux* aux = static_cast<NodeAux*>(workspace);
+    hipLaunchKernelGGL(edges_bwd_prep_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, aux);
+    HIP_TRY_GB(hipGetLastError());
+    const bool vec = (reid_dim & 3) == 0 && ((reinterpret_cast<uintptr_t>(reid) | reinterpret_cast<uintptr_t>(grad_reid_out)) & 15) == 0;
+    const int per_block = kGgThreads * (vec ? 4 : 1);
+    const dim3 grid((unsigned)((n_nodes + kGgRows - 1) / kGgRows), (unsigned)((reid_dim + per_block - 1) / per_block)), block(kGgThreads);
+    if (grid.y > 65535) return GNNCCA_ERR_UNSUPPORTED;
+#define GNNCCA_EDGES_BWD(M, V)                                                                                                          \
+    hipLaunchKernelGGL((edges_bwd_kernel<M, V>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, aux, \
+                       edge_attr, grad_edge_attr, grad_reid_out)
+    if (mode == GNNCCA_EDGE_ATTR_FULL) {
+        if (vec) GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_FULL, true); else GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_FULL, false);
+    } else {
+        if (vec) GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, true); else GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, false);
+    }
+#undef GNNCCA_EDGES_BWD
+    HIP_TRY_GB(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+size_t gnncca_normalize_columns_backward_bytes(int64_t n_rows, int64_t n_cols) {
+    if (n_rows <= 0 || n_cols <= 0) return 0;
+    return (size_t)(2 * ((n_rows + kColChunk - 1) / kColChunk + 1) * n_cols) * sizeof(float);
+}
+
+int gnncca_normalize_columns_backward(const float* x, const float* grad_out, int64_t n_rows, int64_t n_cols, void* scratch, size_t scratch_bytes,
+                                      float* grad_x, gnncca_stream_t stream) {
+    if (n_rows < 0 || n_cols < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_rows == 0 || n_cols == 0) return GNNCCA_OK;
+    if (!x || !grad_out || !scratch || !grad_x) return GNNCCA_ERR_INVALID_ARG;
+    if (scratch_bytes < gnncca_normalize_columns_backward_bytes(n_rows, n_cols)) return GNNCCA_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long chunks = (n_rows + kColChunk - 1) / kColChunk;
+    if (chunks > 65535) return GNNCCA_ERR_UNSUPPORTED;
+    float* sq = static_cast<float*>(scratch);
+    float* dot = sq + (chunks + 1) * n_cols;
+    hipLaunchKernelGGL(colnorm_bwd_partial_kernel, dim3((unsigned)((n_cols + 1023) / 1024), (unsigned)chunks), dim3(256), 0, st, x, grad_out,
+                       (long long)n_rows, (long long)n_cols, sq, dot);
+    HIP_TRY_GB(hipGetLastError());
+    hipLaunchKernelGGL(colnorm_bwd_finish_kernel, dim3((unsigned)((n_cols + 63) / 64)), dim3(256), 0, st, sq, dot, chunks, (long long)n_cols);
+    HIP_TRY_GB(hipGetLastError());
+    const long long total = (long long)n_rows * n_cols;
+    hipLaunchKernelGGL(colnorm_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, grad_out,
+                       (const float*)(sq + chunks * n_cols), (const float*)(dot + chunks * n_cols), total, (long long)n_cols, grad_x);
+    HIP_TRY_GB(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_normalize_columns_backward2(const float* x0, const float* grad_out0, int64_t n_cols0, float* grad_x0, const float* x1,
+                                       const float* grad_out1, int64_t n_cols1, float* grad_x1, int64_t n_rows, gnncca_stream_t stream) {
+    if (n_rows < 0 || n_cols0 < 0 || n_cols1 < 0) return GNNCCA_ERR_INVALID_ARG;
+    if ((n_rows + kColChunk - 1) / kColChunk > kFusedMaxChunks) return GNNCCA_ERR_UNSUPPORTED;
+    if (n_rows == 0) return GNNCCA_OK;
+    if ((n_cols0 > 0 && (!x0 || !grad_out0 || !grad_x0)) || (n_cols1 > 0 && (!x1 || !grad_out1 || !grad_x1))) return GNNCCA_ERR_INVALID_ARG;
+    if (n_cols0 == 0) x0 = x1, grad_out0 = grad_out1, grad_x0 = grad_x1, n_cols0 = n_cols1, n_cols1 = 0;
+    if (n_cols0 == 0) return GNNCCA_OK;
+    const long long b0 = (n_cols0 + kFusedCols - 1) / kFusedCols, b1 = (n_cols1 + kFusedCols - 1) / kFusedCols;
+    if (b0 + b1 >= (1ll << 31)) return GNNCCA_ERR_UNSUPPORTED;
+    ColnormBwdJob j0{x0, grad_out0, grad_x0, (long long)n_cols0, 0};
+    ColnormBwdJob j1{n_cols1 > 0 ? x1 : nullptr, grad_out1, grad_x1, (long long)n_cols1, (int)b0};
+    hipLaunchKernelGGL(colnorm_bwd_fused_kernel, dim3((unsigned)(b0 + b1)), dim3(256), 0, static_cast<hipStream_t>(stream), j0, j1, (long long)n_rows);
     HIP_TRY_GB(hipGetLastError());
     return GNNCCA_OK;
 }

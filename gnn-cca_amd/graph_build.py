@@ -11,6 +11,7 @@ from dataclasses import dataclass
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .sharding import GraphBatch
@@ -90,16 +91,10 @@ def _f32c(x):
     return x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
 
 
-def normalize_columns(x, other=None):
-    """F.normalize(x, p=2, dim=0) (inference.py:189-190) on the GPU; returns a new tensor -- or, given a second matrix with the same
-    number of rows (`other`: the reid and the node embeddings of a batch), the pair, normalised in one launch when the batch has at
-    most 4096 rows (same bits as the three-kernel form, which takes any size)."""
-    if not x.is_cuda or (other is not None and not other.is_cuda):
-        raise RuntimeError("gnn_cca_amd.graph_build runs on MI355X only (no CPU fallback)")
-    x = _f32c(x)
+def _normalize_launch(x, other=None):
+    """The launches of normalize_columns on fp32 contiguous matrices: new tensors, no autograd."""
     out = torch.empty_like(x)
     if other is not None:
-        other = _f32c(other)
         if other.shape[0] != x.shape[0]:
             raise ValueError("normalize_columns(x, other): both matrices must have the same number of rows")
         out2 = torch.empty_like(other)
@@ -117,6 +112,77 @@ def normalize_columns(x, other=None):
     if st:
         nat.check(st, "gnncca_normalize_columns")
     return out if other is None else (out, out2)
+
+
+def _normalize_backward_launch(jobs):
+    """Backward of F.normalize(x, p=2, dim=0) for one or two (x, grad_out) pairs with the same number of rows: [grad_x, ...].  One launch up
+    to FUSED_NORMALIZE_MAX_ROWS rows, the three-kernel form (same bits) beyond."""
+    lib = nat.lib()
+    jobs = [(x, g if g.dtype == torch.float32 and g.is_contiguous() else g.float().contiguous()) for x, g in jobs]
+    outs = [torch.empty_like(x) for x, _ in jobs]
+    dev = jobs[0][0].device
+    with _on(dev):
+        if jobs[0][0].shape[0] <= FUSED_NORMALIZE_MAX_ROWS and jobs[0][0].dim() == 2:
+            (x0, g0), o0 = jobs[0], outs[0]
+            x1, g1, o1 = (jobs[1][0], jobs[1][1], outs[1]) if len(jobs) > 1 else (None, None, None)
+            st = lib.gnncca_normalize_columns_backward2(x0.data_ptr(), g0.data_ptr(), x0.shape[1], o0.data_ptr(),
+                                                        x1.data_ptr() if x1 is not None else None, g1.data_ptr() if x1 is not None else None,
+                                                        x1.shape[1] if x1 is not None else 0, o1.data_ptr() if x1 is not None else None,
+                                                        x0.shape[0], _raw_stream(dev))
+        else:
+            st = 0
+            for (x, g), o in zip(jobs, outs):
+                rows, cols = x.shape[0], x.numel() // max(x.shape[0], 1)
+                nbytes = lib.gnncca_normalize_columns_backward_bytes(rows, cols)
+                scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                st = st or lib.gnncca_normalize_columns_backward(x.data_ptr(), g.data_ptr(), rows, cols, scratch.data_ptr(), nbytes, o.data_ptr(),
+                                                                 _raw_stream(dev))
+    if st:
+        nat.check(st, "gnncca_normalize_columns_backward")
+    return outs
+
+
+class _NormalizeFunction(torch.autograd.Function):
+    """Autograd bridge of normalize_columns: forward = today's launches, backward = gnncca_normalize_columns_backward(2) for the inputs
+    that require grad (nothing is launched or allocated for the others).  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, x, other):
+        ctx.set_materialize_grads(False)   # an output nobody used arrives as None, not as a zero matrix
+        ctx.save_for_backward(x, other)
+        return _normalize_launch(x, other)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        jobs = [(k, saved[k], grads[k]) for k in range(len(grads)) if ctx.needs_input_grad[k] and grads[k] is not None]
+        res = [None, None]
+        if jobs:
+            for (k, _, _), gx in zip(jobs, _normalize_backward_launch([(x, g) for _, x, g in jobs])):
+                res[k] = gx
+        return tuple(res)
+
+
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+def normalize_columns(x, other=None):
+    """F.normalize(x, p=2, dim=0) (inference.py:189-190) on the GPU; returns a new tensor -- or, given a second matrix with the same
+    number of rows (`other`: the reid and the node embeddings of a batch), the pair, normalised in one launch when the batch has at
+    most 4096 rows (same bits as the three-kernel form, which takes any size).  Differentiable (once) when grad is enabled and an
+    input requires grad; otherwise exactly the launches and allocations of the plain call."""
+    if not x.is_cuda or (other is not None and not other.is_cuda):
+        raise RuntimeError("gnn_cca_amd.graph_build runs on MI355X only (no CPU fallback)")
+    x = _f32c(x)
+    if other is not None:
+        other = _f32c(other)
+    if _wants_grad(x, other):
+        if other is not None and other.shape[0] != x.shape[0]:
+            raise ValueError("normalize_columns(x, other): both matrices must have the same number of rows")
+        return _NormalizeFunction.apply(x, other)
+    return _normalize_launch(x, other)
 
 
 class _Staging:
@@ -151,6 +217,108 @@ def _as(a, dtype):
     return a
 
 
+class _EdgeJob:
+    """What the edge kernels of one batch need besides the reid table: the staged frame image and its sizes."""
+    __slots__ = ("staged", "n", "g", "e", "mode")
+
+    def __init__(self, staged, n, g, e, mode):
+        self.staged, self.n, self.g, self.e, self.mode = staged, n, g, e, mode
+
+    def frames(self):
+        n, g = self.n, self.g
+        fr = nat.Frames()
+        p0 = self.staged.data_ptr()
+        fr.xw, fr.yw, fr.max_dist = p0, p0 + 8 * n, p0 + 16 * n
+        base = p0 + 8 * (2 * n + g) + 8 * n
+        fr.person_id, fr.cam, fr.graph_of = base, base + 4 * n, base + 8 * n
+        fr.graph_ptr, fr.src_order, fr.edge_ptr = base + 12 * n, base + 4 * (3 * n + g + 1), base + 4 * (4 * n + g + 1)
+        return fr
+
+
+def _edges_launch(job, reid_embeds):
+    """gnncca_build_edges on the current stream: (edge_index, edge_attr, edge_labels), new tensors."""
+    dev, n, e = reid_embeds.device, job.n, job.e
+    n_attr = 4 if job.mode == MODE_FULL else 2
+    fr = job.frames()
+    edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
+    edge_attr = torch.empty((e, n_attr), dtype=torch.float32, device=dev)
+    edge_labels = torch.empty(e, dtype=torch.float32, device=dev)
+    if e > 0:
+        st = nat.lib().gnncca_build_edges(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode,
+                                          edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
+        if st:
+            nat.check(st, "gnncca_build_edges")
+    return edge_index, edge_attr, edge_labels
+
+
+class _GraphBuildFunction(torch.autograd.Function):
+    """Autograd bridge of build_graph_batch (the reference's statements are torch ops: F.normalize(dim=0), gathers, F.pairwise_distance,
+    F.cosine_similarity -- train.py:257-259, 306-308, 344, 357; with the no_grad around its CNN removed, the association loss reaches
+    the raw embeddings through them).  forward(node_raw | None, reid, job): with node_raw the embeddings are normalised here and the
+    outputs are (x, edge_attr, reid_normalised, edge_index, edge_labels); with None (normalize=False) `reid` is used as given and the
+    outputs are (edge_attr, edge_index, edge_labels).  backward: gnncca_build_edges_backward on grad_edge_attr, plus whatever arrives
+    on the normalised reid table directly, then gnncca_normalize_columns_backward per matrix; an input that does not require grad
+    costs no launch and no allocation.  The ground-plane attributes, edge_index and edge_labels carry no gradient.  Differentiable
+    once (double backward raises torch's error)."""
+
+    @staticmethod
+    def forward(ctx, node_raw, reid, job):
+        ctx.job, ctx.normalized = job, node_raw is not None
+        ctx.set_materialize_grads(False)   # an output nobody used arrives as None, not as a zero matrix
+        if ctx.normalized:
+            reid_n, x = _normalize_launch(reid, node_raw)
+        else:
+            reid_n, x = reid, None
+        edge_index, edge_attr, edge_labels = _edges_launch(job, reid_n)
+        ctx.mark_non_differentiable(edge_index, edge_labels)
+        if ctx.normalized:
+            ctx.save_for_backward(node_raw, reid, reid_n, edge_attr)
+            return x, edge_attr, reid_n, edge_index, edge_labels
+        ctx.save_for_backward(reid, edge_attr)
+        return edge_attr, edge_index, edge_labels
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        job = ctx.job
+        if ctx.normalized:
+            node_raw, reid_raw, reid_n, edge_attr = ctx.saved_tensors
+            g_x, g_ea, g_reid = grads[0], grads[1], grads[2]
+        else:
+            reid_n, edge_attr = ctx.saved_tensors
+            node_raw = reid_raw = g_x = g_reid = None
+            g_ea = grads[0]
+        want_node, want_reid = ctx.needs_input_grad[0] and g_x is not None, ctx.needs_input_grad[1]
+        d_rn = None   # d loss / d (the reid table the edge kernel read)
+        if want_reid:
+            if g_ea is not None and job.e == 0 and job.mode != MODE_ONLY_DIST:
+                d_rn = torch.zeros_like(reid_n)   # no edge: what torch's empty gathers give, and nothing to launch
+            elif g_ea is not None and job.mode != MODE_ONLY_DIST:
+                dev = reid_n.device
+                lib = nat.lib()
+                g_ea = g_ea if g_ea.dtype == torch.float32 and g_ea.is_contiguous() else g_ea.float().contiguous()
+                d_rn = torch.empty_like(reid_n)
+                nbytes = lib.gnncca_build_edges_backward_bytes(job.n)
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                fr = job.frames()
+                with _on(dev):
+                    st = lib.gnncca_build_edges_backward(C.byref(fr), reid_n.data_ptr(), reid_n.shape[1], job.n, job.e, job.mode,
+                                                         edge_attr.data_ptr(), g_ea.data_ptr(), ws.data_ptr(), nbytes, d_rn.data_ptr(),
+                                                         _raw_stream(dev))
+                if st:
+                    nat.check(st, "gnncca_build_edges_backward")
+            if g_reid is not None:   # a gradient on batch.reid_embeds itself (the caller's own ReID loss)
+                d_rn = g_reid if d_rn is None else d_rn.add_(g_reid)
+        if not ctx.normalized:
+            return None, d_rn, None
+        jobs = ([(1, reid_raw, d_rn)] if d_rn is not None else []) + ([(0, node_raw, g_x)] if want_node else [])
+        res = [None, None, None]
+        if jobs:
+            for (k, _, _), gx in zip(jobs, _normalize_backward_launch([(x, g) for _, x, g in jobs])):
+                res[k] = gx
+        return tuple(res)
+
+
 def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds, only_appearance=False,
                       only_dist=False, normalize=True):
     """One call per batch of frames.  Host inputs (numpy, one entry per detection, frames concatenated): xw, yw, ids,
@@ -181,32 +349,27 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
         if -e == nat.ERR_INVALID_ARG:
             raise ValueError("id_cam length does not match graph_sizes")
         nat.check(int(-e), "gnncca_plan_frames")
+    mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
     with _on(dev):
         staged = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         staged.copy_(pinned[:nbytes], non_blocking=True)
         event.record(_current_stream(dev))
-        if normalize:
-            reid_embeds, node_embeds = normalize_columns(reid_embeds, node_embeds)
-        elif reid_embeds.dtype != torch.float32 or not reid_embeds.is_contiguous():
-            reid_embeds = reid_embeds.float().contiguous()
-        mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
-        n_attr = 4 if mode == MODE_FULL else 2
-        fr = nat.Frames()
-        p0 = staged.data_ptr()
-        fr.xw, fr.yw, fr.max_dist = p0, p0 + 8 * n, p0 + 16 * n
-        y_off = 8 * (2 * n + g)
-        i32_off = y_off + 8 * n
-        base = p0 + i32_off
-        fr.person_id, fr.cam, fr.graph_of = base, base + 4 * n, base + 8 * n
-        fr.graph_ptr, fr.src_order, fr.edge_ptr = base + 12 * n, base + 4 * (3 * n + g + 1), base + 4 * (4 * n + g + 1)
-        edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
-        edge_attr = torch.empty((e, n_attr), dtype=torch.float32, device=dev)
-        edge_labels = torch.empty(e, dtype=torch.float32, device=dev)
-        if e > 0:
-            st = lib.gnncca_build_edges(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, mode,
-                                        edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
-            if st:
-                nat.check(st, "gnncca_build_edges")
+        job = _EdgeJob(staged, n, g, e, mode)
+        if _wants_grad(node_embeds, reid_embeds):
+            # the differentiable build: x, edge_attr and reid_embeds are outputs of ONE autograd node (see _GraphBuildFunction)
+            reid_embeds = _f32c(reid_embeds)
+            if normalize:
+                node_embeds, edge_attr, reid_embeds, edge_index, edge_labels = _GraphBuildFunction.apply(_f32c(node_embeds), reid_embeds, job)
+            else:   # x and reid_embeds are the caller's tensors: their history is torch's own
+                edge_attr, edge_index, edge_labels = _GraphBuildFunction.apply(None, reid_embeds, job)
+        else:
+            if normalize:
+                reid_embeds, node_embeds = normalize_columns(reid_embeds, node_embeds)
+            elif reid_embeds.dtype != torch.float32 or not reid_embeds.is_contiguous():
+                reid_embeds = reid_embeds.float().contiguous()
+            edge_index, edge_attr, edge_labels = _edges_launch(job, reid_embeds)
+    y_off = 8 * (2 * n + g)
+    i32_off = y_off + 8 * n
     # per-graph ranges (host copies): graph g owns the nodes graph_ptr[g] .. graph_ptr[g+1] and, edges being emitted graph by graph,
     # the edges edge_ptr_g[g] .. edge_ptr_g[g+1]
     host_i32 = pinned[i32_off:nbytes].numpy().view(np.int32)

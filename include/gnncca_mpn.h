@@ -267,6 +267,34 @@ GNNCCA_API int gnncca_build_edges(const gnncca_frames* frames, const float* reid
                                   int64_t n_edges, int32_t mode, int64_t* edge_index_out, float* edge_attr_out,
                                   float* edge_labels_out, gnncca_stream_t stream);
 
+/* ---- backward of row N1: gradients of the graph build reach the RAW embeddings ------------------------------
+ * The reference's statements are plain torch ops, so with the torch.no_grad() around its CNN (train.py:248-253) removed autograd
+ * differentiates them: F.normalize(.., p=2, dim=0) (train.py:257-259, inference.py:189-190), the gathers, F.pairwise_distance and
+ * F.cosine_similarity of the reid rows (train.py:306-308, inference.py:222-226), the stack of node rows (train.py:344, 357).  The
+ * ground-plane attributes go through numpy / sklearn there and carry no gradient; neither do they here.
+ * Both entry points: no atomics, fp32 accumulation, bit for bit the same from run to run, everything on `stream`, no synchronisation.
+ *
+ * gnncca_build_edges_backward: grad_reid_out [N][R] = d loss / d (the reid table gnncca_build_edges read) from grad_edge_attr
+ * [E][4 or 2] (only its emb / cos columns are read) and the FORWARD's edge_attr (its emb / cos values).  `frames` is the staged image of
+ * the forward.  Overwrites grad_reid_out; detections without a cross-camera partner get a zero row.  E == 0 or
+ * GNNCCA_EDGE_ATTR_ONLY_DIST: zeros (a memset, no kernel).  workspace: gnncca_build_edges_backward_bytes(n_nodes), 16-byte aligned.
+ * A reid row whose norm is below F.cosine_similarity's 1e-8 clamp is outside the parity contract: its gradient is finite, not torch's. */
+GNNCCA_API size_t gnncca_build_edges_backward_bytes(int64_t n_nodes);
+GNNCCA_API int gnncca_build_edges_backward(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                           int64_t n_edges, int32_t mode, const float* edge_attr, const float* grad_edge_attr,
+                                           void* workspace, size_t workspace_bytes, float* grad_reid_out, gnncca_stream_t stream);
+/* Backward of gnncca_normalize_columns (y = x / nrm_c, nrm_c = max(||x[:, c]||, 1e-12)):
+ *   grad_x = (grad_out - y * sum_rows(grad_out * y)) / nrm_c
+ * from the forward's INPUT x (the norms are recomputed with the forward's own ordered sums).  Any number of rows; scratch:
+ * gnncca_normalize_columns_backward_bytes(n_rows, n_cols).  ...backward2: up to two matrices of n_rows <= 4096 rows in ONE launch, bit for
+ * bit the same results; more rows: GNNCCA_ERR_UNSUPPORTED.  x1 may be NULL (n_cols1 = 0). */
+GNNCCA_API size_t gnncca_normalize_columns_backward_bytes(int64_t n_rows, int64_t n_cols);
+GNNCCA_API int gnncca_normalize_columns_backward(const float* x, const float* grad_out, int64_t n_rows, int64_t n_cols, void* scratch,
+                                                 size_t scratch_bytes, float* grad_x, gnncca_stream_t stream);
+GNNCCA_API int gnncca_normalize_columns_backward2(const float* x0, const float* grad_out0, int64_t n_cols0, float* grad_x0,
+                                                  const float* x1, const float* grad_out1, int64_t n_cols1, float* grad_x1,
+                                                  int64_t n_rows, gnncca_stream_t stream);
+
 /* ---- the step after the MPN -- threshold, pruning, flow counts, identity clusters --------
  * probs = sigmoid(logits), predictions = (probs >= 0.5) as int64 0/1 (inference.py:286-291). */
 GNNCCA_API int gnncca_post_threshold(const float* logits, int64_t n_edges, float* probs_out,
