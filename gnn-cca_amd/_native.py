@@ -11,6 +11,8 @@ MAX_LAYERS = 8
 OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_HIP, ERR_NO_DEVICE = range(6)
 AGG = {"sum": 0, "mean": 1, "max": 2}
 GRAPH_UNSORTED, GRAPH_BAD_INDEX = 1, 2
+RANK_BY = {"ground": 0, "reid": 1}   # gnncca_build_edges_topk
+TOPK_MAX_DEG = 4096
 
 
 class Layer(C.Structure):
@@ -109,6 +111,11 @@ _SIGNATURES = {
     "gnncca_build_edges_backward_bytes": (C.c_size_t, [C.c_int64]),
     "gnncca_build_edges_backward": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "gnncca_build_edges_topk": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_build_edges_topk_backward_bytes": (C.c_size_t, [C.c_int64]),
+    "gnncca_build_edges_topk_backward": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gnncca_normalize_columns_backward_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "gnncca_normalize_columns_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
                                                     C.c_void_p]),
@@ -179,6 +186,8 @@ _SIGNATURES = {
     "gnncca_plan_frames_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "gnncca_plan_frames": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_size_t]),
+    "gnncca_plan_frames_ex": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]),
     "gnncca_pad_frame": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "gnncca_read_graph_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),

@@ -44,6 +44,91 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// The per-edge statements gnncca_build_edges and gnncca_build_edges_topk share (the same statements give the same bits).
+// Ground-plane L2 and L1 distance of two detections in float64, no FMA contraction (sklearn paired_distances, inference.py:229-237):
+__device__ __forceinline__ void ground_dists(double xi, double yi, double xj, double yj, double& l2, double& l1) {
+    const double dx = __dsub_rn(xi, xj), dy = __dsub_rn(yi, yj);
+    l2 = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+    l1 = __dadd_rn(fabs(dx), fabs(dy));
+}
+// F.pairwise_distance(p=2, eps=1e-6) and F.cosine_similarity(eps=1e-8) from reid_sums_wave's sums (inference.py:222-226):
+__device__ __forceinline__ float reid_emb(float sd) { return sqrtf(sd); }
+__device__ __forceinline__ float reid_cos(float sab, float saa, float sbb) {
+    return sab / (fmaxf(sqrtf(saa), 1e-8f) * fmaxf(sqrtf(sbb), 1e-8f));
+}
+
+// The raw reid sums of source row `ri` against the candidates held by the lanes of `mask` (row_of(t): the reid row of lane t's
+// candidate), computed by the whole wave, four candidates per round, and parked in each candidate's own lane:
+//   sd = sum (a - b + 1e-6)^2,  sab = sum a b,  saa = sum a^2,  sbb = sum b^2      (a = ri[d], b = the candidate's row)
+// A lane's partial sums run over d = lane, lane + 64, ... (or four adjacent columns per lane when R % 4 == 0) and the 64 partials
+// are added by transpose_reduce16's fixed tree, whose pairing does not depend on the slot a candidate rides in: the bits of a
+// candidate's sums depend on the two rows alone, not on which other candidates share its round (what lets gnncca_build_edges_topk
+// re-group the survivors of a selection and still emit gnncca_build_edges' bits).
+template <class RowOf>
+__device__ __forceinline__ void reid_sums_wave(const float* __restrict__ reid, const float* __restrict__ ri, int R, bool vec4,
+                                               unsigned long long mask, int lane, RowOf row_of, float& sd, float& sab, float& saa,
+                                               float& sbb) {
+    unsigned long long m = mask;
+    while (m != 0ull) {  // wave-uniform: four targets per round (the last round repeats its last target)
+        int t[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (m != 0ull) {
+                t[k] = __ffsll((long long)m) - 1;
+                m &= m - 1;
+            } else {
+                t[k] = t[k - 1 < 0 ? 0 : k - 1];
+            }
+        }
+        const float* __restrict__ rj[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rj[k] = reid + (size_t)row_of(t[k]) * R;
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = 0.f;
+        auto acc = [&](int k, float a, float b) {
+            const float df = (a - b) + 1e-6f;  // F.pairwise_distance adds eps to the difference
+            v[4 * k + 0] = fmaf(df, df, v[4 * k + 0]);
+            v[4 * k + 1] = fmaf(a, b, v[4 * k + 1]);
+            v[4 * k + 2] = fmaf(a, a, v[4 * k + 2]);
+            v[4 * k + 3] = fmaf(b, b, v[4 * k + 3]);
+        };
+        if (vec4) {
+            for (int d = lane * 4; d < R; d += 256) {
+                const float4 a = *reinterpret_cast<const float4*>(ri + d);
+                float4 b[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const float4*>(rj[k] + d);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    acc(k, a.x, b[k].x);
+                    acc(k, a.y, b[k].y);
+                    acc(k, a.z, b[k].z);
+                    acc(k, a.w, b[k].w);
+                }
+            }
+        } else {
+            for (int d = lane; d < R; d += 64) {
+                const float a = ri[d];
+                float b[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) b[k] = rj[k][d];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc(k, a, b[k]);
+            }
+        }
+        const int toti = __float_as_int(transpose_reduce16(v));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float s0 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 0)));
+            const float s1 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 1)));
+            const float s2 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 2)));
+            const float s3 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 3)));
+            if (lane == t[k]) sd = s0, sab = s1, saa = s2, sbb = s3;
+        }
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void build_edges_kernel(const gnncca_frames fr, const float* __restrict__ reid, int R, int N,
                                                           long long E, long long* __restrict__ ei_out,
@@ -77,76 +162,16 @@ __global__ __launch_bounds__(256) void build_edges_kernel(const gnncca_frames fr
                 lab = fr.person_id[j] == pi ? 1.f : 0.f;
                 if (MODE != GNNCCA_EDGE_ATTR_ONLY_APPEARANCE) {
                     // sklearn paired_distances on float64 rows, / max_dist, .type(float32); no FMA contraction
-                    const double dx = __dsub_rn(xi, fr.xw[j]), dy = __dsub_rn(yi, fr.yw[j]);
-                    const double l2 = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
-                    const double l1 = __dadd_rn(fabs(dx), fabs(dy));
+                    double l2, l1;
+                    ground_dists(xi, yi, fr.xw[j], fr.yw[j], l2, l1);
                     a0 = (float)__ddiv_rn(l2, md);
                     a1 = (float)__ddiv_rn(l1, md);
                 }
             }
             if (MODE != GNNCCA_EDGE_ATTR_ONLY_DIST) {
                 float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;  // this lane's candidate: raw sums over the reid row
-                unsigned long long m = mask;
-                while (m != 0ull) {  // wave-uniform: four targets per round (the last round repeats its last target)
-                    int t[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (m != 0ull) {
-                            t[k] = __ffsll((long long)m) - 1;
-                            m &= m - 1;
-                        } else {
-                            t[k] = t[k - 1 < 0 ? 0 : k - 1];
-                        }
-                    }
-                    const float* __restrict__ rj[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) rj[k] = reid + (size_t)(j0 + t[k]) * R;
-                    float v[16];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) v[q] = 0.f;
-                    auto acc = [&](int k, float a, float b) {
-                        const float df = (a - b) + 1e-6f;  // F.pairwise_distance adds eps to the difference
-                        v[4 * k + 0] = fmaf(df, df, v[4 * k + 0]);
-                        v[4 * k + 1] = fmaf(a, b, v[4 * k + 1]);
-                        v[4 * k + 2] = fmaf(a, a, v[4 * k + 2]);
-                        v[4 * k + 3] = fmaf(b, b, v[4 * k + 3]);
-                    };
-                    if (vec4) {
-                        for (int d = lane * 4; d < R; d += 256) {
-                            const float4 a = *reinterpret_cast<const float4*>(ri + d);
-                            float4 b[4];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const float4*>(rj[k] + d);
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                acc(k, a.x, b[k].x);
-                                acc(k, a.y, b[k].y);
-                                acc(k, a.z, b[k].z);
-                                acc(k, a.w, b[k].w);
-                            }
-                        }
-                    } else {
-                        for (int d = lane; d < R; d += 64) {
-                            const float a = ri[d];
-                            float b[4];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) b[k] = rj[k][d];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) acc(k, a, b[k]);
-                        }
-                    }
-                    const int toti = __float_as_int(transpose_reduce16(v));
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float s0 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 0)));
-                        const float s1 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 1)));
-                        const float s2 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 2)));
-                        const float s3 = __int_as_float(__builtin_amdgcn_readlane(toti, lane_of_sum(4 * k + 3)));
-                        if (lane == t[k]) sd = s0, sab = s1, saa = s2, sbb = s3;
-                    }
-                }
-                const float emb = sqrtf(sd);
-                const float cosv = sab / (fmaxf(sqrtf(saa), 1e-8f) * fmaxf(sqrtf(sbb), 1e-8f));
+                reid_sums_wave(reid, ri, R, vec4, mask, lane, [&](int t) { return j0 + t; }, sd, sab, saa, sbb);
+                const float emb = reid_emb(sd), cosv = reid_cos(sab, saa, sbb);
                 if (MODE == GNNCCA_EDGE_ATTR_FULL) {
                     a2 = emb;
                     a3 = cosv;
@@ -404,6 +429,7 @@ __global__ __launch_bounds__(256) void colnorm_fused_lds_kernel(const ColnormJob
 }  // namespace gnncca
 
 #include "graph_grads.cuh"
+#include "graph_topk.cuh"
 
 using namespace gnncca;
 
@@ -469,9 +495,10 @@ int gnncca_normalize_columns(const float* x, int64_t n_rows, int64_t n_cols, flo
 // ---- backward of row N1 (graph_grads.cuh) ----
 size_t gnncca_build_edges_backward_bytes(int64_t n_nodes) { return n_nodes > 0 ? (size_t)n_nodes * sizeof(NodeAux) : 0; }
 
-int gnncca_build_edges_backward(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
-                                const float* edge_attr, const float* grad_edge_attr, void* workspace, size_t workspace_bytes,
-                                float* grad_reid_out, gnncca_stream_t stream) {
+// `edge_index` null: the dense enumeration (gnncca_build_edges); else the pruned edge list of gnncca_build_edges_topk
+static int edges_backward(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                          const int64_t* edge_index, bool pruned, const float* edge_attr, const float* grad_edge_attr, void* workspace,
+                          size_t workspace_bytes, float* grad_reid_out, gnncca_stream_t stream) {
     if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0) return GNNCCA_ERR_INVALID_ARG;
     if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
     if (n_nodes == 0 || reid_dim == 0) return GNNCCA_OK;
@@ -484,6 +511,7 @@ int gnncca_build_edges_backward(const gnncca_frames* fr, const float* reid, int3
     if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
     if (!fr->cam || !fr->graph_of || !fr->graph_ptr || !fr->src_order || !fr->edge_ptr || !reid || !edge_attr || !grad_edge_attr || !workspace)
         return GNNCCA_ERR_INVALID_ARG;
+    if (pruned && !edge_index) return GNNCCA_ERR_INVALID_ARG;
     if (workspace_bytes < gnncca_build_edges_backward_bytes(n_nodes)) return GNNCCA_ERR_WORKSPACE;
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return GNNCCA_ERR_INVALID_ARG;
     NodeAux* aux = static_cast<NodeAux*>(workspace);
@@ -493,15 +521,72 @@ int gnncca_build_edges_backward(const gnncca_frames* fr, const float* reid, int3
     const int per_block = kGgThreads * (vec ? 4 : 1);
     const dim3 grid((unsigned)((n_nodes + kGgRows - 1) / kGgRows), (unsigned)((reid_dim + per_block - 1) / per_block)), block(kGgThreads);
     if (grid.y > 65535) return GNNCCA_ERR_UNSUPPORTED;
-#define GNNCCA_EDGES_BWD(M, V)                                                                                                          \
-    hipLaunchKernelGGL((edges_bwd_kernel<M, V>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, aux, \
-                       edge_attr, grad_edge_attr, grad_reid_out)
+    const long long* dst = pruned ? reinterpret_cast<const long long*>(edge_index) + n_edges : nullptr;
+#define GNNCCA_EDGES_BWD(M, V, P)                                                                                                          \
+    hipLaunchKernelGGL((edges_bwd_kernel<M, V, P>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, aux, \
+                       edge_attr, grad_edge_attr, dst, grad_reid_out)
+#define GNNCCA_EDGES_BWD_V(M, P) \
+    if (vec) GNNCCA_EDGES_BWD(M, true, P); else GNNCCA_EDGES_BWD(M, false, P)
     if (mode == GNNCCA_EDGE_ATTR_FULL) {
-        if (vec) GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_FULL, true); else GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_FULL, false);
+        if (pruned) { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_FULL, true); } else { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_FULL, false); }
     } else {
-        if (vec) GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, true); else GNNCCA_EDGES_BWD(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, false);
+        if (pruned) { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, true); } else { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, false); }
     }
+#undef GNNCCA_EDGES_BWD_V
 #undef GNNCCA_EDGES_BWD
+    HIP_TRY_GB(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_build_edges_backward(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                                const float* edge_attr, const float* grad_edge_attr, void* workspace, size_t workspace_bytes,
+                                float* grad_reid_out, gnncca_stream_t stream) {
+    return edges_backward(fr, reid, reid_dim, n_nodes, n_edges, mode, nullptr, false, edge_attr, grad_edge_attr, workspace, workspace_bytes,
+                          grad_reid_out, stream);
+}
+
+size_t gnncca_build_edges_topk_backward_bytes(int64_t n_nodes) { return gnncca_build_edges_backward_bytes(n_nodes); }
+
+int gnncca_build_edges_topk_backward(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges,
+                                     int32_t mode, const int64_t* edge_index, const float* edge_attr, const float* grad_edge_attr,
+                                     void* workspace, size_t workspace_bytes, float* grad_reid_out, gnncca_stream_t stream) {
+    return edges_backward(fr, reid, reid_dim, n_nodes, n_edges, mode, edge_index, true, edge_attr, grad_edge_attr, workspace, workspace_bytes,
+                          grad_reid_out, stream);
+}
+
+// ---- row N1 with a capped neighbourhood (graph_topk.cuh) ----
+int gnncca_build_edges_topk(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                            int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
+                            float* edge_labels_out, gnncca_stream_t stream) {
+    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0 || top_k < 1 || max_deg < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
+    if (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID) return GNNCCA_ERR_INVALID_ARG;
+    if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
+    if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (!fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr ||
+        !fr->src_order || !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out)
+        return GNNCCA_ERR_INVALID_ARG;
+    if ((mode != GNNCCA_EDGE_ATTR_ONLY_DIST || rank_by == GNNCCA_RANK_BY_REID) && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
+    const int cap = std::max(64, (max_deg + 63) / 64 * 64);
+    const size_t per_wave = (size_t)cap * kTopkSlotBytes;
+    const int waves = per_wave * 4 <= 65536 ? 4 : (per_wave * 2 <= 65536 ? 2 : 1);   // 4096 slots x 12 B = 48 KB: one wave
+    const dim3 grid((unsigned)((n_nodes + waves - 1) / waves)), block(64 * waves);
+    const size_t lds = per_wave * waves;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    long long* ei = reinterpret_cast<long long*>(edge_index_out);
+#define GNNCCA_TOPK(M, K)                                                                                                          \
+    hipLaunchKernelGGL((build_edges_topk_kernel<M, K>), grid, block, lds, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, \
+                       cap, ei, edge_attr_out, edge_labels_out)
+#define GNNCCA_TOPK_R(M) \
+    if (rank_by == GNNCCA_RANK_BY_GROUND) GNNCCA_TOPK(M, GNNCCA_RANK_BY_GROUND); else GNNCCA_TOPK(M, GNNCCA_RANK_BY_REID)
+    switch (mode) {
+        case GNNCCA_EDGE_ATTR_FULL: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_FULL); break;
+        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE); break;
+        default: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_DIST); break;
+    }
+#undef GNNCCA_TOPK_R
+#undef GNNCCA_TOPK
     HIP_TRY_GB(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -605,8 +690,11 @@ size_t gnncca_plan_frames_bytes(int64_t n, int64_t g) {
     return (size_t)(8 * (3 * n + g) + 4 * (5 * n + 2 * g + 3));
 }
 
-int64_t gnncca_plan_frames(const double* xw, const double* yw, const int64_t* ids, const int64_t* id_cam, int64_t n,
-                           const int64_t* graph_sizes, const double* max_dist, int64_t g, void* staging, size_t staging_bytes) {
+// top_k == 0: every candidate (gnncca_plan_frames); top_k >= 1: min(top_k, deg) edges per source (gnncca_build_edges_topk)
+int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, const int64_t* ids, const int64_t* id_cam, int64_t n,
+                              const int64_t* graph_sizes, const double* max_dist, int64_t g, int64_t top_k, void* staging,
+                              size_t staging_bytes, int32_t* max_deg_out) {
+    if (top_k < 0) return -(int64_t)GNNCCA_ERR_INVALID_ARG;
     if (n < 0 || g < 0 || !staging || staging_bytes < gnncca_plan_frames_bytes(n, g)) return -(int64_t)GNNCCA_ERR_INVALID_ARG;
     if ((n > 0 && (!xw || !yw || !ids || !id_cam)) || (g > 0 && (!graph_sizes || !max_dist))) return -(int64_t)GNNCCA_ERR_INVALID_ARG;
     if (n >= (1ll << 31) - 64 || g >= (1ll << 31) - 64) return -(int64_t)GNNCCA_ERR_UNSUPPORTED;
@@ -685,16 +773,24 @@ int64_t gnncca_plan_frames(const double* xw, const double* yw, const int64_t* id
         std::vector<int32_t> cursor(start);
         for (int64_t i = 0; i < n; ++i) o_src[cursor[(size_t)key[(size_t)i]]++] = (int32_t)i;
     }
-    long long e = 0;
+    long long e = 0, max_deg = 0;
     for (int64_t pos = 0; pos < n; ++pos) {
         const int32_t node = o_src[pos];
         o_edge_ptr[pos] = (int32_t)e;
-        e += graph_sizes[o_graph_of[node]] - count[(size_t)key[(size_t)node]];   // every node of the frame's OTHER cameras
+        const long long deg = graph_sizes[o_graph_of[node]] - count[(size_t)key[(size_t)node]];   // every node of the frame's OTHER cameras
+        max_deg = std::max(max_deg, deg);
+        e += top_k > 0 ? std::min<long long>(deg, top_k) : deg;
         if (e >= (1ll << 31) - 64) return -(int64_t)GNNCCA_ERR_UNSUPPORTED;      // more than 2^31 edges in one batch
     }
     o_edge_ptr[n] = (int32_t)e;
     for (int64_t q = 0; q <= g; ++q) o_edge_ptr_g[q] = o_edge_ptr[o_graph_ptr[q]];   // edges are emitted frame by frame
+    if (max_deg_out) *max_deg_out = (int32_t)max_deg;
     return (int64_t)e;
+}
+
+int64_t gnncca_plan_frames(const double* xw, const double* yw, const int64_t* ids, const int64_t* id_cam, int64_t n,
+                           const int64_t* graph_sizes, const double* max_dist, int64_t g, void* staging, size_t staging_bytes) {
+    return gnncca_plan_frames_ex(xw, yw, ids, id_cam, n, graph_sizes, max_dist, g, 0, staging, staging_bytes, nullptr);
 }
 
 }  // extern "C"

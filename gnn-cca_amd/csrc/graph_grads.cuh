@@ -94,11 +94,26 @@ __device__ __forceinline__ int count_below(const int32_t* __restrict__ src_order
     return lo - lo0;
 }
 
-template <int MODE, bool VEC>
+// slot of the edge (source at position `pos` -> j) in a pruned edge list (gnncca_build_edges_topk): a search in the source's run of
+// ascending destination ids dst[edge_ptr[pos], edge_ptr[pos + 1]); -1 when the source did not keep j
+__device__ __forceinline__ long long find_edge(const int32_t* __restrict__ edge_ptr, const long long* __restrict__ dst, long long E, int pos,
+                                               int j) {
+    long long lo = edge_ptr[pos], hi = edge_ptr[pos + 1];
+    if (lo < 0 || hi > E) return -1;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (dst[mid] < j) lo = mid + 1; else hi = mid;
+    }
+    return lo < edge_ptr[pos + 1] && dst[lo] == j ? lo : -1;
+}
+
+// PRUNED (gnncca_build_edges_topk_backward): `dst` is the destination row of the forward's edge_index and fr.edge_ptr counts the kept
+// edges; an edge the selection dropped has p = q = 0.  Every other statement, and with it the order of every sum, is the dense one.
+template <int MODE, bool VEC, bool PRUNED>
 __global__ __launch_bounds__(kGgThreads) void edges_bwd_kernel(const gnncca_frames fr, const float* __restrict__ reid, int R, int N,
                                                                long long E, const NodeAux* __restrict__ aux,
                                                                const float* __restrict__ attr, const float* __restrict__ gattr,
-                                                               float* __restrict__ grad_r) {
+                                                               const long long* __restrict__ dst, float* __restrict__ grad_r) {
     constexpr int NA = MODE == GNNCCA_EDGE_ATTR_FULL ? 4 : 2, CE = NA - 2, CC = NA - 1;   // columns of emb and cos
     constexpr int W = VEC ? 4 : 1;
     __shared__ __attribute__((aligned(16))) float s_c[kGgChunk][kGgRows];
@@ -127,17 +142,29 @@ __global__ __launch_bounds__(kGgThreads) void edges_bwd_kernel(const gnncca_fram
                 if (gi == fr.graph_of[j] && fr.cam[i] != fr.cam[j]) {
                     const int gs = fr.graph_ptr[gi];
                     const NodeAux ai = aux[i], aj = aux[j];
-                    const long long e = (long long)fr.edge_ptr[ai.pos] + (j - gs) - count_below(fr.src_order, ai.cs, ai.ce, j);
-                    const long long er = (long long)fr.edge_ptr[aj.pos] + (i - gs) - count_below(fr.src_order, aj.cs, aj.ce, i);
-                    if ((unsigned long long)e < (unsigned long long)E && (unsigned long long)er < (unsigned long long)E) {
-                        const float emb = attr[e * NA + CE], embr = attr[er * NA + CE];
+                    if (PRUNED) {
+                        const long long e = find_edge(fr.edge_ptr, dst, E, ai.pos, j), er = find_edge(fr.edge_ptr, dst, E, aj.pos, i);
+                        const float emb = e >= 0 ? attr[e * NA + CE] : 0.f, embr = er >= 0 ? attr[er * NA + CE] : 0.f;
                         const float p = emb != 0.f ? gattr[e * NA + CE] / emb : 0.f;
                         const float pr = embr != 0.f ? gattr[er * NA + CE] / embr : 0.f;
-                        const float q = gattr[e * NA + CC], qr = gattr[er * NA + CC];
+                        const float q = e >= 0 ? gattr[e * NA + CC] : 0.f, qr = er >= 0 ? gattr[er * NA + CC] : 0.f;
                         const float ps = p + pr;
                         c = (q + qr) / (ai.nrm * aj.nrm) - ps;
-                        a = ps - fmaf(q, attr[e * NA + CC], qr * attr[er * NA + CC]) / (ai.nrm * ai.nrm);
+                        a = ps - fmaf(q, e >= 0 ? attr[e * NA + CC] : 0.f, qr * (er >= 0 ? attr[er * NA + CC] : 0.f)) / (ai.nrm * ai.nrm);
                         b = p - pr;
+                    } else {
+                        const long long e = (long long)fr.edge_ptr[ai.pos] + (j - gs) - count_below(fr.src_order, ai.cs, ai.ce, j);
+                        const long long er = (long long)fr.edge_ptr[aj.pos] + (i - gs) - count_below(fr.src_order, aj.cs, aj.ce, i);
+                        if ((unsigned long long)e < (unsigned long long)E && (unsigned long long)er < (unsigned long long)E) {
+                            const float emb = attr[e * NA + CE], embr = attr[er * NA + CE];
+                            const float p = emb != 0.f ? gattr[e * NA + CE] / emb : 0.f;
+                            const float pr = embr != 0.f ? gattr[er * NA + CE] / embr : 0.f;
+                            const float q = gattr[e * NA + CC], qr = gattr[er * NA + CC];
+                            const float ps = p + pr;
+                            c = (q + qr) / (ai.nrm * aj.nrm) - ps;
+                            a = ps - fmaf(q, attr[e * NA + CC], qr * attr[er * NA + CC]) / (ai.nrm * ai.nrm);
+                            b = p - pr;
+                        }
                     }
                 }
             }

@@ -7,6 +7,7 @@ numpy, `plan_frames`); one HIP kernel (`gnncca_build_edges`) then writes `edge_i
 for the whole batch of frames, and `gnncca_normalize_columns` does the `F.normalize(..., dim=0)` of the embeddings.
 """
 import ctypes as C
+import numbers
 from dataclasses import dataclass
 
 import numpy as np
@@ -218,11 +219,13 @@ def _as(a, dtype):
 
 
 class _EdgeJob:
-    """What the edge kernels of one batch need besides the reid table: the staged frame image and its sizes."""
-    __slots__ = ("staged", "n", "g", "e", "mode")
+    """What the edge kernels of one batch need besides the reid table: the staged frame image and its sizes; for a capped build
+    (top_k is not None) also the cap, the ranking key and the batch's largest uncapped degree."""
+    __slots__ = ("staged", "n", "g", "e", "mode", "top_k", "rank", "max_deg")
 
-    def __init__(self, staged, n, g, e, mode):
+    def __init__(self, staged, n, g, e, mode, top_k=None, rank=0, max_deg=0):
         self.staged, self.n, self.g, self.e, self.mode = staged, n, g, e, mode
+        self.top_k, self.rank, self.max_deg = top_k, rank, max_deg
 
     def frames(self):
         n, g = self.n, self.g
@@ -236,14 +239,21 @@ class _EdgeJob:
 
 
 def _edges_launch(job, reid_embeds):
-    """gnncca_build_edges on the current stream: (edge_index, edge_attr, edge_labels), new tensors."""
+    """gnncca_build_edges (gnncca_build_edges_topk for a capped job) on the current stream: (edge_index, edge_attr, edge_labels), new
+    tensors."""
     dev, n, e = reid_embeds.device, job.n, job.e
     n_attr = 4 if job.mode == MODE_FULL else 2
     fr = job.frames()
     edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
     edge_attr = torch.empty((e, n_attr), dtype=torch.float32, device=dev)
     edge_labels = torch.empty(e, dtype=torch.float32, device=dev)
-    if e > 0:
+    if job.top_k is not None:
+        # (called with E == 0 too: the entry point checks its arguments, the degree limit among them, before it looks at the sizes)
+        st = nat.lib().gnncca_build_edges_topk(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode, job.top_k, job.rank,
+                                               job.max_deg, edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
+        if st:
+            nat.check(st, "gnncca_build_edges_topk")
+    elif e > 0:
         st = nat.lib().gnncca_build_edges(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode,
                                           edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
         if st:
@@ -256,7 +266,8 @@ class _GraphBuildFunction(torch.autograd.Function):
     F.cosine_similarity -- train.py:257-259, 306-308, 344, 357; with the no_grad around its CNN removed, the association loss reaches
     the raw embeddings through them).  forward(node_raw | None, reid, job): with node_raw the embeddings are normalised here and the
     outputs are (x, edge_attr, reid_normalised, edge_index, edge_labels); with None (normalize=False) `reid` is used as given and the
-    outputs are (edge_attr, edge_index, edge_labels).  backward: gnncca_build_edges_backward on grad_edge_attr, plus whatever arrives
+    outputs are (edge_attr, edge_index, edge_labels).  backward: gnncca_build_edges_backward (gnncca_build_edges_topk_backward for a
+    capped build: the selection is piecewise constant, the gradient flows through the kept edges) on grad_edge_attr, plus whatever arrives
     on the normalised reid table directly, then gnncca_normalize_columns_backward per matrix; an input that does not require grad
     costs no launch and no allocation.  The ground-plane attributes, edge_index and edge_labels carry no gradient.  Differentiable
     once (double backward raises torch's error)."""
@@ -271,21 +282,24 @@ class _GraphBuildFunction(torch.autograd.Function):
             reid_n, x = reid, None
         edge_index, edge_attr, edge_labels = _edges_launch(job, reid_n)
         ctx.mark_non_differentiable(edge_index, edge_labels)
+        pruned = (edge_index,) if job.top_k is not None else ()   # the capped backward looks its edges up in the forward's edge list
         if ctx.normalized:
-            ctx.save_for_backward(node_raw, reid, reid_n, edge_attr)
+            ctx.save_for_backward(node_raw, reid, reid_n, edge_attr, *pruned)
             return x, edge_attr, reid_n, edge_index, edge_labels
-        ctx.save_for_backward(reid, edge_attr)
+        ctx.save_for_backward(reid, edge_attr, *pruned)
         return edge_attr, edge_index, edge_labels
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
         job = ctx.job
+        saved = ctx.saved_tensors
+        edge_index = saved[-1] if job.top_k is not None else None
         if ctx.normalized:
-            node_raw, reid_raw, reid_n, edge_attr = ctx.saved_tensors
+            node_raw, reid_raw, reid_n, edge_attr = saved[:4]
             g_x, g_ea, g_reid = grads[0], grads[1], grads[2]
         else:
-            reid_n, edge_attr = ctx.saved_tensors
+            reid_n, edge_attr = saved[:2]
             node_raw = reid_raw = g_x = g_reid = None
             g_ea = grads[0]
         want_node, want_reid = ctx.needs_input_grad[0] and g_x is not None, ctx.needs_input_grad[1]
@@ -302,9 +316,14 @@ class _GraphBuildFunction(torch.autograd.Function):
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 fr = job.frames()
                 with _on(dev):
-                    st = lib.gnncca_build_edges_backward(C.byref(fr), reid_n.data_ptr(), reid_n.shape[1], job.n, job.e, job.mode,
-                                                         edge_attr.data_ptr(), g_ea.data_ptr(), ws.data_ptr(), nbytes, d_rn.data_ptr(),
-                                                         _raw_stream(dev))
+                    if edge_index is not None:
+                        st = lib.gnncca_build_edges_topk_backward(C.byref(fr), reid_n.data_ptr(), reid_n.shape[1], job.n, job.e, job.mode,
+                                                                  edge_index.data_ptr(), edge_attr.data_ptr(), g_ea.data_ptr(), ws.data_ptr(),
+                                                                  nbytes, d_rn.data_ptr(), _raw_stream(dev))
+                    else:
+                        st = lib.gnncca_build_edges_backward(C.byref(fr), reid_n.data_ptr(), reid_n.shape[1], job.n, job.e, job.mode,
+                                                             edge_attr.data_ptr(), g_ea.data_ptr(), ws.data_ptr(), nbytes, d_rn.data_ptr(),
+                                                             _raw_stream(dev))
                 if st:
                     nat.check(st, "gnncca_build_edges_backward")
             if g_reid is not None:   # a gradient on batch.reid_embeds itself (the caller's own ReID loss)
@@ -320,13 +339,34 @@ class _GraphBuildFunction(torch.autograd.Function):
 
 
 def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds, only_appearance=False,
-                      only_dist=False, normalize=True):
+                      only_dist=False, normalize=True, top_k=None, rank_by="ground"):
     """One call per batch of frames.  Host inputs (numpy, one entry per detection, frames concatenated): xw, yw, ids,
     id_cam; graph_sizes / max_dist per frame.  Device inputs: node_embeds [N, D], reid_embeds [N, R].
     Returns a GraphBatch (x, edge_index, edge_attr) with .edge_labels and .y, laid out exactly like the reference's
     `Batch.from_data_list(batch)` (inference.py:279).
     Host work: one native call that enumerates the edges (gnncca_plan_frames, include/gnncca_mpn.h) into a pinned staging buffer,
-    one non-blocking upload, four launches; the call never synchronises."""
+    one non-blocking upload, four launches; the call never synchronises.
+
+    top_k=None (the default) builds the reference's complete cross-camera graph.  top_k=k (an integer >= 1; no counterpart in the reference)
+    keeps, for every detection i, the min(k, deg_i) of its deg_i cross-camera candidates in its own frame with the smallest key, ties to the
+    smaller destination node id.  rank_by='ground': the ground-plane L2 distance in float64 (before the division by max_dist);
+    rank_by='reid': the F.pairwise_distance value of the (normalised) reid rows, the fp32 number that goes into edge_attr.  The key need
+    not be an emitted attribute ('reid' with only_dist and 'ground' with only_appearance are legal).  The kept edges stay in the dense
+    order, so the result is a subsequence of the dense edge list -- for k >= max deg the dense build, bit for bit -- with
+    E = sum_i min(k, deg_i) known on the host (gnncca_plan_frames_ex): still no synchronisation.  edge_ptr, node_ptr, their device copies,
+    edge_labels and y keep their meaning.
+    The capped graph is DIRECTED: i may keep j while j does not keep i.  postprocess' remove_edges_single_direction therefore keeps
+    mutual pairs only; a caller who wants the union symmetrises edge_index (and the attributes) itself.
+    At most 4096 candidates per source (NotImplementedError beyond).  Differentiable like the dense build: gradients flow through the
+    kept edges' emb / cos attributes."""
+    if rank_by not in nat.RANK_BY:
+        raise ValueError(f"rank_by must be 'ground' or 'reid', not {rank_by!r}")
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
+            raise ValueError(f"top_k must be None or an integer >= 1, not {top_k!r}")
+        if top_k < 1:
+            raise ValueError(f"top_k must be >= 1, not {top_k}")
+        top_k = min(int(top_k), 2 ** 31 - 1)
     if not (node_embeds.is_cuda and reid_embeds.is_cuda):
         raise RuntimeError("gnn_cca_amd.graph_build runs on MI355X only (no CPU fallback)")
     dev = reid_embeds.device
@@ -343,18 +383,26 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
     if ring is None:
         ring = _staging[dev.index] = _Staging()
     pinned, event = ring.take(nbytes)
-    e = lib.gnncca_plan_frames(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data, g,
-                               pinned.data_ptr(), nbytes)
+    max_deg = C.c_int32(0)
+    if top_k is None:
+        e = lib.gnncca_plan_frames(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data, g,
+                                   pinned.data_ptr(), nbytes)
+    else:
+        e = lib.gnncca_plan_frames_ex(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data,
+                                      g, top_k, pinned.data_ptr(), nbytes, C.byref(max_deg))
     if e < 0:
         if -e == nat.ERR_INVALID_ARG:
             raise ValueError("id_cam length does not match graph_sizes")
         nat.check(int(-e), "gnncca_plan_frames")
+    if max_deg.value > nat.TOPK_MAX_DEG:   # (gnncca_build_edges_topk refuses it too; here nothing has been launched yet)
+        raise NotImplementedError(f"build_graph_batch(top_k=...): a detection with {max_deg.value} cross-camera candidates; the capped build "
+                                  f"takes at most {nat.TOPK_MAX_DEG} per detection")
     mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
     with _on(dev):
         staged = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         staged.copy_(pinned[:nbytes], non_blocking=True)
         event.record(_current_stream(dev))
-        job = _EdgeJob(staged, n, g, e, mode)
+        job = _EdgeJob(staged, n, g, e, mode, top_k, nat.RANK_BY[rank_by], max_deg.value)
         if _wants_grad(node_embeds, reid_embeds):
             # the differentiable build: x, edge_attr and reid_embeds are outputs of ONE autograd node (see _GraphBuildFunction)
             reid_embeds = _f32c(reid_embeds)

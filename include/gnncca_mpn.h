@@ -267,6 +267,34 @@ GNNCCA_API int gnncca_build_edges(const gnncca_frames* frames, const float* reid
                                   int64_t n_edges, int32_t mode, int64_t* edge_index_out, float* edge_attr_out,
                                   float* edge_labels_out, gnncca_stream_t stream);
 
+/* ---- row N1 with a capped neighbourhood: every detection keeps its k nearest cross-camera candidates -----------
+ * What is kept identical to the reference (inference.py:207-266): the enumeration (sources camera-major inside a frame, a source's
+ * targets in ascending node id), the four (or two) attributes and the label of every edge that is kept -- the bits gnncca_build_edges
+ * writes for that edge.  THE PRUNING ITSELF HAS NO COUNTERPART IN THE REFERENCE, which only ever builds the complete cross-camera graph.
+ *
+ * For source i with deg_i cross-camera candidates in its own frame, the min(top_k, deg_i) candidates of smallest key are kept:
+ *   GNNCCA_RANK_BY_GROUND  the ground-plane L2 distance in float64, before the division by max_dist (inference.py:229-237)
+ *   GNNCCA_RANK_BY_REID    the F.pairwise_distance value of the reid rows, the fp32 number that goes into edge_attr (inference.py:222)
+ * ties to the smaller destination node id.  The key need not be an emitted attribute (RANK_BY_REID with ONLY_DIST is legal and reads
+ * `reid`).  The kept edges of a source stay in the dense order, so the result is a subsequence of gnncca_build_edges' edge list and, for
+ * top_k >= max deg, that list bit for bit.  The graph is DIRECTED: i may keep j while j drops i.
+ *
+ * gnncca_plan_frames_ex: gnncca_plan_frames with a cap -- the same staging image, edge_ptr / edge_ptr_g counting min(top_k, deg) edges
+ * per source (top_k == 0: no cap, gnncca_plan_frames' image byte for byte; top_k < 0: INVALID_ARG).  Returns E = sum min(top_k, deg)
+ * and writes the largest UNCAPPED deg of the batch through max_deg_out (nullable): what gnncca_build_edges_topk sizes its LDS by.
+ *
+ * gnncca_build_edges_topk: `frames` is the uploaded image of gnncca_plan_frames_ex(top_k), n_edges its return value, max_deg its
+ * max_deg_out (any upper bound of the batch's deg will do; a source with more candidates than declared is left unwritten).  One launch,
+ * no workspace, no atomics, no synchronisation, capturable.  max_deg > GNNCCA_TOPK_MAX_DEG: GNNCCA_ERR_UNSUPPORTED, nothing launched. */
+#define GNNCCA_TOPK_MAX_DEG 4096
+enum { GNNCCA_RANK_BY_GROUND = 0, GNNCCA_RANK_BY_REID = 1 };
+GNNCCA_API int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, const int64_t* ids, const int64_t* id_cam, int64_t n_nodes,
+                                         const int64_t* graph_sizes, const double* max_dist, int64_t n_frames, int64_t top_k,
+                                         void* staging, size_t staging_bytes, int32_t* max_deg_out);
+GNNCCA_API int gnncca_build_edges_topk(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                       int64_t n_edges, int32_t mode, int32_t top_k, int32_t rank_by, int32_t max_deg,
+                                       int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, gnncca_stream_t stream);
+
 /* ---- backward of row N1: gradients of the graph build reach the RAW embeddings ------------------------------
  * The reference's statements are plain torch ops, so with the torch.no_grad() around its CNN (train.py:248-253) removed autograd
  * differentiates them: F.normalize(.., p=2, dim=0) (train.py:257-259, inference.py:189-190), the gathers, F.pairwise_distance and
@@ -283,6 +311,17 @@ GNNCCA_API size_t gnncca_build_edges_backward_bytes(int64_t n_nodes);
 GNNCCA_API int gnncca_build_edges_backward(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
                                            int64_t n_edges, int32_t mode, const float* edge_attr, const float* grad_edge_attr,
                                            void* workspace, size_t workspace_bytes, float* grad_reid_out, gnncca_stream_t stream);
+/* gnncca_build_edges_topk_backward: the same for the edge list of gnncca_build_edges_topk (the selection is piecewise constant: the
+ * gradient flows through the emb / cos attributes of the KEPT edges only).  `frames` is the staged image of that forward
+ * (gnncca_plan_frames_ex), `edge_index` [2][E] the forward's output, edge_attr / grad_edge_attr [E][4 or 2] in its edge order.  Same
+ * kernels and summation order as gnncca_build_edges_backward -- the slot of (i -> j) is searched in i's ascending destination run
+ * instead of derived from the plan, an absent edge contributes zero -- so there are no atomics, the result is bit for bit the same from
+ * run to run, and for top_k >= max deg it is gnncca_build_edges_backward's, bit for bit.  Workspace: ..._topk_backward_bytes(n_nodes). */
+GNNCCA_API size_t gnncca_build_edges_topk_backward_bytes(int64_t n_nodes);
+GNNCCA_API int gnncca_build_edges_topk_backward(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                                int64_t n_edges, int32_t mode, const int64_t* edge_index, const float* edge_attr,
+                                                const float* grad_edge_attr, void* workspace, size_t workspace_bytes,
+                                                float* grad_reid_out, gnncca_stream_t stream);
 /* Backward of gnncca_normalize_columns (y = x / nrm_c, nrm_c = max(||x[:, c]||, 1e-12)):
  *   grad_x = (grad_out - y * sum_rows(grad_out * y)) / nrm_c
  * from the forward's INPUT x (the norms are recomputed with the forward's own ordered sums).  Any number of rows; scratch:
