@@ -15,7 +15,7 @@
 // on arrival order in the last bits exactly like the reference on CUDA (cuBLAS / torch_scatter atomics).
 // Supported: the MFMA family -- both reattach flags, all three aggregators -- with BatchNorm nowhere or inside the
 // classifier only and a two-layer node encoder.
-// Part of the single translation unit mpn_forward.hip.
+// Part of the translation unit mpn_train.hip.
 namespace gnncca {
 
 __device__ __forceinline__ float wave_reduce_sum(float v) {

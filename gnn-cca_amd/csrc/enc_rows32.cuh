@@ -1,6 +1,6 @@
 #pragma once
-// Part of the single translation unit mpn_forward.hip (kernels share device helpers and the launch code below
-// instantiates their templates); see that file for the overall picture.
+// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers and the launch code
+// below instantiates their templates); see that file for the overall picture.
 namespace gnncca {
 
 // ------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 #pragma once
-// Part of the single translation unit mpn_forward.hip (kernels share device helpers and the launch code below
-// instantiates their templates); see that file for the overall picture.
+// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers and the launch code
+// below instantiates their templates); see that file for the overall picture.
 namespace gnncca {
 
 // ------------------------------------------------------------------------------------------------------------
@@ -63,18 +63,7 @@ __device__ __forceinline__ void gemm_tile(int rt, int ks, int cg, const float* _
 // Second half of the plan, run by ONE 256-thread workgroup of the launch that follows the plan blocks on the stream:
 // One launch, two roles: workgroups [0, gemm_blocks) run encoder GEMM tiles, the rest run the graph plan -- the
 // two are independent, so the plan's HBM pass over edge_index hides under the GEMM instead of costing a launch.
-struct EncPlanParams {
-    const float* in;
-    const float* W;
-    float* part;
-    const long long* ei;
-    int* seg_ptr;
-    int* col32;
-    unsigned* blockflags;
-    int M, K, O, kslice, vec_ok, nrt, nks, gemm_blocks, E, N;
-    int ell_S;  // slots per node of the padded step layout to validate the degrees against (0: none)
-    int plan_span;  // 1024-edge plan blocks per plan workgroup (plan.cuh: 1, or kPlanSpan on a plan-only launch of a big batch)
-};
+// (EncPlanParams: internal.h, with the launchers of the kernels other translation units need.)
 
 __global__ __launch_bounds__(256) void enc_gemm_plan_kernel(const EncPlanParams p) {
     __shared__ unsigned s_fl;
@@ -94,6 +83,13 @@ __global__ __launch_bounds__(256) void enc_gemm_plan_kernel(const EncPlanParams 
 __global__ __launch_bounds__(256) void plan_only_kernel(const EncPlanParams p) {
     __shared__ unsigned s_fl;
     plan_block(blockIdx.x, p.ei, p.E, p.N, p.seg_ptr, p.col32, p.blockflags, &s_fl, p.ell_S, p.plan_span);
+}
+
+void launch_plan_only(const EncPlanParams& p, int blocks, gnncca_stream_t stream) {
+    hipLaunchKernelGGL(plan_only_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+}
+void launch_enc_gemm_plan(const EncPlanParams& p, int blocks, gnncca_stream_t stream) {
+    hipLaunchKernelGGL(enc_gemm_plan_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -602,6 +598,10 @@ __global__ __launch_bounds__(256) void reduce_bias_act_kernel(const float* __res
     float v = bias[idx % O];
     for (int s = 0; s < ks; ++s) v += part[(size_t)s * M * O + idx];
     act[idx] = relu ? fmaxf(v, 0.f) : v;
+}
+void launch_reduce_bias_act(const float* part, const float* bias, float* act, int M, int O, int ks, int relu, gnncca_stream_t stream) {
+    hipLaunchKernelGGL(reduce_bias_act_kernel, grid1((size_t)M * O, 256), dim3(256), 0, static_cast<hipStream_t>(stream), part, bias, act, M, O,
+                       ks, relu);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -20,20 +20,11 @@
 
 #include <cstdint>
 
-#include "internal.h"
+#include "hip_try.h"
 
 #pragma clang fp contract(off)
 
 namespace gnncca {
-
-#define HIP_TRY_EV(expr)                   \
-    do {                                   \
-        hipError_t _e = (expr);            \
-        if (_e != hipSuccess) {            \
-            g_last_hip_error = (int)_e;    \
-            return GNNCCA_ERR_HIP;         \
-        }                                  \
-    } while (0)
 
 constexpr int kEvalMaxNodes = GNNCCA_EVAL_MAX_FRAME_NODES;   // 12-bit frame-local ids in the contingency keys
 constexpr int kEvalMaxSizes = 96;   // distinct cluster sizes of one side: k (k + 1) / 2 <= 4096  ->  k <= 90
@@ -371,7 +362,7 @@ int gnncca_eval_frames(const int64_t* edge_index, const float* edge_labels, cons
     else
         hipLaunchKernelGGL(eval_frames_kernel<256>, dim3((unsigned)n_frames), dim3(256), lds, st, ei, (long long)n_edges, edge_labels, pr,
                            labels, (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, gt_labels_out, out, lf);
-    HIP_TRY_EV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 

@@ -1,6 +1,6 @@
 #pragma once
-// Part of the single translation unit mpn_forward.hip (kernels share device helpers and the launch code below
-// instantiates their templates); see that file for the overall picture.
+// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers and the launch code
+// below instantiates their templates); see that file for the overall picture.
 namespace gnncca {
 
 // ============================================================================================================
@@ -11,11 +11,7 @@ namespace gnncca {
 // CSR segments in the caller's edge order (the order torch's CPU index_add_ sums in).  Two kernels do all the work:
 // an LDS-tiled dense layer (eight outputs per thread) and a wave-per-node ordered aggregator.
 // ============================================================================================================
-struct GenSeg {
-    const float* ptr;   // [rows][ld]
-    const int* idx;     // optional row gather (row32 / col32 in the caller's edge order), or null
-    int ld, width;
-};
+// (GenSeg, one segment of a virtual concatenation: internal.h, with the launchers of the kernels other translation units need.)
 
 // out[r][o] = [ReLU](b[o] + sum over the concatenated segments of W[o][:] . in[r][:])
 // Weights arrive transposed and padded, Wt[k][OP] with OP = ceil8(O) (pack_generic).  A thread owns one row and EIGHT
@@ -151,6 +147,31 @@ __global__ __launch_bounds__(256) void gen_poison_kernel(float* __restrict__ out
     if (t < n && (flags[0] & GNNCCA_GRAPH_BAD_INDEX)) out[t] = __builtin_nanf("");
 }
 
+// Host launchers of the op kernels above (declared in internal.h): the layer-by-layer training engine (mpn_train.hip) and the post stage
+// (mpn_post.hip) run the same kernels.
+void launch_gen_plan_finish(const long long* ei, int E, int N, int* seg_ptr, int* col32, int* perm, int* cursor, unsigned* flags,
+                            const unsigned* blockflags, gnncca_stream_t stream) {
+    hipLaunchKernelGGL(gen_plan_finish_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), ei, E, N, seg_ptr, col32, perm, cursor,
+                       flags, blockflags);
+}
+void launch_gen_index32(const long long* ei, int E, int N, int* row32, int* col32, gnncca_stream_t stream) {
+    hipLaunchKernelGGL(gen_index32_kernel, dim3((E + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), ei, E, N, row32, col32);
+}
+void launch_gen_dense(const GenSeg& s0, const GenSeg& s1, const GenSeg& s2, const float* Wt, const float* b, float* out, long long M, int K,
+                      int O, int ldw, int ld_out, int relu, gnncca_stream_t stream) {
+    const int rows_per_block = 256 / ((O + 7) / 8);
+    hipLaunchKernelGGL(gen_dense_kernel, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), s0, s1, s2, Wt, b, out, M, K, O, ldw, ld_out, relu);
+}
+void launch_gen_aggregate(const float* m, const int* seg_ptr, const int* perm, const unsigned* flags, float* h, int N, int H, int agg,
+                          gnncca_stream_t stream) {
+    hipLaunchKernelGGL(gen_aggregate_kernel, dim3((unsigned)N), dim3(256), 0, static_cast<hipStream_t>(stream), m, seg_ptr, perm, flags, h, N, H,
+                       agg);
+}
+void launch_gen_poison(float* out, long long n, const unsigned* flags, gnncca_stream_t stream) {
+    hipLaunchKernelGGL(gen_poison_kernel, grid1((size_t)n, 256), dim3(256), 0, static_cast<hipStream_t>(stream), out, n, flags);
+}
+
 static int gen_run_mlp(const gnncca_mlp& mlp, const float* blob, const int32_t* woff, const int32_t* boff, GenSeg in0,
                        GenSeg in1, GenSeg in2, long long M, float* out_final, int ld_final, float* tmp_a, float* tmp_b,
                        int ld_tmp, hipStream_t st) {
@@ -167,10 +188,7 @@ static int gen_run_mlp(const gnncca_mlp& mlp, const float* blob, const int32_t* 
             const int op_total = (L.out_dim + 7) / 8 * 8;
             for (int o0 = 0; o0 < L.out_dim; o0 += 2048) {  // column groups of at most 2048 outputs (256 threads x 8)
                 const int og = std::min(2048, L.out_dim - o0);
-                const int rows_per_block = 256 / ((og + 7) / 8);
-                hipLaunchKernelGGL(gen_dense_kernel, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0, st,
-                                   a, b, c, blob + woff[l] + o0, blob + boff[l] + o0, dst + o0, M, L.in_dim, og, op_total, ld,
-                                   L.relu);
+                launch_gen_dense(a, b, c, blob + woff[l] + o0, blob + boff[l] + o0, dst + o0, M, L.in_dim, og, op_total, ld, L.relu, st);
             }
             HIP_TRY(hipGetLastError());
         }

@@ -22,19 +22,10 @@
 #include <cstring>
 #include <vector>
 
-#include "internal.h"
+#include "hip_try.h"
 #include "wave_reduce.cuh"
 
 namespace gnncca {
-
-#define HIP_TRY_GB(expr)                   \
-    do {                                   \
-        hipError_t _e = (expr);            \
-        if (_e != hipSuccess) {            \
-            g_last_hip_error = (int)_e;    \
-            return GNNCCA_ERR_HIP;         \
-        }                                  \
-    } while (0)
 
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 
@@ -457,9 +448,9 @@ int gnncca_normalize_columns2(const float* x0, int64_t n_cols0, float* out0, con
         const int lds = (int)((n_rows + kColChunk - 1) / kColChunk) * kLdsChunkBytes;
         static thread_local int attr_dev = -1;
         int dev = 0;
-        HIP_TRY_GB(hipGetDevice(&dev));
+        HIP_TRY(hipGetDevice(&dev));
         if (attr_dev != dev) {
-            HIP_TRY_GB(hipFuncSetAttribute(reinterpret_cast<const void*>(colnorm_fused_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(colnorm_fused_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (kLdsRowsMax / kColChunk) * kLdsChunkBytes));
             attr_dev = dev;
         }
@@ -468,7 +459,7 @@ int gnncca_normalize_columns2(const float* x0, int64_t n_cols0, float* out0, con
     } else {
         hipLaunchKernelGGL(colnorm_fused_kernel, dim3((unsigned)(b0 + b1)), dim3(256), 0, static_cast<hipStream_t>(stream), j0, j1, (long long)n_rows);
     }
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -481,14 +472,14 @@ int gnncca_normalize_columns(const float* x, int64_t n_rows, int64_t n_cols, flo
     if (chunks > 65535) return GNNCCA_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(colnorm_partial_kernel, dim3((unsigned)((n_cols + 1023) / 1024), (unsigned)chunks), dim3(256), 0, st, x,
                        (long long)n_rows, (long long)n_cols, scratch);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(colnorm_finish_kernel, dim3((unsigned)((n_cols + 63) / 64)), dim3(256), 0, st, scratch, chunks,
                        (long long)n_cols);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const long long total = (long long)n_rows * n_cols;
     hipLaunchKernelGGL(colnorm_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x,
                        (const float*)(scratch + chunks * n_cols), total, (long long)n_cols, out);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -505,7 +496,7 @@ static int edges_backward(const gnncca_frames* fr, const float* reid, int32_t re
     if (!grad_reid_out) return GNNCCA_ERR_INVALID_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_edges == 0 || mode == GNNCCA_EDGE_ATTR_ONLY_DIST) {   // no edge attribute depends on the reid table: zeros, nothing launched
-        HIP_TRY_GB(hipMemsetAsync(grad_reid_out, 0, (size_t)n_nodes * (size_t)reid_dim * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(grad_reid_out, 0, (size_t)n_nodes * (size_t)reid_dim * sizeof(float), st));
         return GNNCCA_OK;
     }
     if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
@@ -516,7 +507,7 @@ static int edges_backward(const gnncca_frames* fr, const float* reid, int32_t re
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return GNNCCA_ERR_INVALID_ARG;
     NodeAux* aux = static_cast<NodeAux*>(workspace);
     hipLaunchKernelGGL(edges_bwd_prep_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, aux);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const bool vec = (reid_dim & 3) == 0 && ((reinterpret_cast<uintptr_t>(reid) | reinterpret_cast<uintptr_t>(grad_reid_out)) & 15) == 0;
     const int per_block = kGgThreads * (vec ? 4 : 1);
     const dim3 grid((unsigned)((n_nodes + kGgRows - 1) / kGgRows), (unsigned)((reid_dim + per_block - 1) / per_block)), block(kGgThreads);
@@ -534,7 +525,7 @@ static int edges_backward(const gnncca_frames* fr, const float* reid, int32_t re
     }
 #undef GNNCCA_EDGES_BWD_V
 #undef GNNCCA_EDGES_BWD
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -587,7 +578,7 @@ int gnncca_build_edges_topk(const gnncca_frames* fr, const float* reid, int32_t 
     }
 #undef GNNCCA_TOPK_R
 #undef GNNCCA_TOPK
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -609,13 +600,13 @@ int gnncca_normalize_columns_backward(const float* x, const float* grad_out, int
     float* dot = sq + (chunks + 1) * n_cols;
     hipLaunchKernelGGL(colnorm_bwd_partial_kernel, dim3((unsigned)((n_cols + 1023) / 1024), (unsigned)chunks), dim3(256), 0, st, x, grad_out,
                        (long long)n_rows, (long long)n_cols, sq, dot);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(colnorm_bwd_finish_kernel, dim3((unsigned)((n_cols + 63) / 64)), dim3(256), 0, st, sq, dot, chunks, (long long)n_cols);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const long long total = (long long)n_rows * n_cols;
     hipLaunchKernelGGL(colnorm_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, grad_out,
                        (const float*)(sq + chunks * n_cols), (const float*)(dot + chunks * n_cols), total, (long long)n_cols, grad_x);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -632,7 +623,7 @@ int gnncca_normalize_columns_backward2(const float* x0, const float* grad_out0, 
     ColnormBwdJob j0{x0, grad_out0, grad_x0, (long long)n_cols0, 0};
     ColnormBwdJob j1{n_cols1 > 0 ? x1 : nullptr, grad_out1, grad_x1, (long long)n_cols1, (int)b0};
     hipLaunchKernelGGL(colnorm_bwd_fused_kernel, dim3((unsigned)(b0 + b1)), dim3(256), 0, static_cast<hipStream_t>(stream), j0, j1, (long long)n_rows);
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -675,7 +666,7 @@ int gnncca::build_edges_zeroing(const gnncca_frames* fr, const float* reid, int3
                                (int)n_nodes, (long long)n_edges, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
             break;
     }
-    HIP_TRY_GB(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 

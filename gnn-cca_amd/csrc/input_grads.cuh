@@ -3,7 +3,7 @@
 // module backpropagates to its inputs, models/mpn.py:266-297; fine-tuning a ReID head through the association loss asks for it).
 // Both are products of a gradient the backward already holds with the first encoder layer's weight, so they are overwritten,
 // never accumulated: no atomics, and each is a deterministic function of that gradient.
-// Part of the single translation unit mpn_forward.hip.
+// Part of the translation unit mpn_train.hip.
 
 namespace gnncca {
 

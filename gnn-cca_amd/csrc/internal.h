@@ -1,4 +1,5 @@
-// internal.h -- layouts shared by the host packer (pack.cpp) and the HIP kernels (mpn_forward.hip).
+// internal.h -- layouts and host functions shared by the library's translation units: the host packer (pack.cpp), the inference
+// kernels (mpn_forward.hip), post-processing (mpn_post.hip), training (mpn_train.hip) and the smaller HIP units.  Plain C++, no HIP types.
 // Not part of the public ABI (include/gnncca_mpn.h is).
 #pragma once
 #include <stddef.h>
@@ -8,7 +9,7 @@
 
 namespace gnncca {
 
-extern thread_local int g_last_hip_error;  // hipError_t of the last failed HIP call on this thread
+extern thread_local int g_last_hip_error;  // hipError_t of the last failed HIP call on this thread (defined in pack.cpp, set by HIP_TRY: hip_try.h)
 
 // Diagnostic switches (the A/B experiments of DESIGN.md 5; listed in DESIGN.md 11).  They change kernel SELECTION, hence
 // summation order, so the shipped library ignores every one of them unless GNNCCA_DIAG=1 is set in the same environment:
@@ -154,5 +155,78 @@ int ell_stride(const gnncca_mpn_dims* d, int64_t n, int64_t e);
 // partial slabs for the tail kernel.  One workgroup per CU (144 KB of LDS), so the cost is counted in ROUNDS of 256 workgroups.
 int enc_lds_ksplit(int64_t n_nodes, int K);
 Workspace carve(const gnncca_mpn_dims* d, int64_t n, int64_t e);
+
+// Workspace of the fused backward (gnncca_mpn_backward*, mpn_train.hip): byte offsets, all multiples of 256.  `d` must have passed
+// backward_ok (a two-layer node encoder); F1 is its first layer's width.
+struct BwdWorkspace {
+    size_t gh0_acc, ge0_acc;   // reattach_initial_nodes / _edges: d loss / d h0, d loss / d e0 via the copies
+    size_t deg, Q;
+    size_t hmax;               // 'max' aggregation only: [N][32] maxima, then [N][32] tie counts
+    size_t dP_all;             // one [N][44] table per step, cleared once
+    size_t Hb[2], Gb[2], a1, gz1;
+    size_t part;               // split-K partials of the a1 recompute: 32 slabs [N][F1]
+    size_t bn_sums, bn_red;    // BatchNorm backward scratch: 2 x 64 doubles, 2 x 64 floats
+    size_t total;
+};
+inline BwdWorkspace carve_backward(const gnncca_mpn_dims* d, int64_t n, int64_t e) {
+    BwdWorkspace w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t N = (size_t)(n > 0 ? n : 0), E = (size_t)(e > 0 ? e : 0), F1 = (size_t)d->enc_node.layers[0].out_dim;
+    const size_t L = (size_t)(d->num_enc_steps > 1 ? d->num_enc_steps : 1);
+    w.gh0_acc = take(N * kH * 4), w.ge0_acc = take(E * kEF * 4), w.deg = take(N * 4), w.Q = take(N * kH * 4);
+    w.hmax = take(2 * N * kH * 4), w.dP_all = take(L * N * 44 * 4);
+    for (int i = 0; i < 2; ++i) w.Hb[i] = take(N * kH * 4);
+    for (int i = 0; i < 2; ++i) w.Gb[i] = take(E * kEF * 4);
+    w.a1 = take(N * F1 * 4), w.gz1 = take(N * F1 * 4), w.part = take(32 * N * F1 * 4);
+    w.bn_sums = take(sizeof(double) * 2 * 64), w.bn_red = take(sizeof(float) * 2 * 64), w.total = off;
+    return w;
+}
+
+// Workspace of the pruning / clustering stage (gnncca_post_prune_cluster*, mpn_post.hip): a graph plan of its own.
+struct PostWorkspace { size_t flags, blockflags, seg_ptr, col32, perm, cursor, total; };
+inline PostWorkspace carve_post(int64_t n, int64_t e) {
+    PostWorkspace w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t N = (size_t)(n > 0 ? n : 0), E = (size_t)(e > 0 ? e : 0);
+    w.flags = take(256), w.blockflags = take((E / 256 + 2) * 4), w.seg_ptr = take((N + 1) * 4), w.col32 = take(E * 4);
+    w.perm = take(E * 4), w.cursor = take((N + 1) * 4), w.total = off;
+    return w;
+}
+
+// ---- kernels of mpn_forward.hip that mpn_post.hip and mpn_train.hip launch too ---------------------------------------------------
+// Every __global__ kernel is compiled in exactly one translation unit; where another unit needs one, it calls a host launcher defined
+// beside the kernel (encoder.cuh, generic.cuh).  A launcher only launches -- same grid, block and LDS as a launch written in place -- and
+// the caller checks hipGetLastError() as it does after launches of its own.
+struct EncPlanParams {   // encoder.cuh: enc_gemm_plan_kernel, plan_only_kernel and the GEMMs the graph plan rides in
+    const float* in;
+    const float* W;
+    float* part;
+    const long long* ei;
+    int* seg_ptr;
+    int* col32;
+    unsigned* blockflags;
+    int M, K, O, kslice, vec_ok, nrt, nks, gemm_blocks, E, N;
+    int ell_S;  // slots per node of the padded step layout to validate the degrees against (0: none)
+    int plan_span;  // 1024-edge plan blocks per plan workgroup (plan.cuh: 1, or kPlanSpan on a plan-only launch of a big batch)
+};
+struct GenSeg {          // generic.cuh: one segment of a virtual concatenation
+    const float* ptr;   // [rows][ld]
+    const int* idx;     // optional row gather (row32 / col32 in the caller's edge order), or null
+    int ld, width;
+};
+void launch_plan_only(const EncPlanParams& p, int blocks, gnncca_stream_t stream);
+void launch_enc_gemm_plan(const EncPlanParams& p, int blocks, gnncca_stream_t stream);
+void launch_reduce_bias_act(const float* part, const float* bias, float* act, int M, int O, int ks, int relu, gnncca_stream_t stream);
+void launch_gen_plan_finish(const long long* ei, int E, int N, int* seg_ptr, int* col32, int* perm, int* cursor, unsigned* flags,
+                            const unsigned* blockflags, gnncca_stream_t stream);
+void launch_gen_index32(const long long* ei, int E, int N, int* row32, int* col32, gnncca_stream_t stream);
+// one column group of a dense layer: `O` <= 2048 outputs of a layer whose padded weight rows are `ldw` floats apart
+void launch_gen_dense(const GenSeg& s0, const GenSeg& s1, const GenSeg& s2, const float* Wt, const float* b, float* out, long long M, int K,
+                      int O, int ldw, int ld_out, int relu, gnncca_stream_t stream);
+void launch_gen_aggregate(const float* m, const int* seg_ptr, const int* perm, const unsigned* flags, float* h, int N, int H, int agg,
+                          gnncca_stream_t stream);
+void launch_gen_poison(float* out, long long n, const unsigned* flags, gnncca_stream_t stream);
 
 }  // namespace gnncca

@@ -17,20 +17,11 @@
 #include <cmath>
 #include <cstdint>
 
-#include "internal.h"
+#include "hip_try.h"
 
 #pragma clang fp contract(off)
 
 namespace gnncca {
-
-#define HIP_TRY_LS(expr)                   \
-    do {                                   \
-        hipError_t _e = (expr);            \
-        if (_e != hipSuccess) {            \
-            g_last_hip_error = (int)_e;    \
-            return GNNCCA_ERR_HIP;         \
-        }                                  \
-    } while (0)
 
 constexpr int kLossBlock = 256;
 constexpr int kChunk = 8;                 // steps per workgroup row: the accumulators of 8 steps live in registers
@@ -278,12 +269,12 @@ int gnncca_edge_loss_forward(const float* logits, const float* labels, int32_t n
         else
             hipLaunchKernelGGL(edge_loss_partials_kernel<kChunk>, dim3((unsigned)nb, (unsigned)nchunks), dim3(kLossBlock), 0, st, logits,
                                labels, (long long)n_edges, (int)n_steps, weighted, focal, pw, focusing_param, balance_param, part);
-        HIP_TRY_LS(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(edge_loss_finish_kernel, dim3(1), dim3(kLossBlock), 0, st, part, nb, (long long)n_edges, (int)n_steps, focal,
                        (double)focusing_param, (double)balance_param, loss_out, record, history, (long long)capacity,
                        reinterpret_cast<long long*>(cursor));
-    HIP_TRY_LS(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -298,7 +289,7 @@ int gnncca_edge_loss_backward(const float* logits, const float* labels, int32_t 
     const unsigned blocks = (unsigned)(want < 16384 ? want : 16384);
     hipLaunchKernelGGL(edge_loss_backward_kernel, dim3(blocks), dim3(kLossBlock), 0, static_cast<hipStream_t>(stream), logits, labels,
                        (long long)n_edges, (int)n_steps, weighted, weighted ? pos_weight : 1.f, grad_loss, record, grad);
-    HIP_TRY_LS(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 

@@ -1,4 +1,4 @@
-// mpn_forward.hip -- gfx950 (MI355X / CDNA4) kernels and the C-ABI forward of the GNN-CCA message-passing path.
+// mpn_forward.hip -- gfx950 (MI355X / CDNA4) inference kernels and the C-ABI forward of the GNN-CCA message-passing path.
 //
 // Algebra (derived from models/mpn.py:48,68-69,97-99): with the edge-MLP weight split by the
 // cat order [x[row] | x[col] | e] and the node-MLP weight by [x[row] | e'],
@@ -16,7 +16,12 @@
 //   topology     seg_ptr: [N+1] int32 CSR offsets by source node;  col32 [E] int32 (sorted order)
 // One wave owns (a share of) one source node's contiguous edge segment, so the per-destination reduction needs
 // no atomics and is bitwise reproducible.
-#include "common.cuh"
+//
+// This translation unit is INFERENCE: the graph plan, the node encoder's GEMM forms, the message-passing step kernels, the generic family
+// and the forward's route (forward_impl).  Post-processing and the one-call frame pipeline are mpn_post.hip, training (fused backward,
+// layer-by-layer engine, device packer) is mpn_train.hip; every __global__ kernel is compiled in exactly one of the three, and the few that
+// another unit launches too have host launchers (internal.h).
+#include "forward_diag.cuh"
 #include "wave_reduce.cuh"
 #include "plan.cuh"
 #include "encoder.cuh"
@@ -29,11 +34,6 @@
 #include "enc_f16_slices.cuh"
 #include "generic_fused.cuh"
 #include "generic.cuh"
-#include "postprocess.cuh"
-#include "backward.cuh"
-#include "input_grads.cuh"
-#include "pack_device.cuh"
-#include "train_generic.cuh"
 
 using namespace gnncca;
 
@@ -686,96 +686,6 @@ int gnncca_mpn_forward_train(const gnncca_mpn_dims* d, const void* packed_dev, c
                         trace, stream, nullptr, 0u, dropout);
 }
 
-size_t gnncca_mlp_eval_workspace_bytes(const gnncca_mlp* mlp, int64_t rows) {
-    if (!mlp_shape_ok(mlp) || rows < 0) return 0;
-    return mlp_eval_ws(mlp, rows, nullptr, nullptr, nullptr, nullptr);
-}
-
-int gnncca_mlp_eval(const gnncca_mlp* mlp, const float* const* params_dev, int n_params, const float* in, int64_t rows, float* out,
-                    void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
-    return mlp_eval_impl(mlp, params_dev, n_params, in, rows, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gnncca_gather_cat(const float* a, const int64_t* ia, int wa, int64_t rows_a, const float* b, const int64_t* ib, int wb, int64_t rows_b,
-                      const float* c, const int64_t* ic, int wc, int64_t rows_c, int64_t rows, float* out, gnncca_stream_t stream) {
-    if (rows < 0 || wa < 0 || wb < 0 || wc < 0 || wa + wb + wc <= 0 || !out) return GNNCCA_ERR_INVALID_ARG;
-    if ((wa > 0 && (!a || rows_a <= 0)) || (wb > 0 && (!b || rows_b <= 0)) || (wc > 0 && (!c || rows_c <= 0))) return rows == 0 ? GNNCCA_OK : GNNCCA_ERR_INVALID_ARG;
-    if (rows == 0) return GNNCCA_OK;
-    hipLaunchKernelGGL(tr_cat64_kernel, grid1((size_t)rows * (wa + wb + wc), 256), dim3(256), 0, static_cast<hipStream_t>(stream), a,
-                       reinterpret_cast<const long long*>(ia), wa, (long long)rows_a, b, reinterpret_cast<const long long*>(ib), wb,
-                       (long long)rows_b, c, reinterpret_cast<const long long*>(ic), wc, (long long)rows_c, out, (long long)rows);
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
-}
-
-int gnncca_pad_frame(const float* x, int64_t n_nodes, const int64_t* edge_index, const float* edge_attr, int64_t n_edges, float* x_pad,
-                     int64_t n_real_max, int n_dummy, int64_t* edge_index_pad, float* edge_attr_pad, int64_t e_pad, int node_in, int edge_in,
-                     gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_real_max < n_nodes || e_pad < n_edges || n_dummy < 1 || node_in < 1 || edge_in < 1) return GNNCCA_ERR_INVALID_ARG;
-    if (!x_pad || !edge_index_pad || !edge_attr_pad || (n_nodes > 0 && !x) || (n_edges > 0 && (!edge_index || !edge_attr))) return GNNCCA_ERR_INVALID_ARG;
-    const long long total = (n_real_max + n_dummy) * (long long)node_in + e_pad * (2ll + edge_in);
-    const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(pad_frame_kernel, dim3(std::max(blocks, 1u)), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long long)n_nodes,
-                       reinterpret_cast<const long long*>(edge_index), edge_attr, (long long)n_edges, x_pad, (long long)n_real_max, n_dummy,
-                       reinterpret_cast<long long*>(edge_index_pad), edge_attr_pad, (long long)e_pad, node_in, edge_in);
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
-}
-
-size_t gnncca_aggregate_workspace_bytes(int64_t n_nodes, int64_t n_edges) { return agg_ws(n_nodes, n_edges).total; }
-
-int gnncca_aggregate(const float* messages, const int64_t* edge_index, int64_t n_nodes, int64_t n_edges, int width, int agg, float* out,
-                     void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
-    return aggregate_impl(messages, edge_index, n_nodes, n_edges, width, agg, out, workspace, workspace_bytes,
-                          static_cast<hipStream_t>(stream));
-}
-
-size_t gnncca_train_tape_bytes(const gnncca_mpn_dims* d, int64_t n_nodes, int64_t n_edges) {
-    TrPlan P;
-    if (!d || n_nodes < 0 || n_edges < 0 || !tr_plan(d, n_nodes, n_edges, &P)) return 0;
-    return P.total;
-}
-
-int gnncca_train_tape_latents(const gnncca_mpn_dims* d, int64_t n_nodes, int64_t n_edges, int64_t* offsets_out, int n_offsets) {
-    TrPlan P;
-    if (!d || !offsets_out || n_nodes < 0 || n_edges < 0 || !tr_plan(d, n_nodes, n_edges, &P)) return GNNCCA_ERR_INVALID_ARG;
-    const int L = d->num_enc_steps;
-    if (n_offsets != 2 + 2 * L) return GNNCCA_ERR_INVALID_ARG;
-    auto last = [](const TrCall& c, const gnncca_mlp& m) -> int64_t { return m.n_layers > 0 ? (int64_t)c.lay[m.n_layers - 1].a : -1; };
-    offsets_out[0] = last(P.enc_node, d->enc_node);
-    offsets_out[1] = last(P.enc_edge, d->enc_edge);
-    for (int s = 0; s < L; ++s) {
-        offsets_out[2 + 2 * s] = (int64_t)P.h[s];
-        offsets_out[3 + 2 * s] = last(P.edge[s], d->edge_mlp);
-    }
-    return GNNCCA_OK;
-}
-
-int gnncca_train_forward(const gnncca_mpn_dims* d, float* const* params_dev, int n_params, const float* x, const int64_t* edge_index,
-                         const float* edge_attr, int64_t n_nodes, int64_t n_edges, void* tape, size_t tape_bytes, float* logits_out,
-                         const gnncca_dropout* dropout, gnncca_stream_t stream) {
-    if (!x || (n_edges > 0 && (!edge_index || !edge_attr || !logits_out))) return GNNCCA_ERR_INVALID_ARG;
-    return train_forward_impl(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, tape, tape_bytes, logits_out, dropout,
-                              static_cast<hipStream_t>(stream));
-}
-
-int gnncca_train_backward(const gnncca_mpn_dims* d, float* const* params_dev, int n_params, const float* x, const int64_t* edge_index,
-                          const float* edge_attr, int64_t n_nodes, int64_t n_edges, void* tape, size_t tape_bytes,
-                          const float* grad_logits, float* const* grads_dev, const gnncca_dropout* dropout, gnncca_stream_t stream) {
-    return gnncca_train_backward_inputs(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, tape, tape_bytes, grad_logits,
-                                        grads_dev, dropout, nullptr, stream);
-}
-
-int gnncca_train_backward_inputs(const gnncca_mpn_dims* d, float* const* params_dev, int n_params, const float* x,
-                                 const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges, void* tape,
-                                 size_t tape_bytes, const float* grad_logits, float* const* grads_dev, const gnncca_dropout* dropout,
-                                 const gnncca_input_grads* input_grads, gnncca_stream_t stream) {
-    if (!x || (n_edges > 0 && (!edge_index || !edge_attr))) return GNNCCA_ERR_INVALID_ARG;
-    return train_backward_impl(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, tape, tape_bytes, grad_logits,
-                               grads_dev, dropout, input_grads ? input_grads->dx : nullptr,
-                               input_grads ? input_grads->d_edge_attr : nullptr, static_cast<hipStream_t>(stream));
-}
-
 int gnncca_mpn_forward_profiled(const gnncca_mpn_dims* d, const void* packed_dev, const float* x,
                                 const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
                                 void* workspace, size_t workspace_bytes, float* logits_out, gnncca_stream_t stream,
@@ -791,627 +701,6 @@ int gnncca_mpn_forward_profiled(const gnncca_mpn_dims* d, const void* packed_dev
                      nullptr, stream, &p, profile->options);
     const int s2 = prof_end(&p, st);
     return s != GNNCCA_OK ? s : s2;
-}
-
-
-// ---- SURVEY.md 8f row N2 ------------------------------------------------------------------------------------
-size_t gnncca_post_workspace_bytes(int64_t n_nodes, int64_t n_edges) {
-    if (n_nodes < 0 || n_edges < 0) return 0;
-    const size_t N = (size_t)n_nodes, E = (size_t)n_edges;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    return up(256) + up((E / 256 + 2) * 4) + up((N + 1) * 4) + up(E * 4) + up(E * 4) + up((N + 1) * 4);
-}
-
-int gnncca_post_threshold(const float* logits, int64_t n_edges, float* probs_out, int64_t* predictions_out,
-                          gnncca_stream_t stream) {
-    if (n_edges < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (n_edges == 0) return GNNCCA_OK;
-    if (!logits || !probs_out || !predictions_out) return GNNCCA_ERR_INVALID_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(post_threshold_kernel, grid1((size_t)n_edges, 256), dim3(256), 0, st, logits, (long long)n_edges, probs_out,
-                       reinterpret_cast<long long*>(predictions_out));
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
-}
-
-int gnncca_post_prune_cluster(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                              void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
-                              int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out, gnncca_stream_t stream) {
-    return gnncca_post_prune_cluster_frames(edge_index, predictions, n_nodes, n_edges, nullptr, nullptr, 0, workspace,
-                                            workspace_bytes, pruned_out, flow_out, flow_in, labels_out, n_clusters_out, stream);
-}
-
-int gnncca_post_prune_cluster_frames(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                                     const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
-                                     void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
-                                     int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out,
-                                     gnncca_stream_t stream) {
-    return gnncca_post_prune_cluster_frames_ex(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace,
-                                               workspace_bytes, pruned_out, flow_out, flow_in, labels_out, n_clusters_out, nullptr, nullptr, stream);
-}
-
-// `plan` (internal; null from the public entry points): the graph plan the MPN forward of the same batch left in ITS workspace (seg_ptr,
-// col32, perm, flags) -- gnncca_frames_forward hands it over, so the pruning needs no plan launches of its own
-struct PostPlan {
-    const int* seg_ptr;
-    const int* col32;
-    const int* perm;
-    const unsigned* flags;
-    // gnncca_frames_forward's two other savings: the counters were zeroed by an earlier kernel of the batch (no memset node here), and the
-    // threshold rides in the prune kernel (logits in, probabilities and predictions out)
-    bool counters_zeroed;
-    const float* logits;
-    float* probs_out;
-    int64_t* preds_out;
-};
-static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                                   const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
-                                   size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in, int32_t* labels_out,
-                                   int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out, const PostPlan* plan,
-                                   gnncca_stream_t stream);
-
-int gnncca_post_prune_cluster_frames_ex(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                                        const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
-                                        size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in,
-                                        int32_t* labels_out, int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out,
-                                        gnncca_stream_t stream) {
-    return post_prune_cluster_impl(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace, workspace_bytes,
-                                   pruned_out, flow_out, flow_in, labels_out, n_clusters_out, sizes_scratch, triggers_out, nullptr, stream);
-}
-
-static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                                   const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
-                                   size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in, int32_t* labels_out,
-                                   int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out, const PostPlan* plan,
-                                   gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
-    if ((sizes_scratch == nullptr) != (triggers_out == nullptr)) return GNNCCA_ERR_INVALID_ARG;
-    if ((node_ptr_dev == nullptr) != (edge_ptr_dev == nullptr) || (node_ptr_dev != nullptr && n_frames == 0))
-        return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    const size_t n_trig = (size_t)(node_ptr_dev ? n_frames : 1);
-    if (n_nodes == 0) {
-        if (n_clusters_out) HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
-        if (triggers_out) HIP_TRY(hipMemsetAsync(triggers_out, 0, n_trig * sizeof(int32_t), static_cast<hipStream_t>(stream)));
-        return GNNCCA_OK;
-    }
-    if (!workspace || !flow_out || !flow_in || !labels_out || !n_clusters_out) return GNNCCA_ERR_INVALID_ARG;
-    if (n_edges > 0 && (!edge_index || !predictions || !pruned_out)) return GNNCCA_ERR_INVALID_ARG;
-    if (!plan && workspace_bytes < gnncca_post_workspace_bytes(n_nodes, n_edges)) return GNNCCA_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int N = (int)n_nodes, E = (int)n_edges;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    char* base = static_cast<char*>(workspace);
-    unsigned* flags = reinterpret_cast<unsigned*>(base);
-    size_t off = up(256);
-    unsigned* blockflags = reinterpret_cast<unsigned*>(base + off);
-    off += up(((size_t)E / 256 + 2) * 4);
-    int* seg_ptr = reinterpret_cast<int*>(base + off);
-    off += up(((size_t)N + 1) * 4);
-    int* col32 = reinterpret_cast<int*>(base + off);
-    off += up((size_t)E * 4);
-    int* perm = reinterpret_cast<int*>(base + off);
-    off += up((size_t)E * 4);
-    int* cursor = reinterpret_cast<int*>(base + off);
-    if (plan) {   // the MPN forward's plan of the same edge_index: nothing to build here
-        seg_ptr = const_cast<int*>(plan->seg_ptr), col32 = const_cast<int*>(plan->col32), perm = const_cast<int*>(plan->perm);
-        flags = const_cast<unsigned*>(plan->flags);
-    }
-    const long long* ei = reinterpret_cast<const long long*>(edge_index);
-    const long long* pred = reinterpret_cast<const long long*>(predictions);
-    long long* pruned = reinterpret_cast<long long*>(pruned_out);
-    // zero the counters: one memset when the caller laid flow_out | flow_in | n_clusters out back to back (gnn_cca_amd.postprocess does)
-    const bool one_block = flow_in == flow_out + N && n_clusters_out == flow_in + N;
-    const bool trig_block = one_block && triggers_out && sizes_scratch == n_clusters_out + 1 && triggers_out == sizes_scratch + N;
-    if (plan && plan->counters_zeroed) {
-        // nothing: done launches ago
-    } else if (trig_block) {
-        HIP_TRY(hipMemsetAsync(flow_out, 0, ((size_t)3 * N + 1 + n_trig) * 4, st));
-    } else if (one_block) {
-        HIP_TRY(hipMemsetAsync(flow_out, 0, ((size_t)2 * N + 1) * 4, st));
-    } else {
-        HIP_TRY(hipMemsetAsync(flow_out, 0, (size_t)N * 4, st));
-        HIP_TRY(hipMemsetAsync(flow_in, 0, (size_t)N * 4, st));
-        HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), st));
-    }
-    if (triggers_out && !trig_block && !(plan && plan->counters_zeroed)) {
-        HIP_TRY(hipMemsetAsync(sizes_scratch, 0, (size_t)N * 4, st));
-        HIP_TRY(hipMemsetAsync(triggers_out, 0, n_trig * 4, st));
-    }
-    if (E > 0 && !plan) {
-        EncPlanParams ep;
-        std::memset(&ep, 0, sizeof(ep));
-        ep.ei = ei;
-        ep.seg_ptr = seg_ptr;
-        ep.col32 = col32;
-        ep.blockflags = blockflags;
-        ep.E = E;
-        ep.N = N;
-        hipLaunchKernelGGL(plan_only_kernel, dim3(plan_num_blocks(E)), dim3(256), 0, st, ep);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!plan) {
-        hipLaunchKernelGGL(gen_plan_finish_kernel, dim3(1), dim3(256), 0, st, ei, E, N, seg_ptr, col32, perm, cursor, flags,
-                           (const unsigned*)blockflags);
-        HIP_TRY(hipGetLastError());
-    }
-    if (E > 0) {
-        if (plan && plan->logits)
-            hipLaunchKernelGGL(post_prune_kernel<true>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, (const int*)seg_ptr,
-                               (const int*)col32, (const int*)perm, (const unsigned*)flags, pruned, flow_out, flow_in, plan->logits,
-                               plan->probs_out, reinterpret_cast<long long*>(plan->preds_out));
-        else
-            hipLaunchKernelGGL(post_prune_kernel<false>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, (const int*)seg_ptr,
-                               (const int*)col32, (const int*)perm, (const unsigned*)flags, pruned, flow_out, flow_in, (const float*)nullptr,
-                               (float*)nullptr, (long long*)nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(post_cc_kernel, dim3(node_ptr_dev ? (unsigned)n_frames : 1u), dim3(1024), 0, st, ei,
-                       (const long long*)pruned, (long long)E, N, node_ptr_dev, edge_ptr_dev, labels_out, n_clusters_out,
-                       (const int*)flow_out, (const int*)flow_in, sizes_scratch, triggers_out);
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
-}
-
-
-int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
-                          size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
-                          gnncca_stream_t stream) {
-    if (!d || !io || !io->staged_dev) return GNNCCA_ERR_INVALID_ARG;
-    const int64_t n = io->n_nodes, g = io->n_frames, e = io->n_edges;
-    if (n < 1 || g < 1 || e < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (n > 4096) return GNNCCA_ERR_UNSUPPORTED;   // (the one-launch normalisation's limit; bigger batches take the separate entry points)
-    if (!io->node_embeds || !io->reid_embeds || !io->edge_index || !io->edge_attr || !io->edge_labels || !io->logits || !io->probs ||
-        !io->predictions || !io->pruned || !io->counters || !io->labels || (io->normalize && (!io->node_norm || !io->reid_norm)))
-        return GNNCCA_ERR_INVALID_ARG;
-    if (io->counters_len < 3 * n + 1 + g) return GNNCCA_ERR_INVALID_ARG;   // flow_out | flow_in | n_clusters | sizes | triggers (ABI 2: stated, not assumed)
-    // the staging image (gnncca_plan_frames): f64 xw[n], yw[n], max_dist[g]; i64 ids[n]; i32 person, cam, graph_of, graph_ptr, src_order, edge_ptr, edge_ptr_g
-    const char* base = static_cast<const char*>(io->staged_dev);
-    gnncca_frames fr;
-    fr.xw = reinterpret_cast<const double*>(base);
-    fr.yw = fr.xw + n;
-    fr.max_dist = fr.yw + n;
-    const int32_t* i32 = reinterpret_cast<const int32_t*>(base + 8 * (3 * n + g));
-    fr.person_id = i32, fr.cam = i32 + n, fr.graph_of = i32 + 2 * n, fr.graph_ptr = i32 + 3 * n;
-    fr.src_order = i32 + 3 * n + g + 1, fr.edge_ptr = i32 + 4 * n + g + 1;
-    const int32_t* edge_ptr_g = i32 + 5 * n + g + 2;
-    const float* x = io->node_embeds;
-    const float* reid = io->reid_embeds;
-    int st = GNNCCA_OK;
-    if (io->normalize) {
-        st = gnncca_normalize_columns2(io->reid_embeds, io->reid_dim, io->reid_norm, io->node_embeds, d->node_in, io->node_norm, n, stream);
-        if (st != GNNCCA_OK) return st;
-        x = io->node_norm, reid = io->reid_norm;
-    }
-    // (the post stage's counters -- flow_out | flow_in | n_clusters | sizes | triggers -- are zeroed by this launch: no memset node later)
-    const bool zero_here = e > 0 && mpn_workspace != nullptr;
-    st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, io->edge_index, io->edge_attr, io->edge_labels,
-                             zero_here ? io->counters : nullptr, zero_here ? 3 * n + 1 + g : 0, stream);
-    if (st != GNNCCA_OK) return st;
-    const int n_out = gnncca_num_outputs(d);
-    if (n_out < 1) return GNNCCA_ERR_UNSUPPORTED;
-    if (e > 0) {
-        st = gnncca_mpn_forward_ex(d, packed_dev, x, io->edge_index, io->edge_attr, n, e, mpn_workspace, mpn_workspace_bytes, io->logits, nullptr,
-                                   options, stream);
-        if (st != GNNCCA_OK) return st;
-        if (!zero_here) {   // (no shared plan: the threshold keeps its own launch)
-            st = gnncca_post_threshold(io->logits + (size_t)(n_out - 1) * e, e, io->probs, io->predictions, stream);
-            if (st != GNNCCA_OK) return st;
-        }
-    }
-    // the pruning searches reverse edges in the CSR plan of edge_index -- the one the forward above left in ITS workspace (seg_ptr / col32 /
-    // perm / flag word: same plan_block + plan_finish, same stream): handed over instead of being built a second time (two launches less)
-    PostPlan plan;
-    const PostPlan* have_plan = nullptr;
-    if (e > 0 && mpn_workspace) {
-        char* wb = static_cast<char*>(mpn_workspace);
-        if (classify(d) == kFamilyMfma32x6) {
-            const Workspace ws = carve(d, n, e);
-            plan = PostPlan{reinterpret_cast<const int*>(wb + ws.seg_ptr), reinterpret_cast<const int*>(wb + ws.col32),
-                            reinterpret_cast<const int*>(wb + ws.perm), reinterpret_cast<const unsigned*>(wb + ws.flags), false, nullptr, nullptr, nullptr};
-        } else {
-            const GenWorkspace ws = carve_generic(d, n, e);
-            plan = PostPlan{reinterpret_cast<const int*>(wb + ws.seg_ptr), reinterpret_cast<const int*>(wb + ws.col32),
-                            reinterpret_cast<const int*>(wb + ws.perm), reinterpret_cast<const unsigned*>(wb + ws.flags), false, nullptr, nullptr, nullptr};
-        }
-        plan.counters_zeroed = zero_here;
-        plan.logits = io->logits + (size_t)(n_out - 1) * e, plan.probs_out = io->probs, plan.preds_out = io->predictions;
-        have_plan = &plan;
-    }
-    int32_t* c = io->counters;   // flow_out | flow_in | n_clusters | sizes (scratch) | triggers [G]
-    return post_prune_cluster_impl(io->edge_index, io->predictions, n, e, fr.graph_ptr, edge_ptr_g, (int32_t)g, post_workspace, post_workspace_bytes,
-                                   io->pruned, c, c + n, io->labels, c + 2 * n, c + 2 * n + 1, c + 3 * n + 1, have_plan, stream);
-}
-
-// ---- backward ---------------------------------------------------------------------------
-// gnncca_dropout -> DropCfg; GNNCCA_OK with all p == 0 for a null / inactive one
-static int drop_cfg(const gnncca_dropout* dropout, DropCfg* out) {
-    std::memset(out, 0, sizeof(*out));
-    if (!dropout) return GNNCCA_OK;
-    const float ps[4] = {dropout->p_enc, dropout->p_edge, dropout->p_node, dropout->p_cls};
-    bool any = false;
-    for (float q : ps) {
-        if (!(q >= 0.f && q < 1.f)) return GNNCCA_ERR_INVALID_ARG;
-        any = any || q > 0.f;
-    }
-    if (!any) return GNNCCA_OK;
-    if (!dropout->seed_dev) return GNNCCA_ERR_INVALID_ARG;
-    out->p_enc = dropout->p_enc, out->p_edge = dropout->p_edge, out->p_node = dropout->p_node, out->p_cls = dropout->p_cls;
-    out->seed = reinterpret_cast<const unsigned long long*>(dropout->seed_dev);
-    return GNNCCA_OK;
-}
-
-static bool backward_ok(const gnncca_mpn_dims* d) {
-    if (classify(d) != kFamilyMfma32x6) return false;
-    if (d->num_enc_steps < 1) return false;
-    if (d->enc_node.n_layers != 2) return false;
-    const gnncca_mlp* all[5] = {&d->enc_node, &d->enc_edge, &d->edge_mlp, &d->node_mlp, &d->cls_edge};
-    for (int mi = 0; mi < 5; ++mi)
-        for (int l = 0; l < all[mi]->n_layers; ++l)
-            if (all[mi]->layers[l].has_bn && !(mi == 4 && l == 0 && d->cls_edge.n_layers == 2)) return false;
-    return true;  // BatchNorm is allowed only between the classifier's two layers (the shipped inference config)
-}
-
-// index of the first tensor of layer `l` of MLP `mi` in the canonical parameter order
-static int param_index(const gnncca_mpn_dims* d, int mi, int l) {
-    int idx = 0;
-    for (int m = 0; m < 5; ++m) {
-        const gnncca_mlp& mlp = mlp_by_index(d, m);
-        for (int k = 0; k < mlp.n_layers; ++k) {
-            if (m == mi && k == l) return idx;
-            idx += 2 + (mlp.layers[k].has_bn ? 4 : 0);
-        }
-    }
-    return idx;
-}
-
-// Train-mode classifier with BatchNorm1d between its two layers: batch statistics over the E edges for every
-// classified step (models/mpn.py:290-293 with models/mlp.py:15 in train mode); running buffers updated in place.
-int gnncca_classifier_train(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* e_steps,
-                            int64_t n_edges, void* scratch /* 2*C1 doubles */, float* bn_stat_out /* [n_out][C1][2] */,
-                            float* logits_out, gnncca_stream_t stream) {
-    return gnncca_classifier_train_dropout(d, params_dev, n_params, e_steps, n_edges, scratch, bn_stat_out, logits_out, nullptr, stream);
-}
-
-int gnncca_classifier_train_dropout(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* e_steps,
-                                    int64_t n_edges, void* scratch /* 2*C1 doubles */, float* bn_stat_out /* [n_out][C1][2] */,
-                                    float* logits_out, const gnncca_dropout* dropout, gnncca_stream_t stream) {
-    DropCfg drop;
-    {
-        const int ds = drop_cfg(dropout, &drop);
-        if (ds != GNNCCA_OK) return ds;
-    }
-    if (!dims_valid(d) || !params_dev || n_params != gnncca_param_count(d) || n_edges < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (!backward_ok(d) || d->cls_edge.n_layers != 2 || !d->cls_edge.layers[0].has_bn) return GNNCCA_ERR_UNSUPPORTED;
-    if (n_edges == 0) return GNNCCA_OK;
-    if (!e_steps || !scratch || !bn_stat_out || !logits_out) return GNNCCA_ERR_INVALID_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int C1 = d->cls_edge.layers[0].out_dim, L = d->num_enc_steps, first_cls = L - d->num_class_steps + 1;
-    const int pc = param_index(d, 4, 0);
-    const float *W1 = params_dev[pc], *b1 = params_dev[pc + 1], *gamma = params_dev[pc + 2], *beta = params_dev[pc + 3];
-    float *rm = const_cast<float*>(params_dev[pc + 4]), *rv = const_cast<float*>(params_dev[pc + 5]);
-    const float *W2 = params_dev[pc + 6], *b2 = params_dev[pc + 7];
-    const long long E = n_edges;
-    double* sums = static_cast<double*>(scratch);
-    int li = 0;
-    for (int s = 1; s <= L; ++s) {
-        if (s < first_cls) continue;
-        const float* e = e_steps + (size_t)(s - 1) * E * kEF;
-        float* stat = bn_stat_out + (size_t)li * C1 * 2;
-        HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C1, st));
-        hipLaunchKernelGGL(cls_bn_stats_kernel, grid1((size_t)E, 256), dim3(256), 0, st, e, E, W1, b1, C1, sums);
-        hipLaunchKernelGGL(cls_bn_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, E, C1, stat, rm, rv);
-        hipLaunchKernelGGL(cls_bn_apply_kernel, grid1((size_t)E, 256), dim3(256), 0, st, e, E, W1, b1, gamma, beta, (const float*)stat,
-                           W2, b2, C1, logits_out + (size_t)li * E, drop, li);
-        HIP_TRY(hipGetLastError());
-        ++li;
-    }
-    return GNNCCA_OK;
-}
-
-int gnncca_backward_supported(const gnncca_mpn_dims* d) {
-    if (!dims_valid(d)) return GNNCCA_ERR_INVALID_ARG;
-    return backward_ok(d) ? GNNCCA_OK : GNNCCA_ERR_UNSUPPORTED;
-}
-
-size_t gnncca_backward_workspace_bytes(const gnncca_mpn_dims* d, int64_t n_nodes, int64_t n_edges) {
-    if (!dims_valid(d) || !backward_ok(d) || n_nodes < 0 || n_edges < 0) return 0;
-    const size_t N = (size_t)n_nodes, E = (size_t)n_edges, F1 = (size_t)d->enc_node.layers[0].out_dim;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t L = (size_t)std::max(d->num_enc_steps, 1);
-    return up(N * kH * 4) + up(E * kEF * 4) + up(N * 4) + up(N * kH * 4) + up(2 * N * kH * 4) + up(L * N * 44 * 4) + 2 * up(N * kH * 4) + 2 * up(E * kEF * 4) + 2 * up(N * F1 * 4) +
-           up(32 * N * F1 * 4) + up(sizeof(double) * 128) + up(sizeof(float) * 128);
-}
-
-size_t gnncca_pack_program_bytes(void) { return sizeof(PackProgram); }
-
-int gnncca_pack_program(const gnncca_mpn_dims* d, void* program_host, size_t program_bytes) {
-    if (!dims_valid(d) || !program_host) return GNNCCA_ERR_INVALID_ARG;
-    if (classify(d) != kFamilyMfma32x6) return GNNCCA_ERR_UNSUPPORTED;
-    if (program_bytes < sizeof(PackProgram)) return GNNCCA_ERR_INVALID_ARG;
-    return pack_program(d, static_cast<PackProgram*>(program_host)) ? GNNCCA_OK : GNNCCA_ERR_UNSUPPORTED;
-}
-
-int gnncca_pack_weights_device(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const void* program_dev,
-                               void* packed_dev, size_t packed_bytes, gnncca_stream_t stream) {
-    if (!dims_valid(d) || !params_dev || !program_dev || !packed_dev) return GNNCCA_ERR_INVALID_ARG;
-    if (classify(d) != kFamilyMfma32x6) return GNNCCA_ERR_UNSUPPORTED;
-    if (n_params != gnncca_param_count(d) || n_params > kMaxPackParams) return GNNCCA_ERR_INVALID_ARG;
-    if (packed_bytes < gnncca_packed_weights_bytes(d)) return GNNCCA_ERR_INVALID_ARG;
-    PackProgram host;  // segment count only: the program itself is read on the device
-    if (!pack_program(d, &host)) return GNNCCA_ERR_UNSUPPORTED;
-    PackPtrs ptrs;
-    std::memset(&ptrs, 0, sizeof(ptrs));
-    for (int i = 0; i < n_params; ++i) {
-        if (!params_dev[i]) return GNNCCA_ERR_INVALID_ARG;
-        ptrs.p[i] = params_dev[i];
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(pack_device_kernel, dim3(64, (unsigned)host.n_segs + 1), dim3(256), 0, st,
-                       static_cast<const PackProgram*>(program_dev), ptrs, static_cast<float*>(packed_dev));
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
-}
-
-int gnncca_mpn_backward(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* x,
-                        const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
-                        const gnncca_trace* saved, const float* cls_bn_stat, const float* grad_logits,
-                        float* const* grads_dev, void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
-    return gnncca_mpn_backward_ex(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, saved, cls_bn_stat,
-                                  grad_logits, grads_dev, workspace, workspace_bytes, 0u, stream);
-}
-
-int gnncca_mpn_backward_ex(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* x,
-                           const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
-                           const gnncca_trace* saved, const float* cls_bn_stat, const float* grad_logits,
-                           float* const* grads_dev, void* workspace, size_t workspace_bytes, uint32_t options,
-                           gnncca_stream_t stream) {
-    return gnncca_mpn_backward_train(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, saved, cls_bn_stat,
-                                     grad_logits, grads_dev, workspace, workspace_bytes, options, nullptr, stream);
-}
-
-int gnncca_mpn_backward_train(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* x,
-                              const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
-                              const gnncca_trace* saved, const float* cls_bn_stat, const float* grad_logits,
-                              float* const* grads_dev, void* workspace, size_t workspace_bytes, uint32_t options,
-                              const gnncca_dropout* dropout, gnncca_stream_t stream) {
-    return gnncca_mpn_backward_inputs(d, params_dev, n_params, x, edge_index, edge_attr, n_nodes, n_edges, saved, cls_bn_stat,
-                                      grad_logits, grads_dev, workspace, workspace_bytes, options, dropout, nullptr, stream);
-}
-
-int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* x,
-                               const int64_t* edge_index, const float* edge_attr, int64_t n_nodes, int64_t n_edges,
-                               const gnncca_trace* saved, const float* cls_bn_stat, const float* grad_logits,
-                               float* const* grads_dev, void* workspace, size_t workspace_bytes, uint32_t options,
-                               const gnncca_dropout* dropout, const gnncca_input_grads* input_grads, gnncca_stream_t stream) {
-    float* const dx_out = input_grads ? input_grads->dx : nullptr;
-    float* const dattr_out = input_grads ? input_grads->d_edge_attr : nullptr;
-    DropCfg drop;
-    {
-        const int ds = drop_cfg(dropout, &drop);
-        if (ds != GNNCCA_OK) return ds;
-    }
-    if (!dims_valid(d) || n_nodes < 0 || n_edges < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (!backward_ok(d)) return GNNCCA_ERR_UNSUPPORTED;
-    if (n_params != gnncca_param_count(d) || !params_dev || !grads_dev) return GNNCCA_ERR_INVALID_ARG;
-    for (int i = 0; i < n_params; ++i)
-        if (!params_dev[i] || !grads_dev[i]) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int N = (int)n_nodes, E = (int)n_edges;
-    const int D = d->node_in, F1 = d->enc_node.layers[0].out_dim, A = d->edge_in;
-    const int L = d->num_enc_steps, first_cls = L - d->num_class_steps + 1;
-    const int c1 = d->cls_edge.n_layers == 2 ? d->cls_edge.layers[0].out_dim : 0;
-    // zero every gradient
-    if (!(options & GNNCCA_BWD_GRADS_ZEROED)) {
-        const gnncca_mlp* all[5] = {&d->enc_node, &d->enc_edge, &d->edge_mlp, &d->node_mlp, &d->cls_edge};
-        int pi = 0;
-        for (const gnncca_mlp* m : all)
-            for (int l = 0; l < m->n_layers; ++l) {
-                HIP_TRY(hipMemsetAsync(grads_dev[pi++], 0, (size_t)m->layers[l].in_dim * m->layers[l].out_dim * 4, st));
-                HIP_TRY(hipMemsetAsync(grads_dev[pi++], 0, (size_t)m->layers[l].out_dim * 4, st));
-                if (m->layers[l].has_bn)  // gamma, beta, and the two buffers (no gradient: left at zero)
-                    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemsetAsync(grads_dev[pi++], 0, (size_t)m->layers[l].out_dim * 4, st));
-            }
-    }
-    if (N == 0 || E == 0) {   // no edge, no logit: nothing reaches either input
-        if (dx_out && N > 0) HIP_TRY(hipMemsetAsync(dx_out, 0, (size_t)N * D * 4, st));
-        return GNNCCA_OK;
-    }
-    if (!x || !edge_index || !edge_attr || !saved || !saved->h_enc || !saved->e_enc || !saved->h_steps || !saved->e_steps ||
-        !grad_logits || !workspace)
-        return GNNCCA_ERR_INVALID_ARG;
-    if (workspace_bytes < gnncca_backward_workspace_bytes(d, n_nodes, n_edges)) return GNNCCA_ERR_WORKSPACE;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    char* base = static_cast<char*>(workspace);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = base + off; off += up(bytes); return q; };
-    float* gh0_acc = reinterpret_cast<float*>(take((size_t)N * kH * 4));   // reattach_initial_nodes: d loss / d h0 via the copies
-    float* ge0_acc = reinterpret_cast<float*>(take((size_t)E * kEF * 4));  // reattach_initial_edges: d loss / d e0 via the copies
-    int* deg = reinterpret_cast<int*>(take((size_t)N * 4));
-    float* Q = reinterpret_cast<float*>(take((size_t)N * kH * 4));
-    int* hmax = reinterpret_cast<int*>(take((size_t)2 * N * kH * 4));  // 'max' aggregation only: maxima, then tie counts
-    int* hcnt = hmax + (size_t)N * kH;
-    float* dP_all = reinterpret_cast<float*>(take((size_t)std::max(L, 1) * N * 44 * 4));  // one table per step, cleared once
-    float* Hb[2] = {reinterpret_cast<float*>(take((size_t)N * kH * 4)), reinterpret_cast<float*>(take((size_t)N * kH * 4))};
-    float* Gb[2] = {reinterpret_cast<float*>(take((size_t)E * kEF * 4)), reinterpret_cast<float*>(take((size_t)E * kEF * 4))};
-    float* a1 = reinterpret_cast<float*>(take((size_t)N * F1 * 4));
-    float* gz1 = reinterpret_cast<float*>(take((size_t)N * F1 * 4));
-    float* part = reinterpret_cast<float*>(take((size_t)32 * N * F1 * 4));  // split-K partials of the a1 recompute
-    const float *W1 = params_dev[0], *b1 = params_dev[1], *W2 = params_dev[2];
-    const float *We = params_dev[6], *Wn = params_dev[8], *bn = params_dev[9];
-    const bool cls_bn = d->cls_edge.layers[0].has_bn != 0;
-    if (cls_bn && !cls_bn_stat) return GNNCCA_ERR_INVALID_ARG;
-    const int pw2 = cls_bn ? 16 : 12;  // second classifier layer follows the four BatchNorm tensors
-    const float *Wc1 = params_dev[10], *bc1 = params_dev[11], *Wc2 = c1 ? params_dev[pw2] : nullptr;
-    float *gW1 = grads_dev[0], *gb1 = grads_dev[1], *gW2 = grads_dev[2], *gb2 = grads_dev[3];
-    float *gWe0 = grads_dev[4], *gbe0 = grads_dev[5], *gWe = grads_dev[6], *gbe = grads_dev[7];
-    float *gWn = grads_dev[8], *gbn = grads_dev[9], *gWc1 = grads_dev[10], *gbc1 = grads_dev[11];
-    float *gWc2 = c1 ? grads_dev[pw2] : nullptr, *gbc2 = c1 ? grads_dev[pw2 + 1] : nullptr;
-    double* bn_sums = reinterpret_cast<double*>(take(sizeof(double) * 2 * 64));
-    float* bn_red = reinterpret_cast<float*>(take(sizeof(float) * 2 * 64));
-    const long long* ei = reinterpret_cast<const long long*>(edge_index);
-    if (d->agg == GNNCCA_AGG_MEAN) {
-        HIP_TRY(hipMemsetAsync(deg, 0, (size_t)N * 4, st));
-        hipLaunchKernelGGL(bwd_degree_kernel, grid1((size_t)E, 256), dim3(256), 0, st, ei, (long long)E, N, deg);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemsetAsync(dP_all, 0, (size_t)std::max(L, 1) * N * 44 * 4, st));
-    const bool re_n = d->reattach_nodes != 0, re_e = d->reattach_edges != 0;
-    const int HI = re_n ? 2 * kH : kH, WeLd = 2 * HI + (re_e ? 2 * kEF : kEF), WnLd = HI + kEF;
-    if (re_n) HIP_TRY(hipMemsetAsync(gh0_acc, 0, (size_t)N * kH * 4, st));
-    if (re_e) HIP_TRY(hipMemsetAsync(ge0_acc, 0, (size_t)E * kEF * 4, st));
-    const float* g_h = nullptr;   // d loss / d h_s of the step being processed (null for s = L: its node update is dead)
-    const float* ge_in = nullptr; // d loss / d e_s arriving from step s+1
-    int out_idx = gnncca_num_outputs(d) - 1;
-    for (int s = L; s >= 1; --s) {
-        const float* h_prev = s == 1 ? saved->h_enc : saved->h_steps + (size_t)(s - 2) * N * kH;
-        const float* e_cur = saved->e_steps + (size_t)(s - 1) * E * kEF;
-        const float* e_prev = s == 1 ? saved->e_enc : saved->e_steps + (size_t)(s - 2) * E * kEF;
-        if (g_h) {
-            hipLaunchKernelGGL(bwd_q_kernel, grid1((size_t)N * kH, 256), dim3(256), 0, st, saved->h_enc, h_prev, Wn, bn, Q, N, HI);
-            HIP_TRY(hipGetLastError());
-        }
-        float* dP = dP_all + (size_t)(s - 1) * N * 44;
-        BwdEdgeParams bp;
-        std::memset(&bp, 0, sizeof(bp));
-        bp.ei = ei;
-        bp.e_cur = e_cur;
-        bp.e_prev = e_prev;
-        bp.e0 = re_e ? saved->e_enc : nullptr;
-        bp.ge0_acc = re_e ? ge0_acc : nullptr;
-        bp.HI = HI;
-        bp.Q = Q;
-        bp.g_h = g_h;
-        bp.deg = d->agg == GNNCCA_AGG_MEAN ? deg : nullptr;
-        if (g_h && d->agg == GNNCCA_AGG_MAX) {  // which edge attained each node's maximum
-            HIP_TRY(hipMemsetAsync(hmax, 0, (size_t)2 * N * kH * 4, st));
-            hipLaunchKernelGGL(bwd_max_kernel<false>, grid1((size_t)E, 256), dim3(256), 0, st, ei, e_cur, (const float*)Q, Wn,
-                               (long long)E, N, HI, hmax, hcnt, drop, s);
-            hipLaunchKernelGGL(bwd_max_kernel<true>, grid1((size_t)E, 256), dim3(256), 0, st, ei, e_cur, (const float*)Q, Wn,
-                               (long long)E, N, HI, hmax, hcnt, drop, s);
-            HIP_TRY(hipGetLastError());
-            bp.hmax = hmax;
-            bp.hcnt = hcnt;
-        }
-        bp.g_logit = s >= first_cls ? grad_logits + (size_t)out_idx * E : nullptr;
-        if (bp.g_logit && cls_bn) {  // reductions the BatchNorm backward needs before any per-edge gradient
-            const float* stat = cls_bn_stat + (size_t)out_idx * c1 * 2;
-            HIP_TRY(hipMemsetAsync(bn_sums, 0, sizeof(double) * 2 * c1, st));
-            hipLaunchKernelGGL(bwd_cls_bn_reduce_kernel, grid1((size_t)E, 256), dim3(256), 0, st, e_cur, bp.g_logit, (long long)E, Wc1,
-                               bc1, params_dev[12], params_dev[13], stat, Wc2, c1, bn_sums, gWc2, gbc2, drop, out_idx);
-            hipLaunchKernelGGL(bwd_cls_bn_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)bn_sums, (long long)E, c1, bn_red,
-                               grads_dev[12], grads_dev[13]);
-            HIP_TRY(hipGetLastError());
-            bp.bn_gamma = params_dev[12];
-            bp.bn_beta = params_dev[13];
-            bp.bn_stat = stat;
-            bp.bn_red = bn_red;
-        }
-        if (bp.g_logit) --out_idx;
-        bp.drop = drop;
-        bp.step_no = s;
-        bp.cls_no = bp.g_logit ? out_idx + 1 : 0;   // out_idx was already stepped down past this classified step
-        bp.ge_in = ge_in;
-        bp.ge_out = Gb[s & 1];
-        bp.dP = dP;
-        bp.We = We;
-        bp.Wn = Wn;
-        bp.Wc1 = Wc1;
-        bp.bc1 = bc1;
-        bp.Wc2 = Wc2;
-        bp.gWe = gWe;
-        bp.gbe = gbe;
-        bp.gWn = gWn;
-        bp.gbn = gbn;
-        bp.gWc1 = gWc1;
-        bp.gbc1 = gbc1;
-        bp.gWc2 = gWc2;
-        bp.gbc2 = gbc2;
-        bp.E = E;
-        bp.N = N;
-        bp.cls_hidden = c1;
-        {   // persistent grid: enough workgroups to fill the chip, few enough that the final flush of the LDS-resident
-            // parameter-gradient sums stays a few thousand atomics
-            const unsigned chunks = (unsigned)(((size_t)E + 255) / 256);
-            hipLaunchKernelGGL(bwd_edge_kernel, dim3(std::min(chunks, 512u)), dim3(256), 0, st, bp);
-        }
-        HIP_TRY(hipGetLastError());
-        float* g_h_prev = Hb[s & 1];
-        hipLaunchKernelGGL(bwd_node_kernel, grid1((size_t)N * HI, 256), dim3(256), 0, st, (const float*)dP, We, Wn, g_h_prev, gh0_acc, N,
-                           HI, WeLd);
-        HIP_TRY(hipGetLastError());
-        // d W_src, d W_dst (columns 0..31, 32..63 of the edge-MLP weight), d W_nx (columns 0..31 of the node-MLP weight)
-        // d W_src, d W_dst (columns [0, HI) and [HI, 2 HI) of the edge-MLP weight), d W_nx (columns [0, HI) of the node-MLP
-        // weight): one product dP^T hin [44][HI], rows routed to the three weight blocks; hin = cat(h0, h_prev) with
-        // reattach_initial_nodes, i.e. two 32-column products
-        for (int part = 0; part < (re_n ? 2 : 1); ++part) {
-            const float* hsrc = (re_n && part == 0) ? saved->h_enc : h_prev;
-            const int coff = part * kH;
-            OuterOut oo;
-            oo.ptr[0] = gWe + coff, oo.ptr[1] = gWe + HI + coff, oo.ptr[2] = g_h ? gWn + coff : nullptr;
-            oo.ld[0] = oo.ld[1] = WeLd, oo.ld[2] = WnLd;
-            oo.row_begin[0] = 0, oo.row_begin[1] = 6, oo.row_begin[2] = 12, oo.row_begin[3] = 44;
-            HIP_TRY(launch_outer_multi(dP, 44, hsrc, kH, oo, nullptr, N, g_h ? 44 : 12, kH, st));
-        }
-        g_h = g_h_prev;
-        ge_in = Gb[s & 1];
-    }
-    // gradients that reached the encoder outputs through the reattached copies
-    if (re_n) hipLaunchKernelGGL(bwd_add_kernel, grid1((size_t)N * kH, 256), dim3(256), 0, st, const_cast<float*>(g_h),
-                                 (const float*)gh0_acc, (long long)N * kH);
-    if (re_e) hipLaunchKernelGGL(bwd_add_kernel, grid1((size_t)E * kEF, 256), dim3(256), 0, st, const_cast<float*>(ge_in),
-                                 (const float*)ge0_acc, (long long)E * kEF);
-    // ---- encoders ---------------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(bwd_edge_enc_kernel, dim3(std::min((unsigned)(((size_t)E + 255) / 256), 512u)), dim3(256), 0, st, ge_in,
-                       saved->e_enc, edge_attr, A, (long long)E,
-                       gWe0, gbe0, 1.f / (1.f - drop.p_enc));
-    HIP_TRY(hipGetLastError());
-    {   // a1 = ReLU(x W1^T + b1) is recomputed instead of stored: the forward's split-K MFMA GEMM + its reduce kernel
-        int ks = 1;
-        while (ks < 32 && (size_t)((N + 31) / 32) * ks < 512 && D / (ks * 2) >= 64) ks *= 2;
-        int kslice = (D + ks - 1) / ks;
-        kslice = (kslice + 63) / 64 * 64;
-        EncPlanParams ep;
-        std::memset(&ep, 0, sizeof(ep));
-        ep.in = x;
-        ep.W = W1;
-        ep.part = part;
-        ep.M = N;
-        ep.K = D;
-        ep.O = F1;
-        ep.kslice = kslice;
-        ep.vec_ok = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-        ep.nrt = (N + 31) / 32;
-        ep.nks = ks;
-        ep.gemm_blocks = ep.nrt * ks * ((F1 + 127) / 128);
-        hipLaunchKernelGGL(enc_gemm_plan_kernel, dim3(ep.gemm_blocks), dim3(256), 0, st, ep);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(reduce_bias_act_kernel, grid1((size_t)N * F1, 256), dim3(256), 0, st, (const float*)part, b1, a1, N, F1, ks,
-                           1);
-        HIP_TRY(hipGetLastError());
-        if (drop.p_enc > 0.f) {   // the forward's layer-2 input was a1 AFTER Dropout: re-derive the same mask
-            hipLaunchKernelGGL(apply_dropout_kernel, grid1((size_t)N * F1, 256), dim3(256), 0, st, a1, (long long)N * F1, drop,
-                               (unsigned)kDropEncNode1, drop.p_enc);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    float* gz2 = const_cast<float*>(g_h);  // [N][32] d loss / d h_enc, masked in place
-    const float enc_scale = 1.f / (1.f - drop.p_enc);
-    hipLaunchKernelGGL(bwd_relu_mask_kernel, grid1((size_t)N * kH, 256), dim3(256), 0, st, gz2, saved->h_enc, (long long)N * kH, enc_scale);
-    HIP_TRY(launch_outer(gz2, kH, a1, F1, gW2, F1, gb2, N, kH, F1, st));
-    hipLaunchKernelGGL(bwd_matmul_mask_kernel, grid1((size_t)N * F1, 256), dim3(256), 0, st, (const float*)gz2, W2, (const float*)a1,
-                       gz1, N, kH, F1, enc_scale);
-    HIP_TRY(launch_outer(gz1, F1, x, D, gW1, D, gb1, N, F1, D, st));
-    HIP_TRY(hipGetLastError());
-    // ---- inputs (only what the caller asked for) ----------------------------------------------------------------------
-    if (dattr_out) {
-        hipLaunchKernelGGL(bwd_edge_attr_kernel, grid1((size_t)E * A, 256), dim3(256), 0, st, ge_in, saved->e_enc, params_dev[4],
-                           dattr_out, A, (long long)E, enc_scale);
-        HIP_TRY(hipGetLastError());
-    }
-    if (dx_out) HIP_TRY(launch_dx(gz1, W1, dx_out, N, F1, D, st));
-    return GNNCCA_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,247 @@
+// mpn_post.hip -- post-processing on the device (threshold, pruning, flow counters, connected components; kernels in
+// postprocess.cuh) and the one-call frame pipeline gnncca_frames_forward, which chains graph build, forward and post stage on one stream.
+// The graph-plan kernels it needs are compiled in mpn_forward.hip and reached through their launchers (internal.h).
+#include "common.cuh"
+#include "plan.cuh"
+#include "postprocess.cuh"
+
+using namespace gnncca;
+
+extern "C" {
+
+int gnncca_pad_frame(const float* x, int64_t n_nodes, const int64_t* edge_index, const float* edge_attr, int64_t n_edges, float* x_pad,
+                     int64_t n_real_max, int n_dummy, int64_t* edge_index_pad, float* edge_attr_pad, int64_t e_pad, int node_in, int edge_in,
+                     gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_real_max < n_nodes || e_pad < n_edges || n_dummy < 1 || node_in < 1 || edge_in < 1) return GNNCCA_ERR_INVALID_ARG;
+    if (!x_pad || !edge_index_pad || !edge_attr_pad || (n_nodes > 0 && !x) || (n_edges > 0 && (!edge_index || !edge_attr))) return GNNCCA_ERR_INVALID_ARG;
+    const long long total = (n_real_max + n_dummy) * (long long)node_in + e_pad * (2ll + edge_in);
+    const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(pad_frame_kernel, dim3(std::max(blocks, 1u)), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long long)n_nodes,
+                       reinterpret_cast<const long long*>(edge_index), edge_attr, (long long)n_edges, x_pad, (long long)n_real_max, n_dummy,
+                       reinterpret_cast<long long*>(edge_index_pad), edge_attr_pad, (long long)e_pad, node_in, edge_in);
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- SURVEY.md 8f row N2 ------------------------------------------------------------------------------------
+size_t gnncca_post_workspace_bytes(int64_t n_nodes, int64_t n_edges) {
+    if (n_nodes < 0 || n_edges < 0) return 0;
+    return carve_post(n_nodes, n_edges).total;
+}
+
+int gnncca_post_threshold(const float* logits, int64_t n_edges, float* probs_out, int64_t* predictions_out,
+                          gnncca_stream_t stream) {
+    if (n_edges < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges == 0) return GNNCCA_OK;
+    if (!logits || !probs_out || !predictions_out) return GNNCCA_ERR_INVALID_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(post_threshold_kernel, grid1((size_t)n_edges, 256), dim3(256), 0, st, logits, (long long)n_edges, probs_out,
+                       reinterpret_cast<long long*>(predictions_out));
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_post_prune_cluster(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                              void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
+                              int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out, gnncca_stream_t stream) {
+    return gnncca_post_prune_cluster_frames(edge_index, predictions, n_nodes, n_edges, nullptr, nullptr, 0, workspace,
+                                            workspace_bytes, pruned_out, flow_out, flow_in, labels_out, n_clusters_out, stream);
+}
+
+int gnncca_post_prune_cluster_frames(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                                     const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                     void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
+                                     int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out,
+                                     gnncca_stream_t stream) {
+    return gnncca_post_prune_cluster_frames_ex(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace,
+                                               workspace_bytes, pruned_out, flow_out, flow_in, labels_out, n_clusters_out, nullptr, nullptr, stream);
+}
+
+// `plan` (internal; null from the public entry points): the graph plan the MPN forward of the same batch left in ITS workspace (seg_ptr,
+// col32, perm, flags) -- gnncca_frames_forward hands it over, so the pruning needs no plan launches of its own
+struct PostPlan {
+    const int* seg_ptr;
+    const int* col32;
+    const int* perm;
+    const unsigned* flags;
+    // gnncca_frames_forward's two other savings: the counters were zeroed by an earlier kernel of the batch (no memset node here), and the
+    // threshold rides in the prune kernel (logits in, probabilities and predictions out)
+    bool counters_zeroed;
+    const float* logits;
+    float* probs_out;
+    int64_t* preds_out;
+};
+static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                                   const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
+                                   size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in, int32_t* labels_out,
+                                   int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out, const PostPlan* plan,
+                                   gnncca_stream_t stream);
+
+int gnncca_post_prune_cluster_frames_ex(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                                        const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
+                                        size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in,
+                                        int32_t* labels_out, int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out,
+                                        gnncca_stream_t stream) {
+    return post_prune_cluster_impl(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace, workspace_bytes,
+                                   pruned_out, flow_out, flow_in, labels_out, n_clusters_out, sizes_scratch, triggers_out, nullptr, stream);
+}
+
+static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                                   const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
+                                   size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in, int32_t* labels_out,
+                                   int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out, const PostPlan* plan,
+                                   gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if ((sizes_scratch == nullptr) != (triggers_out == nullptr)) return GNNCCA_ERR_INVALID_ARG;
+    if ((node_ptr_dev == nullptr) != (edge_ptr_dev == nullptr) || (node_ptr_dev != nullptr && n_frames == 0))
+        return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    const size_t n_trig = (size_t)(node_ptr_dev ? n_frames : 1);
+    if (n_nodes == 0) {
+        if (n_clusters_out) HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
+        if (triggers_out) HIP_TRY(hipMemsetAsync(triggers_out, 0, n_trig * sizeof(int32_t), static_cast<hipStream_t>(stream)));
+        return GNNCCA_OK;
+    }
+    if (!workspace || !flow_out || !flow_in || !labels_out || !n_clusters_out) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !predictions || !pruned_out)) return GNNCCA_ERR_INVALID_ARG;
+    const PostWorkspace ws = carve_post(n_nodes, n_edges);
+    if (!plan && workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int N = (int)n_nodes, E = (int)n_edges;
+    char* base = static_cast<char*>(workspace);
+    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.flags);
+    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.blockflags);
+    int* seg_ptr = reinterpret_cast<int*>(base + ws.seg_ptr);
+    int* col32 = reinterpret_cast<int*>(base + ws.col32);
+    int* perm = reinterpret_cast<int*>(base + ws.perm);
+    int* cursor = reinterpret_cast<int*>(base + ws.cursor);
+    if (plan) {   // the MPN forward's plan of the same edge_index: nothing to build here
+        seg_ptr = const_cast<int*>(plan->seg_ptr), col32 = const_cast<int*>(plan->col32), perm = const_cast<int*>(plan->perm);
+        flags = const_cast<unsigned*>(plan->flags);
+    }
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    const long long* pred = reinterpret_cast<const long long*>(predictions);
+    long long* pruned = reinterpret_cast<long long*>(pruned_out);
+    // zero the counters: one memset when the caller laid flow_out | flow_in | n_clusters out back to back (gnn_cca_amd.postprocess does)
+    const bool one_block = flow_in == flow_out + N && n_clusters_out == flow_in + N;
+    const bool trig_block = one_block && triggers_out && sizes_scratch == n_clusters_out + 1 && triggers_out == sizes_scratch + N;
+    if (plan && plan->counters_zeroed) {
+        // nothing: done launches ago
+    } else if (trig_block) {
+        HIP_TRY(hipMemsetAsync(flow_out, 0, ((size_t)3 * N + 1 + n_trig) * 4, st));
+    } else if (one_block) {
+        HIP_TRY(hipMemsetAsync(flow_out, 0, ((size_t)2 * N + 1) * 4, st));
+    } else {
+        HIP_TRY(hipMemsetAsync(flow_out, 0, (size_t)N * 4, st));
+        HIP_TRY(hipMemsetAsync(flow_in, 0, (size_t)N * 4, st));
+        HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), st));
+    }
+    if (triggers_out && !trig_block && !(plan && plan->counters_zeroed)) {
+        HIP_TRY(hipMemsetAsync(sizes_scratch, 0, (size_t)N * 4, st));
+        HIP_TRY(hipMemsetAsync(triggers_out, 0, n_trig * 4, st));
+    }
+    if (E > 0 && !plan) {
+        EncPlanParams ep;
+        std::memset(&ep, 0, sizeof(ep));
+        ep.ei = ei;
+        ep.seg_ptr = seg_ptr;
+        ep.col32 = col32;
+        ep.blockflags = blockflags;
+        ep.E = E;
+        ep.N = N;
+        launch_plan_only(ep, plan_num_blocks(E), st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!plan) {
+        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (E > 0) {
+        if (plan && plan->logits)
+            hipLaunchKernelGGL(post_prune_kernel<true>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, (const int*)seg_ptr,
+                               (const int*)col32, (const int*)perm, (const unsigned*)flags, pruned, flow_out, flow_in, plan->logits,
+                               plan->probs_out, reinterpret_cast<long long*>(plan->preds_out));
+        else
+            hipLaunchKernelGGL(post_prune_kernel<false>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, (const int*)seg_ptr,
+                               (const int*)col32, (const int*)perm, (const unsigned*)flags, pruned, flow_out, flow_in, (const float*)nullptr,
+                               (float*)nullptr, (long long*)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(post_cc_kernel, dim3(node_ptr_dev ? (unsigned)n_frames : 1u), dim3(1024), 0, st, ei,
+                       (const long long*)pruned, (long long)E, N, node_ptr_dev, edge_ptr_dev, labels_out, n_clusters_out,
+                       (const int*)flow_out, (const int*)flow_in, sizes_scratch, triggers_out);
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+
+int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
+                          size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
+                          gnncca_stream_t stream) {
+    if (!d || !io || !io->staged_dev) return GNNCCA_ERR_INVALID_ARG;
+    const int64_t n = io->n_nodes, g = io->n_frames, e = io->n_edges;
+    if (n < 1 || g < 1 || e < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n > 4096) return GNNCCA_ERR_UNSUPPORTED;   // (the one-launch normalisation's limit; bigger batches take the separate entry points)
+    if (!io->node_embeds || !io->reid_embeds || !io->edge_index || !io->edge_attr || !io->edge_labels || !io->logits || !io->probs ||
+        !io->predictions || !io->pruned || !io->counters || !io->labels || (io->normalize && (!io->node_norm || !io->reid_norm)))
+        return GNNCCA_ERR_INVALID_ARG;
+    if (io->counters_len < 3 * n + 1 + g) return GNNCCA_ERR_INVALID_ARG;   // flow_out | flow_in | n_clusters | sizes | triggers (ABI 2: stated, not assumed)
+    // the staging image (gnncca_plan_frames): f64 xw[n], yw[n], max_dist[g]; i64 ids[n]; i32 person, cam, graph_of, graph_ptr, src_order, edge_ptr, edge_ptr_g
+    const char* base = static_cast<const char*>(io->staged_dev);
+    gnncca_frames fr;
+    fr.xw = reinterpret_cast<const double*>(base);
+    fr.yw = fr.xw + n;
+    fr.max_dist = fr.yw + n;
+    const int32_t* i32 = reinterpret_cast<const int32_t*>(base + 8 * (3 * n + g));
+    fr.person_id = i32, fr.cam = i32 + n, fr.graph_of = i32 + 2 * n, fr.graph_ptr = i32 + 3 * n;
+    fr.src_order = i32 + 3 * n + g + 1, fr.edge_ptr = i32 + 4 * n + g + 1;
+    const int32_t* edge_ptr_g = i32 + 5 * n + g + 2;
+    const float* x = io->node_embeds;
+    const float* reid = io->reid_embeds;
+    int st = GNNCCA_OK;
+    if (io->normalize) {
+        st = gnncca_normalize_columns2(io->reid_embeds, io->reid_dim, io->reid_norm, io->node_embeds, d->node_in, io->node_norm, n, stream);
+        if (st != GNNCCA_OK) return st;
+        x = io->node_norm, reid = io->reid_norm;
+    }
+    // (the post stage's counters -- flow_out | flow_in | n_clusters | sizes | triggers -- are zeroed by this launch: no memset node later)
+    const bool zero_here = e > 0 && mpn_workspace != nullptr;
+    st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, io->edge_index, io->edge_attr, io->edge_labels,
+                             zero_here ? io->counters : nullptr, zero_here ? 3 * n + 1 + g : 0, stream);
+    if (st != GNNCCA_OK) return st;
+    const int n_out = gnncca_num_outputs(d);
+    if (n_out < 1) return GNNCCA_ERR_UNSUPPORTED;
+    if (e > 0) {
+        st = gnncca_mpn_forward_ex(d, packed_dev, x, io->edge_index, io->edge_attr, n, e, mpn_workspace, mpn_workspace_bytes, io->logits, nullptr,
+                                   options, stream);
+        if (st != GNNCCA_OK) return st;
+        if (!zero_here) {   // (no shared plan: the threshold keeps its own launch)
+            st = gnncca_post_threshold(io->logits + (size_t)(n_out - 1) * e, e, io->probs, io->predictions, stream);
+            if (st != GNNCCA_OK) return st;
+        }
+    }
+    // the pruning searches reverse edges in the CSR plan of edge_index -- the one the forward above left in ITS workspace (seg_ptr / col32 /
+    // perm / flag word: same plan_block + plan_finish, same stream): handed over instead of being built a second time (two launches less)
+    PostPlan plan;
+    const PostPlan* have_plan = nullptr;
+    if (e > 0 && mpn_workspace) {
+        char* wb = static_cast<char*>(mpn_workspace);
+        if (classify(d) == kFamilyMfma32x6) {
+            const Workspace ws = carve(d, n, e);
+            plan = PostPlan{reinterpret_cast<const int*>(wb + ws.seg_ptr), reinterpret_cast<const int*>(wb + ws.col32),
+                            reinterpret_cast<const int*>(wb + ws.perm), reinterpret_cast<const unsigned*>(wb + ws.flags), false, nullptr, nullptr, nullptr};
+        } else {
+            const GenWorkspace ws = carve_generic(d, n, e);
+            plan = PostPlan{reinterpret_cast<const int*>(wb + ws.seg_ptr), reinterpret_cast<const int*>(wb + ws.col32),
+                            reinterpret_cast<const int*>(wb + ws.perm), reinterpret_cast<const unsigned*>(wb + ws.flags), false, nullptr, nullptr, nullptr};
+        }
+        plan.counters_zeroed = zero_here;
+        plan.logits = io->logits + (size_t)(n_out - 1) * e, plan.probs_out = io->probs, plan.preds_out = io->predictions;
+        have_plan = &plan;
+    }
+    int32_t* c = io->counters;   // flow_out | flow_in | n_clusters | sizes (scratch) | triggers [G]
+    return post_prune_cluster_impl(io->edge_index, io->predictions, n, e, fr.graph_ptr, edge_ptr_g, (int32_t)g, post_workspace, post_workspace_bytes,
+                                   io->pruned, c, c + n, io->labels, c + 2 * n, c + 2 * n + 1, c + 3 * n + 1, have_plan, stream);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 #pragma once
-// Part of the single translation unit mpn_forward.hip.
+// Part of the translation unit mpn_forward.hip, and included by it alone.
 namespace gnncca {
 
 // ------------------------------------------------------------------------------------------------------------

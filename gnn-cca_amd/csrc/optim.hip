@@ -30,20 +30,11 @@
 #include <cmath>
 #include <cstdint>
 
-#include "internal.h"
+#include "hip_try.h"
 
 #pragma clang fp contract(off)
 
 namespace gnncca {
-
-#define HIP_TRY_OP(expr)                   \
-    do {                                   \
-        hipError_t _e = (expr);            \
-        if (_e != hipSuccess) {            \
-            g_last_hip_error = (int)_e;    \
-            return GNNCCA_ERR_HIP;         \
-        }                                  \
-    } while (0)
 
 constexpr int kOptimBlock = 256;
 constexpr int kOptimChunk = 4 * kOptimBlock;   // elements per workgroup: one float4 per thread
@@ -288,7 +279,7 @@ int gnncca_optim_set_hyper(void* block, int32_t rule, double lr, double weight_d
     }
     hipLaunchKernelGGL(optim_set_hyper_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<OptimHeader*>(block), lr,
                        weight_decay, a, b, c, flag ? 1.0 : 0.0, (double)rule);
-    HIP_TRY_OP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
 
@@ -333,7 +324,7 @@ static int optim_step(void* block, int32_t rule, int32_t n_slots, int32_t n_tens
             hipLaunchKernelGGL(optim_step_kernel<GNNCCA_OPTIM_SGD>, dim3(groups), dim3(kOptimBlock), 0, st, static_cast<OptimHeader*>(block), a);
         else
             hipLaunchKernelGGL(optim_step_kernel<GNNCCA_OPTIM_ADAM>, dim3(groups), dim3(kOptimBlock), 0, st, static_cast<OptimHeader*>(block), a);
-        HIP_TRY_OP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return GNNCCA_OK;
 }

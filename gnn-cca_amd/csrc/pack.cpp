@@ -20,6 +20,8 @@
 
 namespace gnncca {
 
+thread_local int g_last_hip_error = 0;  // the one definition (internal.h); every HIP translation unit sets it through HIP_TRY
+
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 int mlp_param_count(const gnncca_mlp& m) {
@@ -770,7 +772,7 @@ int enc_lds_ksplit(int64_t n_nodes, int K) {
     return best;
 }
 
-// INVARIANT (gnncca_frames_forward, csrc/mpn_forward.hip): the plan regions -- flags, seg_ptr, col32, perm -- stay LIVE AND FINAL from the plan's
+// INVARIANT (gnncca_frames_forward, csrc/mpn_post.hip): the plan regions -- flags, seg_ptr, col32, perm -- stay LIVE AND FINAL from the plan's
 // launch(es) until the forward returns: the post stage reads them from this workspace (found by carving it again) instead of building the
 // plan a second time.  Every forward route finishes that plan (the riding plan blocks + plan_finish in a tail / fused-epilogue workgroup, the
 // plan-only launch of big batches, L == 0), and no step kernel may reuse those regions.  tests/test_gpu_pipeline.py holds one pipeline call

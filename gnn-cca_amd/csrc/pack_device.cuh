@@ -1,5 +1,5 @@
 #pragma once
-// Part of the single translation unit mpn_forward.hip.
+// Part of the translation unit mpn_train.hip.
 // Device-side weight packing: interprets the PackProgram of pack.cpp on the GPU, so that a training step (the
 // optimizer has just changed every parameter) or a load_state_dict() never moves the parameters through the host.
 // Same arithmetic as the host packer, operation for operation: BatchNorm fold in double with separately rounded

@@ -1,6 +1,6 @@
 #pragma once
-// Part of the single translation unit mpn_forward.hip (kernels share device helpers and the launch code below
-// instantiates their templates); see that file for the overall picture.
+// The graph plan's device code, compiled into the kernels of mpn_forward.hip that run it; mpn_post.hip and mpn_train.hip include this file
+// for the host-side block arithmetic only (plan_num_blocks) and launch those kernels through internal.h's launchers.
 namespace gnncca {
 
 // ------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 // and the identity clusters of the pruned, now symmetric, edge set (libs/utils.py:295-317: strongly connected
 // components of a symmetric digraph == connected components).  The bridge-based rounding / splitting heuristics
 // (libs/utils.py:25-173, 319-386) stay on the host, as SURVEY.md 8f prescribes.
-// Part of the single translation unit mpn_forward.hip.
+// Part of the translation unit mpn_post.hip.
 namespace gnncca {
 
 __global__ __launch_bounds__(256) void post_threshold_kernel(const float* __restrict__ logits, long long E,

@@ -1,5 +1,5 @@
 #pragma once
-// Part of the single translation unit mpn_forward.hip.
+// Part of the translation unit mpn_train.hip.
 namespace gnncca {
 
 // ============================================================================================================
@@ -453,10 +453,8 @@ static int tr_mlp_forward(const TrCtx& c, const TrCall& call, const float* xin, 
         if (M * O > 0) {
             for (int o0 = 0; o0 < O; o0 += 2048) {
                 const int og = std::min(2048, O - o0);
-                const int rows_per_block = 256 / ((og + 7) / 8);
-                hipLaunchKernelGGL(gen_dense_kernel, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0, c.st,
-                                   GenSeg{cur, nullptr, K, K}, none, none, (const float*)c.at(c.P->wt[call.mlp][l]) + o0,
-                                   (const float*)c.at(c.P->bp[call.mlp][l]) + o0, dst + o0, M, K, og, OP, O, (L.has_bn ? 0 : L.relu));
+                launch_gen_dense(GenSeg{cur, nullptr, K, K}, none, none, (const float*)c.at(c.P->wt[call.mlp][l]) + o0,
+                                 (const float*)c.at(c.P->bp[call.mlp][l]) + o0, dst + o0, M, K, og, OP, O, (L.has_bn ? 0 : L.relu), c.st);
             }
             HIP_TRY(hipGetLastError());
             if (L.has_bn) {
@@ -591,12 +589,11 @@ static int train_forward_impl(const gnncca_mpn_dims* d, float* const* params, in
         EncPlanParams ep;
         std::memset(&ep, 0, sizeof(ep));
         ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
-        hipLaunchKernelGGL(plan_only_kernel, dim3(plan_num_blocks(E)), dim3(256), 0, st, ep);
-        hipLaunchKernelGGL(gen_index32_kernel, dim3((E + 255) / 256), dim3(256), 0, st, ei, E, N, row32, colo32);
+        launch_plan_only(ep, plan_num_blocks(E), st);
+        launch_gen_index32(ei, E, N, row32, colo32, st);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(gen_plan_finish_kernel, dim3(1), dim3(256), 0, st, ei, E, N, seg_ptr, col32, perm, cursor, flags,
-                       (const unsigned*)blockflags);
+    launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
     HIP_TRY(hipGetLastError());
     // operand form of the weights (this iteration's values)
     for (int m = 0; m < 5; ++m) {
@@ -624,7 +621,7 @@ static int train_forward_impl(const gnncca_mpn_dims* d, float* const* params, in
         if (r != GNNCCA_OK) return r;
         float* dst = logits_out + (size_t)out_idx * E;
         HIP_TRY(hipMemcpyAsync(dst, lo, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(gen_poison_kernel, grid1((size_t)E, 256), dim3(256), 0, st, dst, (long long)E, (const unsigned*)flags);
+        launch_gen_poison(dst, (long long)E, flags, st);
         HIP_TRY(hipGetLastError());
         ++out_idx;
         return GNNCCA_OK;
@@ -662,8 +659,7 @@ static int train_forward_impl(const gnncca_mpn_dims* d, float* const* params, in
         const float* msg = nullptr;
         s = tr_mlp_forward(c, P.node[si], c.at(P.node[si].xin), &msg);
         if (s != GNNCCA_OK) return s;
-        hipLaunchKernelGGL(gen_aggregate_kernel, dim3((unsigned)N), dim3(256), 0, st, msg, (const int*)seg_ptr, (const int*)perm,
-                           (const unsigned*)flags, c.at(P.h[si]), N, H, (int)d->agg);
+        launch_gen_aggregate(msg, seg_ptr, perm, flags, c.at(P.h[si]), N, H, (int)d->agg, st);
         HIP_TRY(hipGetLastError());
         h_cur = c.at(P.h[si]);
         e_cur = e_new;
@@ -899,10 +895,8 @@ static int mlp_eval_impl(const gnncca_mlp* m, const float* const* params, int n_
         float* dst = last ? out : reinterpret_cast<float*>(base + buf[l & 1]);
         for (int o0 = 0; o0 < O; o0 += 2048) {
             const int og = std::min(2048, O - o0);
-            const int rows_per_block = 256 / ((og + 7) / 8);
-            hipLaunchKernelGGL(gen_dense_kernel, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0, st,
-                               GenSeg{cur, nullptr, K, K}, none, none, (const float*)Wt + o0, (const float*)bpad + o0, dst + o0, M, K, og, OP, O,
-                               (L.has_bn ? 0 : L.relu));
+            launch_gen_dense(GenSeg{cur, nullptr, K, K}, none, none, (const float*)Wt + o0, (const float*)bpad + o0, dst + o0, M, K, og, OP, O,
+                             (L.has_bn ? 0 : L.relu), st);
         }
         if (L.has_bn) {
             float* sp = reinterpret_cast<float*>(base + stat[l]);
@@ -949,12 +943,10 @@ static int aggregate_impl(const float* msg, const int64_t* edge_index, int64_t n
         EncPlanParams ep;
         std::memset(&ep, 0, sizeof(ep));
         ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
-        hipLaunchKernelGGL(plan_only_kernel, dim3(plan_num_blocks(E)), dim3(256), 0, st, ep);
+        launch_plan_only(ep, plan_num_blocks(E), st);
     }
-    hipLaunchKernelGGL(gen_plan_finish_kernel, dim3(1), dim3(256), 0, st, ei, E, N, seg_ptr, col32, perm, cursor, flags,
-                       (const unsigned*)blockflags);
-    hipLaunchKernelGGL(gen_aggregate_kernel, dim3((unsigned)N), dim3(256), 0, st, msg, (const int*)seg_ptr, (const int*)perm,
-                       (const unsigned*)flags, out, N, H, agg);
+    launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
+    launch_gen_aggregate(msg, seg_ptr, perm, flags, out, N, H, agg, st);
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

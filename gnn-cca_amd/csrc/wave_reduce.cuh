@@ -1,5 +1,5 @@
 #pragma once
-// Wave-level reductions shared by mpn_forward.hip and graph_build.hip.
+// Wave-level reductions shared by mpn_forward.hip, mpn_train.hip and graph_build.hip.
 #include <hip/hip_runtime.h>
 
 namespace gnncca {

@@ -203,7 +203,7 @@ def test_random_graphs_gradients_vs_oracle(agg):
 @pytest.mark.parametrize("node_fc,edge_fc,engine", [([64], [4], "fused"), ([256], [4], "fused"), ([128], [8], "fused"),
                                                     ([128], [1], "layerwise"), ([128], [], "fused"), ([128, 64], [4], "layerwise")])
 def test_random_graphs_other_encoder_and_classifier_shapes_gradients_vs_oracle(node_fc, edge_fc, engine):
-    """backward_ok (csrc/mpn_forward.hip) sends every fast-family model with a two-layer node encoder to the fused engine: first-layer
+    """backward_ok (csrc/mpn_train.hip) sends every fast-family model with a two-layer node encoder to the fused engine: first-layer
     widths other than 128, classifiers with a hidden layer of 8 (BatchNorm after it) or with none.  A hidden layer of width 1 has no
     ReLU (models/mlp.py), which the family's classifier kernels would apply: that model is on the generic family and, like a
     three-layer encoder, trains on the layer-by-layer engine under train_engine = 'auto'.  Irregular graphs of

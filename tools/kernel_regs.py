@@ -7,13 +7,23 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gnn-cca_amd"))
+import build  # noqa: E402  (the library's source list)
+
 out = "/tmp/gnncca_regs.txt"
 if "--reuse" not in sys.argv or not os.path.exists(out):
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-I", os.path.join(ROOT, "include"), "-I",
-           os.path.join(ROOT, "gnn-cca_amd", "csrc"), "-DGNNCCA_BUILD", "-mllvm", "-amdgpu-mfma-vgpr-form", "--cuda-device-only", "-c",
-           os.path.join(ROOT, "gnn-cca_amd", "csrc", "mpn_forward.hip"), "-o", "/tmp/gnncca_dev.o", "-Rpass-analysis=kernel-resource-usage"]
+    units = [s for s in build.SOURCES if s.endswith(".hip")]   # every kernel is compiled in exactly one of them
+    procs = []
+    for u in units:   # side by side, as build.py compiles them
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-I", os.path.join(ROOT, "include"), "-I",
+               build.CSRC, "-DGNNCCA_BUILD", "-mllvm", "-amdgpu-mfma-vgpr-form", "--cuda-device-only", "-c", os.path.join(build.CSRC, u),
+               "-o", "/tmp/gnncca_dev_%s.o" % u, "-Rpass-analysis=kernel-resource-usage"]
+        procs.append(subprocess.Popen(cmd, stderr=open("%s.%s" % (out, u), "w")))
+    if any(p.wait() != 0 for p in procs):
+        sys.exit("hipcc failed: see %s.*" % out)
     with open(out, "w") as f:
-        subprocess.run(cmd, stderr=f, check=True)
+        for u in units:
+            f.write(open("%s.%s" % (out, u)).read())
 want = [a for a in sys.argv[1:] if not a.startswith("--")]
 rows, cur = {}, None
 for line in open(out):
