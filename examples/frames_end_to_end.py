@@ -4,8 +4,12 @@ every GPU-side step taken by this repository: graph construction + edge attribut
 path), threshold / pruning / identity clusters (row N2), and the per-frame scores of inference.py:349-371 aggregated as main.py:335-348
 does (gnn_cca_amd.evaluation).  Needs an MI355X.
 
-    python examples/frames_end_to_end.py [frames] [cams] [detections_per_cam]
+    python examples/frames_end_to_end.py [frames] [cams] [detections_per_cam] [--top-k K] [--rank-by ground|reid]
+
+--top-k K keeps every detection's K nearest cross-camera candidates (build_graph_batch(top_k=K); the graph is then directed and the
+pruning keeps mutual pairs only); the same batch also goes through the one-call form, FramePipeline(model, top_k=K).
 """
+import argparse
 import os
 import sys
 import time
@@ -18,13 +22,20 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
 from gnn_cca_amd.evaluation import EvalAccumulator, evaluate_frames  # noqa: E402
 from gnn_cca_amd.graph_build import build_graph_batch  # noqa: E402
+from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
 from gnn_cca_amd.postprocess import prune_and_cluster, threshold  # noqa: E402
 
 
 def main():
-    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-    cams = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-    per = int(sys.argv[3]) if len(sys.argv) > 3 else 8
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("frames", nargs="?", type=int, default=8)
+    ap.add_argument("cams", nargs="?", type=int, default=4)
+    ap.add_argument("per", nargs="?", type=int, default=8, metavar="detections_per_cam")
+    ap.add_argument("--top-k", type=int, default=None, metavar="K", help="keep each detection's K nearest cross-camera candidates (default: all)")
+    ap.add_argument("--rank-by", choices=("ground", "reid"), default="ground", help="what 'nearest' means for --top-k")
+    a = ap.parse_args()
+    frames, cams, per = a.frames, a.cams, a.per
+    cap = dict(top_k=a.top_k, rank_by=a.rank_by)
     rng = np.random.default_rng(0)
     n_g = cams * per
     n = frames * n_g
@@ -41,7 +52,7 @@ def main():
     model = bench.build_model(bench.graph_net_params(), n_g).cuda().eval()
 
     def run():
-        batch = build_graph_batch(xw, yw, ids, id_cam, [n_g] * frames, max_dist, node_embeds, reid_embeds)
+        batch = build_graph_batch(xw, yw, ids, id_cam, [n_g] * frames, max_dist, node_embeds, reid_embeds, **cap)
         with torch.no_grad():
             out = model(batch)
         probs, preds = threshold(out["classified_edges"][-1])
@@ -65,11 +76,16 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / reps
     e = batch.edge_index.shape[1]
-    print(f"{frames} frames x {cams} cameras x {per} detections: N={n} E={e}")
+    print(f"{frames} frames x {cams} cameras x {per} detections: N={n} E={e}" + (f" (top_k={a.top_k} by {a.rank_by})" if a.top_k else ""))
     print(f"graph build + MPN (L=4) + threshold/prune/cluster: {dt * 1e3:.3f} ms per batch "
           f"({e / dt / 1e6:.1f} M edges/s end to end, host planning included)")
     print(f"active edges after pruning: {int(post['pruned'].sum())}, identity clusters: {int(post['n_clusters'].item())}, "
           f"max out-flow per node: {int(post['flow_out'].max())}")
+    # the same batch in ONE native call (gnn_cca_amd.pipeline): bit for bit the steps above
+    pipe = FramePipeline(model, **cap)
+    r = pipe(xw, yw, ids, id_cam, [n_g] * frames, max_dist, node_embeds, reid_embeds)
+    same = torch.equal(r.pruned, post["pruned"]) and torch.equal(r.labels, post["labels"])
+    print(f"FramePipeline, one call: identity clusters {int(r.n_clusters.item())}, equal to the step-by-step result: {same}")
     # per-frame metrics against the ground truth the graph build wrote (batch.edge_labels: same person id), then main.py's aggregates
     acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"]))
     print("aggregates over the frames:", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))

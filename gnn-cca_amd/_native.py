@@ -11,7 +11,7 @@ MAX_LAYERS = 8
 OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_HIP, ERR_NO_DEVICE = range(6)
 AGG = {"sum": 0, "mean": 1, "max": 2}
 GRAPH_UNSORTED, GRAPH_BAD_INDEX = 1, 2
-RANK_BY = {"ground": 0, "reid": 1}   # gnncca_build_edges_topk
+RANK_BY = {"ground": 0, "reid": 1}   # gnncca_build_edges_topk, gnncca_frames_forward_topk
 TOPK_MAX_DEG = 4096
 
 
@@ -183,6 +183,8 @@ _SIGNATURES = {
                                                C.POINTER(Dropout), C.POINTER(InputGrads), C.c_void_p]),
     "gnncca_normalize_columns2": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gnncca_frames_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "gnncca_frames_forward_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_void_p]),
     "gnncca_plan_frames_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "gnncca_plan_frames": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_size_t]),

@@ -549,37 +549,8 @@ int gnncca_build_edges_topk_backward(const gnncca_frames* fr, const float* reid,
 int gnncca_build_edges_topk(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
                             int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
                             float* edge_labels_out, gnncca_stream_t stream) {
-    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0 || top_k < 1 || max_deg < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
-    if (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID) return GNNCCA_ERR_INVALID_ARG;
-    if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
-    if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    if (!fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr ||
-        !fr->src_order || !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out)
-        return GNNCCA_ERR_INVALID_ARG;
-    if ((mode != GNNCCA_EDGE_ATTR_ONLY_DIST || rank_by == GNNCCA_RANK_BY_REID) && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
-    const int cap = std::max(64, (max_deg + 63) / 64 * 64);
-    const size_t per_wave = (size_t)cap * kTopkSlotBytes;
-    const int waves = per_wave * 4 <= 65536 ? 4 : (per_wave * 2 <= 65536 ? 2 : 1);   // 4096 slots x 12 B = 48 KB: one wave
-    const dim3 grid((unsigned)((n_nodes + waves - 1) / waves)), block(64 * waves);
-    const size_t lds = per_wave * waves;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    long long* ei = reinterpret_cast<long long*>(edge_index_out);
-#define GNNCCA_TOPK(M, K)                                                                                                          \
-    hipLaunchKernelGGL((build_edges_topk_kernel<M, K>), grid, block, lds, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, \
-                       cap, ei, edge_attr_out, edge_labels_out)
-#define GNNCCA_TOPK_R(M) \
-    if (rank_by == GNNCCA_RANK_BY_GROUND) GNNCCA_TOPK(M, GNNCCA_RANK_BY_GROUND); else GNNCCA_TOPK(M, GNNCCA_RANK_BY_REID)
-    switch (mode) {
-        case GNNCCA_EDGE_ATTR_FULL: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_FULL); break;
-        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE); break;
-        default: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_DIST); break;
-    }
-#undef GNNCCA_TOPK_R
-#undef GNNCCA_TOPK
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
+    return gnncca::build_edges_topk_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, top_k, rank_by, max_deg, edge_index_out, edge_attr_out,
+                                            edge_labels_out, nullptr, 0, stream);
 }
 
 size_t gnncca_normalize_columns_backward_bytes(int64_t n_rows, int64_t n_cols) {
@@ -666,6 +637,42 @@ int gnncca::build_edges_zeroing(const gnncca_frames* fr, const float* reid, int3
                                (int)n_nodes, (long long)n_edges, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
             break;
     }
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca::build_edges_topk_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                                     int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
+                                     float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream) {
+    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0 || top_k < 1 || max_deg < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
+    if (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID) return GNNCCA_ERR_INVALID_ARG;
+    if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
+    if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (!fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr ||
+        !fr->src_order || !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out)
+        return GNNCCA_ERR_INVALID_ARG;
+    if ((mode != GNNCCA_EDGE_ATTR_ONLY_DIST || rank_by == GNNCCA_RANK_BY_REID) && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
+    const int cap = std::max(64, (max_deg + 63) / 64 * 64);
+    const size_t per_wave = (size_t)cap * kTopkSlotBytes;
+    const int waves = per_wave * 4 <= 65536 ? 4 : (per_wave * 2 <= 65536 ? 2 : 1);   // 4096 slots x 12 B = 48 KB: one wave
+    const dim3 grid((unsigned)((n_nodes + waves - 1) / waves)), block(64 * waves);
+    const size_t lds = per_wave * waves;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    long long* ei = reinterpret_cast<long long*>(edge_index_out);
+#define GNNCCA_TOPK(M, K)                                                                                                          \
+    hipLaunchKernelGGL((build_edges_topk_kernel<M, K>), grid, block, lds, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, \
+                       cap, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n)
+#define GNNCCA_TOPK_R(M) \
+    if (rank_by == GNNCCA_RANK_BY_GROUND) GNNCCA_TOPK(M, GNNCCA_RANK_BY_GROUND); else GNNCCA_TOPK(M, GNNCCA_RANK_BY_REID)
+    switch (mode) {
+        case GNNCCA_EDGE_ATTR_FULL: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_FULL); break;
+        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE); break;
+        default: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_DIST); break;
+    }
+#undef GNNCCA_TOPK_R
+#undef GNNCCA_TOPK
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

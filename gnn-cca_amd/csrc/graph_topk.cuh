@@ -38,9 +38,15 @@ __device__ __forceinline__ void wave_lds_fence() {
 template <int MODE, int RANK>
 __global__ __launch_bounds__(256) void build_edges_topk_kernel(const gnncca_frames fr, const float* __restrict__ reid, int R, int N,
                                                                long long E, int cap, long long* __restrict__ ei_out,
-                                                               float* __restrict__ attr_out, float* __restrict__ lab_out) {
+                                                               float* __restrict__ attr_out, float* __restrict__ lab_out,
+                                                               int* __restrict__ zero_ptr, int zero_n) {
     constexpr int NA = MODE == GNNCCA_EDGE_ATTR_FULL ? 4 : 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_topk[];
+    // (gnncca_frames_forward_topk: the post-processing counters of the same batch are zeroed here, as build_edges_kernel does for the dense
+    // chain -- by every thread of the launch, ahead of the early returns: a wave without a source, or a source without a candidate, still
+    // does its share)
+    if (zero_ptr)
+        for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < zero_n; t += gridDim.x * blockDim.x) zero_ptr[t] = 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int p = blockIdx.x * (blockDim.x >> 6) + wave;
     if (p >= N) return;

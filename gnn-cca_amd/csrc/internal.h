@@ -135,6 +135,10 @@ GenWorkspace carve_generic(const gnncca_mpn_dims* d, int64_t n, int64_t e);
 int build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
                         int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n,
                         gnncca_stream_t stream);
+// gnncca_build_edges_topk likewise (gnncca_frames_forward_topk); zero_ptr == nullptr: the public entry point, bit for bit
+int build_edges_topk_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                             int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
+                             float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream);
 
 Family classify(const gnncca_mpn_dims* d);
 bool blob_header(const gnncca_mpn_dims* d, BlobHeader* out);  // false if unsupported

@@ -174,10 +174,11 @@ static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* pre
     return GNNCCA_OK;
 }
 
-
-int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
-                          size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
-                          gnncca_stream_t stream) {
+// The one-call chain of gnncca_frames_forward (top_k == 0: the complete graph) and gnncca_frames_forward_topk (top_k >= 1: the staging image
+// and n_edges are gnncca_plan_frames_ex(top_k)'s, the build is the capped kernel).  Everything after the build sees an ordinary edge list.
+static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
+                               size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
+                               int32_t top_k, int32_t rank_by, int32_t max_deg, gnncca_stream_t stream) {
     if (!d || !io || !io->staged_dev) return GNNCCA_ERR_INVALID_ARG;
     const int64_t n = io->n_nodes, g = io->n_frames, e = io->n_edges;
     if (n < 1 || g < 1 || e < 0) return GNNCCA_ERR_INVALID_ARG;
@@ -186,6 +187,9 @@ int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, cons
         !io->predictions || !io->pruned || !io->counters || !io->labels || (io->normalize && (!io->node_norm || !io->reid_norm)))
         return GNNCCA_ERR_INVALID_ARG;
     if (io->counters_len < 3 * n + 1 + g) return GNNCCA_ERR_INVALID_ARG;   // flow_out | flow_in | n_clusters | sizes | triggers (ABI 2: stated, not assumed)
+    // (what gnncca_build_edges_topk would refuse, refused here: before the normalisation's launch)
+    if (top_k > 0 && (io->mode < GNNCCA_EDGE_ATTR_FULL || io->mode > GNNCCA_EDGE_ATTR_ONLY_DIST)) return GNNCCA_ERR_INVALID_ARG;
+    if (top_k > 0 && rank_by == GNNCCA_RANK_BY_REID && io->reid_dim <= 0) return GNNCCA_ERR_INVALID_ARG;   // the ranking reads the table in every mode
     // the staging image (gnncca_plan_frames): f64 xw[n], yw[n], max_dist[g]; i64 ids[n]; i32 person, cam, graph_of, graph_ptr, src_order, edge_ptr, edge_ptr_g
     const char* base = static_cast<const char*>(io->staged_dev);
     gnncca_frames fr;
@@ -206,8 +210,13 @@ int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, cons
     }
     // (the post stage's counters -- flow_out | flow_in | n_clusters | sizes | triggers -- are zeroed by this launch: no memset node later)
     const bool zero_here = e > 0 && mpn_workspace != nullptr;
-    st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, io->edge_index, io->edge_attr, io->edge_labels,
-                             zero_here ? io->counters : nullptr, zero_here ? 3 * n + 1 + g : 0, stream);
+    int32_t* zero_ptr = zero_here ? io->counters : nullptr;
+    const int64_t zero_n = zero_here ? 3 * n + 1 + g : 0;
+    if (top_k > 0)
+        st = build_edges_topk_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, top_k, rank_by, max_deg, io->edge_index, io->edge_attr,
+                                      io->edge_labels, zero_ptr, zero_n, stream);
+    else
+        st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, io->edge_index, io->edge_attr, io->edge_labels, zero_ptr, zero_n, stream);
     if (st != GNNCCA_OK) return st;
     const int n_out = gnncca_num_outputs(d);
     if (n_out < 1) return GNNCCA_ERR_UNSUPPORTED;
@@ -242,6 +251,21 @@ int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, cons
     int32_t* c = io->counters;   // flow_out | flow_in | n_clusters | sizes (scratch) | triggers [G]
     return post_prune_cluster_impl(io->edge_index, io->predictions, n, e, fr.graph_ptr, edge_ptr_g, (int32_t)g, post_workspace, post_workspace_bytes,
                                    io->pruned, c, c + n, io->labels, c + 2 * n, c + 2 * n + 1, c + 3 * n + 1, have_plan, stream);
+}
+
+int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
+                          size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
+                          gnncca_stream_t stream) {
+    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, 0, 0, 0, stream);
+}
+
+int gnncca_frames_forward_topk(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
+                               size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
+                               int32_t top_k, int32_t rank_by, int32_t max_deg, gnncca_stream_t stream) {
+    if (top_k < 1 || max_deg < 0 || (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID)) return GNNCCA_ERR_INVALID_ARG;
+    if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
+    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, top_k,
+                               rank_by, max_deg, stream);
 }
 
 }  // extern "C"

@@ -25,8 +25,18 @@ pool while the caller enqueues the next batch -- and returns a `PendingFinal`; `
 (it is final for them), the others go through the reference's rounding / splitting heuristics on the host (csrc/post_host.cpp), frame by
 frame as the reference's batch-size-1 validation loop does.  The constructor's `rounding` / `pruning` / `splitting` mirror CONFIG's keys.
 
-Batches of more than 4096 detections, train mode and forward hooks take the step-by-step path (same results).  No CPU fallback."""
+`FramePipeline(model, top_k=k, rank_by='ground' | 'reid')` runs the same chain on a CAPPED graph: every detection keeps the k nearest
+cross-camera candidates of its own frame (graph_build.build_graph_batch(top_k=k) has the definition), planned by `gnncca_plan_frames_ex` and
+issued by `gnncca_frames_forward_topk` -- bit for bit what build_graph_batch(top_k=k) -> model -> threshold -> prune_and_cluster give
+(tests/test_gpu_pipeline_topk.py), from one arena sized by the capped E.  The capped list is DIRECTED: i may keep j while j does not keep i.
+The pipeline's pruning (PRUNING = True) keeps an active edge only if its reverse is in the list and active too, so the identity clusters
+come from mutual-k pairs; `r.batch`, `final()` and `final_async()` work on the kept edges, and `evaluate()` scores the kept edges only (a
+same-identity pair the cap dropped is neither a hit nor a miss).  top_k=None (the default) is the complete graph, down to the native call.
+
+Batches of more than 4096 detections, train mode and forward hooks take the step-by-step path (same results; a capped pipeline passes its
+cap on to build_graph_batch, whose limit of 4096 candidates per detection then raises NotImplementedError).  No CPU fallback."""
 import ctypes as C
+import numbers
 
 import numpy as np
 import torch
@@ -161,10 +171,21 @@ class _Finished:
 
 
 class FramePipeline:
-    def __init__(self, model, only_appearance=False, only_dist=False, normalize=True, rounding=True, pruning=True, splitting=True):
+    def __init__(self, model, only_appearance=False, only_dist=False, normalize=True, rounding=True, pruning=True, splitting=True, top_k=None,
+                 rank_by="ground"):
         self.model = model
         if not pruning:
             raise ValueError("FramePipeline prunes on the device (PRUNING = True, as config_inference.yaml:7 ships it)")
+        # the cap: build_graph_batch's arguments and its refusals, here before any batch (or the GPU) is touched
+        if rank_by not in nat.RANK_BY:
+            raise ValueError(f"rank_by must be 'ground' or 'reid', not {rank_by!r}")
+        if top_k is not None:
+            if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
+                raise ValueError(f"top_k must be None or an integer >= 1, not {top_k!r}")
+            if top_k < 1:
+                raise ValueError(f"top_k must be >= 1, not {top_k}")
+            top_k = min(int(top_k), 2 ** 31 - 1)
+        self.top_k, self.rank_by = top_k, rank_by
         self.switches = (bool(rounding), bool(pruning), bool(splitting))
         self.mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
         self.normalize = bool(normalize)
@@ -232,9 +253,13 @@ class FramePipeline:
         self._outstanding += 1
         return PendingFinal(self, ticket, host, views, (r._keep, node_ptr, edge_ptr))
 
+    def _arena(self, nbytes, device):
+        """The per-batch device arena (uninitialised: every word the chain reads it writes first)."""
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
     def _slow(self, xw, yw, ids, id_cam, sizes, max_dist, node, reid):
         b = build_graph_batch(xw, yw, ids, id_cam, sizes, max_dist, node, reid, only_appearance=self.mode == MODE_ONLY_APPEARANCE,
-                              only_dist=self.mode == MODE_ONLY_DIST, normalize=self.normalize)
+                              only_dist=self.mode == MODE_ONLY_DIST, normalize=self.normalize, top_k=self.top_k, rank_by=self.rank_by)
         with torch.no_grad():
             out = self.model(b)
         r = FrameResult()
@@ -272,8 +297,13 @@ class FramePipeline:
         if ring is None:
             ring = _staging[dev.index] = _Staging()
         pinned, event = ring.take(nbytes)
-        e = lib.gnncca_plan_frames(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data, g,
-                                   pinned.data_ptr(), nbytes)
+        top_k, max_deg = self.top_k, C.c_int32(0)
+        if top_k is None:
+            e = lib.gnncca_plan_frames(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data, g,
+                                       pinned.data_ptr(), nbytes)
+        else:
+            e = lib.gnncca_plan_frames_ex(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data,
+                                          md.ctypes.data, g, top_k, pinned.data_ptr(), nbytes, C.byref(max_deg))
         if e < 0:
             if -e == nat.ERR_INVALID_ARG:
                 raise ValueError("id_cam length does not match graph_sizes")
@@ -318,7 +348,7 @@ class FramePipeline:
             b_i64 = b_f32 + up256(4 * (o_prob + e))
             b_i32 = b_i64 + up256(8 * (o_prun + e))
             b_post = b_i32 + up256(4 * (o_labels + n))
-            arena = torch.empty(b_post + post_bytes, dtype=torch.uint8, device=dev)
+            arena = self._arena(b_post + post_bytes, dev)
             staged = arena[:nbytes]
             staged.copy_(pinned[:nbytes], non_blocking=True)
             event.record(_current_stream(dev))
@@ -337,10 +367,14 @@ class FramePipeline:
             io.logits, io.probs = fp + 4 * o_log, fp + 4 * o_prob
             io.edge_index, io.predictions, io.pruned = ip + 8 * o_ei, preds.data_ptr(), ip + 8 * o_prun
             io.counters, io.labels, io.counters_len = cp, cp + 4 * o_labels, o_labels
-            st = lib.gnncca_frames_forward(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(), post_ws.numel(),
-                                           m._options(), _raw_stream(dev))
+            if top_k is None:
+                st = lib.gnncca_frames_forward(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(), post_ws.numel(),
+                                               m._options(), _raw_stream(dev))
+            else:
+                st = lib.gnncca_frames_forward_topk(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(),
+                                                    post_ws.numel(), m._options(), top_k, nat.RANK_BY[self.rank_by], max_deg.value, _raw_stream(dev))
         if st:
-            nat.check(st, "gnncca_frames_forward")
+            nat.check(st, "gnncca_frames_forward" if top_k is None else "gnncca_frames_forward_topk")
         # views (the reference's containers): x, edge_index, edge_attr, logits as [E, 1] per classified step
         x = f32[o_node:o_node + n * d_in].view(n, d_in) if self.normalize else node_embeds
         reid_n = f32[o_reid:o_reid + n * r_dim].view(n, r_dim) if self.normalize else reid_embeds

@@ -472,6 +472,17 @@ typedef struct gnncca_frames_io {
 GNNCCA_API int gnncca_frames_forward(const gnncca_mpn_dims* dims, const void* packed_dev, const gnncca_frames_io* io,
                                      void* mpn_workspace, size_t mpn_workspace_bytes, void* post_workspace,
                                      size_t post_workspace_bytes, uint32_t options, gnncca_stream_t stream);
+/* gnncca_frames_forward on a capped graph (no counterpart in the reference): the same chain and the same gnncca_frames_io, with
+ * `staged_dev` the uploaded image of gnncca_plan_frames_ex(top_k) -- capped edge_ptr / edge_ptr_g -- `n_edges` its return value, `max_deg`
+ * its max_deg_out, and the build gnncca_build_edges_topk's kernel (which also zeroes the counters, as the dense build does for the dense
+ * chain).  The capped list is directed, so the pruning keeps an active edge only where its reverse was kept and is active too: clusters
+ * come from mutual-k pairs.  Refused before any launch: top_k < 1, an unknown rank_by, max_deg < 0 (GNNCCA_ERR_INVALID_ARG);
+ * max_deg > GNNCCA_TOPK_MAX_DEG (GNNCCA_ERR_UNSUPPORTED); whatever gnncca_frames_forward refuses.  GNNCCA_RANK_BY_REID reads the reid table
+ * in every mode, GNNCCA_EDGE_ATTR_ONLY_DIST included. */
+GNNCCA_API int gnncca_frames_forward_topk(const gnncca_mpn_dims* dims, const void* packed_dev, const gnncca_frames_io* io,
+                                          void* mpn_workspace, size_t mpn_workspace_bytes, void* post_workspace,
+                                          size_t post_workspace_bytes, uint32_t options, int32_t top_k, int32_t rank_by, int32_t max_deg,
+                                          gnncca_stream_t stream);
 
 /* ---- backward pass (training through the HIP kernels, train.py:454-494) -----------------
  * Supported (GNNCCA_OK from gnncca_backward_supported): the MFMA family (both reattach flags, all three
