@@ -4,10 +4,13 @@ every GPU-side step taken by this repository: graph construction + edge attribut
 path), threshold / pruning / identity clusters (row N2), and the per-frame scores of inference.py:349-371 aggregated as main.py:335-348
 does (gnn_cca_amd.evaluation).  Needs an MI355X.
 
-    python examples/frames_end_to_end.py [frames] [cams] [detections_per_cam] [--top-k K] [--rank-by ground|reid]
+    python examples/frames_end_to_end.py [frames] [cams] [detections_per_cam] [--top-k K] [--rank-by ground|reid] [--symmetric union|mutual]
 
 --top-k K keeps every detection's K nearest cross-camera candidates (build_graph_batch(top_k=K); the graph is then directed and the
 pruning keeps mutual pairs only); the same batch also goes through the one-call form, FramePipeline(model, top_k=K).
+--symmetric union|mutual (with --top-k) closes that list under reversal: an edge is kept if either / both of its endpoints selected the
+other.  The build then waits once for its edge count, and the pipeline takes its step-by-step path.  With --top-k the scores are also
+printed against the dense truth (evaluate_frames(against='dense'): every dropped edge counts as predicted 0).
 """
 import argparse
 import os
@@ -33,9 +36,13 @@ def main():
     ap.add_argument("per", nargs="?", type=int, default=8, metavar="detections_per_cam")
     ap.add_argument("--top-k", type=int, default=None, metavar="K", help="keep each detection's K nearest cross-camera candidates (default: all)")
     ap.add_argument("--rank-by", choices=("ground", "reid"), default="ground", help="what 'nearest' means for --top-k")
+    ap.add_argument("--symmetric", choices=("union", "mutual"), default=None,
+                    help="close the --top-k list under reversal: keep an edge if either (union) / both (mutual) endpoints selected the other")
     a = ap.parse_args()
+    if a.symmetric and not a.top_k:
+        ap.error("--symmetric needs --top-k")
     frames, cams, per = a.frames, a.cams, a.per
-    cap = dict(top_k=a.top_k, rank_by=a.rank_by)
+    cap = dict(top_k=a.top_k, rank_by=a.rank_by, symmetric=a.symmetric)
     rng = np.random.default_rng(0)
     n_g = cams * per
     n = frames * n_g
@@ -76,7 +83,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / reps
     e = batch.edge_index.shape[1]
-    print(f"{frames} frames x {cams} cameras x {per} detections: N={n} E={e}" + (f" (top_k={a.top_k} by {a.rank_by})" if a.top_k else ""))
+    print(f"{frames} frames x {cams} cameras x {per} detections: N={n} E={e}" + (f" (top_k={a.top_k} by {a.rank_by}" + (f", {a.symmetric}" if a.symmetric else "") + ")" if a.top_k else ""))
     print(f"graph build + MPN (L=4) + threshold/prune/cluster: {dt * 1e3:.3f} ms per batch "
           f"({e / dt / 1e6:.1f} M edges/s end to end, host planning included)")
     print(f"active edges after pruning: {int(post['pruned'].sum())}, identity clusters: {int(post['n_clusters'].item())}, "
@@ -85,10 +92,13 @@ def main():
     pipe = FramePipeline(model, **cap)
     r = pipe(xw, yw, ids, id_cam, [n_g] * frames, max_dist, node_embeds, reid_embeds)
     same = torch.equal(r.pruned, post["pruned"]) and torch.equal(r.labels, post["labels"])
-    print(f"FramePipeline, one call: identity clusters {int(r.n_clusters.item())}, equal to the step-by-step result: {same}")
+    print(f"FramePipeline, {'one call' if r._d2h is not None else 'step by step'}: identity clusters {int(r.n_clusters.item())}, equal to the step-by-step result: {same}")
     # per-frame metrics against the ground truth the graph build wrote (batch.edge_labels: same person id), then main.py's aggregates
     acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"]))
     print("aggregates over the frames:", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))
+    if a.top_k:   # a capped graph: the same predictions scored as the dense graph would have been, dropped edges predicted 0
+        acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"], against="dense"))
+        print("against the dense truth:   ", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))
     print("random weights / random embeddings: the cluster structure is meaningless, the plumbing is what is shown")
 
 

@@ -13,6 +13,7 @@ AGG = {"sum": 0, "mean": 1, "max": 2}
 GRAPH_UNSORTED, GRAPH_BAD_INDEX = 1, 2
 RANK_BY = {"ground": 0, "reid": 1}   # gnncca_build_edges_topk, gnncca_frames_forward_topk
 TOPK_MAX_DEG = 4096
+SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
 
 
 class Layer(C.Structure):
@@ -113,6 +114,11 @@ _SIGNATURES = {
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gnncca_build_edges_topk": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_build_edges_topk_sym_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
+    "gnncca_build_edges_topk_sym_count": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "gnncca_build_edges_topk_sym_emit": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnncca_build_edges_topk_backward_bytes": (C.c_size_t, [C.c_int64]),
     "gnncca_build_edges_topk_backward": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -197,6 +203,8 @@ _SIGNATURES = {
     "gnncca_eval_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "gnncca_eval_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnncca_eval_frames_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnncca_edge_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "gnncca_edge_loss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -31,7 +31,7 @@ constexpr int kEvalMaxSizes = 96;   // distinct cluster sizes of one side: k (k 
 constexpr double kEps = 2.220446049250313e-16;   // np.finfo(np.float64).eps
 
 // integer accumulators of a frame (LDS atomics: order-independent)
-enum { I_TP, I_FP, I_TN, I_FN, I_C1, I_C0, I_SSQ, I_SA2, I_SB2, I_KA, I_KB, I_NGT, I_NPRED, I_COUNT };
+enum { I_TP, I_FP, I_TN, I_FN, I_C1, I_C0, I_SSQ, I_SA2, I_SB2, I_KA, I_KB, I_NGT, I_NPRED, I_D1, I_D0, I_COUNT };
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -57,11 +57,18 @@ __device__ __forceinline__ int lds_load(const int* p) { return __hip_atomic_load
 // out[g][16] = P, R, F, TP, FP, FN, TN, ARI, AMI, homogeneity, completeness, V, precision0, precision1, n_clusters_gt, n_clusters_pred.
 // P_lds: ints per LDS region (a power of two >= every frame's node count, <= kEvalMaxNodes).  lf_ws: the lgamma tables, frame g's at
 // lf_ws + node_ptr[g] + g.  A frame whose ranges do not fit (node count above P_lds, ranges outside the arrays) gets a NaN row.
-template <int BLOCK>
+// DENSE (gnncca_eval_frames_dense): the batch is a capped graph, scored as the dense graph with every dropped edge predicted 0.  The GT
+// partition then comes from the person ids and cameras, not from the kept edges: thread v walks the frame (person / cam staged in the LDS
+// regions steps 2-3 use later) for the smallest detection with v's identity, whether that identity is on another camera too (then the
+// dense graph's label-1 edges join all its detections: any two on one camera meet through one on another), and v's dense out-degree per
+// class, whose sums minus the kept edges of the class are the dropped pairs: FN += D1 - C1, TN += D0 - C0.  n^2 / BLOCK LDS reads per
+// thread (64 k at 4096 nodes).  person / cam are null otherwise and nothing of this runs: the instantiation is the kernel as it was.
+template <int BLOCK, bool DENSE>
 __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __restrict__ ei, long long E, const float* __restrict__ elab,
                                                             const long long* __restrict__ pred, const int* __restrict__ labels, int N_all,
                                                             const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int P_lds,
-                                                            int* __restrict__ gt_out, double* __restrict__ out, double* __restrict__ lf_ws) {
+                                                            int* __restrict__ gt_out, double* __restrict__ out, double* __restrict__ lf_ws,
+                                                            const int* __restrict__ person, const int* __restrict__ cam) {
     extern __shared__ int s_dyn[];
     __shared__ unsigned long long s_int[I_COUNT];
     __shared__ double s_red[BLOCK / 64];
@@ -83,11 +90,34 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
     double* lf = lf_ws + v0 + g;
     for (int v = tid; v < n; v += BLOCK) {
         parent[v] = v;
-        cnt[v] = 0;
+        cnt[v] = DENSE ? (unsigned)cam[v0 + v] : 0u;
+        if (DENSE) keys[v] = (unsigned)person[v0 + v];
     }
     for (int k = tid; k <= n; k += BLOCK) lf[k] = lgamma((double)k + 1.0);   // read only after the barriers below
     if (tid < I_COUNT) s_int[tid] = 0;
     __syncthreads();
+    if (DENSE) {
+        unsigned long long d1 = 0, d0 = 0;
+        for (int v = tid; v < n; v += BLOCK) {
+            const unsigned pv = keys[v], cv = cnt[v];
+            int first = v;
+            unsigned same_other = 0, diff_other = 0;
+            for (int u = 0; u < n; ++u) {
+                const bool same = keys[u] == pv, other = cnt[u] != cv;
+                first = same && u < first ? u : first;
+                same_other += same && other;
+                diff_other += !same && other;
+            }
+            parent[v] = same_other ? first : v;   // (roots point at themselves: `first` has the same identity and sees the same cameras)
+            d1 += same_other;
+            d0 += diff_other;
+        }
+        if (d1) atomicAdd(&s_int[I_D1], d1);
+        if (d0) atomicAdd(&s_int[I_D0], d0);
+        __syncthreads();
+        for (int v = tid; v < n; v += BLOCK) cnt[v] = 0;
+        __syncthreads();
+    }
 
     // ---- 1. edge counts (compute_P_R_F) and the GT partition, one pass over the frame's edges ----------------------------------------
     // Union-find over the edges with label 1: a root is hooked under the smaller root by compare-and-swap (it fails when another thread
@@ -105,7 +135,7 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
                 tp += p == 1;
                 fn += p == 0;
                 int ra = (int)a, rb = (int)b;
-                while (true) {
+                while (!DENSE) {   // (DENSE: the partition is the dense graph's, made above)
                     for (int q = lds_load(&parent[ra]); q != ra; q = lds_load(&parent[ra])) ra = q;
                     for (int q = lds_load(&parent[rb]); q != rb; q = lds_load(&parent[rb])) rb = q;
                     if (ra == rb) break;
@@ -279,7 +309,12 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
 
     // ---- the row ------------------------------------------------------------------------------------------------------------------
     if (tid != 0) return;
-    const unsigned long long TP = s_int[I_TP], FP = s_int[I_FP], TN = s_int[I_TN], FN = s_int[I_FN], C1 = s_int[I_C1], C0 = s_int[I_C0];
+    unsigned long long TP = s_int[I_TP], FP = s_int[I_FP], TN = s_int[I_TN], FN = s_int[I_FN], C1 = s_int[I_C1], C0 = s_int[I_C0];
+    if (DENSE) {   // the dropped ordered pairs of each class: predicted 0
+        const unsigned long long D1 = s_int[I_D1], D0 = s_int[I_D0];
+        if (D1 > C1) FN += D1 - C1, C1 = D1;
+        if (D0 > C0) TN += D0 - C0, C0 = D0;
+    }
     // compute_P_R_F, expression for expression
     const double P = (TP + FP) != 0 ? (double)TP / (double)(TP + FP) : 0.0;
     const double R = (TP + FN) != 0 ? (double)TP / (double)(TP + FN) : 0.0;
@@ -337,15 +372,16 @@ size_t gnncca_eval_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_f
     return bytes < 256 ? 256 : (bytes + 255) / 256 * 256;
 }
 
-int gnncca_eval_frames(const int64_t* edge_index, const float* edge_labels, const int64_t* predictions, const int32_t* labels,
-                       int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
-                       int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace, size_t workspace_bytes,
-                       gnncca_stream_t stream) {
+static int eval_frames(const int64_t* edge_index, const float* edge_labels, const int64_t* predictions, const int32_t* labels,
+                       const int32_t* person_id, const int32_t* cam, bool dense, int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev,
+                       const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes, int32_t* gt_labels_out, double* out,
+                       void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
     if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
     if (max_frame_nodes < 0 || max_frame_nodes > kEvalMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
     if (n_frames == 0) return GNNCCA_OK;
     if (!node_ptr_dev || !edge_ptr_dev || !out || !workspace) return GNNCCA_ERR_INVALID_ARG;
     if (n_nodes > 0 && !labels) return GNNCCA_ERR_INVALID_ARG;
+    if (dense && n_nodes > 0 && (!person_id || !cam)) return GNNCCA_ERR_INVALID_ARG;
     if (n_edges > 0 && (!edge_index || !edge_labels || !predictions)) return GNNCCA_ERR_INVALID_ARG;
     if (workspace_bytes < gnncca_eval_workspace_bytes(n_nodes, n_edges, n_frames)) return GNNCCA_ERR_WORKSPACE;
     if (n_nodes >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
@@ -356,14 +392,33 @@ int gnncca_eval_frames(const int64_t* edge_index, const float* edge_labels, cons
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
     const long long* pr = reinterpret_cast<const long long*>(predictions);
     double* lf = static_cast<double*>(workspace);
-    if (P <= 64)   // small frames (a Terrace frame has ~20 detections): one wave per frame
-        hipLaunchKernelGGL(eval_frames_kernel<64>, dim3((unsigned)n_frames), dim3(64), lds, st, ei, (long long)n_edges, edge_labels, pr,
-                           labels, (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, gt_labels_out, out, lf);
-    else
-        hipLaunchKernelGGL(eval_frames_kernel<256>, dim3((unsigned)n_frames), dim3(256), lds, st, ei, (long long)n_edges, edge_labels, pr,
-                           labels, (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, gt_labels_out, out, lf);
+#define GNNCCA_EVAL(B, D)                                                                                                            \
+    hipLaunchKernelGGL((eval_frames_kernel<B, D>), dim3((unsigned)n_frames), dim3(B), lds, st, ei, (long long)n_edges, edge_labels, pr, \
+                       labels, (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, gt_labels_out, out, lf, person_id, cam)
+    if (P <= 64) {   // small frames (a Terrace frame has ~20 detections): one wave per frame
+        if (dense) GNNCCA_EVAL(64, true); else GNNCCA_EVAL(64, false);
+    } else {
+        if (dense) GNNCCA_EVAL(256, true); else GNNCCA_EVAL(256, false);
+    }
+#undef GNNCCA_EVAL
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
+}
+
+int gnncca_eval_frames(const int64_t* edge_index, const float* edge_labels, const int64_t* predictions, const int32_t* labels,
+                       int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                       int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace, size_t workspace_bytes,
+                       gnncca_stream_t stream) {
+    return eval_frames(edge_index, edge_labels, predictions, labels, nullptr, nullptr, false, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev,
+                       n_frames, max_frame_nodes, gt_labels_out, out, workspace, workspace_bytes, stream);
+}
+
+int gnncca_eval_frames_dense(const int64_t* edge_index, const float* edge_labels, const int64_t* predictions, const int32_t* labels,
+                             const int32_t* person_id, const int32_t* cam, int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev,
+                             const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes, int32_t* gt_labels_out, double* out,
+                             void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
+    return eval_frames(edge_index, edge_labels, predictions, labels, person_id, cam, true, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev,
+                       n_frames, max_frame_nodes, gt_labels_out, out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -421,6 +421,7 @@ __global__ __launch_bounds__(256) void colnorm_fused_lds_kernel(const ColnormJob
 
 #include "graph_grads.cuh"
 #include "graph_topk.cuh"
+#include "graph_topk_sym.cuh"
 
 using namespace gnncca;
 
@@ -551,6 +552,105 @@ int gnncca_build_edges_topk(const gnncca_frames* fr, const float* reid, int32_t 
                             float* edge_labels_out, gnncca_stream_t stream) {
     return gnncca::build_edges_topk_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, top_k, rank_by, max_deg, edge_index_out, edge_attr_out,
                                             edge_labels_out, nullptr, 0, stream);
+}
+
+// ---- the capped neighbourhood closed under reversal (graph_topk_sym.cuh) ----
+size_t gnncca_build_edges_topk_sym_bytes(const int64_t* graph_sizes, int64_t n_frames) {
+    if (n_frames < 0 || (n_frames > 0 && !graph_sizes)) return 0;
+    long long nodes = 0;
+    const long long words = topk_sym_words(graph_sizes, n_frames, &nodes);
+    if (words < 0) return 0;
+    const size_t bytes = (size_t)words * 16 + (size_t)nodes * sizeof(int32_t);
+    return bytes < 16 ? 16 : (bytes + 15) / 16 * 16;
+}
+
+// what both entry points check of the frame sizes and the workspace; *words_out: words of one bit matrix
+static int topk_sym_layout(const int64_t* graph_sizes, int64_t n_frames, int64_t n_nodes, const void* workspace, size_t workspace_bytes,
+                           long long* words_out) {
+    if (n_frames < 0 || (n_frames > 0 && !graph_sizes)) return GNNCCA_ERR_INVALID_ARG;
+    long long nodes = 0;
+    const long long words = topk_sym_words(graph_sizes, n_frames, &nodes);
+    if (words < 0 || nodes != n_nodes) return GNNCCA_ERR_INVALID_ARG;   // graph_sizes do not describe these n_nodes detections
+    if (n_frames >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7)) return GNNCCA_ERR_INVALID_ARG;
+    if (workspace_bytes < gnncca_build_edges_topk_sym_bytes(graph_sizes, n_frames)) return GNNCCA_ERR_WORKSPACE;
+    *words_out = words;
+    return GNNCCA_OK;
+}
+
+int gnncca_build_edges_topk_sym_count(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                      const int64_t* graph_sizes, int64_t n_frames, int32_t top_k, int32_t rank_by, int32_t max_deg,
+                                      int32_t symmetric, void* workspace, size_t workspace_bytes, int32_t* edge_ptr_g_dev,
+                                      gnncca_stream_t stream) {
+    if (!fr || n_nodes < 0 || reid_dim < 0 || top_k < 1 || max_deg < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID) return GNNCCA_ERR_INVALID_ARG;
+    if (symmetric != GNNCCA_SYMMETRIC_UNION && symmetric != GNNCCA_SYMMETRIC_MUTUAL) return GNNCCA_ERR_INVALID_ARG;
+    if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
+    if (n_nodes >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (!fr->xw || !fr->yw || !fr->cam || !fr->graph_of || !fr->graph_ptr || !fr->src_order || !fr->edge_ptr || !edge_ptr_g_dev)
+        return GNNCCA_ERR_INVALID_ARG;
+    if (rank_by == GNNCCA_RANK_BY_REID && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
+    long long words = 0;
+    if (const int bad = topk_sym_layout(graph_sizes, n_frames, n_nodes, workspace, workspace_bytes, &words)) return bad;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long* bits_a = static_cast<unsigned long long*>(workspace);
+    unsigned long long* bits_b = bits_a + words;
+    int* counts = reinterpret_cast<int*>(bits_b + words);
+    int* edge_ptr = const_cast<int*>(fr->edge_ptr);   // the staging image's own words: the plan's capped values are replaced
+    if (n_nodes > 0) {
+        const int cap = std::max(64, (max_deg + 63) / 64 * 64);
+        const size_t per_wave = (size_t)cap * kTopkSlotBytes;
+        const int waves = per_wave * 4 <= 65536 ? 4 : (per_wave * 2 <= 65536 ? 2 : 1);
+        const dim3 grid((unsigned)((n_nodes + waves - 1) / waves)), block(64 * waves);
+        if (rank_by == GNNCCA_RANK_BY_GROUND)
+            hipLaunchKernelGGL((topk_sym_select_kernel<GNNCCA_RANK_BY_GROUND>), grid, block, per_wave * waves, st, *fr, reid, (int)reid_dim,
+                               (int)n_nodes, (int)top_k, cap, bits_a, words);
+        else
+            hipLaunchKernelGGL((topk_sym_select_kernel<GNNCCA_RANK_BY_REID>), grid, block, per_wave * waves, st, *fr, reid, (int)reid_dim,
+                               (int)n_nodes, (int)top_k, cap, bits_a, words);
+        HIP_TRY(hipGetLastError());
+        const dim3 grid4((unsigned)((n_nodes + 3) / 4));
+        if (symmetric == GNNCCA_SYMMETRIC_UNION)
+            hipLaunchKernelGGL((topk_sym_close_kernel<true>), grid4, dim3(256), 0, st, *fr, (int)n_nodes, bits_a, bits_b, words, counts);
+        else
+            hipLaunchKernelGGL((topk_sym_close_kernel<false>), grid4, dim3(256), 0, st, *fr, (int)n_nodes, bits_a, bits_b, words, counts);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(topk_sym_scan_kernel, dim3(1), dim3(256), 0, st, counts, (int)n_nodes, (int)n_frames, fr->graph_ptr, edge_ptr,
+                       edge_ptr_g_dev);
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_build_edges_topk_sym_emit(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                     const int64_t* graph_sizes, int64_t n_frames, int64_t n_edges, int32_t mode, const void* workspace,
+                                     size_t workspace_bytes, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                                     gnncca_stream_t stream) {
+    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    long long words = 0;
+    if (const int bad = topk_sym_layout(graph_sizes, n_frames, n_nodes, workspace, workspace_bytes, &words)) return bad;
+    if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
+    if (!fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr || !fr->src_order ||
+        !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out)
+        return GNNCCA_ERR_INVALID_ARG;
+    if (mode != GNNCCA_EDGE_ATTR_ONLY_DIST && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned long long* bits_b = static_cast<const unsigned long long*>(workspace) + words;
+    long long* ei = reinterpret_cast<long long*>(edge_index_out);
+    const dim3 grid((unsigned)((n_nodes + 3) / 4)), block(256);
+#define GNNCCA_SYM_EMIT(M)                                                                                                              \
+    hipLaunchKernelGGL((topk_sym_emit_kernel<M>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, bits_b, \
+                       words, ei, edge_attr_out, edge_labels_out)
+    switch (mode) {
+        case GNNCCA_EDGE_ATTR_FULL: GNNCCA_SYM_EMIT(GNNCCA_EDGE_ATTR_FULL); break;
+        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE: GNNCCA_SYM_EMIT(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE); break;
+        default: GNNCCA_SYM_EMIT(GNNCCA_EDGE_ATTR_ONLY_DIST); break;
+    }
+#undef GNNCCA_SYM_EMIT
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
 }
 
 size_t gnncca_normalize_columns_backward_bytes(int64_t n_rows, int64_t n_cols) {

@@ -23,6 +23,7 @@
 // Terrace-sized frame), else two or one.  GNNCCA_TOPK_MAX_DEG = 4096 candidates per source is what one wave's 48 KB holds; more is
 // refused on the host (GNNCCA_ERR_UNSUPPORTED), and a source whose frame turns out to hold more candidates than the caller declared
 // is left unwritten rather than overrunning its slots.
+// Passes 1 and 2 are the device functions topk_keys / topk_threshold: the symmetric build (graph_topk_sym.cuh) runs the same code.
 // Part of the translation unit graph_build.hip.
 
 namespace gnncca {
@@ -33,6 +34,59 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- passes 1 and 2, shared with the symmetric build (graph_topk_sym.cuh): one wave, the same statements, the same bits ----
+// 1. keys of source i (camera ci, at xi / yi, reid row ri) against its frame [gs, ge): key and node id of every cross-camera candidate at
+// its rank among the candidates -> s_key / s_node (slots below `cap` only).  Returns deg, the number of candidates found.
+template <int RANK>
+__device__ __forceinline__ int topk_keys(const gnncca_frames& fr, const float* __restrict__ reid, const float* __restrict__ ri, int R, bool vec4,
+                                         int gs, int ge, int ci, double xi, double yi, int cap, int lane,
+                                         unsigned long long* __restrict__ s_key, int* __restrict__ s_node) {
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int deg = 0;
+    for (int j0 = gs; j0 < ge; j0 += 64) {
+        const int j = j0 + lane;
+        const bool valid = j < ge && fr.cam[j] != ci;   // same camera: no edge (inference.py:210-211)
+        const unsigned long long mask = __ballot(valid);
+        if (mask == 0ull) continue;
+        unsigned long long key = 0ull;
+        if (RANK == GNNCCA_RANK_BY_GROUND) {
+            if (valid) {
+                double l2, l1;
+                ground_dists(xi, yi, fr.xw[j], fr.yw[j], l2, l1);
+                key = (unsigned long long)__double_as_longlong(l2);
+            }
+        } else {
+            float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;
+            reid_sums_wave(reid, ri, R, vec4, mask, lane, [&](int t) { return j0 + t; }, sd, sab, saa, sbb);
+            key = (unsigned long long)__float_as_uint(reid_emb(sd));
+        }
+        const int idx = deg + __popcll(mask & below);
+        if (valid && idx < cap) s_key[idx] = key, s_node[idx] = j;
+        deg += __popcll(mask);
+    }
+    return deg;
+}
+
+// 2. the n_keep-th smallest of the deg keys in s_key (n_keep < deg): T, and `need`, how many of the keys equal to T survive.
+template <int RANK>
+__device__ __forceinline__ void topk_threshold(const unsigned long long* __restrict__ s_key, int deg, int n_keep, int lane,
+                                               unsigned long long& T, int& need) {
+    auto count_below_key = [&](unsigned long long c) {
+        int cnt = 0;
+        for (int base = 0; base < deg; base += 64) {
+            const int idx = base + lane;
+            cnt += __popcll(__ballot(idx < deg && s_key[idx] < c));
+        }
+        return cnt;
+    };
+    T = 0ull;
+    for (int b = RANK == GNNCCA_RANK_BY_GROUND ? 63 : 31; b >= 0; --b) {
+        const unsigned long long c = T | (1ull << b);
+        if (count_below_key(c) < n_keep) T = c;
+    }
+    need = n_keep - count_below_key(T);
 }
 
 template <int MODE, int RANK>
@@ -65,28 +119,7 @@ __global__ __launch_bounds__(256) void build_edges_topk_kernel(const gnncca_fram
     const unsigned long long below = (1ull << lane) - 1ull;
 
     // ---- 1. keys ----
-    int deg = 0;
-    for (int j0 = gs; j0 < ge; j0 += 64) {
-        const int j = j0 + lane;
-        const bool valid = j < ge && fr.cam[j] != ci;   // same camera: no edge (inference.py:210-211)
-        const unsigned long long mask = __ballot(valid);
-        if (mask == 0ull) continue;
-        unsigned long long key = 0ull;
-        if (RANK == GNNCCA_RANK_BY_GROUND) {
-            if (valid) {
-                double l2, l1;
-                ground_dists(xi, yi, fr.xw[j], fr.yw[j], l2, l1);
-                key = (unsigned long long)__double_as_longlong(l2);
-            }
-        } else {
-            float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;
-            reid_sums_wave(reid, ri, R, vec4, mask, lane, [&](int t) { return j0 + t; }, sd, sab, saa, sbb);
-            key = (unsigned long long)__float_as_uint(reid_emb(sd));
-        }
-        const int idx = deg + __popcll(mask & below);
-        if (valid && idx < cap) s_key[idx] = key, s_node[idx] = j;
-        deg += __popcll(mask);
-    }
+    const int deg = topk_keys<RANK>(fr, reid, ri, R, vec4, gs, ge, ci, xi, yi, cap, lane, s_key, s_node);
     if (deg > cap || n_keep > deg) return;   // more candidates than the caller declared, or a plan of another batch: nothing is written
     wave_lds_fence();
 
@@ -94,21 +127,7 @@ __global__ __launch_bounds__(256) void build_edges_topk_kernel(const gnncca_fram
     const bool all = n_keep >= deg;
     unsigned long long T = 0ull;
     int need = 0;   // how many of the keys equal to T survive
-    if (!all) {
-        auto count_below_key = [&](unsigned long long c) {
-            int cnt = 0;
-            for (int base = 0; base < deg; base += 64) {
-                const int idx = base + lane;
-                cnt += __popcll(__ballot(idx < deg && s_key[idx] < c));
-            }
-            return cnt;
-        };
-        for (int b = RANK == GNNCCA_RANK_BY_GROUND ? 63 : 31; b >= 0; --b) {
-            const unsigned long long c = T | (1ull << b);
-            if (count_below_key(c) < n_keep) T = c;
-        }
-        need = n_keep - count_below_key(T);
-    }
+    if (!all) topk_threshold<RANK>(s_key, deg, n_keep, lane, T, need);
 
     // ---- 3. the survivors, in candidate order ----
     int emitted = 0, ties = 0;

@@ -3,6 +3,8 @@ and the aggregation main.py:335-348 makes of it, without copying frames to the h
 
     rows = evaluate_frames(batch, predictions, labels)       # float64 [G, 16] on the device, columns METRICS; one launch, no sync
     rows = r.evaluate()                                      # r: a pipeline.FrameResult (its final() predictions / labels)
+    rows = evaluate_frames(batch, predictions, labels, against='dense')   # a capped batch (top_k=k) scored as the dense graph, every
+    rows = r.evaluate(against='dense')                                    # dropped edge predicted 0: comparable with a dense run
     acc = EvalAccumulator(); acc.add(rows) ...; acc.result() # {'P': ..., 'R': ..., 'TP': ..., 'RI': ..., 'MI': ...} as main.py prints them
 
 Per frame (csrc/evaluate.hip, one workgroup each): TP / FP / FN / TN, P, R, F and the two per-class precisions exactly as
@@ -38,11 +40,29 @@ def _dev_i32(t, like):
     return t if t.dtype == torch.int32 and t.is_contiguous() else t.to(device=like.device, dtype=torch.int32).contiguous()
 
 
-def evaluate_frames(batch, predictions, labels, gt_labels=False):
+AGAINST = ("kept", "dense")
+
+
+def evaluate_frames(batch, predictions, labels, gt_labels=False, against="kept"):
     """Scores every frame of `batch` (a GraphBatch with edge_index, edge_labels, host node_ptr / edge_ptr and device node_ptr_dev /
     edge_ptr_dev, as graph_build.build_graph_batch and pipeline.FramePipeline make it) against `predictions` int64 [E] (0/1) and
     `labels` int32 [N] (the predicted partition, a node's label the smallest node id of its cluster).  Enqueued on the current stream;
-    returns float64 [G, 16] (columns METRICS) on the device, and with gt_labels=True also ID_GT as int32 [N] in the same convention."""
+    returns float64 [G, 16] (columns METRICS) on the device, and with gt_labels=True also ID_GT as int32 [N] in the same convention.
+
+    against='kept' (the default) scores the batch's own edges: on a capped batch (top_k=k) a same-identity pair the cap dropped is
+    neither a hit nor a miss, and ID_GT is made of the kept label-1 edges.  against='dense' scores a capped batch as the DENSE graph would
+    have been scored with every dropped edge predicted 0 (no counterpart in the reference, which has no capped graph): TP and FP as
+    before; FN grows by the dropped label-1 ordered pairs and TN by the dropped label-0 ones (counted from the per-frame person ids and
+    cameras: ordered cross-camera pairs with the same / a different id, minus the kept ones); ID_GT is the dense graph's -- all
+    detections of an identity seen on at least two cameras form one component, every other detection its own; P, R, F, the class
+    precisions and the clustering scores are the same expressions on those inputs.  It needs batch.person_dev / batch.cam_dev (int32 [N]
+    on the device: build_graph_batch and FramePipeline provide them), runs in the same one-workgroup-per-frame launch and does not
+    synchronise; on a dense batch it returns the default's rows."""
+    if against not in AGAINST:
+        raise ValueError(f"against must be 'kept' or 'dense', not {against!r}")
+    dense = against == "dense"
+    if dense and (getattr(batch, "person_dev", None) is None or getattr(batch, "cam_dev", None) is None):
+        raise ValueError("evaluate_frames(against='dense') needs batch.person_dev and batch.cam_dev (int32 [N] on the device)")
     node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
     g = len(node_ptr) - 1
     n = int(node_ptr[-1]) if g > 0 else 0
@@ -66,9 +86,18 @@ def evaluate_frames(batch, predictions, labels, gt_labels=False):
         gt = torch.empty(n, dtype=torch.int32, device=dev) if gt_labels else None
         ws_bytes = lib.gnncca_eval_workspace_bytes(n, e, g)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        st = lib.gnncca_eval_frames(ei.data_ptr() if e else None, el.data_ptr() if e else None, pr.data_ptr() if e else None,
-                                    lb.data_ptr() if n else None, n, e, nptr.data_ptr(), eptr.data_ptr(), g, max_n,
-                                    gt.data_ptr() if gt_labels and n else None, out.data_ptr(), ws.data_ptr(), ws_bytes, _raw_stream(dev))
+        if dense:
+            person, cam = _dev_i32(batch.person_dev, lb), _dev_i32(batch.cam_dev, lb)
+            if person.numel() != n or cam.numel() != n:
+                raise ValueError(f"batch.person_dev [{person.numel()}] / batch.cam_dev [{cam.numel()}] do not match the batch (N={n})")
+            st = lib.gnncca_eval_frames_dense(ei.data_ptr() if e else None, el.data_ptr() if e else None, pr.data_ptr() if e else None,
+                                              lb.data_ptr() if n else None, person.data_ptr() if n else None, cam.data_ptr() if n else None,
+                                              n, e, nptr.data_ptr(), eptr.data_ptr(), g, max_n, gt.data_ptr() if gt_labels and n else None,
+                                              out.data_ptr(), ws.data_ptr(), ws_bytes, _raw_stream(dev))
+        else:
+            st = lib.gnncca_eval_frames(ei.data_ptr() if e else None, el.data_ptr() if e else None, pr.data_ptr() if e else None,
+                                        lb.data_ptr() if n else None, n, e, nptr.data_ptr(), eptr.data_ptr(), g, max_n,
+                                        gt.data_ptr() if gt_labels and n else None, out.data_ptr(), ws.data_ptr(), ws_bytes, _raw_stream(dev))
         if st:
             nat.check(st, "gnncca_eval_frames")
         # the workspace is freed by the caching allocator in stream order (it was allocated on this stream): nothing to keep

@@ -220,12 +220,14 @@ def _as(a, dtype):
 
 class _EdgeJob:
     """What the edge kernels of one batch need besides the reid table: the staged frame image and its sizes; for a capped build
-    (top_k is not None) also the cap, the ranking key and the batch's largest uncapped degree."""
-    __slots__ = ("staged", "n", "g", "e", "mode", "top_k", "rank", "max_deg")
+    (top_k is not None) also the cap, the ranking key and the batch's largest uncapped degree; for a symmetric one (sym != 0) the host
+    array of frame sizes too -- and `e` / `edge_ptr_g` are what its count read back, set by _edges_launch."""
+    __slots__ = ("staged", "n", "g", "e", "mode", "top_k", "rank", "max_deg", "sym", "sizes", "edge_ptr_g")
 
-    def __init__(self, staged, n, g, e, mode, top_k=None, rank=0, max_deg=0):
+    def __init__(self, staged, n, g, e, mode, top_k=None, rank=0, max_deg=0, sym=0, sizes=None):
         self.staged, self.n, self.g, self.e, self.mode = staged, n, g, e, mode
         self.top_k, self.rank, self.max_deg = top_k, rank, max_deg
+        self.sym, self.sizes, self.edge_ptr_g = sym, sizes, None
 
     def frames(self):
         n, g = self.n, self.g
@@ -238,9 +240,52 @@ class _EdgeJob:
         return fr
 
 
+_readback = {}   # device index -> (pinned int32 buffer, event) of the symmetric build's one read-back
+
+
+def _sym_edges_launch(job, reid_embeds):
+    """The symmetric capped build on the current stream: gnncca_build_edges_topk_sym_count, ONE pinned device-to-host copy of the G + 1
+    per-frame edge offsets (the last is E) queued behind it and waited on through an event -- the call's only host wait -- then the
+    outputs are allocated and gnncca_build_edges_topk_sym_emit fills them.  Sets job.e and job.edge_ptr_g (host list)."""
+    dev, n, g = reid_embeds.device, job.n, job.g
+    lib = nat.lib()
+    fr = job.frames()
+    sizes = job.sizes
+    nbytes = lib.gnncca_build_edges_topk_sym_bytes(sizes.ctypes.data, g)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    eptr_g = job.staged[8 * (3 * n + g) + 4 * (5 * n + g + 2):8 * (3 * n + g) + 4 * (5 * n + 2 * g + 3)].view(torch.int32)
+    st = lib.gnncca_build_edges_topk_sym_count(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, sizes.ctypes.data, g, job.top_k,
+                                               job.rank, job.max_deg, job.sym, ws.data_ptr(), nbytes, eptr_g.data_ptr(), _raw_stream(dev))
+    if st:
+        nat.check(st, "gnncca_build_edges_topk_sym_count")
+    hit = _readback.get(dev.index)
+    if hit is None or hit[0].numel() < g + 1:
+        hit = _readback[dev.index] = (torch.empty(max(2 * (g + 1), 256), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
+    host, event = hit
+    host[:g + 1].copy_(eptr_g, non_blocking=True)
+    event.record(_current_stream(dev))
+    event.synchronize()
+    job.edge_ptr_g = host[:g + 1].tolist()
+    e = job.e = job.edge_ptr_g[-1]
+    if e >= 2 ** 31 - 64:
+        raise NotImplementedError("more than 2^31 edges in one batch")
+    n_attr = 4 if job.mode == MODE_FULL else 2
+    edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
+    edge_attr = torch.empty((e, n_attr), dtype=torch.float32, device=dev)
+    edge_labels = torch.empty(e, dtype=torch.float32, device=dev)
+    st = lib.gnncca_build_edges_topk_sym_emit(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, sizes.ctypes.data, g, e, job.mode,
+                                              ws.data_ptr(), nbytes, edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(),
+                                              _raw_stream(dev))
+    if st:
+        nat.check(st, "gnncca_build_edges_topk_sym_emit")
+    return edge_index, edge_attr, edge_labels
+
+
 def _edges_launch(job, reid_embeds):
-    """gnncca_build_edges (gnncca_build_edges_topk for a capped job) on the current stream: (edge_index, edge_attr, edge_labels), new
-    tensors."""
+    """gnncca_build_edges (gnncca_build_edges_topk for a capped job, the two ..._topk_sym_* calls for a symmetric one) on the current
+    stream: (edge_index, edge_attr, edge_labels), new tensors."""
+    if job.sym:
+        return _sym_edges_launch(job, reid_embeds)
     dev, n, e = reid_embeds.device, job.n, job.e
     n_attr = 4 if job.mode == MODE_FULL else 2
     fr = job.frames()
@@ -339,7 +384,7 @@ class _GraphBuildFunction(torch.autograd.Function):
 
 
 def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds, only_appearance=False,
-                      only_dist=False, normalize=True, top_k=None, rank_by="ground"):
+                      only_dist=False, normalize=True, top_k=None, rank_by="ground", symmetric=None):
     """One call per batch of frames.  Host inputs (numpy, one entry per detection, frames concatenated): xw, yw, ids,
     id_cam; graph_sizes / max_dist per frame.  Device inputs: node_embeds [N, D], reid_embeds [N, R].
     Returns a GraphBatch (x, edge_index, edge_attr) with .edge_labels and .y, laid out exactly like the reference's
@@ -356,11 +401,30 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
     E = sum_i min(k, deg_i) known on the host (gnncca_plan_frames_ex): still no synchronisation.  edge_ptr, node_ptr, their device copies,
     edge_labels and y keep their meaning.
     The capped graph is DIRECTED: i may keep j while j does not keep i.  postprocess' remove_edges_single_direction therefore keeps
-    mutual pairs only; a caller who wants the union symmetrises edge_index (and the attributes) itself.
+    mutual pairs only, and a kept edge without its reverse can never become an association (symmetric= below closes the list).
     At most 4096 candidates per source (NotImplementedError beyond).  Differentiable like the dense build: gradients flow through the
-    kept edges' emb / cos attributes."""
+    kept edges' emb / cos attributes.
+
+    symmetric=None (the default) is that directed list D, down to the native call.  symmetric='union' keeps the dense edge (i, j) iff
+    (i, j) or (j, i) is in D, symmetric='mutual' iff both are (no counterpart in the reference either: it only builds complete graphs,
+    every pair in both directions, and its pruning deletes an active edge without an active reverse).  Whether i is in j's list is j's
+    own selection, made with the key bits j ranks with ('reid' keys are not symmetric: F.pairwise_distance adds its eps to a - b); no key
+    is evaluated from two sides.  The result is a subsequence of the dense edge list in dense order, a kept edge carries the dense
+    build's bits (attributes, label, ids), it is closed under reversal, mutual <= D <= union, and for k >= max deg both modes are the
+    dense build, bit for bit (edge_index, edge_attr, edge_labels, x, y, edge_ptr, node_ptr and the device copies).  edge_ptr,
+    edge_ptr_dev, node_ptr, edge_labels and y keep their meaning; a frame or a source may end with no edge, and E = 0 is legal.  The
+    limit of 4096 candidates per source stays (NotImplementedError before any launch), and the build stays differentiable.
+    symmetric without top_k, or an unknown value, is a ValueError raised before the GPU is touched.
+    E now depends on the data, so a symmetric build SYNCHRONISES ONCE: one small pinned device-to-host copy carries the G + 1 per-frame
+    edge offsets (the last one is E), queued behind the count launches and waited on through an event; there is no other host wait.
+    Under stream capture it raises RuntimeError before anything is launched.  The directed build (symmetric=None) still never waits."""
     if rank_by not in nat.RANK_BY:
         raise ValueError(f"rank_by must be 'ground' or 'reid', not {rank_by!r}")
+    if symmetric is not None:
+        if not isinstance(symmetric, str) or symmetric not in nat.SYMMETRIC:
+            raise ValueError(f"symmetric must be None, 'union' or 'mutual', not {symmetric!r}")
+        if top_k is None:
+            raise ValueError("symmetric=... closes a capped graph under reversal: it needs top_k")
     if top_k is not None:
         if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
             raise ValueError(f"top_k must be None or an integer >= 1, not {top_k!r}")
@@ -378,6 +442,8 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
         raise ValueError("per-detection / per-frame arrays disagree on their lengths")
     if reid_embeds.shape[0] != n or node_embeds.shape[0] != n:
         raise RuntimeError("embeddings and detections disagree on the number of nodes")
+    if symmetric is not None and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("build_graph_batch(symmetric=...) waits for its edge count and cannot be captured into a graph")
     nbytes = lib.gnncca_plan_frames_bytes(n, g)
     ring = _staging.get(dev.index)
     if ring is None:
@@ -402,7 +468,7 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
         staged = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         staged.copy_(pinned[:nbytes], non_blocking=True)
         event.record(_current_stream(dev))
-        job = _EdgeJob(staged, n, g, e, mode, top_k, nat.RANK_BY[rank_by], max_deg.value)
+        job = _EdgeJob(staged, n, g, e, mode, top_k, nat.RANK_BY[rank_by], max_deg.value, nat.SYMMETRIC[symmetric] if symmetric else 0, sizes)
         if _wants_grad(node_embeds, reid_embeds):
             # the differentiable build: x, edge_attr and reid_embeds are outputs of ONE autograd node (see _GraphBuildFunction)
             reid_embeds = _f32c(reid_embeds)
@@ -422,12 +488,14 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
     # the edges edge_ptr_g[g] .. edge_ptr_g[g+1]
     host_i32 = pinned[i32_off:nbytes].numpy().view(np.int32)
     node_ptr = host_i32[3 * n:3 * n + g + 1].tolist()
-    edge_ptr = host_i32[5 * n + g + 2:5 * n + 2 * g + 3].tolist()
+    # (a symmetric build: the offsets its count read back; the device image holds the same, the pinned one still the plan's)
+    edge_ptr = job.edge_ptr_g if job.sym else host_i32[5 * n + g + 2:5 * n + 2 * g + 3].tolist()
     batch = GraphBatch(node_embeds, edge_index, edge_attr, edge_ptr, node_ptr)
     # device copies of the frame ranges (int32 [G + 1]) for the per-frame post-processing (postprocess.prune_and_cluster)
     i32_dev = staged[i32_off:].view(torch.int32)
     batch.node_ptr_dev = i32_dev[3 * n:3 * n + g + 1]
     batch.edge_ptr_dev = i32_dev[5 * n + g + 2:5 * n + 2 * g + 3]
+    batch._frames_i32 = i32_dev   # batch.person_dev / batch.cam_dev (GraphBatch.__getattr__)
     batch.edge_labels = edge_labels
     batch.y = staged[y_off:y_off + 8 * n].view(torch.int64)
     batch.reid_embeds = reid_embeds

@@ -31,7 +31,11 @@ issued by `gnncca_frames_forward_topk` -- bit for bit what build_graph_batch(top
 (tests/test_gpu_pipeline_topk.py), from one arena sized by the capped E.  The capped list is DIRECTED: i may keep j while j does not keep i.
 The pipeline's pruning (PRUNING = True) keeps an active edge only if its reverse is in the list and active too, so the identity clusters
 come from mutual-k pairs; `r.batch`, `final()` and `final_async()` work on the kept edges, and `evaluate()` scores the kept edges only (a
-same-identity pair the cap dropped is neither a hit nor a miss).  top_k=None (the default) is the complete graph, down to the native call.
+same-identity pair the cap dropped is neither a hit nor a miss) unless asked for `evaluate(against='dense')`, which scores the batch as the
+dense graph with every dropped edge predicted 0.  top_k=None (the default) is the complete graph, down to the native call.
+`FramePipeline(model, top_k=k, symmetric='union' | 'mutual')` closes the capped list under reversal (build_graph_batch has the definition;
+no counterpart in the reference either): every kept edge then has its reverse.  E depends on the data, so such a pipeline takes the
+step-by-step path below and waits once per batch for its edge count; the one-call entry is not extended.
 
 Batches of more than 4096 detections, train mode and forward hooks take the step-by-step path (same results; a capped pipeline passes its
 cap on to build_graph_batch, whose limit of 4096 candidates per detection then raises NotImplementedError).  No CPU fallback."""
@@ -137,21 +141,25 @@ class FrameResult:
                                    "frames_finalized": res["frames_finalized"], "triggers": res["triggers"]}
         return self._final
 
-    def evaluate(self, final=True):
+    def evaluate(self, final=True, against="kept"):
         """The per-frame metrics of inference.py:349-371 for this batch (gnn_cca_amd.evaluation.evaluate_frames): float64 [G, 16] on the
         device, columns evaluation.METRICS.  final=True scores final()'s predictions / partition (which waits for this batch's host
-        heuristics), final=False the device chain's pruned predictions / labels.  Computed once per mode."""
-        from .evaluation import evaluate_frames
+        heuristics), final=False the device chain's pruned predictions / labels.  against='kept' (the default) scores the batch's own
+        edges; against='dense' scores a capped batch as the dense graph with every dropped edge predicted 0 (evaluate_frames has the
+        definition).  Computed once per mode."""
+        from .evaluation import AGAINST, evaluate_frames
+        if against not in AGAINST:
+            raise ValueError(f"against must be 'kept' or 'dense', not {against!r}")
         cache = getattr(self, "_eval", None)
         if cache is None:
             cache = self._eval = {}
-        key = bool(final)
+        key = bool(final) if against == "kept" else (bool(final), against)
         if key not in cache:
-            if key:
+            if final:
                 f = self.final()
-                cache[key] = evaluate_frames(self.batch, f["predictions"], f["labels"])
+                cache[key] = evaluate_frames(self.batch, f["predictions"], f["labels"], against=against)
             else:
-                cache[key] = evaluate_frames(self.batch, self.pruned, self.labels)
+                cache[key] = evaluate_frames(self.batch, self.pruned, self.labels, against=against)
         return cache[key]
 
 
@@ -172,7 +180,7 @@ class _Finished:
 
 class FramePipeline:
     def __init__(self, model, only_appearance=False, only_dist=False, normalize=True, rounding=True, pruning=True, splitting=True, top_k=None,
-                 rank_by="ground"):
+                 rank_by="ground", symmetric=None):
         self.model = model
         if not pruning:
             raise ValueError("FramePipeline prunes on the device (PRUNING = True, as config_inference.yaml:7 ships it)")
@@ -185,7 +193,12 @@ class FramePipeline:
             if top_k < 1:
                 raise ValueError(f"top_k must be >= 1, not {top_k}")
             top_k = min(int(top_k), 2 ** 31 - 1)
-        self.top_k, self.rank_by = top_k, rank_by
+        if symmetric is not None:
+            if not isinstance(symmetric, str) or symmetric not in nat.SYMMETRIC:
+                raise ValueError(f"symmetric must be None, 'union' or 'mutual', not {symmetric!r}")
+            if top_k is None:
+                raise ValueError("symmetric=... closes a capped graph under reversal: it needs top_k")
+        self.top_k, self.rank_by, self.symmetric = top_k, rank_by, symmetric
         self.switches = (bool(rounding), bool(pruning), bool(splitting))
         self.mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
         self.normalize = bool(normalize)
@@ -259,7 +272,8 @@ class FramePipeline:
 
     def _slow(self, xw, yw, ids, id_cam, sizes, max_dist, node, reid):
         b = build_graph_batch(xw, yw, ids, id_cam, sizes, max_dist, node, reid, only_appearance=self.mode == MODE_ONLY_APPEARANCE,
-                              only_dist=self.mode == MODE_ONLY_DIST, normalize=self.normalize, top_k=self.top_k, rank_by=self.rank_by)
+                              only_dist=self.mode == MODE_ONLY_DIST, normalize=self.normalize, top_k=self.top_k, rank_by=self.rank_by,
+                              symmetric=self.symmetric)
         with torch.no_grad():
             out = self.model(b)
         r = FrameResult()
@@ -277,7 +291,7 @@ class FramePipeline:
         if not (node_embeds.is_cuda and reid_embeds.is_cuda):
             raise RuntimeError("gnn_cca_amd.pipeline runs on MI355X only (no CPU fallback)")
         n = int(node_embeds.shape[0])
-        if m.training or n > MAX_NODES or n == 0 or m._containers_hooked():
+        if m.training or n > MAX_NODES or n == 0 or self.symmetric is not None or m._containers_hooked():
             return self._slow(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds)
         dev = reid_embeds.device
         lib = nat.lib()
@@ -385,6 +399,7 @@ class FramePipeline:
         i32_dev = staged[i32_off:].view(torch.int32)
         batch.node_ptr_dev = i32_dev[3 * n:3 * n + g + 1]
         batch.edge_ptr_dev = i32_dev[5 * n + g + 2:5 * n + 2 * g + 3]
+        batch._frames_i32 = i32_dev   # batch.person_dev / batch.cam_dev (GraphBatch.__getattr__)
         batch.edge_labels = f32[o_lab:o_lab + e]
         batch.y = staged[8 * (2 * n + g):8 * (3 * n + g)].view(torch.int64)
         batch.reid_embeds = reid_n

@@ -30,6 +30,16 @@ class GraphBatch:
         self.x, self.edge_index, self.edge_attr = x, edge_index, edge_attr
         self.edge_ptr, self.node_ptr = edge_ptr, node_ptr
 
+    def __getattr__(self, name):
+        # person_dev / cam_dev: the int32 [N] person ids (relabelled, equality preserved) and camera ids the staging image of
+        # graph_build.build_graph_batch / pipeline.FramePipeline holds on the device, sliced when asked for (evaluate_frames(against='dense'))
+        if name in ("person_dev", "cam_dev"):
+            image = self.__dict__.get("_frames_i32")
+            if image is not None:
+                n = int(self.node_ptr[-1])
+                return image[:n] if name == "person_dev" else image[n:2 * n]
+        raise AttributeError(name)
+
 
 def union_graphs(graphs):
     """Disjoint union of graphs given as (x [n, D], edge_index [2, e] with LOCAL node ids, edge_attr [e, A]):

@@ -277,7 +277,8 @@ GNNCCA_API int gnncca_build_edges(const gnncca_frames* frames, const float* reid
  *   GNNCCA_RANK_BY_REID    the F.pairwise_distance value of the reid rows, the fp32 number that goes into edge_attr (inference.py:222)
  * ties to the smaller destination node id.  The key need not be an emitted attribute (RANK_BY_REID with ONLY_DIST is legal and reads
  * `reid`).  The kept edges of a source stay in the dense order, so the result is a subsequence of gnncca_build_edges' edge list and, for
- * top_k >= max deg, that list bit for bit.  The graph is DIRECTED: i may keep j while j drops i.
+ * top_k >= max deg, that list bit for bit.  The graph is DIRECTED: i may keep j while j drops i (gnncca_build_edges_topk_sym_* below
+ * close it under reversal, as the union or as the mutual pairs).
  *
  * gnncca_plan_frames_ex: gnncca_plan_frames with a cap -- the same staging image, edge_ptr / edge_ptr_g counting min(top_k, deg) edges
  * per source (top_k == 0: no cap, gnncca_plan_frames' image byte for byte; top_k < 0: INVALID_ARG).  Returns E = sum min(top_k, deg)
@@ -294,6 +295,41 @@ GNNCCA_API int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, con
 GNNCCA_API int gnncca_build_edges_topk(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
                                        int64_t n_edges, int32_t mode, int32_t top_k, int32_t rank_by, int32_t max_deg,
                                        int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, gnncca_stream_t stream);
+
+/* ---- the capped neighbourhood, closed under reversal ('union' / 'mutual') ------------------------------------------------------
+ * With D the directed edge set of gnncca_build_edges_topk for the same top_k / rank_by (same keys, ties to the smaller destination id):
+ *   GNNCCA_SYMMETRIC_UNION   keeps the dense edge (i, j) iff (i, j) in D or  (j, i) in D
+ *   GNNCCA_SYMMETRIC_MUTUAL  keeps it                   iff (i, j) in D and (j, i) in D
+ * Whether i is in j's list is j's own selection (the key bits j's wave ranks with: the reid key is not symmetric, F.pairwise_distance
+ * adds its eps to a - b); no key is evaluated from two sides, so the result is closed under reversal by construction.  It is a
+ * subsequence of gnncca_build_edges' list in its order, a kept edge carries that build's bits, mutual is a subset of D and D of union,
+ * and for top_k >= max deg both are the dense build.  A frame or a source may end with no edge (E == 0 is legal).
+ * LIKE THE CAP, THE CLOSURE HAS NO COUNTERPART IN THE REFERENCE, which only builds complete graphs (every pair in both directions;
+ * its remove_edges_single_direction deletes an active edge whose reverse is not active -- what a directed capped list feeds it).
+ *
+ * E depends on the data, so the build is two calls with one host wait between them:
+ *   gnncca_build_edges_topk_sym_count   three launches: every source's selection as a bit row, the closure and the per-source counts,
+ *       and a scan that OVERWRITES frames->edge_ptr [N + 1] (the staging image's words; the plan's capped values) and edge_ptr_g_dev
+ *       [G + 1] (the image's per-frame edge offsets, or any int32 [G + 1]) with the symmetric layout.  edge_ptr_g_dev[G] is E: the caller
+ *       copies those G + 1 words to the host behind this call and waits for them.
+ *   gnncca_build_edges_topk_sym_emit    one launch: edge_index / edge_attr / edge_labels [n_edges = E] from the closed rows.
+ * `frames` is the uploaded image of gnncca_plan_frames_ex (any top_k; its max_deg_out is `max_deg`), graph_sizes the HOST array the plan
+ * was made from (it sizes the bit matrices; sizes that do not sum to n_nodes: INVALID_ARG).  workspace: ..._sym_bytes(graph_sizes,
+ * n_frames) = two bit matrices of sum_g n_g ceil(n_g / 64) 64-bit words + n_nodes int32 counts, 8-byte aligned, the SAME buffer in both
+ * calls.  No atomics; bit for bit the same from run to run.  Every argument is checked before the first launch (max_deg >
+ * GNNCCA_TOPK_MAX_DEG: GNNCCA_ERR_UNSUPPORTED); a source with more candidates than declared selects nothing.  Afterwards the image
+ * serves gnncca_build_edges_topk_backward, the post-processing and gnncca_eval_frames unchanged (a source's run is ascending in the
+ * destination, frames are contiguous). */
+enum { GNNCCA_SYMMETRIC_UNION = 1, GNNCCA_SYMMETRIC_MUTUAL = 2 };
+GNNCCA_API size_t gnncca_build_edges_topk_sym_bytes(const int64_t* graph_sizes, int64_t n_frames);
+GNNCCA_API int gnncca_build_edges_topk_sym_count(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                                 const int64_t* graph_sizes, int64_t n_frames, int32_t top_k, int32_t rank_by,
+                                                 int32_t max_deg, int32_t symmetric, void* workspace, size_t workspace_bytes,
+                                                 int32_t* edge_ptr_g_dev, gnncca_stream_t stream);
+GNNCCA_API int gnncca_build_edges_topk_sym_emit(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                                const int64_t* graph_sizes, int64_t n_frames, int64_t n_edges, int32_t mode,
+                                                const void* workspace, size_t workspace_bytes, int64_t* edge_index_out,
+                                                float* edge_attr_out, float* edge_labels_out, gnncca_stream_t stream);
 
 /* ---- backward of row N1: gradients of the graph build reach the RAW embeddings ------------------------------
  * The reference's statements are plain torch ops, so with the torch.no_grad() around its CNN (train.py:248-253) removed autograd
@@ -618,7 +654,13 @@ GNNCCA_API int gnncca_pad_frame(const float* x, int64_t n_nodes, const int64_t* 
  * int32 [N] = ID_GT in the smallest-id convention.  Frames of at most GNNCCA_EVAL_MAX_FRAME_NODES nodes: `max_frame_nodes` (the largest
  * frame, known to the caller from its host copy of node_ptr) above that is GNNCCA_ERR_INVALID_ARG before any launch; a frame the device
  * offsets make larger than max_frame_nodes gets a NaN row.  The workspace (gnncca_eval_workspace_bytes) holds per-frame lgamma tables;
- * no host synchronisation, no allocation: capturable. */
+ * no host synchronisation, no allocation: capturable.
+ * gnncca_eval_frames_dense scores a CAPPED batch (gnncca_build_edges_topk, ..._topk_sym_*) as the dense graph would have been scored with
+ * every dropped edge predicted 0: person_id / cam are the int32 [N] arrays of the batch's staging image (gnncca_frames); per frame the
+ * ordered cross-camera pairs with the same / a different person id that are NOT in the edge list are added to FN / TN (precision1 /
+ * precision0 divide by the dense class counts), and ID_GT is the dense graph's: all detections of an identity seen on at least two
+ * cameras form one component, every other detection its own.  Everything else -- TP, FP, the formulas, the predicted partition -- as
+ * above; on a dense batch the rows are gnncca_eval_frames' bit for bit.  No counterpart in the reference (it has no capped graph). */
 #define GNNCCA_EVAL_MAX_FRAME_NODES 4096
 #define GNNCCA_EVAL_COLUMNS "P R F TP FP FN TN rand_index mutual_index homogeneity completeness v_measure precision0 precision1 " \
                             "n_clusters_gt n_clusters_pred"
@@ -627,6 +669,11 @@ GNNCCA_API int gnncca_eval_frames(const int64_t* edge_index, const float* edge_l
                                   int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev,
                                   int32_t n_frames, int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace,
                                   size_t workspace_bytes, gnncca_stream_t stream);
+GNNCCA_API int gnncca_eval_frames_dense(const int64_t* edge_index, const float* edge_labels, const int64_t* predictions,
+                                        const int32_t* labels, const int32_t* person_id, const int32_t* cam, int64_t n_nodes,
+                                        int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                        int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace,
+                                        size_t workspace_bytes, gnncca_stream_t stream);
 
 /* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
  * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).
