@@ -20,6 +20,7 @@
 #include <climits>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "hip_try.h"
@@ -425,6 +426,42 @@ __global__ __launch_bounds__(256) void colnorm_fused_lds_kernel(const ColnormJob
 
 using namespace gnncca;
 
+// ---- what the host code of the edge entry points shares ----
+// The template arguments of a launch chosen at run time: f(std::integral_constant<int, MODE>) for the edge-attribute mode (the callers have
+// checked its range), f(std::true_type / std::false_type) for a flag.
+template <class F>
+static void with_mode(int32_t mode, F&& f) {
+    switch (mode) {
+        case GNNCCA_EDGE_ATTR_FULL: f(std::integral_constant<int, GNNCCA_EDGE_ATTR_FULL>{}); break;
+        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE: f(std::integral_constant<int, GNNCCA_EDGE_ATTR_ONLY_APPEARANCE>{}); break;
+        default: f(std::integral_constant<int, GNNCCA_EDGE_ATTR_ONLY_DIST>{}); break;
+    }
+}
+template <class F>
+static void with_flag(bool flag, F&& f) { flag ? f(std::true_type{}) : f(std::false_type{}); }
+template <class Ground>
+constexpr int rank_of(Ground) { return Ground::value ? GNNCCA_RANK_BY_GROUND : GNNCCA_RANK_BY_REID; }   // (the callers have checked rank_by)
+
+// Launch geometry of the capped kernels (graph_topk.cuh, graph_topk_sym.cuh): a wave per source, whose LDS holds the keys of `cap` candidates.
+struct TopkGeometry { int cap; size_t lds_bytes; dim3 grid, block; };
+static TopkGeometry topk_geometry(int32_t max_deg, int64_t n_nodes) {
+    const int cap = std::max(64, (max_deg + 63) / 64 * 64);
+    const size_t per_wave = (size_t)cap * kTopkSlotBytes;
+    const int waves = per_wave * 4 <= 65536 ? 4 : (per_wave * 2 <= 65536 ? 2 : 1);   // 4096 slots x 12 B = 48 KB: one wave
+    return TopkGeometry{cap, per_wave * waves, dim3((unsigned)((n_nodes + waves - 1) / waves)), dim3(64 * waves)};
+}
+
+// Two refusals (GNNCCA_ERR_INVALID_ARG) that the dense, capped, symmetric-emit and backward entry points state alike.  What lies between them
+// keeps each entry point's own order, which the tests pin: the capped entry refuses max_deg before its early return for an empty batch, the
+// symmetric emit checks the 2^31 limits and its workspace before that return; the symmetric count has no n_edges and stays apart.
+static bool edge_sizes_invalid(const gnncca_frames* fr, int64_t n_nodes, int64_t n_edges, int32_t reid_dim, int32_t mode) {
+    return !fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0 || mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST;
+}
+static bool edge_pointers_null(const gnncca_frames* fr, const void* edge_index_out, const void* edge_attr_out, const void* edge_labels_out) {
+    return !fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr || !fr->src_order ||
+           !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out;
+}
+
 extern "C" {
 
 int gnncca_normalize_columns2(const float* x0, int64_t n_cols0, float* out0, const float* x1, int64_t n_cols1, float* out1, int64_t n_rows,
@@ -491,8 +528,7 @@ size_t gnncca_build_edges_backward_bytes(int64_t n_nodes) { return n_nodes > 0 ?
 static int edges_backward(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
                           const int64_t* edge_index, bool pruned, const float* edge_attr, const float* grad_edge_attr, void* workspace,
                           size_t workspace_bytes, float* grad_reid_out, gnncca_stream_t stream) {
-    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
+    if (edge_sizes_invalid(fr, n_nodes, n_edges, reid_dim, mode)) return GNNCCA_ERR_INVALID_ARG;
     if (n_nodes == 0 || reid_dim == 0) return GNNCCA_OK;
     if (!grad_reid_out) return GNNCCA_ERR_INVALID_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -514,18 +550,11 @@ static int edges_backward(const gnncca_frames* fr, const float* reid, int32_t re
     const dim3 grid((unsigned)((n_nodes + kGgRows - 1) / kGgRows), (unsigned)((reid_dim + per_block - 1) / per_block)), block(kGgThreads);
     if (grid.y > 65535) return GNNCCA_ERR_UNSUPPORTED;
     const long long* dst = pruned ? reinterpret_cast<const long long*>(edge_index) + n_edges : nullptr;
-#define GNNCCA_EDGES_BWD(M, V, P)                                                                                                          \
-    hipLaunchKernelGGL((edges_bwd_kernel<M, V, P>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, aux, \
-                       edge_attr, grad_edge_attr, dst, grad_reid_out)
-#define GNNCCA_EDGES_BWD_V(M, P) \
-    if (vec) GNNCCA_EDGES_BWD(M, true, P); else GNNCCA_EDGES_BWD(M, false, P)
-    if (mode == GNNCCA_EDGE_ATTR_FULL) {
-        if (pruned) { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_FULL, true); } else { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_FULL, false); }
-    } else {
-        if (pruned) { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, true); } else { GNNCCA_EDGES_BWD_V(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE, false); }
-    }
-#undef GNNCCA_EDGES_BWD_V
-#undef GNNCCA_EDGES_BWD
+    with_mode(mode, [&](auto M) { with_flag(pruned, [&](auto P) { with_flag(vec, [&](auto V) {
+        if constexpr (M() != GNNCCA_EDGE_ATTR_ONLY_DIST)   // (returned above: the kernel has no such instance)
+            hipLaunchKernelGGL((edges_bwd_kernel<M(), V(), P()>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges,
+                               aux, edge_attr, grad_edge_attr, dst, grad_reid_out);
+    }); }); });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -550,8 +579,8 @@ int gnncca_build_edges_topk_backward(const gnncca_frames* fr, const float* reid,
 int gnncca_build_edges_topk(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
                             int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
                             float* edge_labels_out, gnncca_stream_t stream) {
-    return gnncca::build_edges_topk_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, top_k, rank_by, max_deg, edge_index_out, edge_attr_out,
-                                            edge_labels_out, nullptr, 0, stream);
+    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, true, top_k, rank_by, max_deg, edge_index_out, edge_attr_out,
+                                       edge_labels_out, nullptr, 0, stream);
 }
 
 // ---- the capped neighbourhood closed under reversal (graph_topk_sym.cuh) ----
@@ -598,22 +627,16 @@ int gnncca_build_edges_topk_sym_count(const gnncca_frames* fr, const float* reid
     int* counts = reinterpret_cast<int*>(bits_b + words);
     int* edge_ptr = const_cast<int*>(fr->edge_ptr);   // the staging image's own words: the plan's capped values are replaced
     if (n_nodes > 0) {
-        const int cap = std::max(64, (max_deg + 63) / 64 * 64);
-        const size_t per_wave = (size_t)cap * kTopkSlotBytes;
-        const int waves = per_wave * 4 <= 65536 ? 4 : (per_wave * 2 <= 65536 ? 2 : 1);
-        const dim3 grid((unsigned)((n_nodes + waves - 1) / waves)), block(64 * waves);
-        if (rank_by == GNNCCA_RANK_BY_GROUND)
-            hipLaunchKernelGGL((topk_sym_select_kernel<GNNCCA_RANK_BY_GROUND>), grid, block, per_wave * waves, st, *fr, reid, (int)reid_dim,
-                               (int)n_nodes, (int)top_k, cap, bits_a, words);
-        else
-            hipLaunchKernelGGL((topk_sym_select_kernel<GNNCCA_RANK_BY_REID>), grid, block, per_wave * waves, st, *fr, reid, (int)reid_dim,
-                               (int)n_nodes, (int)top_k, cap, bits_a, words);
+        const TopkGeometry geo = topk_geometry(max_deg, n_nodes);
+        with_flag(rank_by == GNNCCA_RANK_BY_GROUND, [&](auto ground) {
+            hipLaunchKernelGGL((topk_sym_select_kernel<rank_of(ground)>), geo.grid, geo.block, geo.lds_bytes, st, *fr, reid, (int)reid_dim, (int)n_nodes,
+                               (int)top_k, geo.cap, bits_a, words);
+        });
         HIP_TRY(hipGetLastError());
         const dim3 grid4((unsigned)((n_nodes + 3) / 4));
-        if (symmetric == GNNCCA_SYMMETRIC_UNION)
-            hipLaunchKernelGGL((topk_sym_close_kernel<true>), grid4, dim3(256), 0, st, *fr, (int)n_nodes, bits_a, bits_b, words, counts);
-        else
-            hipLaunchKernelGGL((topk_sym_close_kernel<false>), grid4, dim3(256), 0, st, *fr, (int)n_nodes, bits_a, bits_b, words, counts);
+        with_flag(symmetric == GNNCCA_SYMMETRIC_UNION, [&](auto U) {
+            hipLaunchKernelGGL((topk_sym_close_kernel<U()>), grid4, dim3(256), 0, st, *fr, (int)n_nodes, bits_a, bits_b, words, counts);
+        });
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(topk_sym_scan_kernel, dim3(1), dim3(256), 0, st, counts, (int)n_nodes, (int)n_frames, fr->graph_ptr, edge_ptr,
@@ -626,29 +649,21 @@ int gnncca_build_edges_topk_sym_emit(const gnncca_frames* fr, const float* reid,
                                      const int64_t* graph_sizes, int64_t n_frames, int64_t n_edges, int32_t mode, const void* workspace,
                                      size_t workspace_bytes, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                                      gnncca_stream_t stream) {
-    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
+    if (edge_sizes_invalid(fr, n_nodes, n_edges, reid_dim, mode)) return GNNCCA_ERR_INVALID_ARG;
     if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
     long long words = 0;
     if (const int bad = topk_sym_layout(graph_sizes, n_frames, n_nodes, workspace, workspace_bytes, &words)) return bad;
     if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
-    if (!fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr || !fr->src_order ||
-        !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out)
-        return GNNCCA_ERR_INVALID_ARG;
+    if (edge_pointers_null(fr, edge_index_out, edge_attr_out, edge_labels_out)) return GNNCCA_ERR_INVALID_ARG;
     if (mode != GNNCCA_EDGE_ATTR_ONLY_DIST && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned long long* bits_b = static_cast<const unsigned long long*>(workspace) + words;
     long long* ei = reinterpret_cast<long long*>(edge_index_out);
     const dim3 grid((unsigned)((n_nodes + 3) / 4)), block(256);
-#define GNNCCA_SYM_EMIT(M)                                                                                                              \
-    hipLaunchKernelGGL((topk_sym_emit_kernel<M>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, bits_b, \
-                       words, ei, edge_attr_out, edge_labels_out)
-    switch (mode) {
-        case GNNCCA_EDGE_ATTR_FULL: GNNCCA_SYM_EMIT(GNNCCA_EDGE_ATTR_FULL); break;
-        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE: GNNCCA_SYM_EMIT(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE); break;
-        default: GNNCCA_SYM_EMIT(GNNCCA_EDGE_ATTR_ONLY_DIST); break;
-    }
-#undef GNNCCA_SYM_EMIT
+    with_mode(mode, [&](auto M) {
+        hipLaunchKernelGGL((topk_sym_emit_kernel<M()>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, bits_b,
+                           words, ei, edge_attr_out, edge_labels_out);
+    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -701,78 +716,43 @@ int gnncca_normalize_columns_backward2(const float* x0, const float* grad_out0, 
 int gnncca_build_edges(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges,
                        int32_t mode, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                        gnncca_stream_t stream) {
-    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, edge_index_out, edge_attr_out, edge_labels_out, nullptr, 0, stream);
+    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, false, 0, 0, 0, edge_index_out, edge_attr_out, edge_labels_out,
+                                       nullptr, 0, stream);
 }
 
 }  // extern "C"
 
-int gnncca::build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges,
-                                int32_t mode, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, int32_t* zero_ptr,
-                                int64_t zero_n, gnncca_stream_t stream) {
-    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
+// gnncca_build_edges (capped == false: top_k, rank_by and max_deg are not looked at) and gnncca_build_edges_topk.  The capped entry's own
+// refusals stand where it stated them: its degree limit before the early return for an empty batch.
+int gnncca::build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                                bool capped, int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
+                                float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream) {
+    if (edge_sizes_invalid(fr, n_nodes, n_edges, reid_dim, mode) || (capped && (top_k < 1 || max_deg < 0))) return GNNCCA_ERR_INVALID_ARG;
+    if (capped && rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID) return GNNCCA_ERR_INVALID_ARG;
+    if (capped && max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
     if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
     if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    if (!fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr ||
-        !fr->src_order || !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out)
-        return GNNCCA_ERR_INVALID_ARG;
-    if (mode != GNNCCA_EDGE_ATTR_ONLY_DIST && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // few sources: split each source's candidate chunks over up to 16 waves so that the launch still fills the chip
-    unsigned slices = 1;
-    while (slices < 16 && (long long)n_nodes * slices < 4096) slices *= 2;
-    const dim3 grid((unsigned)((n_nodes + 3) / 4), slices), block(256);
-    long long* ei = reinterpret_cast<long long*>(edge_index_out);
-    switch (mode) {
-        case GNNCCA_EDGE_ATTR_FULL:
-            hipLaunchKernelGGL((build_edges_kernel<GNNCCA_EDGE_ATTR_FULL>), grid, block, 0, st, *fr, reid, (int)reid_dim,
-                               (int)n_nodes, (long long)n_edges, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
-            break;
-        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE:
-            hipLaunchKernelGGL((build_edges_kernel<GNNCCA_EDGE_ATTR_ONLY_APPEARANCE>), grid, block, 0, st, *fr, reid,
-                               (int)reid_dim, (int)n_nodes, (long long)n_edges, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
-            break;
-        default:
-            hipLaunchKernelGGL((build_edges_kernel<GNNCCA_EDGE_ATTR_ONLY_DIST>), grid, block, 0, st, *fr, reid, (int)reid_dim,
-                               (int)n_nodes, (long long)n_edges, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
-            break;
-    }
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
-}
-
-int gnncca::build_edges_topk_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
-                                     int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
-                                     float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream) {
-    if (!fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0 || top_k < 1 || max_deg < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST) return GNNCCA_ERR_INVALID_ARG;
-    if (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID) return GNNCCA_ERR_INVALID_ARG;
-    if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
-    if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    if (!fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr ||
-        !fr->src_order || !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out)
-        return GNNCCA_ERR_INVALID_ARG;
-    if ((mode != GNNCCA_EDGE_ATTR_ONLY_DIST || rank_by == GNNCCA_RANK_BY_REID) && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
-    const int cap = std::max(64, (max_deg + 63) / 64 * 64);
-    const size_t per_wave = (size_t)cap * kTopkSlotBytes;
-    const int waves = per_wave * 4 <= 65536 ? 4 : (per_wave * 2 <= 65536 ? 2 : 1);   // 4096 slots x 12 B = 48 KB: one wave
-    const dim3 grid((unsigned)((n_nodes + waves - 1) / waves)), block(64 * waves);
-    const size_t lds = per_wave * waves;
+    if (edge_pointers_null(fr, edge_index_out, edge_attr_out, edge_labels_out)) return GNNCCA_ERR_INVALID_ARG;
+    const bool reads_reid = mode != GNNCCA_EDGE_ATTR_ONLY_DIST || (capped && rank_by == GNNCCA_RANK_BY_REID);
+    if (reads_reid && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     long long* ei = reinterpret_cast<long long*>(edge_index_out);
-#define GNNCCA_TOPK(M, K)                                                                                                          \
-    hipLaunchKernelGGL((build_edges_topk_kernel<M, K>), grid, block, lds, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, \
-                       cap, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n)
-#define GNNCCA_TOPK_R(M) \
-    if (rank_by == GNNCCA_RANK_BY_GROUND) GNNCCA_TOPK(M, GNNCCA_RANK_BY_GROUND); else GNNCCA_TOPK(M, GNNCCA_RANK_BY_REID)
-    switch (mode) {
-        case GNNCCA_EDGE_ATTR_FULL: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_FULL); break;
-        case GNNCCA_EDGE_ATTR_ONLY_APPEARANCE: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_APPEARANCE); break;
-        default: GNNCCA_TOPK_R(GNNCCA_EDGE_ATTR_ONLY_DIST); break;
+    if (!capped) {
+        // few sources: split each source's candidate chunks over up to 16 waves so that the launch still fills the chip
+        unsigned slices = 1;
+        while (slices < 16 && (long long)n_nodes * slices < 4096) slices *= 2;
+        const dim3 grid((unsigned)((n_nodes + 3) / 4), slices), block(256);
+        with_mode(mode, [&](auto M) {
+            hipLaunchKernelGGL((build_edges_kernel<M()>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, ei,
+                               edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
+        });
+    } else {
+        const TopkGeometry geo = topk_geometry(max_deg, n_nodes);
+        with_mode(mode, [&](auto M) { with_flag(rank_by == GNNCCA_RANK_BY_GROUND, [&](auto ground) {
+            hipLaunchKernelGGL((build_edges_topk_kernel<M(), rank_of(ground)>), geo.grid, geo.block, geo.lds_bytes, st, *fr, reid, (int)reid_dim,
+                               (int)n_nodes, (long long)n_edges, geo.cap, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
+        }); });
     }
-#undef GNNCCA_TOPK_R
-#undef GNNCCA_TOPK
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -780,13 +760,8 @@ int gnncca::build_edges_topk_zeroing(const gnncca_frames* fr, const float* reid,
 extern "C" {
 
 // ---- host side of row N1: the edge enumeration of a batch of frames (inference.py:207-212), written straight into the staging image ----
-// Layout of `staging` (what gnn_cca_amd.graph_build uploads in ONE transfer; 8-byte fields first):
-//   f64 xw[n], yw[n], max_dist[g];  i64 ids[n];  i32 person[n], cam[n], graph_of[n], graph_ptr[g + 1], src_order[n], edge_ptr[n + 1],
-//   edge_ptr_g[g + 1]
-size_t gnncca_plan_frames_bytes(int64_t n, int64_t g) {
-    if (n < 0 || g < 0) return 0;
-    return (size_t)(8 * (3 * n + g) + 4 * (5 * n + 2 * g + 3));
-}
+// (the layout of `staging`: internal.h, StagingImage)
+size_t gnncca_plan_frames_bytes(int64_t n, int64_t g) { return staging_image_bytes(n, g); }
 
 // top_k == 0: every candidate (gnncca_plan_frames); top_k >= 1: min(top_k, deg) edges per source (gnncca_build_edges_topk)
 int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, const int64_t* ids, const int64_t* id_cam, int64_t n,
@@ -802,24 +777,13 @@ int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, const int64_t*
         total += graph_sizes[q];
     }
     if (total != n) return -(int64_t)GNNCCA_ERR_INVALID_ARG;   // id_cam length does not match graph_sizes
-    char* base = static_cast<char*>(staging);
-    double* o_xw = reinterpret_cast<double*>(base);
-    double* o_yw = o_xw + n;
-    double* o_md = o_yw + n;
-    int64_t* o_ids = reinterpret_cast<int64_t*>(o_md + g);
-    int32_t* o_person = reinterpret_cast<int32_t*>(o_ids + n);
-    int32_t* o_cam = o_person + n;
-    int32_t* o_graph_of = o_cam + n;
-    int32_t* o_graph_ptr = o_graph_of + n;
-    int32_t* o_src = o_graph_ptr + g + 1;
-    int32_t* o_edge_ptr = o_src + n;
-    int32_t* o_edge_ptr_g = o_edge_ptr + n + 1;
+    const StagingImage img = staging_image(staging, n, g);
     if (n) {
-        std::memcpy(o_xw, xw, 8 * (size_t)n);
-        std::memcpy(o_yw, yw, 8 * (size_t)n);
-        std::memcpy(o_ids, ids, 8 * (size_t)n);
+        std::memcpy(img.xw, xw, 8 * (size_t)n);
+        std::memcpy(img.yw, yw, 8 * (size_t)n);
+        std::memcpy(img.ids, ids, 8 * (size_t)n);
     }
-    if (g) std::memcpy(o_md, max_dist, 8 * (size_t)g);
+    if (g) std::memcpy(img.max_dist, max_dist, 8 * (size_t)g);
     // cameras: np.unique order (ascending camera id) inside every frame = the rank among the batch's distinct camera ids
     std::vector<int64_t> cams;
     for (int64_t i = 0; i < n; ++i) {
@@ -845,7 +809,7 @@ int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, const int64_t*
             size_t slot = (size_t)(hsh >> 20) & (cap - 1);
             while (vals[slot] >= 0 && keys[slot] != ids[i]) slot = (slot + 1) & (cap - 1);
             if (vals[slot] < 0) keys[slot] = ids[i], vals[slot] = next++;
-            o_person[i] = vals[slot];
+            img.person[i] = vals[slot];
         }
     }
     // stable counting sort by (frame, camera rank): frame-major, camera order inside a frame, node id ascending inside a camera
@@ -853,35 +817,35 @@ int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, const int64_t*
     std::vector<int32_t> count((size_t)(g * n_cam) + 1, 0);
     {
         int64_t i = 0;
-        o_graph_ptr[0] = 0;
+        img.graph_ptr[0] = 0;
         for (int64_t q = 0; q < g; ++q) {
             for (int64_t k = 0; k < graph_sizes[q]; ++k, ++i) {
                 const int32_t rank = (int32_t)(std::lower_bound(cams.begin(), cams.end(), id_cam[i]) - cams.begin());
-                o_graph_of[i] = (int32_t)q;
-                o_cam[i] = (int32_t)id_cam[i];
+                img.graph_of[i] = (int32_t)q;
+                img.cam[i] = (int32_t)id_cam[i];
                 key[(size_t)i] = (int32_t)(q * n_cam + rank);
                 ++count[(size_t)key[(size_t)i]];
             }
-            o_graph_ptr[q + 1] = (int32_t)i;
+            img.graph_ptr[q + 1] = (int32_t)i;
         }
     }
     std::vector<int32_t> start((size_t)(g * n_cam) + 1, 0);
     for (size_t k = 0; k + 1 < start.size(); ++k) start[k + 1] = start[k] + count[k];
     {
         std::vector<int32_t> cursor(start);
-        for (int64_t i = 0; i < n; ++i) o_src[cursor[(size_t)key[(size_t)i]]++] = (int32_t)i;
+        for (int64_t i = 0; i < n; ++i) img.src_order[cursor[(size_t)key[(size_t)i]]++] = (int32_t)i;
     }
     long long e = 0, max_deg = 0;
     for (int64_t pos = 0; pos < n; ++pos) {
-        const int32_t node = o_src[pos];
-        o_edge_ptr[pos] = (int32_t)e;
-        const long long deg = graph_sizes[o_graph_of[node]] - count[(size_t)key[(size_t)node]];   // every node of the frame's OTHER cameras
+        const int32_t node = img.src_order[pos];
+        img.edge_ptr[pos] = (int32_t)e;
+        const long long deg = graph_sizes[img.graph_of[node]] - count[(size_t)key[(size_t)node]];   // every node of the frame's OTHER cameras
         max_deg = std::max(max_deg, deg);
         e += top_k > 0 ? std::min<long long>(deg, top_k) : deg;
         if (e >= (1ll << 31) - 64) return -(int64_t)GNNCCA_ERR_UNSUPPORTED;      // more than 2^31 edges in one batch
     }
-    o_edge_ptr[n] = (int32_t)e;
-    for (int64_t q = 0; q <= g; ++q) o_edge_ptr_g[q] = o_edge_ptr[o_graph_ptr[q]];   // edges are emitted frame by frame
+    img.edge_ptr[n] = (int32_t)e;
+    for (int64_t q = 0; q <= g; ++q) img.edge_ptr_g[q] = img.edge_ptr[img.graph_ptr[q]];   // edges are emitted frame by frame
     if (max_deg_out) *max_deg_out = (int32_t)max_deg;
     return (int64_t)e;
 }

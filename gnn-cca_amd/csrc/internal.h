@@ -131,14 +131,34 @@ struct GenWorkspace {
 };
 GenWorkspace carve_generic(const gnncca_mpn_dims* d, int64_t n, int64_t e);
 
-// gnncca_build_edges that also zeroes `zero_n` int32 words at `zero_ptr` (graph_build.hip; gnncca_frames_forward hands it the post stage's counters)
-int build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
-                        int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n,
-                        gnncca_stream_t stream);
-// gnncca_build_edges_topk likewise (gnncca_frames_forward_topk); zero_ptr == nullptr: the public entry point, bit for bit
-int build_edges_topk_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
-                             int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
-                             float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream);
+// The staging image of a batch of frames: what gnncca_plan_frames writes on the host, gnn_cca_amd.frames uploads in ONE transfer and
+// gnncca_frames_io::staged_dev hands to the one-call pipeline.  Eleven arrays back to back, 8-byte fields first (n detections, g frames):
+//   f64 xw[n], yw[n], max_dist[g];  i64 ids[n];  i32 person[n], cam[n], graph_of[n], graph_ptr[g + 1], src_order[n], edge_ptr[n + 1],
+//   edge_ptr_g[g + 1]
+// The order is ABI (include/gnncca_mpn.h describes it); it is written down here and in gnn_cca_amd/frames.py (FrameLayout), nowhere else.
+struct StagingImage {
+    double *xw, *yw, *max_dist;
+    int64_t* ids;
+    int32_t *person, *cam, *graph_of, *graph_ptr, *src_order, *edge_ptr, *edge_ptr_g;
+    size_t bytes;
+    gnncca_frames frames() const { return gnncca_frames{xw, yw, max_dist, person, cam, graph_of, graph_ptr, src_order, edge_ptr}; }
+};
+inline StagingImage staging_image(const void* base, int64_t n, int64_t g) {
+    uintptr_t at = reinterpret_cast<uintptr_t>(base);
+    auto take = [&at](auto*& field, int64_t count) { field = reinterpret_cast<decltype(+field)>(at), at += sizeof(*field) * (size_t)count; };
+    StagingImage s;
+    take(s.xw, n), take(s.yw, n), take(s.max_dist, g), take(s.ids, n), take(s.person, n), take(s.cam, n), take(s.graph_of, n);
+    take(s.graph_ptr, g + 1), take(s.src_order, n), take(s.edge_ptr, n + 1), take(s.edge_ptr_g, g + 1);
+    s.bytes = at - reinterpret_cast<uintptr_t>(base);
+    return s;
+}
+inline size_t staging_image_bytes(int64_t n, int64_t g) { return n < 0 || g < 0 ? 0 : staging_image(nullptr, n, g).bytes; }
+
+// gnncca_build_edges (capped == false) / gnncca_build_edges_topk that also zero `zero_n` int32 words at `zero_ptr` (graph_build.hip;
+// gnncca_frames_forward hands them the post stage's counters); zero_ptr == nullptr: the public entry points, bit for bit
+int build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode, bool capped,
+                        int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                        int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream);
 
 Family classify(const gnncca_mpn_dims* d);
 bool blob_header(const gnncca_mpn_dims* d, BlobHeader* out);  // false if unsupported

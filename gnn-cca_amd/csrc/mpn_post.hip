@@ -190,16 +190,8 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
     // (what gnncca_build_edges_topk would refuse, refused here: before the normalisation's launch)
     if (top_k > 0 && (io->mode < GNNCCA_EDGE_ATTR_FULL || io->mode > GNNCCA_EDGE_ATTR_ONLY_DIST)) return GNNCCA_ERR_INVALID_ARG;
     if (top_k > 0 && rank_by == GNNCCA_RANK_BY_REID && io->reid_dim <= 0) return GNNCCA_ERR_INVALID_ARG;   // the ranking reads the table in every mode
-    // the staging image (gnncca_plan_frames): f64 xw[n], yw[n], max_dist[g]; i64 ids[n]; i32 person, cam, graph_of, graph_ptr, src_order, edge_ptr, edge_ptr_g
-    const char* base = static_cast<const char*>(io->staged_dev);
-    gnncca_frames fr;
-    fr.xw = reinterpret_cast<const double*>(base);
-    fr.yw = fr.xw + n;
-    fr.max_dist = fr.yw + n;
-    const int32_t* i32 = reinterpret_cast<const int32_t*>(base + 8 * (3 * n + g));
-    fr.person_id = i32, fr.cam = i32 + n, fr.graph_of = i32 + 2 * n, fr.graph_ptr = i32 + 3 * n;
-    fr.src_order = i32 + 3 * n + g + 1, fr.edge_ptr = i32 + 4 * n + g + 1;
-    const int32_t* edge_ptr_g = i32 + 5 * n + g + 2;
+    const StagingImage img = staging_image(io->staged_dev, n, g);
+    const gnncca_frames fr = img.frames();
     const float* x = io->node_embeds;
     const float* reid = io->reid_embeds;
     int st = GNNCCA_OK;
@@ -212,11 +204,8 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
     const bool zero_here = e > 0 && mpn_workspace != nullptr;
     int32_t* zero_ptr = zero_here ? io->counters : nullptr;
     const int64_t zero_n = zero_here ? 3 * n + 1 + g : 0;
-    if (top_k > 0)
-        st = build_edges_topk_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, top_k, rank_by, max_deg, io->edge_index, io->edge_attr,
-                                      io->edge_labels, zero_ptr, zero_n, stream);
-    else
-        st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, io->edge_index, io->edge_attr, io->edge_labels, zero_ptr, zero_n, stream);
+    st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, top_k > 0, top_k, rank_by, max_deg, io->edge_index, io->edge_attr,
+                             io->edge_labels, zero_ptr, zero_n, stream);
     if (st != GNNCCA_OK) return st;
     const int n_out = gnncca_num_outputs(d);
     if (n_out < 1) return GNNCCA_ERR_UNSUPPORTED;
@@ -249,7 +238,7 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
         have_plan = &plan;
     }
     int32_t* c = io->counters;   // flow_out | flow_in | n_clusters | sizes (scratch) | triggers [G]
-    return post_prune_cluster_impl(io->edge_index, io->predictions, n, e, fr.graph_ptr, edge_ptr_g, (int32_t)g, post_workspace, post_workspace_bytes,
+    return post_prune_cluster_impl(io->edge_index, io->predictions, n, e, fr.graph_ptr, img.edge_ptr_g, (int32_t)g, post_workspace, post_workspace_bytes,
                                    io->pruned, c, c + n, io->labels, c + 2 * n, c + 2 * n + 1, c + 3 * n + 1, have_plan, stream);
 }
 

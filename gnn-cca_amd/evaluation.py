@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .graph_build import _on, _raw_stream
+from .frames import _on, _raw_stream
 
 METRICS = ("P", "R", "F", "TP", "FP", "FN", "TN", "rand_index", "mutual_index", "homogeneity", "completeness", "v_measure",
            "precision0", "precision1", "n_clusters_gt", "n_clusters_pred")

@@ -7,7 +7,6 @@ numpy, `plan_frames`); one HIP kernel (`gnncca_build_edges`) then writes `edge_i
 for the whole batch of frames, and `gnncca_normalize_columns` does the `F.normalize(..., dim=0)` of the embeddings.
 """
 import ctypes as C
-import numbers
 from dataclasses import dataclass
 
 import numpy as np
@@ -15,6 +14,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native as nat
+from .frames import StagedFrames, _current_stream, _f32c, _on, _raw_stream, attach, check_cap  # noqa: F401  (the lean device helpers live there)
 from .sharding import GraphBatch
 
 MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST = 0, 1, 2
@@ -53,43 +53,7 @@ def plan_frames(id_cam, graph_sizes):
     return FramePlan(src_order, edge_ptr.astype(np.int32), graph_ptr, graph_of, int(edge_ptr[-1]))
 
 
-def _raw_stream(dev):
-    return torch._C._cuda_getCurrentRawStream(dev.index)
-
-
-_stream_objs = {}
-
-
-def _current_stream(dev):
-    """torch.cuda.current_stream(dev) through a cache keyed by the raw handle (the call itself costs ~10 us of host time)."""
-    raw = _raw_stream(dev)
-    hit = _stream_objs.get(dev.index)
-    if hit is None or hit[0] != raw:
-        hit = _stream_objs[dev.index] = (raw, torch.cuda.current_stream(dev))
-    return hit[1]
-
-
-class _on:
-    """`with torch.cuda.device(dev)` only when `dev` is not the current device already (the context manager costs ~5 us of host
-    time per use, more than a launch)."""
-
-    def __init__(self, dev):
-        self._ctx = None if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self._ctx is not None:
-            self._ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self._ctx is not None:
-            self._ctx.__exit__(*a)
-
-
 FUSED_NORMALIZE_MAX_ROWS = 4096   # gnncca_normalize_columns2: one launch for up to two matrices of a batch of frames
-
-
-def _f32c(x):
-    return x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
 
 
 def _normalize_launch(x, other=None):
@@ -186,58 +150,16 @@ def normalize_columns(x, other=None):
     return _normalize_launch(x, other)
 
 
-class _Staging:
-    """Ring of pinned host buffers for the per-batch staging image (gnncca_plan_frames writes it, ONE non-blocking copy uploads
-    it): the host never waits for the GPU, so the graph of the next batch of frames is planned while this one's kernels run.
-    A slot is reused only after the copy that read it has completed (its event)."""
-    SLOTS = 8
-
-    def __init__(self):
-        self._bufs, self._events, self._next = [None] * self.SLOTS, [None] * self.SLOTS, 0
-
-    def take(self, nbytes):
-        i = self._next
-        self._next = (i + 1) % self.SLOTS
-        if self._events[i] is not None:
-            self._events[i].synchronize()
-        buf = self._bufs[i]
-        if buf is None or buf.numel() < nbytes:
-            buf = self._bufs[i] = torch.empty(max(2 * nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-        if self._events[i] is None:
-            self._events[i] = torch.cuda.Event()
-        return buf, self._events[i]
-
-
-_staging = {}
-
-
-def _as(a, dtype):
-    a = np.asarray(a)
-    if a.dtype != dtype or not a.flags.c_contiguous:
-        a = np.ascontiguousarray(a, dtype=dtype)
-    return a
-
-
 class _EdgeJob:
-    """What the edge kernels of one batch need besides the reid table: the staged frame image and its sizes; for a capped build
+    """What the edge kernels of one batch need besides the reid table: the staged frame image and its layout; for a capped build
     (top_k is not None) also the cap, the ranking key and the batch's largest uncapped degree; for a symmetric one (sym != 0) the host
     array of frame sizes too -- and `e` / `edge_ptr_g` are what its count read back, set by _edges_launch."""
-    __slots__ = ("staged", "n", "g", "e", "mode", "top_k", "rank", "max_deg", "sym", "sizes", "edge_ptr_g")
+    __slots__ = ("staged", "layout", "n", "g", "e", "mode", "top_k", "rank", "max_deg", "sym", "sizes", "edge_ptr_g")
 
-    def __init__(self, staged, n, g, e, mode, top_k=None, rank=0, max_deg=0, sym=0, sizes=None):
-        self.staged, self.n, self.g, self.e, self.mode = staged, n, g, e, mode
+    def __init__(self, staged, layout, e, mode, top_k=None, rank=0, max_deg=0, sym=0, sizes=None):
+        self.staged, self.layout, self.n, self.g, self.e, self.mode = staged, layout, layout.n, layout.g, e, mode
         self.top_k, self.rank, self.max_deg = top_k, rank, max_deg
         self.sym, self.sizes, self.edge_ptr_g = sym, sizes, None
-
-    def frames(self):
-        n, g = self.n, self.g
-        fr = nat.Frames()
-        p0 = self.staged.data_ptr()
-        fr.xw, fr.yw, fr.max_dist = p0, p0 + 8 * n, p0 + 16 * n
-        base = p0 + 8 * (2 * n + g) + 8 * n
-        fr.person_id, fr.cam, fr.graph_of = base, base + 4 * n, base + 8 * n
-        fr.graph_ptr, fr.src_order, fr.edge_ptr = base + 12 * n, base + 4 * (3 * n + g + 1), base + 4 * (4 * n + g + 1)
-        return fr
 
 
 _readback = {}   # device index -> (pinned int32 buffer, event) of the symmetric build's one read-back
@@ -249,11 +171,11 @@ def _sym_edges_launch(job, reid_embeds):
     outputs are allocated and gnncca_build_edges_topk_sym_emit fills them.  Sets job.e and job.edge_ptr_g (host list)."""
     dev, n, g = reid_embeds.device, job.n, job.g
     lib = nat.lib()
-    fr = job.frames()
+    fr = job.layout.frames(job.staged.data_ptr())
     sizes = job.sizes
     nbytes = lib.gnncca_build_edges_topk_sym_bytes(sizes.ctypes.data, g)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    eptr_g = job.staged[8 * (3 * n + g) + 4 * (5 * n + g + 2):8 * (3 * n + g) + 4 * (5 * n + 2 * g + 3)].view(torch.int32)
+    eptr_g = job.layout.view(job.staged, "edge_ptr_g")
     st = lib.gnncca_build_edges_topk_sym_count(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, sizes.ctypes.data, g, job.top_k,
                                                job.rank, job.max_deg, job.sym, ws.data_ptr(), nbytes, eptr_g.data_ptr(), _raw_stream(dev))
     if st:
@@ -288,7 +210,7 @@ def _edges_launch(job, reid_embeds):
         return _sym_edges_launch(job, reid_embeds)
     dev, n, e = reid_embeds.device, job.n, job.e
     n_attr = 4 if job.mode == MODE_FULL else 2
-    fr = job.frames()
+    fr = job.layout.frames(job.staged.data_ptr())
     edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
     edge_attr = torch.empty((e, n_attr), dtype=torch.float32, device=dev)
     edge_labels = torch.empty(e, dtype=torch.float32, device=dev)
@@ -359,7 +281,7 @@ class _GraphBuildFunction(torch.autograd.Function):
                 d_rn = torch.empty_like(reid_n)
                 nbytes = lib.gnncca_build_edges_backward_bytes(job.n)
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                fr = job.frames()
+                fr = job.layout.frames(job.staged.data_ptr())
                 with _on(dev):
                     if edge_index is not None:
                         st = lib.gnncca_build_edges_topk_backward(C.byref(fr), reid_n.data_ptr(), reid_n.shape[1], job.n, job.e, job.mode,
@@ -418,57 +340,21 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
     E now depends on the data, so a symmetric build SYNCHRONISES ONCE: one small pinned device-to-host copy carries the G + 1 per-frame
     edge offsets (the last one is E), queued behind the count launches and waited on through an event; there is no other host wait.
     Under stream capture it raises RuntimeError before anything is launched.  The directed build (symmetric=None) still never waits."""
-    if rank_by not in nat.RANK_BY:
-        raise ValueError(f"rank_by must be 'ground' or 'reid', not {rank_by!r}")
-    if symmetric is not None:
-        if not isinstance(symmetric, str) or symmetric not in nat.SYMMETRIC:
-            raise ValueError(f"symmetric must be None, 'union' or 'mutual', not {symmetric!r}")
-        if top_k is None:
-            raise ValueError("symmetric=... closes a capped graph under reversal: it needs top_k")
-    if top_k is not None:
-        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
-            raise ValueError(f"top_k must be None or an integer >= 1, not {top_k!r}")
-        if top_k < 1:
-            raise ValueError(f"top_k must be >= 1, not {top_k}")
-        top_k = min(int(top_k), 2 ** 31 - 1)
+    top_k, rank, sym = check_cap(top_k, rank_by, symmetric)
     if not (node_embeds.is_cuda and reid_embeds.is_cuda):
         raise RuntimeError("gnn_cca_amd.graph_build runs on MI355X only (no CPU fallback)")
     dev = reid_embeds.device
-    lib = nat.lib()
-    xw, yw, md = _as(xw, np.float64), _as(yw, np.float64), _as(max_dist, np.float64)
-    ids64, cam64, sizes = _as(ids, np.int64), _as(id_cam, np.int64), _as(graph_sizes, np.int64)
-    n, g = len(cam64), len(sizes)
-    if not (len(xw) == len(yw) == len(ids64) == n) or len(md) != g:
-        raise ValueError("per-detection / per-frame arrays disagree on their lengths")
-    if reid_embeds.shape[0] != n or node_embeds.shape[0] != n:
+    frames = StagedFrames(xw, yw, ids, id_cam, graph_sizes, max_dist)
+    if reid_embeds.shape[0] != frames.n or node_embeds.shape[0] != frames.n:
         raise RuntimeError("embeddings and detections disagree on the number of nodes")
     if symmetric is not None and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("build_graph_batch(symmetric=...) waits for its edge count and cannot be captured into a graph")
-    nbytes = lib.gnncca_plan_frames_bytes(n, g)
-    ring = _staging.get(dev.index)
-    if ring is None:
-        ring = _staging[dev.index] = _Staging()
-    pinned, event = ring.take(nbytes)
-    max_deg = C.c_int32(0)
-    if top_k is None:
-        e = lib.gnncca_plan_frames(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data, g,
-                                   pinned.data_ptr(), nbytes)
-    else:
-        e = lib.gnncca_plan_frames_ex(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data,
-                                      g, top_k, pinned.data_ptr(), nbytes, C.byref(max_deg))
-    if e < 0:
-        if -e == nat.ERR_INVALID_ARG:
-            raise ValueError("id_cam length does not match graph_sizes")
-        nat.check(int(-e), "gnncca_plan_frames")
-    if max_deg.value > nat.TOPK_MAX_DEG:   # (gnncca_build_edges_topk refuses it too; here nothing has been launched yet)
-        raise NotImplementedError(f"build_graph_batch(top_k=...): a detection with {max_deg.value} cross-camera candidates; the capped build "
-                                  f"takes at most {nat.TOPK_MAX_DEG} per detection")
+    frames.plan(dev, top_k)
     mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
     with _on(dev):
-        staged = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        staged.copy_(pinned[:nbytes], non_blocking=True)
-        event.record(_current_stream(dev))
-        job = _EdgeJob(staged, n, g, e, mode, top_k, nat.RANK_BY[rank_by], max_deg.value, nat.SYMMETRIC[symmetric] if symmetric else 0, sizes)
+        staged = torch.empty(frames.layout.nbytes, dtype=torch.uint8, device=dev)
+        frames.upload(staged)
+        job = _EdgeJob(staged, frames.layout, frames.e, mode, top_k, rank, frames.max_deg, sym, frames.arrays[4])
         if _wants_grad(node_embeds, reid_embeds):
             # the differentiable build: x, edge_attr and reid_embeds are outputs of ONE autograd node (see _GraphBuildFunction)
             reid_embeds = _f32c(reid_embeds)
@@ -482,22 +368,10 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
             elif reid_embeds.dtype != torch.float32 or not reid_embeds.is_contiguous():
                 reid_embeds = reid_embeds.float().contiguous()
             edge_index, edge_attr, edge_labels = _edges_launch(job, reid_embeds)
-    y_off = 8 * (2 * n + g)
-    i32_off = y_off + 8 * n
-    # per-graph ranges (host copies): graph g owns the nodes graph_ptr[g] .. graph_ptr[g+1] and, edges being emitted graph by graph,
-    # the edges edge_ptr_g[g] .. edge_ptr_g[g+1]
-    host_i32 = pinned[i32_off:nbytes].numpy().view(np.int32)
-    node_ptr = host_i32[3 * n:3 * n + g + 1].tolist()
+    node_ptr, edge_ptr = frames.layout.host_ptrs(frames.pinned)
     # (a symmetric build: the offsets its count read back; the device image holds the same, the pinned one still the plan's)
-    edge_ptr = job.edge_ptr_g if job.sym else host_i32[5 * n + g + 2:5 * n + 2 * g + 3].tolist()
-    batch = GraphBatch(node_embeds, edge_index, edge_attr, edge_ptr, node_ptr)
-    # device copies of the frame ranges (int32 [G + 1]) for the per-frame post-processing (postprocess.prune_and_cluster)
-    i32_dev = staged[i32_off:].view(torch.int32)
-    batch.node_ptr_dev = i32_dev[3 * n:3 * n + g + 1]
-    batch.edge_ptr_dev = i32_dev[5 * n + g + 2:5 * n + 2 * g + 3]
-    batch._frames_i32 = i32_dev   # batch.person_dev / batch.cam_dev (GraphBatch.__getattr__)
+    batch = GraphBatch(node_embeds, edge_index, edge_attr, job.edge_ptr_g if sym else edge_ptr, node_ptr)
+    attach(batch, staged, frames.layout)
     batch.edge_labels = edge_labels
-    batch.y = staged[y_off:y_off + 8 * n].view(torch.int64)
     batch.reid_embeds = reid_embeds
-    batch._keepalive = staged
     return batch

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .graph_build import _on, _raw_stream
+from .frames import _on, _raw_stream
 
 CRITERIA = {"BCE": 0, "BCE_weighted": 1, "Focal": 2}
 MODES = ("train", "validate")

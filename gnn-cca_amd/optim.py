@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _native as nat
-from .graph_build import _on, _raw_stream
+from .frames import _on, _raw_stream
 
 _REFUSED = ("maximize", "differentiable", "decoupled_weight_decay")
 

@@ -40,13 +40,13 @@ step-by-step path below and waits once per batch for its edge count; the one-cal
 Batches of more than 4096 detections, train mode and forward hooks take the step-by-step path (same results; a capped pipeline passes its
 cap on to build_graph_batch, whose limit of 4096 candidates per detection then raises NotImplementedError).  No CPU fallback."""
 import ctypes as C
-import numbers
 
 import numpy as np
 import torch
 
 from . import _native as nat
-from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, _as, _current_stream, _on, _raw_stream, _Staging, _staging, build_graph_batch
+from .frames import StagedFrames, _on, _raw_stream, attach, check_cap
+from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, build_graph_batch
 from .postprocess import finalize, prune_and_cluster, threshold
 from .sharding import GraphBatch
 
@@ -185,19 +185,7 @@ class FramePipeline:
         if not pruning:
             raise ValueError("FramePipeline prunes on the device (PRUNING = True, as config_inference.yaml:7 ships it)")
         # the cap: build_graph_batch's arguments and its refusals, here before any batch (or the GPU) is touched
-        if rank_by not in nat.RANK_BY:
-            raise ValueError(f"rank_by must be 'ground' or 'reid', not {rank_by!r}")
-        if top_k is not None:
-            if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
-                raise ValueError(f"top_k must be None or an integer >= 1, not {top_k!r}")
-            if top_k < 1:
-                raise ValueError(f"top_k must be >= 1, not {top_k}")
-            top_k = min(int(top_k), 2 ** 31 - 1)
-        if symmetric is not None:
-            if not isinstance(symmetric, str) or symmetric not in nat.SYMMETRIC:
-                raise ValueError(f"symmetric must be None, 'union' or 'mutual', not {symmetric!r}")
-            if top_k is None:
-                raise ValueError("symmetric=... closes a capped graph under reversal: it needs top_k")
+        top_k = check_cap(top_k, rank_by, symmetric)[0]
         self.top_k, self.rank_by, self.symmetric = top_k, rank_by, symmetric
         self.switches = (bool(rounding), bool(pruning), bool(splitting))
         self.mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
@@ -295,35 +283,20 @@ class FramePipeline:
             return self._slow(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds)
         dev = reid_embeds.device
         lib = nat.lib()
-        xw, yw, md = _as(xw, np.float64), _as(yw, np.float64), _as(max_dist, np.float64)
-        ids64, cam64, sizes = _as(ids, np.int64), _as(id_cam, np.int64), _as(graph_sizes, np.int64)
-        g = len(sizes)
-        if not (len(xw) == len(yw) == len(ids64) == len(cam64) == n) or len(md) != g or reid_embeds.shape[0] != n:
-            raise ValueError("per-detection / per-frame arrays disagree on their lengths")
+        frames = StagedFrames(xw, yw, ids, id_cam, graph_sizes, max_dist)
+        g, layout, top_k = frames.g, frames.layout, self.top_k
+        if frames.n != n or reid_embeds.shape[0] != n:
+            raise ValueError(frames.LENGTHS_DISAGREE)
         d = m.native_dims()
         if node_embeds.dim() != 2 or node_embeds.shape[1] != d.node_in or node_embeds.dtype != torch.float32 or reid_embeds.dtype != torch.float32:
             raise RuntimeError(f"expected float32 embeddings [N, {d.node_in}] / [N, R], got {tuple(node_embeds.shape)} {node_embeds.dtype}, "
                                f"{tuple(reid_embeds.shape)} {reid_embeds.dtype}")
         node_embeds = node_embeds if node_embeds.is_contiguous() else node_embeds.contiguous()
         reid_embeds = reid_embeds if reid_embeds.is_contiguous() else reid_embeds.contiguous()
-        nbytes = lib.gnncca_plan_frames_bytes(n, g)
-        ring = _staging.get(dev.index)
-        if ring is None:
-            ring = _staging[dev.index] = _Staging()
-        pinned, event = ring.take(nbytes)
-        top_k, max_deg = self.top_k, C.c_int32(0)
-        if top_k is None:
-            e = lib.gnncca_plan_frames(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data, md.ctypes.data, g,
-                                       pinned.data_ptr(), nbytes)
-        else:
-            e = lib.gnncca_plan_frames_ex(xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, n, sizes.ctypes.data,
-                                          md.ctypes.data, g, top_k, pinned.data_ptr(), nbytes, C.byref(max_deg))
-        if e < 0:
-            if -e == nat.ERR_INVALID_ARG:
-                raise ValueError("id_cam length does not match graph_sizes")
-            nat.check(int(-e), "gnncca_plan_frames")
+        frames.plan(dev, top_k)
+        e = frames.e
         if e == 0:   # no cross-camera pair in the whole batch: nothing to launch on the path (the step-by-step functions return the empty containers)
-            return self._slow(xw, yw, ids64, cam64, sizes, md, node_embeds, reid_embeds)
+            return self._slow(*frames.arrays, node_embeds, reid_embeds)
         n_attr = 4 if self.mode == MODE_FULL else 2
         if n_attr != d.edge_in:
             raise RuntimeError(f"the model takes {d.edge_in} edge attributes, this pipeline's mode builds {n_attr}")
@@ -357,15 +330,14 @@ class FramePipeline:
             # every region on a 256-byte boundary
             def up256(v):
                 return (v + 255) // 256 * 256
-            b_pred = up256(nbytes)
+            b_pred = up256(layout.nbytes)
             b_f32 = b_pred + up256(8 * e)
             b_i64 = b_f32 + up256(4 * (o_prob + e))
             b_i32 = b_i64 + up256(8 * (o_prun + e))
             b_post = b_i32 + up256(4 * (o_labels + n))
             arena = self._arena(b_post + post_bytes, dev)
-            staged = arena[:nbytes]
-            staged.copy_(pinned[:nbytes], non_blocking=True)
-            event.record(_current_stream(dev))
+            staged = arena[:layout.nbytes]
+            frames.upload(staged)
             f32 = arena[b_f32:b_f32 + 4 * (o_prob + e)].view(torch.float32)
             i64 = arena[b_i64:b_i64 + 8 * (o_prun + e)].view(torch.int64)
             preds = arena[b_pred:b_pred + 8 * e].view(torch.int64)
@@ -386,22 +358,16 @@ class FramePipeline:
                                                m._options(), _raw_stream(dev))
             else:
                 st = lib.gnncca_frames_forward_topk(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(),
-                                                    post_ws.numel(), m._options(), top_k, nat.RANK_BY[self.rank_by], max_deg.value, _raw_stream(dev))
+                                                    post_ws.numel(), m._options(), top_k, nat.RANK_BY[self.rank_by], frames.max_deg, _raw_stream(dev))
         if st:
             nat.check(st, "gnncca_frames_forward" if top_k is None else "gnncca_frames_forward_topk")
         # views (the reference's containers): x, edge_index, edge_attr, logits as [E, 1] per classified step
         x = f32[o_node:o_node + n * d_in].view(n, d_in) if self.normalize else node_embeds
         reid_n = f32[o_reid:o_reid + n * r_dim].view(n, r_dim) if self.normalize else reid_embeds
-        i32_off = 8 * (3 * n + g)
-        host_i32 = pinned[i32_off:nbytes].numpy().view(np.int32)
-        batch = GraphBatch(x, i64[o_ei:o_ei + 2 * e].view(2, e), f32[o_attr:o_attr + e * n_attr].view(e, n_attr),
-                           host_i32[5 * n + g + 2:5 * n + 2 * g + 3].tolist(), host_i32[3 * n:3 * n + g + 1].tolist())
-        i32_dev = staged[i32_off:].view(torch.int32)
-        batch.node_ptr_dev = i32_dev[3 * n:3 * n + g + 1]
-        batch.edge_ptr_dev = i32_dev[5 * n + g + 2:5 * n + 2 * g + 3]
-        batch._frames_i32 = i32_dev   # batch.person_dev / batch.cam_dev (GraphBatch.__getattr__)
+        node_ptr, edge_ptr = layout.host_ptrs(frames.pinned)
+        batch = GraphBatch(x, i64[o_ei:o_ei + 2 * e].view(2, e), f32[o_attr:o_attr + e * n_attr].view(e, n_attr), edge_ptr, node_ptr)
+        attach(batch, staged, layout)
         batch.edge_labels = f32[o_lab:o_lab + e]
-        batch.y = staged[8 * (2 * n + g):8 * (3 * n + g)].view(torch.int64)
         batch.reid_embeds = reid_n
         r = FrameResult()
         r.batch = batch

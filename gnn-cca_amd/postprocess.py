@@ -18,7 +18,7 @@ import torch
 from . import _native as nat
 
 
-from .graph_build import _on, _raw_stream as _stream   # the lean device guard / raw stream handle (host time matters here: ~6 launches)
+from .frames import _on, _raw_stream as _stream   # the lean device guard / raw stream handle (host time matters here: ~6 launches)
 
 
 def threshold(logits):

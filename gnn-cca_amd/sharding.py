@@ -32,12 +32,12 @@ class GraphBatch:
 
     def __getattr__(self, name):
         # person_dev / cam_dev: the int32 [N] person ids (relabelled, equality preserved) and camera ids the staging image of
-        # graph_build.build_graph_batch / pipeline.FramePipeline holds on the device, sliced when asked for (evaluate_frames(against='dense'))
+        # graph_build.build_graph_batch / pipeline.FramePipeline holds on the device (frames.attach), sliced when asked for (evaluate_frames)
         if name in ("person_dev", "cam_dev"):
-            image = self.__dict__.get("_frames_i32")
-            if image is not None:
-                n = int(self.node_ptr[-1])
-                return image[:n] if name == "person_dev" else image[n:2 * n]
+            frames = self.__dict__.get("_frames")
+            if frames is not None:
+                image, layout = frames
+                return layout.view(image, name[:-4])
         raise AttributeError(name)
 
 

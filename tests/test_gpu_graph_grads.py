@@ -203,9 +203,9 @@ def test_forward_and_backward_under_graph_capture(monkeypatch):
     """build_graph_batch + backward captured into one HIP graph on a single stream and replayed: the replay's gradients are bit for bit the
     eager ones, so nothing on the path synchronises (the capture would fail).  The staging ring is private to this test: an event
     recorded during a capture must not be waited on by a later, eager batch."""
-    from gnn_cca_amd import graph_build as gbm
+    from gnn_cca_amd import frames, graph_build as gbm
     a = load_grads("batch3")
-    monkeypatch.setattr(gbm, "_staging", {})
+    monkeypatch.setattr(frames, "_staging", {})
     node = torch.from_numpy(a["node_embeds_raw"]).cuda().requires_grad_()
     reid = torch.from_numpy(a["reid_embeds_raw"]).cuda().requires_grad_()
     gx, gea = torch.from_numpy(a["g_x"]).cuda(), torch.from_numpy(a["g_edge_attr"]).cuda()
@@ -214,7 +214,7 @@ def test_forward_and_backward_under_graph_capture(monkeypatch):
         b = gbm.build_graph_batch(a["xw"], a["yw"], a["id"], a["id_cam"], a["graph_sizes"], a["max_dist"], node, reid)
         torch.autograd.backward([b.x, b.edge_attr], [gx, gea])
 
-    for _ in range(gbm._Staging.SLOTS):   # every slot of the ring gets its pinned buffer and event outside the capture
+    for _ in range(frames._Staging.SLOTS):   # every slot of the ring gets its pinned buffer and event outside the capture
         node.grad = reid.grad = None
         step()
     torch.cuda.synchronize()

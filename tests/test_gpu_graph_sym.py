@@ -153,7 +153,7 @@ def test_two_runs_give_identical_bits():
 
 
 def test_capture_is_refused_before_anything_is_launched(monkeypatch):
-    from gnn_cca_amd import graph_build as gbm
+    from gnn_cca_amd import frames, graph_build as gbm
     a = load("batch3")
     node = torch.from_numpy(a["node_embeds_raw"]).cuda()
     reid = torch.from_numpy(a["reid_embeds_raw"]).cuda()
@@ -164,7 +164,7 @@ def test_capture_is_refused_before_anything_is_launched(monkeypatch):
     def no_staging(self, nbytes):
         raise AssertionError("the refusal must come before the plan and the upload")
 
-    monkeypatch.setattr(gbm._Staging, "take", no_staging)
+    monkeypatch.setattr(frames._Staging, "take", no_staging)
     graph = torch.cuda.CUDAGraph()
     with pytest.raises(RuntimeError, match="captured"):
         with torch.cuda.graph(graph):

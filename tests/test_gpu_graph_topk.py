@@ -204,16 +204,16 @@ def test_downstream_mpn_postprocess_evaluation():
 
 def test_capture_and_replay(monkeypatch):
     """The capped build inside a HIP graph (nothing on the path synchronises), replayed with different embeddings in the static inputs."""
-    from gnn_cca_amd import graph_build as gbm
+    from gnn_cca_amd import frames, graph_build as gbm
     a = load("batch3")
-    monkeypatch.setattr(gbm, "_staging", {})      # an event recorded during a capture must not be waited on by a later, eager batch
+    monkeypatch.setattr(frames, "_staging", {})      # an event recorded during a capture must not be waited on by a later, eager batch
     node = torch.from_numpy(a["node_embeds_raw"]).cuda()
     reid = torch.from_numpy(a["reid_embeds_raw"]).cuda()
 
     def step():
         return gbm.build_graph_batch(a["xw"], a["yw"], a["id"], a["id_cam"], a["graph_sizes"], a["max_dist"], node, reid, top_k=3, rank_by="reid")
 
-    for _ in range(gbm._Staging.SLOTS):      # every slot of the ring gets its pinned buffer and event outside the capture
+    for _ in range(frames._Staging.SLOTS):      # every slot of the ring gets its pinned buffer and event outside the capture
         step()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()

@@ -73,7 +73,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     args = ap.parse_args()
     from gnn_cca_amd import _native as nat
-    from gnn_cca_amd.graph_build import _raw_stream
+    from gnn_cca_amd.frames import _raw_stream
     from gnn_cca_amd.loss import CRITERIA, EdgeLoss, TrainMeters, record_len
 
     dev = torch.device("cuda:0")
