@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""Track ids over time on synthetic frames: FramePipeline results -> per-cluster summaries (fused position, mean appearance, size,
+camera count) -> persistent track ids across frames and batches (gnn_cca_amd.tracking).  Everything stays on the GPU until the final
+print.  The reference has no counterpart of this stage: it scores single frames (inference.py:349-371).  Needs an MI355X.
+
+    python examples/track_frames.py [batches] [frames_per_batch] [cams] [persons]
+
+Persons walk on the ground plane; every camera sees every person, with noise on the position.  The model has random weights, so its
+clusters mean nothing: the ids are shown for the model's partition AND for the ground-truth partition of the same detections, where a
+person keeps one id as long as the walk stays inside max_step.  What linking does to tracking quality with a trained model has not
+been measured.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
+from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
+from gnn_cca_amd.tracking import FrameLinker, cluster_summaries  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("batches", nargs="?", type=int, default=3)
+    ap.add_argument("frames", nargs="?", type=int, default=8, metavar="frames_per_batch")
+    ap.add_argument("cams", nargs="?", type=int, default=4)
+    ap.add_argument("persons", nargs="?", type=int, default=6)
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    n_g = a.cams * a.persons
+    n = a.frames * n_g
+    model = bench.build_model(bench.graph_net_params(), n_g).cuda().eval()
+    pipe = FramePipeline(model)
+    by_model, by_truth = FrameLinker(max_step=1.0, lam=1.0), FrameLinker(max_step=1.0, lam=1.0)
+    where = rng.uniform(-8, 8, size=(a.persons, 2))
+    look = rng.standard_normal((a.persons, 256)).astype(np.float32)
+    id_cam = np.tile(np.repeat(np.arange(a.cams), a.persons), a.frames)
+    ids = np.tile(np.tile(np.arange(a.persons), a.cams), a.frames).astype(np.int64)
+    frame_of = np.repeat(np.arange(a.frames), n_g)
+    # the ground-truth partition in the pipeline's convention: a detection's label is the smallest node id of its person in its frame
+    truth = torch.from_numpy((frame_of * n_g + ids).astype(np.int32)).cuda()
+    for k in range(a.batches):
+        steps = np.cumsum(rng.normal(0, 0.15, size=(a.frames, a.persons, 2)), axis=0)
+        walk = where[None] + steps
+        where = walk[-1]
+        xw = walk[frame_of, ids, 0] + rng.normal(0, 0.05, n)
+        yw = walk[frame_of, ids, 1] + rng.normal(0, 0.05, n)
+        node = torch.randn(n, 2048, device="cuda")
+        reid = torch.from_numpy(look[ids] + 0.1 * rng.standard_normal((n, 256)).astype(np.float32)).cuda()
+        r = pipe(xw, yw, ids, id_cam, [n_g] * a.frames, [80.0] * a.frames, node, reid)
+        s = r.identities(final=False)            # the device chain's partition, no wait for the host heuristics (final=True: r.final()'s)
+        t = by_model(s)                          # or by_model(r): a FrameResult's identities() are taken
+        st = cluster_summaries(r.batch, truth)   # any partition of the batch's detections can be summarised
+        tt = by_truth(st)
+        # ---- only the printing below waits for the GPU ----
+        last = slice(r.batch.node_ptr[-2], r.batch.node_ptr[-1])
+        k_model, k_truth = int(s.count[-1].item()), int(st.count[-1].item())
+        print(f"batch {k}: {a.frames} frames, N={n}; model partition: {int(s.count.sum().item())} clusters, tracks so far {int(t.next_id.item())}; "
+              f"true partition: {int(st.count.sum().item())} clusters, tracks so far {int(tt.next_id.item())}")
+        print(f"  last frame, true partition: ids {tt.cluster_track[last][:k_truth].tolist()} at "
+              f"{[[round(v, 2) for v in p] for p in st.pos[last][:k_truth].tolist()]}, cameras {st.n_cams[last][:k_truth].tolist()}")
+        print(f"  last frame, model partition: {k_model} clusters, sizes {s.size[last][:k_model].tolist()}")
+    print("random weights: the model's clusters are meaningless, the plumbing is what is shown; on the true partition a person keeps its id")
+
+
+if __name__ == "__main__":
+    main()

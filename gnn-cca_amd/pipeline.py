@@ -13,6 +13,8 @@ and the Python between five calls is a third of it: 0.143 -> 0.11 ms per batch.
     r.triggers                                                      # [G] int32 on the device: frames the host heuristics can change
     f = r.final()                                                   # the reference's FINAL predictions / ID_pred partition under
     f['predictions'], f['labels'], f['n_clusters']                  # ROUNDING / PRUNING / SPLITTING (config_inference.yaml:6-8)
+    s = r.identities()                                              # per-cluster position / appearance / size / cameras on the device;
+    #                                                                 tracking.FrameLinker turns them into track ids (no reference counterpart)
 
 `r.final_async()` (round 6) hands the batch to a persistent pool of host threads WITHOUT synchronising -- one D2H copy of the batch's trigger
 words / edges / probabilities / pruned predictions / labels enqueued behind the chain, the flagged frames finalized by the
@@ -104,7 +106,7 @@ class PendingFinal:
 class FrameResult:
     """Outputs of one batch; tensors are views of ONE device buffer owned by this object."""
     __slots__ = ("batch", "outputs", "probs", "preds", "pruned", "flow_out", "flow_in", "labels", "n_clusters", "triggers", "_switches", "_final", "_keep",
-                 "_pipe", "_d2h", "_pending", "_eval")
+                 "_pipe", "_d2h", "_pending", "_eval", "_ident")
 
     def final_async(self):
         """Hand this batch to the pipeline's pool of host threads (no synchronisation) -> PendingFinal.  Results that did not come from the
@@ -160,6 +162,20 @@ class FrameResult:
                 cache[key] = evaluate_frames(self.batch, f["predictions"], f["labels"], against=against)
             else:
                 cache[key] = evaluate_frames(self.batch, self.pruned, self.labels, against=against)
+        return cache[key]
+
+    def identities(self, final=True):
+        """The per-cluster summaries of this batch (gnn_cca_amd.tracking.cluster_summaries: fused position, mean appearance, size and
+        camera count of every identity cluster, as device tensors; no counterpart in the reference).  final=True summarises final()'s
+        partition (which waits for this batch's host heuristics), final=False the device chain's labels without that wait.  Computed
+        once per mode; a tracking.FrameLinker takes this result (or the FrameResult itself) and hands out persistent track ids."""
+        from .tracking import cluster_summaries
+        cache = getattr(self, "_ident", None)
+        if cache is None:
+            cache = self._ident = {}
+        key = bool(final)
+        if key not in cache:
+            cache[key] = cluster_summaries(self.batch, self.final()["labels"] if final else self.labels)
         return cache[key]
 
 

@@ -675,6 +675,58 @@ GNNCCA_API int gnncca_eval_frames_dense(const int64_t* edge_index, const float* 
                                         int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace,
                                         size_t workspace_bytes, gnncca_stream_t stream);
 
+/* ---- Cluster summaries and frame-to-frame track ids (csrc/identities.hip) -----------------------------------------------------------
+ * No counterpart in the reference, which scores single frames (inference.py:349-371) and neither fuses a cluster nor links two frames.
+ * Both stages take a batch laid out as above (node_ptr_dev: int32 [n_frames + 1] in DEVICE memory) and `max_frame_nodes`, the largest
+ * frame as the caller's host copy of node_ptr knows it: above GNNCCA_TRACK_MAX_FRAME_NODES it is GNNCCA_ERR_INVALID_ARG before any launch.
+ * Every argument is checked before any launch; no host synchronisation, no allocation: capturable.  Deterministic: every floating-point
+ * sum has a fixed order, no float atomics.
+ *
+ * gnncca_cluster_summaries.  Inputs: labels int32 [N] (a node's label is the smallest batch-global node id of its cluster, as
+ * gnncca_post_prune_cluster_frames and the host finalisation write it), xw / yw fp64 [N], cam int32 [N] (any values), embeds fp32
+ * [N][reid_dim] (NULL with reid_dim = 0).  Outputs, all of fixed shape -- nothing is compacted across frames, so nobody waits for a count:
+ *   count int32 [n_frames]   clusters of frame g
+ *   rank  int32 [N]          the frame-local index of the node's cluster; clusters are ordered by ascending root id
+ *   cluster c of frame g is ROW node_ptr[g] + c of  size int32 [N],  n_cams int32 [N] (distinct cam values among the members),
+ *   pos fp64 [N][2] (the sums of xw and of yw over the members in ascending node id, one addition per member from 0.0, then ONE division
+ *   by (double)size)  and  emb fp32 [N][reid_dim] (per column the fp32 sum over the members in ascending node id, from 0.0f, then ONE
+ *   division by (float)size).  Rows at or beyond count[g] of a frame are zero.
+ * An empty frame gives count 0.  A frame that does not fit -- more nodes than max_frame_nodes, a node range outside [0, N], a label
+ * outside the node's own frame, a label that is not a root (labels[label] != label) -- reads nothing out of bounds and gets count -1,
+ * rank -1 and zero rows (where its node range lies inside [0, N]: there are no rows to speak of otherwise); its neighbours are not
+ * affected.  Workspace: gnncca_cluster_summaries_bytes (every cluster's member list).
+ *
+ * gnncca_link_frames.  Frame t of the batch is linked to frame t - 1, frame 0 to `state_in`, which holds the last frame of the previous
+ * call (NULL: nothing to link to, ids start at 0).  Frames are taken to be consecutive and in order.  For cluster a of the current and
+ * cluster b of the previous frame, from their `pos` / `emb` rows:  d = sqrt(dx dx + dy dy) (fp64);  dcos = 1 - dot / (sqrt(na) sqrt(nb))
+ * with dot, na, nb accumulated in fp64 (1 when a norm is 0);  cost = d / max_step + lam * dcos;  admissible iff d <= max_step and (with
+ * has_max_cos) dcos <= max_cos.  With lam == 0 and no max_cos the embeddings are not read (emb may be NULL) and cost = d / max_step.
+ * fwd[a] = the admissible b of smallest cost, bwd[b] = the admissible a of smallest cost, ties to the smaller index; a continues b iff
+ * fwd[a] == b and bwd[b] == a (one-to-one by construction).  A matched cluster takes its partner's track id; the unmatched ones get
+ * next_id, next_id + 1, ... in ascending (frame, rank) order.  A frame with count <= 0 links to nothing.  Outputs: cluster_track int64
+ * [N] (row-aligned with the summaries, -1 beyond count), node_track int64 [N] (a detection's track, -1 in a refused frame), matched_prev
+ * int32 [N] (the partner's rank in the previous frame, or -1), and state_out: the last frame's count, pos, emb, track ids and next_id
+ * (an int64 at offset 0), gnncca_link_state_bytes(capacity, reid_dim) bytes for a capacity of at least the last frame's node count
+ * (it bounds the cluster count; a frame with more clusters than state_out_capacity is carried as empty).  state_in must have been
+ * written with the same reid_dim and its own capacity (<= GNNCCA_TRACK_MAX_FRAME_NODES); it is not modified.  n_frames = 0 launches
+ * nothing and writes nothing.  Out of scope: re-identification after a frame in which a track was not seen, optimal assignment, time
+ * stamps.  Workspace: gnncca_link_workspace_bytes. */
+#define GNNCCA_TRACK_MAX_FRAME_NODES 4096
+GNNCCA_API size_t gnncca_cluster_summaries_bytes(int64_t n_nodes, int64_t n_frames);
+GNNCCA_API int gnncca_cluster_summaries(const int32_t* labels, const int32_t* node_ptr_dev, const double* xw, const double* yw,
+                                        const int32_t* cam, const float* embeds, int32_t reid_dim, int64_t n_nodes, int32_t n_frames,
+                                        int32_t max_frame_nodes, int32_t* count_out, int32_t* rank_out, int32_t* size_out,
+                                        int32_t* n_cams_out, double* pos_out, float* emb_out, void* workspace, size_t workspace_bytes,
+                                        gnncca_stream_t stream);
+GNNCCA_API size_t gnncca_link_state_bytes(int64_t capacity, int32_t reid_dim);
+GNNCCA_API size_t gnncca_link_workspace_bytes(int64_t n_nodes, int64_t n_frames);
+GNNCCA_API int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
+                                  const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                  double max_step, double lam, int32_t has_max_cos, double max_cos, const void* state_in,
+                                  int64_t state_in_capacity, void* state_out, int64_t state_out_capacity, int64_t* cluster_track,
+                                  int64_t* node_track, int32_t* matched_prev, void* workspace, size_t workspace_bytes,
+                                  gnncca_stream_t stream);
+
 /* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
  * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).
  * criterion: GNNCCA_LOSS_BCE, GNNCCA_LOSS_BCE_WEIGHTED (pos_weight > 0) or GNNCCA_LOSS_FOCAL (utils.FocalLoss_binary: focusing_param,

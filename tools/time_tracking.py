@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Times gnn_cca_amd.tracking on a Terrace-shaped batch: cluster summaries plus frame linking for 64 frames of 4 cameras x 8 detections
+(N = 2048, every person seen once per camera: 8 clusters of 4 per frame) with R = 2048 appearance columns.  Needs an MI355X.
+
+    python tools/time_tracking.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3]
+
+Two ways to the same result, timed in alternating rounds in one process (host clock around work that ends in a device synchronise):
+  device   cluster summaries (2 launches) + FrameLinker (3 launches) on tensors that are already on the GPU, as a FramePipeline
+           result holds them; the state carries from one repetition to the next, as it would from batch to batch
+  host     labels, positions, cameras and embeddings copied back (the copies and their synchronisation included), then the numpy
+           restatement of the rules (tests/tracking_oracle.py: plain loops for the sums, float64 matching)
+and, as the floor under ANY host implementation, `copy`: those device-to-host copies and their synchronisation alone.
+The two results are compared once (summaries bit for bit, ids exactly).  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import tracking_oracle as to  # noqa: E402
+from gnn_cca_amd.tracking import FrameLinker, cluster_summaries_raw  # noqa: E402
+
+
+def make_batch(frames, cams, per, reid, seed=0):
+    rng = np.random.default_rng(seed)
+    n_g = cams * per
+    n = frames * n_g
+    cam = np.tile(np.repeat(np.arange(cams), per), frames).astype(np.int32)
+    person = np.tile(np.tile(np.arange(per), cams), frames)
+    frame_of = np.repeat(np.arange(frames), n_g)
+    walk = rng.uniform(-8, 8, size=(1, per, 2)) + np.cumsum(rng.normal(0, 0.1, size=(frames, per, 2)), axis=0)
+    xw = walk[frame_of, person, 0] + rng.normal(0, 0.05, n)
+    yw = walk[frame_of, person, 1] + rng.normal(0, 0.05, n)
+    look = rng.standard_normal((per, reid)).astype(np.float32)
+    emb = look[person] + 0.1 * rng.standard_normal((n, reid)).astype(np.float32)
+    emb /= np.linalg.norm(emb, axis=1, keepdims=True)
+    # a person's detections are one cluster; its label is the smallest node id (the person's detection on camera 0)
+    labels = (frame_of * n_g + person).astype(np.int32)
+    node_ptr = (np.arange(frames + 1) * n_g).astype(np.int64)
+    return dict(labels=labels, node_ptr=node_ptr, xw=xw, yw=yw, cam=cam, emb=emb.astype(np.float32), n=n)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--cams", type=int, default=4)
+    ap.add_argument("--per", type=int, default=8)
+    ap.add_argument("--reid", type=int, default=2048)
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--host-reps", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/time_tracking.py measures on the GPU; no device is visible")
+    b = make_batch(a.frames, a.cams, a.per, a.reid)
+    dev = torch.device("cuda")
+    d = {k: torch.from_numpy(b[k]).to(dev) for k in ("labels", "xw", "yw", "cam", "emb")}
+    ptr_host = b["node_ptr"].tolist()
+    max_step, lam = 1.0, 1.0
+    link = FrameLinker(max_step, lam=lam)
+
+    def device_once():
+        s = cluster_summaries_raw(d["labels"], ptr_host, d["xw"], d["yw"], d["cam"], d["emb"])
+        return s, link(s)
+
+    def copy_once():
+        out = [d[k].cpu() for k in ("labels", "xw", "yw", "cam", "emb")]   # (.cpu() of a device tensor synchronises)
+        return [t.numpy() for t in out]
+
+    def host_once(state):
+        labels, xw, yw, cam, emb = copy_once()
+        s = to.summaries(labels, b["node_ptr"], xw, yw, cam, emb)
+        return s, to.link(s, b["node_ptr"], max_step, lam, None, state)
+
+    # one comparison of the two results, from a fresh state
+    s_dev, t_dev = device_once()
+    s_host, (t_host, _) = host_once(None)
+    torch.cuda.synchronize()
+    same = all(np.array_equal(getattr(s_dev, k).cpu().numpy(), s_host[k]) for k in ("count", "rank", "size", "n_cams", "pos", "emb"))
+    same_ids = all(np.array_equal(getattr(t_dev, k).cpu().numpy(), t_host[k]) for k in ("cluster_track", "node_track", "matched_prev"))
+    for _ in range(10):   # warm-up: code objects, allocator
+        device_once()
+    torch.cuda.synchronize()
+    dev_ms, host_ms, copy_ms = [], [], []
+    for _ in range(a.rounds):
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            device_once()
+        torch.cuda.synchronize()
+        dev_ms.append((time.perf_counter() - t0) / a.reps * 1e3)
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            copy_once()
+        copy_ms.append((time.perf_counter() - t0) / a.reps * 1e3)
+        t0 = time.perf_counter()
+        for _ in range(a.host_reps):
+            host_once(None)
+        host_ms.append((time.perf_counter() - t0) / a.host_reps * 1e3)
+    print(json.dumps({"frames": a.frames, "cams": a.cams, "per_cam": a.per, "n_nodes": b["n"], "reid_dim": a.reid, "reps": a.reps,
+                      "host_reps": a.host_reps, "device_ms": [round(v, 4) for v in dev_ms], "host_ms": [round(v, 2) for v in host_ms],
+                      "copy_ms": [round(v, 4) for v in copy_ms], "summaries_equal": bool(same), "ids_equal": bool(same_ids),
+                      "tracks": int(t_dev.next_id.item())}))
+
+
+if __name__ == "__main__":
+    main()
