@@ -7,8 +7,9 @@ print.  The reference has no counterpart of this stage: it scores single frames 
 
 Persons walk on the ground plane; every camera sees every person, with noise on the position.  The model has random weights, so its
 clusters mean nothing: the ids are shown for the model's partition AND for the ground-truth partition of the same detections, where a
-person keeps one id as long as the walk stays inside max_step.  What linking does to tracking quality with a trained model has not
-been measured.
+person keeps one id as long as the walk stays inside max_step.  In the middle frame of every batch person 0 is hidden from every camera:
+the linker with max_gap=1 finds them again one frame later under the same id, the linker without max_gap hands out a new one.  What
+linking does to tracking quality with a trained model has not been measured.
 """
 import argparse
 import os
@@ -33,17 +34,23 @@ def main():
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     n_g = a.cams * a.persons
-    n = a.frames * n_g
     model = bench.build_model(bench.graph_net_params(), n_g).cuda().eval()
     pipe = FramePipeline(model)
     by_model, by_truth = FrameLinker(max_step=1.0, lam=1.0), FrameLinker(max_step=1.0, lam=1.0)
+    by_truth_gap = FrameLinker(max_step=1.0, lam=1.0, max_gap=1)   # a track survives one frame that misses it
     where = rng.uniform(-8, 8, size=(a.persons, 2))
     look = rng.standard_normal((a.persons, 256)).astype(np.float32)
     id_cam = np.tile(np.repeat(np.arange(a.cams), a.persons), a.frames)
     ids = np.tile(np.tile(np.arange(a.persons), a.cams), a.frames).astype(np.int64)
     frame_of = np.repeat(np.arange(a.frames), n_g)
+    hidden = a.frames // 2                                    # the frame in which nobody sees person 0 (none in a one-frame batch)
+    seen = ~((frame_of == hidden) & (ids == 0)) if a.frames > 1 else np.ones(len(ids), bool)
+    id_cam, ids, frame_of = id_cam[seen], ids[seen], frame_of[seen]
+    sizes = np.bincount(frame_of, minlength=a.frames).tolist()
+    n = len(ids)
     # the ground-truth partition in the pipeline's convention: a detection's label is the smallest node id of its person in its frame
-    truth = torch.from_numpy((frame_of * n_g + ids).astype(np.int32)).cuda()
+    first = {}
+    truth = torch.tensor([first.setdefault((q, p), v) for v, (q, p) in enumerate(zip(frame_of.tolist(), ids.tolist()))], dtype=torch.int32).cuda()
     for k in range(a.batches):
         steps = np.cumsum(rng.normal(0, 0.15, size=(a.frames, a.persons, 2)), axis=0)
         walk = where[None] + steps
@@ -52,11 +59,12 @@ def main():
         yw = walk[frame_of, ids, 1] + rng.normal(0, 0.05, n)
         node = torch.randn(n, 2048, device="cuda")
         reid = torch.from_numpy(look[ids] + 0.1 * rng.standard_normal((n, 256)).astype(np.float32)).cuda()
-        r = pipe(xw, yw, ids, id_cam, [n_g] * a.frames, [80.0] * a.frames, node, reid)
+        r = pipe(xw, yw, ids, id_cam, sizes, [80.0] * a.frames, node, reid)
         s = r.identities(final=False)            # the device chain's partition, no wait for the host heuristics (final=True: r.final()'s)
         t = by_model(s)                          # or by_model(r): a FrameResult's identities() are taken
         st = cluster_summaries(r.batch, truth)   # any partition of the batch's detections can be summarised
         tt = by_truth(st)
+        tg = by_truth_gap(st)                    # tg.matched_gap: 1 where a cluster continues one that was last seen two frames ago
         # ---- only the printing below waits for the GPU ----
         last = slice(r.batch.node_ptr[-2], r.batch.node_ptr[-1])
         k_model, k_truth = int(s.count[-1].item()), int(st.count[-1].item())
@@ -65,6 +73,11 @@ def main():
         print(f"  last frame, true partition: ids {tt.cluster_track[last][:k_truth].tolist()} at "
               f"{[[round(v, 2) for v in p] for p in st.pos[last][:k_truth].tolist()]}, cameras {st.n_cams[last][:k_truth].tolist()}")
         print(f"  last frame, model partition: {k_model} clusters, sizes {s.size[last][:k_model].tolist()}")
+        if a.frames > 2:   # person 0 is cluster 0 of every frame that shows them (their camera-0 detection is the frame's first node)
+            before, after = r.batch.node_ptr[hidden - 1], r.batch.node_ptr[hidden + 1]
+            print(f"  person 0, hidden in frame {hidden}: id {int(tt.cluster_track[before])} -> {int(tt.cluster_track[after])} without max_gap, "
+                  f"{int(tg.cluster_track[before])} -> {int(tg.cluster_track[after])} with max_gap=1 "
+                  f"(matched_gap {int(tg.matched_gap[after])}); tracks so far {int(tt.next_id.item())} against {int(tg.next_id.item())}")
     print("random weights: the model's clusters are meaningless, the plumbing is what is shown; on the true partition a person keeps its id")
 
 

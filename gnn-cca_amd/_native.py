@@ -13,6 +13,7 @@ AGG = {"sum": 0, "mean": 1, "max": 2}
 GRAPH_UNSORTED, GRAPH_BAD_INDEX = 1, 2
 RANK_BY = {"ground": 0, "reid": 1}   # gnncca_build_edges_topk, gnncca_frames_forward_topk
 TOPK_MAX_DEG = 4096
+TRACK_MAX_GAP = 8                    # gnncca_link_frames_gap
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
 
 
@@ -214,6 +215,12 @@ _SIGNATURES = {
     "gnncca_link_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnncca_link_gap_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gnncca_link_gap_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "gnncca_link_frames_gap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
+                                         C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
     "gnncca_edge_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "gnncca_edge_loss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -20,6 +20,8 @@
 //   3. one workgroup per frame: a matched cluster follows matched_prev back to the head of its chain (an unmatched cluster: next_id + the
 //      prefix of its frame + its rank among the unmatched; or a cluster of the carried state: its id), then node_track; the last frame's
 //      workgroup writes the new state.
+// Gap-tolerant linking (gnncca_link_frames_gap: a track survives up to max_gap frames that miss it) is identities_gap.cuh, included at the
+// end of this file: its own kernels and state layout, the scan kernel shared.
 // Deterministic: every fp sum has a fixed order, integer counts go through LDS atomics, no fp64 atomics.  No host wait, no allocation:
 // capturable.  The file is compiled without fp contraction: the sums, the divisions and the cost are the documented operations one by one.
 #include <hip/hip_runtime.h>
@@ -526,3 +528,5 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
 }
 
 }  // extern "C"
+
+#include "identities_gap.cuh"   // gnncca_link_frames_gap: the gap-tolerant linker (its own kernels; nothing above changes)

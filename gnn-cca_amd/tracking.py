@@ -7,6 +7,7 @@ over the frames of a batch and from one batch to the next.
     link = FrameLinker(max_step=0.8, lam=1.0)     # metres a person may move between two frames; weight of the appearance term
     t = link(r)                                   # Tracks: cluster_track [N], node_track [N], matched_prev [N], next_id [1]
     t = link(next_r)                              # ... frame 0 of this batch continues the last frame of the previous one
+    link = FrameLinker(max_step=0.8, max_gap=2)   # a track survives up to 2 frames that miss it; t.matched_gap [N]: frames skipped
 
 The reference has NO counterpart: it scores single frames (inference.py:349-371), never fuses the views of a cluster into a position and
 never carries an identity from one frame to the next.  What these rules do to tracking quality with a trained model has NOT been measured.
@@ -24,8 +25,18 @@ cost = d / max_step + lam * dcos;  the pair is admissible iff d <= max_step and 
 smallest cost, bwd[b] the admissible a of smallest cost, ties to the smaller index; a continues b iff each is the other's best -- one to
 one by construction, and deterministic.  A matched cluster takes its partner's id; the others get next_id, next_id + 1, ... in ascending
 (frame, cluster) order.  With lam == 0 and no max_cos the embeddings are not read.
-Limits: frames of a batch are taken to be CONSECUTIVE and IN ORDER (there are no time stamps); a track that is not seen in one frame ends
-(no re-identification after a gap, no `max_gap`); the matching is mutual-best, not an optimal assignment.  No CPU fallback."""
+Gaps (max_gap = M > 0: csrc/identities_gap.cuh, M + 4 launches).  Every cluster has a predecessor (none at first) and a has-a-successor
+flag (clear at first).  Levels k = 0 .. M run one after the other, all frames of the batch in parallel within a level: the clusters of frame
+t WITHOUT a predecessor meet the clusters of frame t - 1 - k (of this batch or of the carried history) WITHOUT a successor, under
+gate_k = max_step * (k + 1): admissible iff d <= gate_k (and dcos <= max_cos), cost = d / gate_k + lam * dcos, mutual best as above with
+ties to the smaller rank within the frame.  Level 0 is the rule above word for word, so a shorter gap always wins over a longer one, even
+at higher cost.  Time is the frame index over all calls since reset(): an empty or refused frame still counts as a frame, an empty batch
+passes no time.  The rule is causal, so the ids do not depend on how a sequence is cut into batches; the state holds the last M + 1 frames.
+Limits: frames are taken to be CONSECUTIVE and IN ORDER (there are no time stamps); a track unseen for more than max_gap frames ends (with
+the default max_gap = 0: in the first frame that misses it); a cluster is looked for where it was last seen -- there is no motion
+prediction (no velocity term), only a gate that grows with the gap; the matching is mutual-best, not an optimal assignment.
+No CPU fallback."""
+import ctypes as C
 import math
 import numbers
 
@@ -36,6 +47,7 @@ from . import _native as nat
 from .frames import _on, _raw_stream
 
 MAX_FRAME_NODES = 4096
+MAX_GAP = nat.TRACK_MAX_GAP
 
 
 class ClusterSummaries:
@@ -51,12 +63,20 @@ class ClusterSummaries:
 
 class Tracks:
     """Track ids of a batch (device tensors): cluster_track int64 [N] (row-aligned with the summaries, -1 beyond a frame's count),
-    node_track int64 [N] (a detection's track), matched_prev int32 [N] (the rank of the cluster's partner in the previous frame, or -1),
-    next_id int64 [1] (the first id nobody has yet)."""
-    __slots__ = ("cluster_track", "node_track", "matched_prev", "next_id", "_state")
+    node_track int64 [N] (a detection's track), matched_prev int32 [N] (the rank of the cluster's predecessor in ITS OWN frame, or -1),
+    matched_gap int32 [N] (-1: no predecessor; k: the predecessor is k + 1 frames back, k frames were skipped -- all 0 / -1 from a linker
+    without max_gap, where it is derived from matched_prev when first read), next_id int64 [1] (the first id nobody has yet)."""
+    __slots__ = ("cluster_track", "node_track", "matched_prev", "next_id", "_state", "_matched_gap")
 
-    def __init__(self, cluster_track, node_track, matched_prev, next_id, state):
+    def __init__(self, cluster_track, node_track, matched_prev, next_id, state, matched_gap=None):
         self.cluster_track, self.node_track, self.matched_prev, self.next_id, self._state = cluster_track, node_track, matched_prev, next_id, state
+        self._matched_gap = matched_gap
+
+    @property
+    def matched_gap(self):
+        if self._matched_gap is None:   # the max_gap = 0 path launches nothing for it unless somebody asks: -1 stays, a rank becomes 0
+            self._matched_gap = torch.clamp(self.matched_prev, max=0)
+        return self._matched_gap
 
 
 def _host_ptr(node_ptr):
@@ -147,10 +167,14 @@ class FrameLinker:
     max_step: the largest ground-plane distance (the units of xw / yw) a cluster may move between two frames, finite and > 0.
     lam: the weight of the cosine distance of the mean appearances in the cost, finite and >= 0 (0 with max_cos=None: position only, the
     embeddings are not read).  max_cos: None, or the largest admissible cosine distance, in [0, 2].
-    Frames are taken to be consecutive and in order; a track missing from one frame ends there (no `max_gap`); mutual-best matching, not
-    an optimal assignment.  No counterpart in the reference; the effect on tracking quality with a trained model has not been measured."""
+    max_gap: an integer in 0 .. 8, the number of consecutive frames a track may be missing from and still be continued (gate
+    max_step * (k + 1) after k missed frames; a shorter gap always wins).  0: the adjacent-frame linker, three launches, as ever; M > 0:
+    M + 4 launches, and the state holds the last M + 1 frames (sized from their node counts, which the linker keeps on the host).
+    Frames are taken to be consecutive and in order (no time stamps); a track missing from more than max_gap frames ends; there is no
+    motion prediction (no velocity term) and the matching is mutual-best, not an optimal assignment.  No counterpart in the reference; the
+    effect on tracking quality with a trained model has not been measured."""
 
-    def __init__(self, max_step, lam=1.0, max_cos=None):
+    def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0):
         def real(v):
             return isinstance(v, numbers.Real) and not isinstance(v, bool)
         if not real(max_step) or not math.isfinite(max_step) or not max_step > 0:
@@ -159,12 +183,16 @@ class FrameLinker:
             raise ValueError(f"lam must be a finite number >= 0, not {lam!r}")
         if max_cos is not None and (not real(max_cos) or not 0 <= max_cos <= 2):
             raise ValueError(f"max_cos must be None or a number in [0, 2], not {max_cos!r}")
+        if isinstance(max_gap, bool) or not isinstance(max_gap, numbers.Integral) or not 0 <= max_gap <= MAX_GAP:
+            raise ValueError(f"max_gap must be an integer in [0, {MAX_GAP}], not {max_gap!r}")
         self.max_step, self.lam, self.max_cos = float(max_step), float(lam), None if max_cos is None else float(max_cos)
+        self.max_gap = int(max_gap)
         self.reset()
 
     def reset(self):
-        """Forget the carried frame and the id counter."""
+        """Forget the carried frames and the id counter."""
         self._state, self._cap, self._reid_dim = None, 0, None
+        self._frame_rows = []   # max_gap > 0: the node counts of the frames the state holds, oldest first (they bound the cluster counts)
 
     @property
     def needs_embeddings(self):
@@ -191,7 +219,9 @@ class FrameLinker:
             if g == 0:   # nothing to link: the state stays
                 nid = self._state[:8].view(torch.int64) if self._state is not None else torch.zeros(1, dtype=torch.int64, device=dev)
                 e64, e32 = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
-                return Tracks(e64, e64.clone(), e32, nid, self._state)
+                return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone())
+            if self.max_gap > 0:
+                return self._link_gap(lib, s, dev, sizes, g, n, max_n, r)
             cap = int(sizes[-1])
             state = torch.empty(lib.gnncca_link_state_bytes(cap, r), dtype=torch.uint8, device=dev)
             tracks = torch.empty((2, n), dtype=torch.int64, device=dev)   # cluster_track | node_track
@@ -210,5 +240,28 @@ class FrameLinker:
         self._state, self._cap = state, cap
         return Tracks(tracks[0], tracks[1], matched, state[:8].view(torch.int64), state)
 
+    def _link_gap(self, lib, s, dev, sizes, g, n, max_n, r):
+        """The max_gap > 0 call (inside _on(dev), g > 0): everything is sized from host-known node counts, nothing waits for the GPU."""
+        in_rows = self._frame_rows
+        out_rows = (in_rows + [int(v) for v in sizes])[-(self.max_gap + 1):]
+        c_in, c_out = (C.c_int32 * max(len(in_rows), 1))(*in_rows), (C.c_int32 * len(out_rows))(*out_rows)
+        state = torch.empty(lib.gnncca_link_gap_state_bytes(sum(out_rows), len(out_rows), r), dtype=torch.uint8, device=dev)
+        tracks = torch.empty((2, n), dtype=torch.int64, device=dev)   # cluster_track | node_track
+        matched = torch.empty((2, n), dtype=torch.int32, device=dev)   # matched_prev | matched_gap
+        ws_bytes = lib.gnncca_link_gap_workspace_bytes(n, g, sum(in_rows))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        st = lib.gnncca_link_frames_gap(s.node_ptr_dev.data_ptr(), s.count.data_ptr(), s.rank.data_ptr() if n else None,
+                                        s.pos.data_ptr() if n else None, s.emb.data_ptr() if r and n else None, r, n, g, max_n, self.max_step,
+                                        self.lam, int(self.max_cos is not None), self.max_cos if self.max_cos is not None else 0.0,
+                                        self.max_gap, self._state.data_ptr() if in_rows else None, c_in, len(in_rows), state.data_ptr(), c_out,
+                                        len(out_rows), tracks[0].data_ptr() if n else None, tracks[1].data_ptr() if n else None,
+                                        matched[0].data_ptr() if n else None, matched[1].data_ptr() if n else None, ws.data_ptr(), ws_bytes,
+                                        _raw_stream(dev))
+        if st:
+            nat.check(st, "gnncca_link_frames_gap")
+        # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
+        self._state, self._frame_rows = state, out_rows
+        return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1])
 
-__all__ = ["MAX_FRAME_NODES", "ClusterSummaries", "Tracks", "cluster_summaries", "cluster_summaries_raw", "FrameLinker"]
+
+__all__ = ["MAX_FRAME_NODES", "MAX_GAP", "ClusterSummaries", "Tracks", "cluster_summaries", "cluster_summaries_raw", "FrameLinker"]

@@ -709,8 +709,8 @@ GNNCCA_API int gnncca_eval_frames_dense(const int64_t* edge_index, const float* 
  * (an int64 at offset 0), gnncca_link_state_bytes(capacity, reid_dim) bytes for a capacity of at least the last frame's node count
  * (it bounds the cluster count; a frame with more clusters than state_out_capacity is carried as empty).  state_in must have been
  * written with the same reid_dim and its own capacity (<= GNNCCA_TRACK_MAX_FRAME_NODES); it is not modified.  n_frames = 0 launches
- * nothing and writes nothing.  Out of scope: re-identification after a frame in which a track was not seen, optimal assignment, time
- * stamps.  Workspace: gnncca_link_workspace_bytes. */
+ * nothing and writes nothing.  Out of scope: re-identification after a frame in which a track was not seen (gnncca_link_frames_gap
+ * below does that), optimal assignment, time stamps.  Workspace: gnncca_link_workspace_bytes. */
 #define GNNCCA_TRACK_MAX_FRAME_NODES 4096
 GNNCCA_API size_t gnncca_cluster_summaries_bytes(int64_t n_nodes, int64_t n_frames);
 GNNCCA_API int gnncca_cluster_summaries(const int32_t* labels, const int32_t* node_ptr_dev, const double* xw, const double* yw,
@@ -726,6 +726,43 @@ GNNCCA_API int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* co
                                   int64_t state_in_capacity, void* state_out, int64_t state_out_capacity, int64_t* cluster_track,
                                   int64_t* node_track, int32_t* matched_prev, void* workspace, size_t workspace_bytes,
                                   gnncca_stream_t stream);
+
+/* gnncca_link_frames_gap: gnncca_link_frames that carries a track across up to max_gap frames that miss it (0 <= max_gap <=
+ * GNNCCA_TRACK_MAX_GAP; max_gap = 0 gives gnncca_link_frames' ids).  Time is the frame index over all calls since the state was NULL; a
+ * frame without usable clusters (empty, count -1, a node range outside [0, N]) still counts as a frame; n_frames = 0 passes no time,
+ * launches nothing and writes nothing.  Every cluster has a predecessor (none at first) and a has-a-successor flag (clear at first).
+ * Levels k = 0 .. max_gap run one after the other, within a level all frames t in parallel:  A = the clusters of frame t without a
+ * predecessor, B = the clusters of frame t - 1 - k (of this batch or of state_in; no such frame: nothing to do) without a successor;
+ * d and dcos as above;  gate_k = max_step * (k + 1), one fp64 multiplication;  admissible iff d <= gate_k and (with has_max_cos) dcos <=
+ * max_cos;  cost = d / gate_k + lam * dcos;  fwd / bwd / ties as above over A x B, ties to the smaller rank within the frame;  a continues
+ * b iff each is the other's best: then a's predecessor is (frame t - 1 - k, b) and b's flag is set.  Level 0 is gnncca_link_frames' rule
+ * with nothing masked; a shorter gap always wins over a longer one; a frame's links depend on earlier frames only, so the result does not
+ * depend on how a sequence is cut into calls.  After the last level a cluster with a predecessor takes its id, the others get next_id,
+ * next_id + 1, ... in ascending (frame, rank) order.  Outputs as above, where matched_prev is the predecessor's rank in ITS OWN frame,
+ * plus matched_gap int32 [N]: the k of the level that found it (frames skipped), -1 without a predecessor.
+ * The state holds the last min(max_gap + 1, frames seen) frames, oldest first:  a 64-byte header { int64 next_id (offset 0); int32
+ * n_frames; int32 reid_dim; int32 count[GNNCCA_TRACK_MAX_GAP + 1]; padding },  then for C rows in all  pos fp64 [C][2], track int64 [C],
+ * emb fp32 [C][R], succ int32 [C] (the final flags),  R = reid_dim if the rule reads embeddings, else 0.  Frame f owns the rows from the sum
+ * of the capacities before it; the capacities are HOST arrays (state_in_frame_rows [state_in_frames], state_out_frame_rows
+ * [state_out_frames]: per frame at least its node count, which bounds its cluster count, at most GNNCCA_TRACK_MAX_FRAME_NODES) passed to the
+ * kernels by value: nothing is read back.  state_out_frames must be min(max_gap + 1, state_in_frames + n_frames); its newest frames are
+ * the batch's, the older ones the newest of state_in copied along with the capacities they had there or larger.  state_in (NULL with
+ * state_in_frames = 0: nothing seen yet, ids start at 0) must have been written by this entry with the same rule and reid_dim and at most
+ * max_gap + 1 frames; it is not modified.  state_out: gnncca_link_gap_state_bytes(C, n_frames_kept, R) bytes.  GNNCCA_ERR_INVALID_ARG:
+ * max_gap outside [0, GNNCCA_TRACK_MAX_GAP], a frame capacity above GNNCCA_TRACK_MAX_FRAME_NODES, the checks of gnncca_link_frames.
+ * max_gap + 4 launches; deterministic (integer flags, fixed sum orders, no atomics), no host wait, no allocation: capturable.
+ * Out of scope: motion prediction (a velocity term), optimal assignment, time stamps.
+ * Workspace: gnncca_link_gap_workspace_bytes(n_nodes, n_frames, state_rows = the sum of state_in_frame_rows). */
+#define GNNCCA_TRACK_MAX_GAP 8
+GNNCCA_API size_t gnncca_link_gap_state_bytes(int64_t capacity_rows, int32_t n_frames_kept, int32_t reid_dim);
+GNNCCA_API size_t gnncca_link_gap_workspace_bytes(int64_t n_nodes, int64_t n_frames, int64_t state_rows);
+GNNCCA_API int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
+                                      const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                      double max_step, double lam, int32_t has_max_cos, double max_cos, int32_t max_gap,
+                                      const void* state_in, const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                                      const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track,
+                                      int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, void* workspace,
+                                      size_t workspace_bytes, gnncca_stream_t stream);
 
 /* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
  * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).

@@ -2,7 +2,7 @@
 """Times gnn_cca_amd.tracking on a Terrace-shaped batch: cluster summaries plus frame linking for 64 frames of 4 cameras x 8 detections
 (N = 2048, every person seen once per camera: 8 clusters of 4 per frame) with R = 2048 appearance columns.  Needs an MI355X.
 
-    python tools/time_tracking.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3]
+    python tools/time_tracking.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3] [--max-gap 0] [--hide 0]
 
 Two ways to the same result, timed in alternating rounds in one process (host clock around work that ends in a device synchronise):
   device   cluster summaries (2 launches) + FrameLinker (3 launches) on tensors that are already on the GPU, as a FramePipeline
@@ -10,7 +10,9 @@ Two ways to the same result, timed in alternating rounds in one process (host cl
   host     labels, positions, cameras and embeddings copied back (the copies and their synchronisation included), then the numpy
            restatement of the rules (tests/tracking_oracle.py: plain loops for the sums, float64 matching)
 and, as the floor under ANY host implementation, `copy`: those device-to-host copies and their synchronisation alone.
-The two results are compared once (summaries bit for bit, ids exactly).  Prints one JSON line."""
+The two results are compared once (summaries bit for bit, ids exactly).  Prints one JSON line.
+--max-gap M > 0 times FrameLinker(max_gap=M) (M + 4 launches instead of 3; --hide P then hides each person's cluster with probability P per
+frame, so that there is something to find again) against the numpy restatement of ITS rule (tests/tracking_gap_oracle.py)."""
 import argparse
 import json
 import os
@@ -23,11 +25,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import tracking_gap_oracle as tg  # noqa: E402
 import tracking_oracle as to  # noqa: E402
 from gnn_cca_amd.tracking import FrameLinker, cluster_summaries_raw  # noqa: E402
 
 
-def make_batch(frames, cams, per, reid, seed=0):
+def make_batch(frames, cams, per, reid, seed=0, hide=0.0):
     rng = np.random.default_rng(seed)
     n_g = cams * per
     n = frames * n_g
@@ -42,6 +45,12 @@ def make_batch(frames, cams, per, reid, seed=0):
     emb /= np.linalg.norm(emb, axis=1, keepdims=True)
     # a person's detections are one cluster; its label is the smallest node id (the person's detection on camera 0)
     labels = (frame_of * n_g + person).astype(np.int32)
+    if hide > 0:   # a hidden person: its detections stay in the batch as clusters of their own, far away from everybody
+        gone = rng.random((frames, per)) < hide
+        gone[0] = False
+        out = gone[frame_of, person]
+        labels[out] = np.arange(n, dtype=np.int32)[out]
+        xw[out] += 1000.0 + 50.0 * np.arange(n)[out]
     node_ptr = (np.arange(frames + 1) * n_g).astype(np.int64)
     return dict(labels=labels, node_ptr=node_ptr, xw=xw, yw=yw, cam=cam, emb=emb.astype(np.float32), n=n)
 
@@ -55,15 +64,17 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--max-gap", type=int, default=0)
+    ap.add_argument("--hide", type=float, default=0.0)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_tracking.py measures on the GPU; no device is visible")
-    b = make_batch(a.frames, a.cams, a.per, a.reid)
+    b = make_batch(a.frames, a.cams, a.per, a.reid, hide=a.hide)
     dev = torch.device("cuda")
     d = {k: torch.from_numpy(b[k]).to(dev) for k in ("labels", "xw", "yw", "cam", "emb")}
     ptr_host = b["node_ptr"].tolist()
     max_step, lam = 1.0, 1.0
-    link = FrameLinker(max_step, lam=lam)
+    link = FrameLinker(max_step, lam=lam, max_gap=a.max_gap)
 
     def device_once():
         s = cluster_summaries_raw(d["labels"], ptr_host, d["xw"], d["yw"], d["cam"], d["emb"])
@@ -76,6 +87,8 @@ def main():
     def host_once(state):
         labels, xw, yw, cam, emb = copy_once()
         s = to.summaries(labels, b["node_ptr"], xw, yw, cam, emb)
+        if a.max_gap > 0:
+            return s, tg.link_gap(s, b["node_ptr"], max_step, lam, None, a.max_gap, state)
         return s, to.link(s, b["node_ptr"], max_step, lam, None, state)
 
     # one comparison of the two results, from a fresh state
@@ -84,6 +97,9 @@ def main():
     torch.cuda.synchronize()
     same = all(np.array_equal(getattr(s_dev, k).cpu().numpy(), s_host[k]) for k in ("count", "rank", "size", "n_cams", "pos", "emb"))
     same_ids = all(np.array_equal(getattr(t_dev, k).cpu().numpy(), t_host[k]) for k in ("cluster_track", "node_track", "matched_prev"))
+    gaps = t_dev.matched_gap.cpu().numpy()
+    if a.max_gap > 0:
+        same_ids = same_ids and np.array_equal(gaps, t_host["matched_gap"])
     for _ in range(10):   # warm-up: code objects, allocator
         device_once()
     torch.cuda.synchronize()
@@ -105,7 +121,8 @@ def main():
     print(json.dumps({"frames": a.frames, "cams": a.cams, "per_cam": a.per, "n_nodes": b["n"], "reid_dim": a.reid, "reps": a.reps,
                       "host_reps": a.host_reps, "device_ms": [round(v, 4) for v in dev_ms], "host_ms": [round(v, 2) for v in host_ms],
                       "copy_ms": [round(v, 4) for v in copy_ms], "summaries_equal": bool(same), "ids_equal": bool(same_ids),
-                      "tracks": int(t_dev.next_id.item())}))
+                      "tracks": int(t_dev.next_id.item()), "max_gap": a.max_gap, "hide": a.hide,
+                      "matches_per_gap": [int((gaps == k).sum()) for k in range(a.max_gap + 1)]}))
 
 
 if __name__ == "__main__":
