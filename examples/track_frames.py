@@ -8,8 +8,9 @@ print.  The reference has no counterpart of this stage: it scores single frames 
 Persons walk on the ground plane; every camera sees every person, with noise on the position.  The model has random weights, so its
 clusters mean nothing: the ids are shown for the model's partition AND for the ground-truth partition of the same detections, where a
 person keeps one id as long as the walk stays inside max_step.  In the middle frame of every batch person 0 is hidden from every camera:
-the linker with max_gap=1 finds them again one frame later under the same id, the linker without max_gap hands out a new one.  What
-linking does to tracking quality with a trained model has not been measured.
+the linker with max_gap=1 finds them again one frame later under the same id, the linker without max_gap hands out a new one.  Two
+TrackScorers accumulate, on the device, the identity scores of both linkers against the person ids; their result() is the last thing
+printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
 """
 import argparse
 import os
@@ -22,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
 from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
-from gnn_cca_amd.tracking import FrameLinker, cluster_summaries  # noqa: E402
+from gnn_cca_amd.tracking import FrameLinker, TrackScorer, cluster_summaries  # noqa: E402
 
 
 def main():
@@ -38,6 +39,7 @@ def main():
     pipe = FramePipeline(model)
     by_model, by_truth = FrameLinker(max_step=1.0, lam=1.0), FrameLinker(max_step=1.0, lam=1.0)
     by_truth_gap = FrameLinker(max_step=1.0, lam=1.0, max_gap=1)   # a track survives one frame that misses it
+    score, score_gap = TrackScorer(max_ids=a.persons, max_cams=a.cams), TrackScorer(max_ids=a.persons, max_cams=a.cams)
     where = rng.uniform(-8, 8, size=(a.persons, 2))
     look = rng.standard_normal((a.persons, 256)).astype(np.float32)
     id_cam = np.tile(np.repeat(np.arange(a.cams), a.persons), a.frames)
@@ -65,6 +67,8 @@ def main():
         st = cluster_summaries(r.batch, truth)   # any partition of the batch's detections can be summarised
         tt = by_truth(st)
         tg = by_truth_gap(st)                    # tg.matched_gap: 1 where a cluster continues one that was last seen two frames ago
+        score.add(r, tt)                         # ids (batch.y), cameras and node tracks joined over time: nothing waits for the GPU
+        score_gap.add(r, tg)
         # ---- only the printing below waits for the GPU ----
         last = slice(r.batch.node_ptr[-2], r.batch.node_ptr[-1])
         k_model, k_truth = int(s.count[-1].item()), int(st.count[-1].item())
@@ -79,6 +83,9 @@ def main():
                   f"{int(tg.cluster_track[before])} -> {int(tg.cluster_track[after])} with max_gap=1 "
                   f"(matched_gap {int(tg.matched_gap[after])}); tracks so far {int(tt.next_id.item())} against {int(tg.next_id.item())}")
     print("random weights: the model's clusters are meaningless, the plumbing is what is shown; on the true partition a person keeps its id")
+    for name, sc in (("without max_gap", score), ("with max_gap=1", score_gap)):   # result(): the one synchronisation of a scorer
+        res = sc.result()
+        print(f"true partition {name}: " + ", ".join(f"{q} {v:.3f}" if isinstance(v, float) else f"{q} {v}" for q, v in res.items()))
 
 
 if __name__ == "__main__":

@@ -22,6 +22,8 @@
 //      workgroup writes the new state.
 // Gap-tolerant linking (gnncca_link_frames_gap: a track survives up to max_gap frames that miss it) is identities_gap.cuh, included at the
 // end of this file: its own kernels and state layout, the scan kernel shared.
+// Scoring the track ids against ground-truth person ids over a sequence (gnncca_track_score_*) is track_score.cuh, included after it:
+// integer kernels of its own, nothing shared but this translation unit.
 // Deterministic: every fp sum has a fixed order, integer counts go through LDS atomics, no fp64 atomics.  No host wait, no allocation:
 // capturable.  The file is compiled without fp contraction: the sums, the divisions and the cost are the documented operations one by one.
 #include <hip/hip_runtime.h>
@@ -530,3 +532,5 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
 }  // extern "C"
 
 #include "identities_gap.cuh"   // gnncca_link_frames_gap: the gap-tolerant linker (its own kernels; nothing above changes)
+
+#include "track_score.cuh"   // gnncca_track_score_*: identity-tracking scores over a sequence (its own kernels; nothing above changes)

@@ -8,9 +8,14 @@ over the frames of a batch and from one batch to the next.
     t = link(r)                                   # Tracks: cluster_track [N], node_track [N], matched_prev [N], next_id [1]
     t = link(next_r)                              # ... frame 0 of this batch continues the last frame of the previous one
     link = FrameLinker(max_step=0.8, max_gap=2)   # a track survives up to 2 frames that miss it; t.matched_gap [N]: frames skipped
+    score = TrackScorer(max_ids=1024, max_cams=8) # identity-tracking scores against the caller's person ids, accumulated on the device
+    score.add(r, t).switched                      # int32 [N]: -1 not scored, 0, 1 = this detection is an identity switch
+    score.result()                                # IDSW, IDTP, IDF1, AssA, purity, coverage, MT / PT / ML ...: ONE synchronisation
 
 The reference has NO counterpart: it scores single frames (inference.py:349-371), never fuses the views of a cluster into a position and
-never carries an identity from one frame to the next.  What these rules do to tracking quality with a trained model has NOT been measured.
+never carries an identity from one frame to the next.  What these rules do to tracking quality CAN now be measured wherever ground-truth
+person ids exist (TrackScorer; DESIGN.md section 9 has a table on synthetic sequences with ground-truth clusters); with a trained model it
+still has NOT been measured.
 
 Summaries (csrc/identities.hip, two launches).  `labels` is int32 [N] in the convention of postprocess.prune_and_cluster / finalize: a
 node's label is the smallest node id of its cluster.  Nothing is compacted across frames, so every output has a fixed shape: cluster c of
@@ -35,6 +40,15 @@ passes no time.  The rule is causal, so the ids do not depend on how a sequence 
 Limits: frames are taken to be CONSECUTIVE and IN ORDER (there are no time stamps); a track unseen for more than max_gap frames ends (with
 the default max_gap = 0: in the first frame that misses it); a cluster is looked for where it was last seen -- there is no motion
 prediction (no velocity term), only a gate that grows with the gap; the matching is mutual-best, not an optimal assignment.
+Scores (csrc/track_score.cuh; per call one memset and two launches).  TrackScorer joins ids (batch.y), cam and Tracks.node_track over time.
+Detection i is VALID iff 0 <= ids[i] < max_ids, 0 <= cam[i] < max_cams and 0 <= node_track[i] < 2**40; it is SCORED iff it is valid and no
+valid detection j > i of its frame has the same (id, cam) (the largest node id wins a duplicate); every other detection is IGNORED (a
+negative id says "no ground truth"; the -1 tracks of a refused frame are not scored).  A stream is a (person, camera) pair -- the
+per-camera trajectories of the reference's gt.txt files.  A scored detection with track t is a SWITCH iff the latest earlier scored
+detection of its stream, however many frames or calls back, had another track; IDSW counts them.  n[p][t] counts the scored detections of
+person p (over all cameras) with track t; result() derives IDTP / IDF1, AssA, purity, coverage and MT / PT / ML from it on the host, in a
+fixed order (tests/track_score_oracle.py restates all of it as loops and the device path equals it exactly).  The rule is causal: the
+scores do not depend on how a sequence is cut into calls.
 No CPU fallback."""
 import ctypes as C
 import math
@@ -171,8 +185,9 @@ class FrameLinker:
     max_step * (k + 1) after k missed frames; a shorter gap always wins).  0: the adjacent-frame linker, three launches, as ever; M > 0:
     M + 4 launches, and the state holds the last M + 1 frames (sized from their node counts, which the linker keeps on the host).
     Frames are taken to be consecutive and in order (no time stamps); a track missing from more than max_gap frames ends; there is no
-    motion prediction (no velocity term) and the matching is mutual-best, not an optimal assignment.  No counterpart in the reference; the
-    effect on tracking quality with a trained model has not been measured."""
+    motion prediction (no velocity term) and the matching is mutual-best, not an optimal assignment.  No counterpart in the reference; what
+    max_step, lam, max_cos and max_gap do to tracking quality can be measured with TrackScorer wherever person ids exist; with a trained model
+    it has not been."""
 
     def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0):
         def real(v):
@@ -264,4 +279,181 @@ class FrameLinker:
         return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1])
 
 
-__all__ = ["MAX_FRAME_NODES", "MAX_GAP", "ClusterSummaries", "Tracks", "cluster_summaries", "cluster_summaries_raw", "FrameLinker"]
+class TrackScores:
+    """What one TrackScorer.add returns: switched int32 [N] on the device -- -1: the detection is not scored, 0, 1: it is an identity
+    switch (its stream's latest earlier scored detection had another track)."""
+    __slots__ = ("switched",)
+
+    def __init__(self, switched):
+        self.switched = switched
+
+
+_TRACK_BITS = 40
+
+
+def _scores_of(cells, ignored, idsw):
+    """result() from the integer state: cells = the non-zero (p, t, n) of the pair table in ascending (p, t), Python ints throughout."""
+    from scipy.optimize import linear_sum_assignment
+    total = sum(c[2] for c in cells)
+    if total == 0:
+        raise ValueError("TrackScorer.result: no detection was scored")
+    row, col, best_of_p, best_of_t = {}, {}, {}, {}
+    for p, t, n in cells:
+        row[p], col[t] = row.get(p, 0) + n, col.get(t, 0) + n
+        best_of_p[p], best_of_t[t] = max(best_of_p.get(p, 0), n), max(best_of_t.get(t, 0), n)
+    pi, ti = {p: i for i, p in enumerate(sorted(row))}, {t: i for i, t in enumerate(sorted(col))}
+    dense = np.zeros((len(pi), len(ti)), np.int64)
+    for p, t, n in cells:
+        dense[pi[p], ti[t]] = n
+    rr, cc = linear_sum_assignment(dense, maximize=True)   # the assignment may not be unique, its total is
+    idtp = int(dense[rr, cc].sum())
+    assa = math.fsum(n * n / (row[p] + col[t] - n) for p, t, n in cells) / total
+    mt = sum(1 for p in row if best_of_p[p] / row[p] >= 0.8)
+    ml = sum(1 for p in row if best_of_p[p] / row[p] <= 0.2)
+    return {"detections": total, "ignored": ignored, "ids": len(row), "tracks": len(col), "pairs": len(cells), "IDSW": idsw, "IDTP": idtp,
+            "IDF1": idtp / total, "AssA": assa, "purity": sum(best_of_t.values()) / total, "coverage": sum(best_of_p.values()) / total,
+            "MT": mt, "PT": len(row) - mt - ml, "ML": ml, "tracks_per_id": len(cells) / len(row)}
+
+
+class TrackScorer:
+    """Identity-tracking scores of track ids against the caller's person ids, accumulated over the frames of a sequence on the device (the
+    module docstring has the rule).  `add(x, tracks)` takes x, a pipeline.FrameResult or a GraphBatch of build_graph_batch / FramePipeline
+    (ids = batch.y, cam and the frame offsets from the batch), and the Tracks a FrameLinker made of it; `add_raw` plain device tensors.
+    Both enqueue on the current stream, never wait for the GPU and return a TrackScores (switched int32 [N]).  `counts` is an int64 [4]
+    device view of scored, ignored, switches, pairs (the non-zero cells of n[person][track]), cumulative since reset() (zeros on the host
+    before the first add).  `result()` copies the state back ONCE and returns a dict:
+      detections (N, the scored ones), ignored, ids / tracks (persons / tracks with a scored detection), pairs, IDSW;
+      IDTP  the largest total of n over one-to-one assignments of persons to tracks (scipy's linear_sum_assignment on the dense matrix);
+      IDF1 = IDTP / N.  Every ground-truth detection is also a hypothesis detection here, so IDP = IDR = IDF1;
+      AssA = fsum(n * n / (row[p] + col[t] - n) over the cells in ascending (p, t)) / N: HOTA's association accuracy at perfect detection;
+      purity = sum_t max_p n / N, coverage = sum_p max_t n / N;
+      MT, PT, ML  persons with max_t n[p][t] / row[p] >= 0.8, in between, <= 0.2 (on identity coverage: detection is perfect here);
+      tracks_per_id = pairs / ids.
+    ValueError if nothing was scored.  The state is sized from numbers the host knows: last [max_ids * max_cams] and a hash table of `cap`
+    cells, cap >= 2 x the detections passed so far (they bound the pairs) and >= 1024; a call that needs more allocates the next power of
+    two and one launch re-inserts the old cells.  A batch whose slot image [G][max_ids * max_cams] exceeds 2**22 entries is cut into runs
+    of frames (the rule is causal).  Frames have no size limit here.  No counterpart in the reference."""
+
+    def __init__(self, max_ids=1024, max_cams=8):
+        def integer(v):
+            return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+        if not integer(max_ids) or not 1 <= max_ids <= nat.SCORE_MAX_IDS:
+            raise ValueError(f"max_ids must be an integer in [1, {nat.SCORE_MAX_IDS}], not {max_ids!r}")
+        if not integer(max_cams) or not 1 <= max_cams <= nat.SCORE_MAX_CAMS:
+            raise ValueError(f"max_cams must be an integer in [1, {nat.SCORE_MAX_CAMS}], not {max_cams!r}")
+        if max_ids * max_cams > nat.SCORE_MAX_STREAMS:
+            raise ValueError(f"max_ids * max_cams = {max_ids * max_cams} streams; TrackScorer takes at most {nat.SCORE_MAX_STREAMS}")
+        self.max_ids, self.max_cams, self.n_streams = int(max_ids), int(max_cams), int(max_ids) * int(max_cams)
+        self.reset()
+
+    def reset(self):
+        """Forget everything scored so far."""
+        self._table, self._last, self._cap, self._seen = None, None, 0, 0
+
+    @property
+    def cap(self):
+        """The cells of the pair table as it stands (0 before the first add)."""
+        return self._cap
+
+    @property
+    def counts(self):
+        return self._table[:4] if self._table is not None else torch.zeros(4, dtype=torch.int64)
+
+    def _grow(self, lib, dev, n):
+        """The state for n more detections (inside _on(dev)): first use, or a table of the next sufficient power of two."""
+        need = nat.SCORE_MIN_CAP
+        while need < 2 * (self._seen + n):
+            need *= 2
+        if self._table is not None and self._table.device != dev:
+            raise ValueError(f"the scorer's state is on {self._table.device}, the batch on {dev}: reset() it first")
+        if self._table is not None and need <= self._cap:
+            return
+        table = torch.empty(nat.SCORE_HEADER_LEN + 2 * need, dtype=torch.int64, device=dev)
+        if self._table is None:
+            self._last = torch.empty(self.n_streams, dtype=torch.int64, device=dev)
+            st = lib.gnncca_track_score_reset(table.data_ptr(), need, self._last.data_ptr(), self.n_streams, _raw_stream(dev))
+        else:   # (the old table is freed in stream order: the launch above it still reads it)
+            st = lib.gnncca_track_score_rehash(self._table.data_ptr(), self._cap, table.data_ptr(), need, _raw_stream(dev))
+        if st:
+            nat.check(st, "gnncca_track_score_reset / rehash")
+        self._table, self._cap = table, need
+
+    def add_raw(self, ids, cam, node_track, node_ptr, node_ptr_dev=None):
+        """ids int64 [N], cam int32 [N], node_track int64 [N] on the device; node_ptr: the G + 1 frame offsets as a HOST sequence (uploaded
+        here unless node_ptr_dev, its int32 device copy, is given).  Enqueued on the current stream -> TrackScores."""
+        ptr = _host_ptr(node_ptr)
+        g = len(ptr) - 1
+        for name, t, dt in (("ids", ids, torch.int64), ("cam", cam, torch.int32), ("node_track", node_track, torch.int64)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1:
+                raise ValueError(f"{name} must be a 1-D {dt} tensor")
+        n = int(ids.numel())
+        if cam.numel() != n or node_track.numel() != n or int(ptr[0]) != 0 or int(ptr[-1]) != n or (g > 0 and int(np.diff(ptr).min()) < 0):
+            raise ValueError(f"ids [{n}], cam [{cam.numel()}], node_track [{node_track.numel()}] and node_ptr ({ptr[0]} .. {ptr[-1]}) disagree")
+        if n >= 2 ** 31 - 256:
+            raise ValueError(f"{n} detections in one call; TrackScorer takes fewer than 2**31")
+        if node_ptr_dev is not None and (node_ptr_dev.dtype != torch.int32 or node_ptr_dev.numel() != g + 1):
+            raise ValueError(f"node_ptr_dev must be int32 [{g + 1}]")
+        if not (ids.is_cuda and cam.is_cuda and node_track.is_cuda):
+            raise RuntimeError("gnn_cca_amd.tracking runs on MI355X only (no CPU fallback)")
+        dev = ids.device
+        lib = nat.lib()
+        with _on(dev):
+            switched = torch.empty(n, dtype=torch.int32, device=dev)
+            if g == 0:   # no time passes (and the state holds no time anyway)
+                return TrackScores(switched)
+            self._grow(lib, dev, n)
+            if n:
+                ids, cam, node_track = ids.contiguous(), cam.contiguous(), node_track.contiguous()
+                nptr = (node_ptr_dev if node_ptr_dev is not None else torch.from_numpy(ptr.astype(np.int32))).to(device=dev).contiguous()
+                per_run = nat.SCORE_MAX_SLOTS // self.n_streams   # frames per native call: its slot image holds at most 2**22 entries
+                slot = torch.empty(min(g, per_run) * self.n_streams, dtype=torch.int32, device=dev)
+                for f0 in range(0, g, per_run):
+                    f1 = min(g, f0 + per_run)
+                    v0, v1 = int(ptr[f0]), int(ptr[f1])
+                    if v1 == v0:
+                        continue
+                    st = lib.gnncca_track_score_add(ids.data_ptr() + 8 * v0, cam.data_ptr() + 4 * v0, node_track.data_ptr() + 8 * v0,
+                                                    nptr.data_ptr() + 4 * f0, v0, v1 - v0, f1 - f0, self.max_ids, self.max_cams,
+                                                    self._table.data_ptr(), self._cap, self._last.data_ptr(), slot.data_ptr(),
+                                                    switched.data_ptr() + 4 * v0, _raw_stream(dev))
+                    if st:
+                        nat.check(st, "gnncca_track_score_add")
+                # the slot image is freed in stream order (allocated on this stream): the launches above still use it
+                self._seen += n
+        return TrackScores(switched)
+
+    def add(self, x, tracks):
+        """x: a pipeline.FrameResult or a GraphBatch (ids = batch.y, cam from its staging image, frame offsets batch.node_ptr / node_ptr_dev);
+        tracks: the Tracks a FrameLinker returned for it.  Enqueued on the current stream, no synchronisation -> TrackScores."""
+        batch = getattr(x, "batch", x)
+        frames = getattr(batch, "_frames", None)
+        if frames is None:
+            raise ValueError("TrackScorer.add needs a FrameResult or a batch of build_graph_batch / FramePipeline (its staging image holds the "
+                             "cameras); use add_raw for plain tensors")
+        if not isinstance(tracks, Tracks):
+            raise ValueError("TrackScorer.add takes the Tracks of a FrameLinker")
+        image, layout = frames
+        return self.add_raw(batch.y, layout.view(image, "cam"), tracks.node_track, batch.node_ptr, node_ptr_dev=batch.node_ptr_dev)
+
+    def result(self):
+        """The scores so far as a dict (the class docstring has the keys): ONE copy of the state, one synchronisation, then integer work on
+        the host in a fixed order.  ValueError if nothing was scored; RuntimeError if the pair table overflowed (a sizing bug: it cannot)."""
+        if self._table is None:
+            raise ValueError("TrackScorer.result: no detection was scored")
+        host = self._table.cpu().numpy()   # the one synchronisation
+        scored, ignored, switches, pairs, overflow = (int(v) for v in host[:5])
+        if overflow:
+            raise RuntimeError("TrackScorer: the pair table overflowed and dropped counts (its capacity was sized wrongly)")
+        keys = host[nat.SCORE_HEADER_LEN:nat.SCORE_HEADER_LEN + self._cap].view(np.uint64)
+        cnt = host[nat.SCORE_HEADER_LEN + self._cap:]
+        used = np.flatnonzero(keys != np.uint64(2 ** 64 - 1))
+        used = used[np.argsort(keys[used], kind="stable")]   # ascending key = ascending (p, t); the keys are distinct
+        cells = [(int(k) >> _TRACK_BITS, int(k) & (2 ** _TRACK_BITS - 1), int(c)) for k, c in zip(keys[used].tolist(), cnt[used].tolist())]
+        if len(cells) != pairs or sum(c[2] for c in cells) != scored:
+            raise RuntimeError(f"TrackScorer: the pair table ({len(cells)} cells, {sum(c[2] for c in cells)} detections) and the counters "
+                               f"({pairs}, {scored}) disagree")
+        return _scores_of(cells, ignored, switches)
+
+
+__all__ = ["MAX_FRAME_NODES", "MAX_GAP", "ClusterSummaries", "Tracks", "cluster_summaries", "cluster_summaries_raw", "FrameLinker", "TrackScorer",
+           "TrackScores"]

@@ -764,6 +764,44 @@ GNNCCA_API int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t
                                       int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, void* workspace,
                                       size_t workspace_bytes, gnncca_stream_t stream);
 
+/* ---- Identity-tracking scores over a sequence (csrc/track_score.cuh, included by csrc/identities.hip) --------------------------------
+ * Joins ids int64 [N] (the caller's person id of every detection), cam int32 [N] and node_track int64 [N] (gnncca_link_frames*) over the
+ * frames of a sequence, on the device and without a host wait.  No counterpart in the reference.  The rule:
+ *   detection i is VALID iff 0 <= ids[i] < max_ids, 0 <= cam[i] < max_cams and 0 <= node_track[i] < 2^40;  it is SCORED iff it is valid
+ *   and no valid detection j > i of its frame has the same (id, cam) -- the largest node id wins a duplicate;  every other detection is
+ *   IGNORED (switched = -1).  A stream is a pair (person p, camera c), k = p * max_cams + c.  A scored detection with track t is a SWITCH
+ *   (switched = 1, else 0) iff the latest earlier scored detection of its stream, in this call or any earlier one since the reset and
+ *   however many frames back, had a track != t.  n[p][t] counts the scored detections of person p with track t.
+ * The rule is causal: the result does not depend on how a sequence is cut into calls; the state holds no time, so a call without frames
+ * or without detections changes nothing.
+ * State, all sized by the caller from numbers it knows on the host:  `table`, ONE int64 buffer [GNNCCA_SCORE_HEADER_LEN + 2 cap] =
+ * { scored, ignored, switches, pairs (non-zero cells of n), overflow, 3 unused | keys uint64 [cap] | counts int64 [cap] }, an
+ * open-addressing table with linear probing: cap a power of two >= GNNCCA_SCORE_MIN_CAP, key = p << 40 | t, all ones = empty;  `last`
+ * int64 [K = max_ids * max_cams], the last track of every stream, -1 for none.  gnncca_track_score_reset initialises both.  The caller
+ * keeps cap >= 2 x the detections passed since the reset (pairs <= detections): gnncca_track_score_rehash fills a larger table from a
+ * smaller one (table_out is overwritten, table_in is not modified; the counters carry over).  A probe gives up after cap steps, sets
+ * `overflow` and drops its run, so no size can make a kernel spin; with the sizing above it cannot happen.
+ * gnncca_track_score_add scores the n_frames frames whose offsets are node_ptr_dev[0 .. n_frames] - node_base (DEVICE int32; node_base is
+ * the HOST copy of node_ptr_dev[0], so a run of frames inside a larger batch is passed with shifted pointers); ids, cam, node_track and
+ * switched int32 [n_nodes] (output) start at the run's first detection.  `slot` is scratch: int32 [n_frames][K], at most
+ * GNNCCA_SCORE_MAX_SLOTS entries -- a larger batch is cut into runs of frames by the caller, which the rule's causality allows.  One memset
+ * and two launches; all atomics are integer and device scope, so every number is reproducible (only the cell a pair lands in is not).
+ * No allocation, no synchronisation: capturable.  GNNCCA_ERR_INVALID_ARG before any launch: max_ids outside [1, GNNCCA_SCORE_MAX_IDS],
+ * max_cams outside [1, GNNCCA_SCORE_MAX_CAMS], K above GNNCCA_SCORE_MAX_STREAMS, n_frames * K above GNNCCA_SCORE_MAX_SLOTS, n_nodes >=
+ * 2^31 - 256, a cap that is no power of two >= GNNCCA_SCORE_MIN_CAP, null pointers. */
+#define GNNCCA_SCORE_MAX_IDS 65536
+#define GNNCCA_SCORE_MAX_CAMS 64
+#define GNNCCA_SCORE_MAX_STREAMS 1048576
+#define GNNCCA_SCORE_MAX_SLOTS 4194304
+#define GNNCCA_SCORE_MIN_CAP 1024
+#define GNNCCA_SCORE_HEADER_LEN 8
+GNNCCA_API size_t gnncca_track_score_table_bytes(int64_t cap);
+GNNCCA_API int gnncca_track_score_reset(void* table, int64_t cap, int64_t* last, int64_t n_streams, gnncca_stream_t stream);
+GNNCCA_API int gnncca_track_score_rehash(const void* table_in, int64_t cap_in, void* table_out, int64_t cap_out, gnncca_stream_t stream);
+GNNCCA_API int gnncca_track_score_add(const int64_t* ids, const int32_t* cam, const int64_t* node_track, const int32_t* node_ptr_dev,
+                                      int64_t node_base, int64_t n_nodes, int32_t n_frames, int32_t max_ids, int32_t max_cams, void* table,
+                                      int64_t cap, int64_t* last, int32_t* slot, int32_t* switched, gnncca_stream_t stream);
+
 /* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
  * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).
  * criterion: GNNCCA_LOSS_BCE, GNNCCA_LOSS_BCE_WEIGHTED (pos_weight > 0) or GNNCCA_LOSS_FOCAL (utils.FocalLoss_binary: focusing_param,
