@@ -39,7 +39,9 @@ def main():
     pipe = FramePipeline(model)
     by_model, by_truth = FrameLinker(max_step=1.0, lam=1.0), FrameLinker(max_step=1.0, lam=1.0)
     by_truth_gap = FrameLinker(max_step=1.0, lam=1.0, max_gap=1)   # a track survives one frame that misses it
+    by_truth_opt = FrameLinker(max_step=1.0, lam=1.0, max_gap=1, matching="optimal")   # per frame pair the min-cost assignment, not mutual best
     score, score_gap = TrackScorer(max_ids=a.persons, max_cams=a.cams), TrackScorer(max_ids=a.persons, max_cams=a.cams)
+    score_opt = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     where = rng.uniform(-8, 8, size=(a.persons, 2))
     look = rng.standard_normal((a.persons, 256)).astype(np.float32)
     id_cam = np.tile(np.repeat(np.arange(a.cams), a.persons), a.frames)
@@ -69,6 +71,7 @@ def main():
         tg = by_truth_gap(st)                    # tg.matched_gap: 1 where a cluster continues one that was last seen two frames ago
         score.add(r, tt)                         # ids (batch.y), cameras and node tracks joined over time: nothing waits for the GPU
         score_gap.add(r, tg)
+        score_opt.add(r, by_truth_opt(st))
         # ---- only the printing below waits for the GPU ----
         last = slice(r.batch.node_ptr[-2], r.batch.node_ptr[-1])
         k_model, k_truth = int(s.count[-1].item()), int(st.count[-1].item())
@@ -83,7 +86,7 @@ def main():
                   f"{int(tg.cluster_track[before])} -> {int(tg.cluster_track[after])} with max_gap=1 "
                   f"(matched_gap {int(tg.matched_gap[after])}); tracks so far {int(tt.next_id.item())} against {int(tg.next_id.item())}")
     print("random weights: the model's clusters are meaningless, the plumbing is what is shown; on the true partition a person keeps its id")
-    for name, sc in (("without max_gap", score), ("with max_gap=1", score_gap)):   # result(): the one synchronisation of a scorer
+    for name, sc in (("without max_gap", score), ("with max_gap=1", score_gap), ("with max_gap=1, matching='optimal'", score_opt)):   # result(): the one synchronisation of a scorer
         res = sc.result()
         print(f"true partition {name}: " + ", ".join(f"{q} {v:.3f}" if isinstance(v, float) else f"{q} {v}" for q, v in res.items()))
 

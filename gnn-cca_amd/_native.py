@@ -14,6 +14,8 @@ GRAPH_UNSORTED, GRAPH_BAD_INDEX = 1, 2
 RANK_BY = {"ground": 0, "reid": 1}   # gnncca_build_edges_topk, gnncca_frames_forward_topk
 TOPK_MAX_DEG = 4096
 TRACK_MAX_GAP = 8                    # gnncca_link_frames_gap
+TRACK_MAX_OPTIMAL_FRAME_NODES = 128  # gnncca_link_frames_gap_ex with matching = 1: a frame pair's table lives in LDS
+MATCHING = {"mutual": 0, "optimal": 1}   # gnncca_link_frames_gap_ex
 SCORE_MAX_IDS, SCORE_MAX_CAMS, SCORE_MAX_STREAMS, SCORE_MAX_SLOTS = 65536, 64, 1 << 20, 1 << 22   # gnncca_track_score_add
 SCORE_MIN_CAP, SCORE_HEADER_LEN = 1024, 8
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
@@ -223,6 +225,10 @@ _SIGNATURES = {
                                          C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
                                          C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p]),
+    "gnncca_link_frames_gap_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                            C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_void_p,
+                                            C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnncca_track_score_table_bytes": (C.c_size_t, [C.c_int64]),
     "gnncca_track_score_reset": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gnncca_track_score_rehash": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

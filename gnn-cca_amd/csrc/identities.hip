@@ -21,7 +21,8 @@
 //      prefix of its frame + its rank among the unmatched; or a cluster of the carried state: its id), then node_track; the last frame's
 //      workgroup writes the new state.
 // Gap-tolerant linking (gnncca_link_frames_gap: a track survives up to max_gap frames that miss it) is identities_gap.cuh, included at the
-// end of this file: its own kernels and state layout, the scan kernel shared.
+// end of this file: its own kernels and state layout, the scan kernel shared.  Its level kernel has a second form that picks the pairs of a
+// frame pair by a min-cost assignment instead of mutual best (gnncca_link_frames_gap_ex, matching = 1): identities_assign.cuh, after it.
 // Scoring the track ids against ground-truth person ids over a sequence (gnncca_track_score_*) is track_score.cuh, included after it:
 // integer kernels of its own, nothing shared but this translation unit.
 // Deterministic: every fp sum has a fixed order, integer counts go through LDS atomics, no fp64 atomics.  No host wait, no allocation:
@@ -532,5 +533,7 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
 }  // extern "C"
 
 #include "identities_gap.cuh"   // gnncca_link_frames_gap: the gap-tolerant linker (its own kernels; nothing above changes)
+
+#include "identities_assign.cuh"   // gnncca_link_frames_gap_ex: the level kernel's min-cost-assignment form (matching = 1)
 
 #include "track_score.cuh"   // gnncca_track_score_*: identity-tracking scores over a sequence (its own kernels; nothing above changes)

@@ -24,6 +24,7 @@ namespace gnncca {
 
 constexpr int kTrackMaxGap = GNNCCA_TRACK_MAX_GAP;
 constexpr int kGapMaxFrames = kTrackMaxGap + 1;
+constexpr int kTrackMaxOptimalNodes = GNNCCA_TRACK_MAX_OPTIMAL_FRAME_NODES;   // matching = 1: a frame pair's table lives in LDS
 
 struct GapHeader {
     long long next_id;
@@ -317,13 +318,23 @@ size_t gnncca_link_gap_workspace_bytes(int64_t n_nodes, int64_t n_frames, int64_
     return gnncca::round256(((size_t)state_rows + 2 * (size_t)n_nodes + 2 * (size_t)n_frames + 1) * sizeof(int32_t));
 }
 
-int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
-                           int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
-                           int32_t has_max_cos, double max_cos, int32_t max_gap, const void* state_in, const int32_t* state_in_frame_rows,
-                           int32_t state_in_frames, void* state_out, const int32_t* state_out_frame_rows, int32_t state_out_frames,
-                           int64_t* cluster_track, int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, void* workspace,
-                           size_t workspace_bytes, gnncca_stream_t stream) {
-    using namespace gnncca;
+}  // extern "C"
+
+namespace gnncca {
+
+// the level launch of matching = 1 (identities_assign.cuh, included after this file)
+static int assign_level_launch(hipStream_t st, int n_frames, int P, const int* node_ptr_dev, int n_nodes, const int* count, const double* pos,
+                               const float* emb, int R, const LinkRule& level_rule, int level, int last_level, const char* sin,
+                               const GapFrames& in, int* succ_ws, int* matched_prev, int* matched_gap, int* new_rank_ws, int* n_new_ws,
+                               double miss_cost);
+
+// gnncca_link_frames_gap (matching 0) and gnncca_link_frames_gap_ex: one body, the form of the level kernel chosen by `matching`
+static int link_frames_gap_run(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
+                               int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
+                               int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t matching, double miss_cost, const void* state_in,
+                               const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                               const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track,
+                               int32_t* matched_prev, int32_t* matched_gap, void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
     if (n_nodes < 0 || n_frames < 0 || reid_dim < 0) return GNNCCA_ERR_INVALID_ARG;
     if (max_gap < 0 || max_gap > kTrackMaxGap) return GNNCCA_ERR_INVALID_ARG;
     if (max_frame_nodes < 0 || max_frame_nodes > kTrackMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
@@ -331,6 +342,11 @@ int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t* count, co
         return GNNCCA_ERR_INVALID_ARG;
     GapFrames in, out;
     if (!gap_frames(state_in_frame_rows, state_in ? state_in_frames : 0, in)) return GNNCCA_ERR_INVALID_ARG;   // a history frame above the limit
+    if (matching) {   // the table of a frame pair lives in LDS: before any launch, for the batch and for the carried history alike
+        if (max_frame_nodes > kTrackMaxOptimalNodes) return GNNCCA_ERR_INVALID_ARG;
+        for (int f = 0; f < in.n; ++f)
+            if (in.off[f + 1] - in.off[f] > kTrackMaxOptimalNodes) return GNNCCA_ERR_INVALID_ARG;
+    }
     if (!(max_step > 0.0) || !(max_step < __builtin_inf()) || !(lam >= 0.0) || !(lam < __builtin_inf())) return GNNCCA_ERR_INVALID_ARG;
     if (has_max_cos && !(max_cos >= 0.0 && max_cos <= 2.0)) return GNNCCA_ERR_INVALID_ARG;
     if (n_frames == 0) return GNNCCA_OK;   // no time passes: the caller keeps its state
@@ -366,6 +382,12 @@ int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t* count, co
     for (int k = 0; k <= max_gap; ++k) {
         LinkRule level_rule = rule;
         level_rule.max_step = max_step * (double)(k + 1);   // gate_k: one fp64 multiplication
+        if (matching) {
+            const int rc = assign_level_launch(st, (int)n_frames, P, node_ptr_dev, (int)n_nodes, count, pos, emb, R, level_rule, k, (int)(k == max_gap),
+                                               sin, in, succ_ws, matched_prev, matched_gap, new_rank_ws, n_new_ws, miss_cost);
+            if (rc != GNNCCA_OK) return rc;
+            continue;
+        }
         hipLaunchKernelGGL((gap_level_kernel<256>), dim3((unsigned)n_frames), dim3(256), (size_t)2 * P * sizeof(int), st, node_ptr_dev, (int)n_nodes,
                            count, pos, emb, R, level_rule, k, (int)(k == max_gap), sin, in, P, succ_ws, matched_prev, matched_gap, new_rank_ws,
                            n_new_ws);
@@ -380,6 +402,21 @@ int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t* count, co
                        reinterpret_cast<long long*>(node_track));
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
+}
+
+}  // namespace gnncca
+
+extern "C" {
+
+int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
+                           int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
+                           int32_t has_max_cos, double max_cos, int32_t max_gap, const void* state_in, const int32_t* state_in_frame_rows,
+                           int32_t state_in_frames, void* state_out, const int32_t* state_out_frame_rows, int32_t state_out_frames,
+                           int64_t* cluster_track, int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, void* workspace,
+                           size_t workspace_bytes, gnncca_stream_t stream) {
+    return gnncca::link_frames_gap_run(node_ptr_dev, count, rank, pos, emb, reid_dim, n_nodes, n_frames, max_frame_nodes, max_step, lam, has_max_cos,
+                                       max_cos, max_gap, 0, 0.0, state_in, state_in_frame_rows, state_in_frames, state_out, state_out_frame_rows,
+                                       state_out_frames, cluster_track, node_track, matched_prev, matched_gap, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

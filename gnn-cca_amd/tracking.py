@@ -8,6 +8,7 @@ over the frames of a batch and from one batch to the next.
     t = link(r)                                   # Tracks: cluster_track [N], node_track [N], matched_prev [N], next_id [1]
     t = link(next_r)                              # ... frame 0 of this batch continues the last frame of the previous one
     link = FrameLinker(max_step=0.8, max_gap=2)   # a track survives up to 2 frames that miss it; t.matched_gap [N]: frames skipped
+    link = FrameLinker(max_step=0.8, matching='optimal')   # per frame pair the min-cost assignment instead of mutual best
     score = TrackScorer(max_ids=1024, max_cams=8) # identity-tracking scores against the caller's person ids, accumulated on the device
     score.add(r, t).switched                      # int32 [N]: -1 not scored, 0, 1 = this detection is an identity switch
     score.result()                                # IDSW, IDTP, IDF1, AssA, purity, coverage, MT / PT / ML ...: ONE synchronisation
@@ -39,7 +40,19 @@ at higher cost.  Time is the frame index over all calls since reset(): an empty 
 passes no time.  The rule is causal, so the ids do not depend on how a sequence is cut into batches; the state holds the last M + 1 frames.
 Limits: frames are taken to be CONSECUTIVE and IN ORDER (there are no time stamps); a track unseen for more than max_gap frames ends (with
 the default max_gap = 0: in the first frame that misses it); a cluster is looked for where it was last seen -- there is no motion
-prediction (no velocity term), only a gate that grows with the gap; the matching is mutual-best, not an optimal assignment.
+prediction (no velocity term), only a gate that grows with the gap.
+Optimal matching (matching='optimal': csrc/identities_assign.cuh, the same M + 4 launches, also with max_gap = 0).  Mutual best leaves a
+cluster unlinked whenever its best partner prefers somebody else, even when a second admissible partner is free.  In this mode the levels,
+gates, masks and cost stay as above and only the choice of pairs inside a (level, frame pair) table changes: with A the clusters of frame t
+without a predecessor and B those of frame t - 1 - k without a successor, both in ascending rank, w = cost - miss_cost for every admissible
+pair whose cost is not NaN, the one-to-one set of pairs that minimises the sum of w is linked, where leaving a pair's clusters unlinked is
+worth 0 -- so a pair dearer than miss_cost is never taken.  miss_cost defaults to 1 + lam * (max_cos if given, else 2), the dearest an
+admissible pair can be.  The optimum's total is unique, its pairs need not be, so the algorithm is the contract: shortest augmenting
+paths, rows inserted in ascending rank, ties to the smaller column (include/gnncca_mpn.h has it step by step, tests/tracking_assign_oracle.py
+as loops, and the kernel equals them bit for bit).  The table of a frame pair lives in LDS, so such a linker takes frames of at most
+MAX_OPTIMAL_FRAME_NODES = 128 detections (ValueError before any launch, for a frame of the batch or of the carried history).  The
+assignment is optimal per (level, frame pair), NOT over time: a shorter gap still wins over a longer one at any cost, there is still no
+motion prediction and there are still no time stamps.
 Scores (csrc/track_score.cuh; per call one memset and two launches).  TrackScorer joins ids (batch.y), cam and Tracks.node_track over time.
 Detection i is VALID iff 0 <= ids[i] < max_ids, 0 <= cam[i] < max_cams and 0 <= node_track[i] < 2**40; it is SCORED iff it is valid and no
 valid detection j > i of its frame has the same (id, cam) (the largest node id wins a duplicate); every other detection is IGNORED (a
@@ -62,6 +75,7 @@ from .frames import _on, _raw_stream
 
 MAX_FRAME_NODES = 4096
 MAX_GAP = nat.TRACK_MAX_GAP
+MAX_OPTIMAL_FRAME_NODES = nat.TRACK_MAX_OPTIMAL_FRAME_NODES
 
 
 class ClusterSummaries:
@@ -184,12 +198,16 @@ class FrameLinker:
     max_gap: an integer in 0 .. 8, the number of consecutive frames a track may be missing from and still be continued (gate
     max_step * (k + 1) after k missed frames; a shorter gap always wins).  0: the adjacent-frame linker, three launches, as ever; M > 0:
     M + 4 launches, and the state holds the last M + 1 frames (sized from their node counts, which the linker keeps on the host).
+    matching: 'mutual' (each of a pair is the other's best: the code paths above, untouched) or 'optimal' (per level and frame pair the
+    min-cost assignment, where staying unlinked costs miss_cost: always the gap path, M + 4 launches also with max_gap = 0, and frames of
+    at most MAX_OPTIMAL_FRAME_NODES = 128 detections).  miss_cost: None (1 + lam * (max_cos, or 2 without one): the dearest an admissible
+    pair can be) or a finite number > 0; a pair dearer than it is never linked.  Only with matching='optimal'.
     Frames are taken to be consecutive and in order (no time stamps); a track missing from more than max_gap frames ends; there is no
-    motion prediction (no velocity term) and the matching is mutual-best, not an optimal assignment.  No counterpart in the reference; what
-    max_step, lam, max_cos and max_gap do to tracking quality can be measured with TrackScorer wherever person ids exist; with a trained model
-    it has not been."""
+    motion prediction (no velocity term); the assignment is optimal per (level, frame pair), not over time.  No counterpart in the
+    reference; what max_step, lam, max_cos, max_gap and matching do to tracking quality can be measured with TrackScorer wherever person
+    ids exist (DESIGN.md section 9 has both matchings on synthetic sequences); with a trained model it has not been."""
 
-    def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0):
+    def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0, matching="mutual", miss_cost=None):
         def real(v):
             return isinstance(v, numbers.Real) and not isinstance(v, bool)
         if not real(max_step) or not math.isfinite(max_step) or not max_step > 0:
@@ -201,7 +219,16 @@ class FrameLinker:
         if isinstance(max_gap, bool) or not isinstance(max_gap, numbers.Integral) or not 0 <= max_gap <= MAX_GAP:
             raise ValueError(f"max_gap must be an integer in [0, {MAX_GAP}], not {max_gap!r}")
         self.max_step, self.lam, self.max_cos = float(max_step), float(lam), None if max_cos is None else float(max_cos)
+        if not isinstance(matching, str) or matching not in nat.MATCHING:
+            raise ValueError(f"matching must be 'mutual' or 'optimal', not {matching!r}")
+        if miss_cost is not None:
+            if matching != "optimal":
+                raise ValueError("miss_cost is the price of staying unlinked under matching='optimal'; matching='mutual' has no such price")
+            if not real(miss_cost) or not math.isfinite(miss_cost) or not miss_cost > 0:
+                raise ValueError(f"miss_cost must be None or a finite number > 0, not {miss_cost!r}")
         self.max_gap = int(max_gap)
+        self.matching = matching
+        self.miss_cost = float(miss_cost) if miss_cost is not None else 1.0 + self.lam * (self.max_cos if self.max_cos is not None else 2.0)
         self.reset()
 
     def reset(self):
@@ -226,6 +253,15 @@ class FrameLinker:
         max_n = int(sizes.max()) if g > 0 else 0
         if max_n > MAX_FRAME_NODES:
             raise ValueError(f"a frame has {max_n} detections; FrameLinker takes frames of at most {MAX_FRAME_NODES}")
+        if self.matching == "optimal":   # before any launch, and before the state moves
+            if self._state is not None and not self._frame_rows:   # (only by changing `matching` on a linker that has linked already)
+                raise ValueError("the carried state was written by the adjacent-frame linker (matching='mutual', max_gap=0), which "
+                                 "matching='optimal' cannot continue: reset() it first")
+            worst = max([max_n] + self._frame_rows)
+            if worst > MAX_OPTIMAL_FRAME_NODES:
+                where = "the batch" if max_n > MAX_OPTIMAL_FRAME_NODES else "the carried history"
+                raise ValueError(f"a frame of {where} has {worst} detections; FrameLinker(matching='optimal') takes frames of at most "
+                                 f"{MAX_OPTIMAL_FRAME_NODES} (reset() forgets the history)")
         dev = s.count.device
         self._reid_dim = r_all
         r = r_all if self.needs_embeddings else 0
@@ -235,7 +271,7 @@ class FrameLinker:
                 nid = self._state[:8].view(torch.int64) if self._state is not None else torch.zeros(1, dtype=torch.int64, device=dev)
                 e64, e32 = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
                 return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone())
-            if self.max_gap > 0:
+            if self.max_gap > 0 or self.matching == "optimal":
                 return self._link_gap(lib, s, dev, sizes, g, n, max_n, r)
             cap = int(sizes[-1])
             state = torch.empty(lib.gnncca_link_state_bytes(cap, r), dtype=torch.uint8, device=dev)
@@ -256,7 +292,8 @@ class FrameLinker:
         return Tracks(tracks[0], tracks[1], matched, state[:8].view(torch.int64), state)
 
     def _link_gap(self, lib, s, dev, sizes, g, n, max_n, r):
-        """The max_gap > 0 call (inside _on(dev), g > 0): everything is sized from host-known node counts, nothing waits for the GPU."""
+        """The max_gap > 0 or matching='optimal' call (inside _on(dev), g > 0): everything is sized from host-known node counts, nothing
+        waits for the GPU."""
         in_rows = self._frame_rows
         out_rows = (in_rows + [int(v) for v in sizes])[-(self.max_gap + 1):]
         c_in, c_out = (C.c_int32 * max(len(in_rows), 1))(*in_rows), (C.c_int32 * len(out_rows))(*out_rows)
@@ -265,13 +302,16 @@ class FrameLinker:
         matched = torch.empty((2, n), dtype=torch.int32, device=dev)   # matched_prev | matched_gap
         ws_bytes = lib.gnncca_link_gap_workspace_bytes(n, g, sum(in_rows))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        st = lib.gnncca_link_frames_gap(s.node_ptr_dev.data_ptr(), s.count.data_ptr(), s.rank.data_ptr() if n else None,
-                                        s.pos.data_ptr() if n else None, s.emb.data_ptr() if r and n else None, r, n, g, max_n, self.max_step,
-                                        self.lam, int(self.max_cos is not None), self.max_cos if self.max_cos is not None else 0.0,
-                                        self.max_gap, self._state.data_ptr() if in_rows else None, c_in, len(in_rows), state.data_ptr(), c_out,
-                                        len(out_rows), tracks[0].data_ptr() if n else None, tracks[1].data_ptr() if n else None,
-                                        matched[0].data_ptr() if n else None, matched[1].data_ptr() if n else None, ws.data_ptr(), ws_bytes,
-                                        _raw_stream(dev))
+        head = (s.node_ptr_dev.data_ptr(), s.count.data_ptr(), s.rank.data_ptr() if n else None, s.pos.data_ptr() if n else None,
+                s.emb.data_ptr() if r and n else None, r, n, g, max_n, self.max_step, self.lam, int(self.max_cos is not None),
+                self.max_cos if self.max_cos is not None else 0.0, self.max_gap)
+        tail = (self._state.data_ptr() if in_rows else None, c_in, len(in_rows), state.data_ptr(), c_out, len(out_rows),
+                tracks[0].data_ptr() if n else None, tracks[1].data_ptr() if n else None, matched[0].data_ptr() if n else None,
+                matched[1].data_ptr() if n else None, ws.data_ptr(), ws_bytes, _raw_stream(dev))
+        if self.matching == "optimal":
+            st = lib.gnncca_link_frames_gap_ex(*head, nat.MATCHING[self.matching], self.miss_cost, *tail)
+        else:   # 'mutual': the entry, and with it the code, it has always run
+            st = lib.gnncca_link_frames_gap(*head, *tail)
         if st:
             nat.check(st, "gnncca_link_frames_gap")
         # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
@@ -455,5 +495,5 @@ class TrackScorer:
         return _scores_of(cells, ignored, switches)
 
 
-__all__ = ["MAX_FRAME_NODES", "MAX_GAP", "ClusterSummaries", "Tracks", "cluster_summaries", "cluster_summaries_raw", "FrameLinker", "TrackScorer",
+__all__ = ["MAX_FRAME_NODES", "MAX_GAP", "MAX_OPTIMAL_FRAME_NODES", "ClusterSummaries", "Tracks", "cluster_summaries", "cluster_summaries_raw", "FrameLinker", "TrackScorer",
            "TrackScores"]

@@ -710,7 +710,8 @@ GNNCCA_API int gnncca_eval_frames_dense(const int64_t* edge_index, const float* 
  * (it bounds the cluster count; a frame with more clusters than state_out_capacity is carried as empty).  state_in must have been
  * written with the same reid_dim and its own capacity (<= GNNCCA_TRACK_MAX_FRAME_NODES); it is not modified.  n_frames = 0 launches
  * nothing and writes nothing.  Out of scope: re-identification after a frame in which a track was not seen (gnncca_link_frames_gap
- * below does that), optimal assignment, time stamps.  Workspace: gnncca_link_workspace_bytes. */
+ * below does that), an optimal assignment per frame pair in place of mutual best (gnncca_link_frames_gap_ex below does that), time
+ * stamps.  Workspace: gnncca_link_workspace_bytes. */
 #define GNNCCA_TRACK_MAX_FRAME_NODES 4096
 GNNCCA_API size_t gnncca_cluster_summaries_bytes(int64_t n_nodes, int64_t n_frames);
 GNNCCA_API int gnncca_cluster_summaries(const int32_t* labels, const int32_t* node_ptr_dev, const double* xw, const double* yw,
@@ -751,7 +752,8 @@ GNNCCA_API int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* co
  * max_gap + 1 frames; it is not modified.  state_out: gnncca_link_gap_state_bytes(C, n_frames_kept, R) bytes.  GNNCCA_ERR_INVALID_ARG:
  * max_gap outside [0, GNNCCA_TRACK_MAX_GAP], a frame capacity above GNNCCA_TRACK_MAX_FRAME_NODES, the checks of gnncca_link_frames.
  * max_gap + 4 launches; deterministic (integer flags, fixed sum orders, no atomics), no host wait, no allocation: capturable.
- * Out of scope: motion prediction (a velocity term), optimal assignment, time stamps.
+ * Out of scope: motion prediction (a velocity term), time stamps; the pairs of a (level, frame pair) table are chosen by mutual best
+ * here and by a min-cost assignment in gnncca_link_frames_gap_ex below, in both cases per table, never over time.
  * Workspace: gnncca_link_gap_workspace_bytes(n_nodes, n_frames, state_rows = the sum of state_in_frame_rows). */
 #define GNNCCA_TRACK_MAX_GAP 8
 GNNCCA_API size_t gnncca_link_gap_state_bytes(int64_t capacity_rows, int32_t n_frames_kept, int32_t reid_dim);
@@ -763,6 +765,39 @@ GNNCCA_API int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t
                                       const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track,
                                       int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, void* workspace,
                                       size_t workspace_bytes, gnncca_stream_t stream);
+
+/* gnncca_link_frames_gap_ex: gnncca_link_frames_gap with the choice of pairs inside a (level, frame pair) table as an argument.
+ * matching = 0: mutual best, gnncca_link_frames_gap itself (which calls through with 0; miss_cost is checked and not used).
+ * matching = 1: the min-cost assignment of the table (csrc/identities_assign.cuh).  Levels, gates, masks, d, dcos, cost, admissibility,
+ * the ids, the outputs, the state and its layout, the workspace and the launch count are gnncca_link_frames_gap's; a state written with
+ * one matching is a valid state_in for the other as far as the layout goes, but the ids then follow neither rule.  At level k let A be
+ * the clusters of frame t without a predecessor in ascending rank, i = 0 .. n - 1, and B those of frame t - 1 - k without a successor,
+ * j = 0 .. m - 1.  A pair is an EDGE iff it is admissible and its cost is not NaN;  w[i][j] = cost - miss_cost (one fp64 subtraction).
+ * Chosen is a one-to-one set of edges that minimises the sum of w, where leaving both clusters of a pair unlinked is worth 0: a pair
+ * dearer than miss_cost is never worth taking.  The optimum's total is unique, its pairs need not be, so the ALGORITHM is the contract:
+ * shortest augmenting paths over n rows and m + n columns, column m + i being row i's "stay unlinked" column (0 for row i, no edge for any
+ * other row).  u[] = v[] = 0, p[column] = none; the rows are inserted in the order i = 0 .. n - 1; for each, minv[] = +inf, used[] =
+ * false, i0 = i, j0 = none, then repeat:  (1) for every unused column j in ascending order  cur = (w[i0][j] - u[i0]) - v[j];  if cur <
+ * minv[j] then minv[j] = cur, way[j] = j0;  if minv[j] < delta (strict, delta = +inf at first) then delta = minv[j], j1 = j -- a tie goes
+ * to the smaller column, real columns before the unlinked ones;  (2) u[i] += delta; for every used j: u[p[j]] += delta, v[j] -= delta;
+ * for every unused j: minv[j] -= delta;  (3) j1 becomes used; if p[j1] is none, p is flipped back along way[] from j1 (p[j] = p[way[j]],
+ * the first column of the path takes row i) and the next row follows; otherwise i0 = p[j1], j0 = j1 and (1) again.  Every operation is
+ * an elementwise fp64 one (no contraction); a row needs at most min(n, m) + 1 rounds, which bounds the kernel's loops at launch.
+ * a continues b iff p[j] = i at the end.  miss_cost must be finite and > 0; FrameLinker's default is 1 + lam * (max_cos, or 2 without
+ * one), the dearest an admissible pair can be.
+ * The table lives in LDS (8 P^2 + 76 P + 16 bytes for frames of up to P clusters, P a power of two: 140,816 bytes at 128), so with
+ * matching = 1 max_frame_nodes and every state_in_frame_rows entry are at most GNNCCA_TRACK_MAX_OPTIMAL_FRAME_NODES.
+ * GNNCCA_ERR_INVALID_ARG, before any launch: a matching other than 0 or 1, a miss_cost that is not finite and > 0, a frame of the batch
+ * or of the history above that limit with matching = 1, the checks of gnncca_link_frames_gap.  max_gap + 4 launches; deterministic, no
+ * host wait, no allocation: capturable.  Out of scope: an assignment over time (across levels or frames), motion prediction, time stamps. */
+#define GNNCCA_TRACK_MAX_OPTIMAL_FRAME_NODES 128
+GNNCCA_API int gnncca_link_frames_gap_ex(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
+                                         const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                         double max_step, double lam, int32_t has_max_cos, double max_cos, int32_t max_gap,
+                                         int32_t matching, double miss_cost, const void* state_in, const int32_t* state_in_frame_rows,
+                                         int32_t state_in_frames, void* state_out, const int32_t* state_out_frame_rows,
+                                         int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track, int32_t* matched_prev,
+                                         int32_t* matched_gap, void* workspace, size_t workspace_bytes, gnncca_stream_t stream);
 
 /* ---- Identity-tracking scores over a sequence (csrc/track_score.cuh, included by csrc/identities.hip) --------------------------------
  * Joins ids int64 [N] (the caller's person id of every detection), cam int32 [N] and node_track int64 [N] (gnncca_link_frames*) over the

@@ -12,8 +12,8 @@ measurement run twice:
            (tests/track_score_oracle.py) on a carried state
   copy     those device-to-host copies and their synchronisation alone: the floor under ANY host implementation
 and, for scale, `link`: FrameLinker's own call on the summaries of the same batch.  The two results are compared once (switched and
-counts exactly, result() by ==).  Prints one JSON line per run, then result() for max_gap 0, 1 and 3 on the --hide 0.1 batch: SYNTHETIC
-data with ground-truth clusters, not a trained model."""
+counts exactly, result() by ==).  Prints one JSON line per run, then result() for max_gap 0, 1 and 3 and for both matchings on the
+--hide 0.1 batch: SYNTHETIC data with ground-truth clusters, not a trained model."""
 import argparse
 import json
 import os
@@ -32,12 +32,12 @@ from time_tracking import make_batch  # noqa: E402
 from gnn_cca_amd.tracking import FrameLinker, TrackScorer, cluster_summaries_raw  # noqa: E402
 
 
-def on_device(b, a, max_gap):
+def on_device(b, a, max_gap, matching="mutual"):
     """The batch's ground-truth clusters summarised and linked on the device -> (summaries, linker, ids, cam, node_track, node_ptr_dev)."""
     dev = torch.device("cuda")
     d = {k: torch.from_numpy(b[k]).to(dev) for k in ("labels", "xw", "yw", "cam", "emb")}
     s = cluster_summaries_raw(d["labels"], b["node_ptr"].tolist(), d["xw"], d["yw"], d["cam"], d["emb"])
-    link = FrameLinker(1.0, lam=1.0, max_gap=max_gap)
+    link = FrameLinker(1.0, lam=1.0, max_gap=max_gap, matching=matching)
     ids = torch.from_numpy(np.tile(np.tile(np.arange(a.per), a.cams), a.frames).astype(np.int64)).to(dev)
     return s, link, ids, d["cam"], link(s).node_track, s.node_ptr_dev
 
@@ -116,11 +116,12 @@ def main():
     for run in range(2):
         print(json.dumps(dict(measure(a, b), run=run)), flush=True)
     hidden = make_batch(a.frames, a.cams, a.per, a.reid, hide=0.1)
-    for gap in (0, 1, 3):   # what max_gap does to the scores: synthetic walks, ground-truth clusters
-        _, _, ids, cam, track, nptr = on_device(hidden, a, gap)
-        score = TrackScorer(max_ids=1024, max_cams=8)
-        score.add_raw(ids, cam, track, hidden["node_ptr"].tolist(), node_ptr_dev=nptr)
-        print(json.dumps(dict(score.result(), max_gap=gap, hide=0.1, synthetic=True)), flush=True)
+    for gap in (0, 1, 3):   # what max_gap and the matching do to the scores: synthetic walks, ground-truth clusters
+        for matching in ("mutual", "optimal"):
+            _, _, ids, cam, track, nptr = on_device(hidden, a, gap, matching)
+            score = TrackScorer(max_ids=1024, max_cams=8)
+            score.add_raw(ids, cam, track, hidden["node_ptr"].tolist(), node_ptr_dev=nptr)
+            print(json.dumps(dict(score.result(), max_gap=gap, matching=matching, hide=0.1, synthetic=True)), flush=True)
 
 
 if __name__ == "__main__":

@@ -3,6 +3,7 @@
 (N = 2048, every person seen once per camera: 8 clusters of 4 per frame) with R = 2048 appearance columns.  Needs an MI355X.
 
     python tools/time_tracking.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3] [--max-gap 0] [--hide 0]
+                                  [--matching mutual|optimal] [--crowded]
 
 Two ways to the same result, timed in alternating rounds in one process (host clock around work that ends in a device synchronise):
   device   cluster summaries (2 launches) + FrameLinker (3 launches) on tensors that are already on the GPU, as a FramePipeline
@@ -12,7 +13,11 @@ Two ways to the same result, timed in alternating rounds in one process (host cl
 and, as the floor under ANY host implementation, `copy`: those device-to-host copies and their synchronisation alone.
 The two results are compared once (summaries bit for bit, ids exactly).  Prints one JSON line.
 --max-gap M > 0 times FrameLinker(max_gap=M) (M + 4 launches instead of 3; --hide P then hides each person's cluster with probability P per
-frame, so that there is something to find again) against the numpy restatement of ITS rule (tests/tracking_gap_oracle.py)."""
+frame, so that there is something to find again) against the numpy restatement of ITS rule (tests/tracking_gap_oracle.py).
+--matching optimal times FrameLinker(matching='optimal') (the gap path, M + 4 launches also at --max-gap 0) against
+tests/tracking_assign_oracle.py.  --crowded times, instead of all of the above, the linker's call alone on a crowded synthetic sequence
+(12 frames, 120 persons on 10 x 10, the first frame 102 single-node clusters, position only, --max-gap 1 unless given): both matchings in
+alternating rounds, each compared with its oracle once."""
 import argparse
 import json
 import os
@@ -25,9 +30,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import tracking_assign_oracle as ta  # noqa: E402
 import tracking_gap_oracle as tg  # noqa: E402
 import tracking_oracle as to  # noqa: E402
-from gnn_cca_amd.tracking import FrameLinker, cluster_summaries_raw  # noqa: E402
+from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, cluster_summaries_raw  # noqa: E402
 
 
 def make_batch(frames, cams, per, reid, seed=0, hide=0.0):
@@ -55,6 +61,39 @@ def make_batch(frames, cams, per, reid, seed=0, hide=0.0):
     return dict(labels=labels, node_ptr=node_ptr, xw=xw, yw=yw, cam=cam, emb=emb.astype(np.float32), n=n)
 
 
+def crowded(a):
+    """The linker's call alone on the crowded sequence, both matchings."""
+    m = a.max_gap if a.max_gap > 0 else 1
+    summ = tg.hide_sequence(np.random.default_rng(7), 12, 120, 8, arena=10.0, max_hide=1, noise=0.3, max_alive=120)
+    n = len(summ["rank"])
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    ones = t(np.ones(n, np.int32))
+    s = ClusterSummaries(t(summ["count"]), t(summ["rank"]), ones, ones, t(summ["pos"]), t(summ["emb"]), summ["node_ptr"].tolist(),
+                         t(summ["node_ptr"].astype(np.int32)))
+    links = {k: FrameLinker(0.8, lam=0.0, max_gap=m, matching=k) for k in ("mutual", "optimal")}
+    out = {"crowded": True, "clusters_per_frame": summ["count"].tolist(), "max_gap": m, "reps": a.reps}
+    for k, link in links.items():
+        want, _ = ta.link_gap(summ, summ["node_ptr"], 0.8, 0.0, None, m, matching=k)
+        got = link(s)
+        out[k + "_ids_equal"] = bool(all(np.array_equal(getattr(got, f).cpu().numpy(), want[f])
+                                         for f in ("cluster_track", "node_track", "matched_prev", "matched_gap")))
+        out[k + "_tracks"] = int(got.next_id.item())
+        out[k + "_ms"] = []
+        for _ in range(10):
+            link.reset()
+            link(s)
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for k, link in links.items():
+            t0 = time.perf_counter()
+            for _ in range(a.reps):
+                link.reset()   # (every call links the whole sequence from nothing: the same work each time)
+                link(s)
+            torch.cuda.synchronize()
+            out[k + "_ms"].append(round((time.perf_counter() - t0) / a.reps * 1e3, 4))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", type=int, default=64)
@@ -66,15 +105,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--max-gap", type=int, default=0)
     ap.add_argument("--hide", type=float, default=0.0)
+    ap.add_argument("--matching", choices=("mutual", "optimal"), default="mutual")
+    ap.add_argument("--crowded", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_tracking.py measures on the GPU; no device is visible")
+    if a.crowded:
+        return crowded(a)
     b = make_batch(a.frames, a.cams, a.per, a.reid, hide=a.hide)
     dev = torch.device("cuda")
     d = {k: torch.from_numpy(b[k]).to(dev) for k in ("labels", "xw", "yw", "cam", "emb")}
     ptr_host = b["node_ptr"].tolist()
     max_step, lam = 1.0, 1.0
-    link = FrameLinker(max_step, lam=lam, max_gap=a.max_gap)
+    link = FrameLinker(max_step, lam=lam, max_gap=a.max_gap, matching=a.matching)
 
     def device_once():
         s = cluster_summaries_raw(d["labels"], ptr_host, d["xw"], d["yw"], d["cam"], d["emb"])
@@ -87,6 +130,8 @@ def main():
     def host_once(state):
         labels, xw, yw, cam, emb = copy_once()
         s = to.summaries(labels, b["node_ptr"], xw, yw, cam, emb)
+        if a.matching == "optimal":
+            return s, ta.link_gap(s, b["node_ptr"], max_step, lam, None, a.max_gap, state, matching="optimal")
         if a.max_gap > 0:
             return s, tg.link_gap(s, b["node_ptr"], max_step, lam, None, a.max_gap, state)
         return s, to.link(s, b["node_ptr"], max_step, lam, None, state)
@@ -98,7 +143,7 @@ def main():
     same = all(np.array_equal(getattr(s_dev, k).cpu().numpy(), s_host[k]) for k in ("count", "rank", "size", "n_cams", "pos", "emb"))
     same_ids = all(np.array_equal(getattr(t_dev, k).cpu().numpy(), t_host[k]) for k in ("cluster_track", "node_track", "matched_prev"))
     gaps = t_dev.matched_gap.cpu().numpy()
-    if a.max_gap > 0:
+    if a.max_gap > 0 or a.matching == "optimal":
         same_ids = same_ids and np.array_equal(gaps, t_host["matched_gap"])
     for _ in range(10):   # warm-up: code objects, allocator
         device_once()
@@ -121,7 +166,7 @@ def main():
     print(json.dumps({"frames": a.frames, "cams": a.cams, "per_cam": a.per, "n_nodes": b["n"], "reid_dim": a.reid, "reps": a.reps,
                       "host_reps": a.host_reps, "device_ms": [round(v, 4) for v in dev_ms], "host_ms": [round(v, 2) for v in host_ms],
                       "copy_ms": [round(v, 4) for v in copy_ms], "summaries_equal": bool(same), "ids_equal": bool(same_ids),
-                      "tracks": int(t_dev.next_id.item()), "max_gap": a.max_gap, "hide": a.hide,
+                      "tracks": int(t_dev.next_id.item()), "max_gap": a.max_gap, "hide": a.hide, "matching": a.matching,
                       "matches_per_gap": [int((gaps == k).sum()) for k in range(a.max_gap + 1)]}))
 
 
