@@ -9,8 +9,10 @@ Persons walk on the ground plane; every camera sees every person, with noise on 
 clusters mean nothing: the ids are shown for the model's partition AND for the ground-truth partition of the same detections, where a
 person keeps one id as long as the walk stays inside max_step.  In the middle frame of every batch person 0 is hidden from every camera:
 the linker with max_gap=1 finds them again one frame later under the same id, the linker without max_gap hands out a new one.  Two
-TrackScorers accumulate, on the device, the identity scores of both linkers against the person ids; their result() is the last thing
-printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
+more linkers on the true partition show matching='optimal' and motion='velocity' (a cluster is looked for at its last position plus its
+last displacement per frame; these persons wander without a heading, so it has little to predict here: DESIGN.md section 9 has people
+crossing each other).  Four TrackScorers accumulate, on the device, the identity scores of the four linkers on the true partition
+against the person ids; their result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
 """
 import argparse
 import os
@@ -42,6 +44,8 @@ def main():
     by_truth_opt = FrameLinker(max_step=1.0, lam=1.0, max_gap=1, matching="optimal")   # per frame pair the min-cost assignment, not mutual best
     score, score_gap = TrackScorer(max_ids=a.persons, max_cams=a.cams), TrackScorer(max_ids=a.persons, max_cams=a.cams)
     score_opt = TrackScorer(max_ids=a.persons, max_cams=a.cams)
+    by_truth_vel = FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity")   # a cluster is looked for where it is heading
+    score_vel = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     where = rng.uniform(-8, 8, size=(a.persons, 2))
     look = rng.standard_normal((a.persons, 256)).astype(np.float32)
     id_cam = np.tile(np.repeat(np.arange(a.cams), a.persons), a.frames)
@@ -72,6 +76,8 @@ def main():
         score.add(r, tt)                         # ids (batch.y), cameras and node tracks joined over time: nothing waits for the GPU
         score_gap.add(r, tg)
         score_opt.add(r, by_truth_opt(st))
+        tv = by_truth_vel(st)                    # tv.velocity: float64 [N, 2], the displacement per frame since the predecessor
+        score_vel.add(r, tv)
         # ---- only the printing below waits for the GPU ----
         last = slice(r.batch.node_ptr[-2], r.batch.node_ptr[-1])
         k_model, k_truth = int(s.count[-1].item()), int(st.count[-1].item())
@@ -80,13 +86,16 @@ def main():
         print(f"  last frame, true partition: ids {tt.cluster_track[last][:k_truth].tolist()} at "
               f"{[[round(v, 2) for v in p] for p in st.pos[last][:k_truth].tolist()]}, cameras {st.n_cams[last][:k_truth].tolist()}")
         print(f"  last frame, model partition: {k_model} clusters, sizes {s.size[last][:k_model].tolist()}")
+        print(f"  last frame, true partition, motion='velocity': ids {tv.cluster_track[last][:k_truth].tolist()}, velocities "
+              f"{[[round(v, 2) for v in p] for p in tv.velocity[last][:k_truth].tolist()]}")
         if a.frames > 2:   # person 0 is cluster 0 of every frame that shows them (their camera-0 detection is the frame's first node)
             before, after = r.batch.node_ptr[hidden - 1], r.batch.node_ptr[hidden + 1]
             print(f"  person 0, hidden in frame {hidden}: id {int(tt.cluster_track[before])} -> {int(tt.cluster_track[after])} without max_gap, "
                   f"{int(tg.cluster_track[before])} -> {int(tg.cluster_track[after])} with max_gap=1 "
                   f"(matched_gap {int(tg.matched_gap[after])}); tracks so far {int(tt.next_id.item())} against {int(tg.next_id.item())}")
     print("random weights: the model's clusters are meaningless, the plumbing is what is shown; on the true partition a person keeps its id")
-    for name, sc in (("without max_gap", score), ("with max_gap=1", score_gap), ("with max_gap=1, matching='optimal'", score_opt)):   # result(): the one synchronisation of a scorer
+    for name, sc in (("without max_gap", score), ("with max_gap=1", score_gap), ("with max_gap=1, matching='optimal'", score_opt),
+                     ("with max_gap=1, motion='velocity'", score_vel)):   # result(): the one synchronisation of a scorer
         res = sc.result()
         print(f"true partition {name}: " + ", ".join(f"{q} {v:.3f}" if isinstance(v, float) else f"{q} {v}" for q, v in res.items()))
 

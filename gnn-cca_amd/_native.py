@@ -16,6 +16,7 @@ TOPK_MAX_DEG = 4096
 TRACK_MAX_GAP = 8                    # gnncca_link_frames_gap
 TRACK_MAX_OPTIMAL_FRAME_NODES = 128  # gnncca_link_frames_gap_ex with matching = 1: a frame pair's table lives in LDS
 MATCHING = {"mutual": 0, "optimal": 1}   # gnncca_link_frames_gap_ex
+MOTION = {"none": 0, "velocity": 1}      # gnncca_link_frames_motion takes 1; "none" is the entries above
 SCORE_MAX_IDS, SCORE_MAX_CAMS, SCORE_MAX_STREAMS, SCORE_MAX_SLOTS = 65536, 64, 1 << 20, 1 << 22   # gnncca_track_score_add
 SCORE_MIN_CAP, SCORE_HEADER_LEN = 1024, 8
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
@@ -229,6 +230,12 @@ _SIGNATURES = {
                                             C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_void_p,
                                             C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnncca_link_motion_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gnncca_link_motion_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "gnncca_link_frames_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                            C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
+                                            C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnncca_track_score_table_bytes": (C.c_size_t, [C.c_int64]),
     "gnncca_track_score_reset": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gnncca_track_score_rehash": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

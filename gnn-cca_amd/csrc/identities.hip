@@ -537,3 +537,5 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
 #include "identities_assign.cuh"   // gnncca_link_frames_gap_ex: the level kernel's min-cost-assignment form (matching = 1)
 
 #include "track_score.cuh"   // gnncca_track_score_*: identity-tracking scores over a sequence (its own kernels; nothing above changes)
+
+#include "identities_motion.cuh"   // gnncca_link_frames_motion: the gap-tolerant linker with a velocity prediction (one walking workgroup)

@@ -9,6 +9,7 @@ over the frames of a batch and from one batch to the next.
     t = link(next_r)                              # ... frame 0 of this batch continues the last frame of the previous one
     link = FrameLinker(max_step=0.8, max_gap=2)   # a track survives up to 2 frames that miss it; t.matched_gap [N]: frames skipped
     link = FrameLinker(max_step=0.8, matching='optimal')   # per frame pair the min-cost assignment instead of mutual best
+    link = FrameLinker(max_step=0.4, max_gap=2, motion='velocity')   # look for a track where it is heading; t.velocity [N, 2]
     score = TrackScorer(max_ids=1024, max_cams=8) # identity-tracking scores against the caller's person ids, accumulated on the device
     score.add(r, t).switched                      # int32 [N]: -1 not scored, 0, 1 = this detection is an identity switch
     score.result()                                # IDSW, IDTP, IDF1, AssA, purity, coverage, MT / PT / ML ...: ONE synchronisation
@@ -40,7 +41,19 @@ at higher cost.  Time is the frame index over all calls since reset(): an empty 
 passes no time.  The rule is causal, so the ids do not depend on how a sequence is cut into batches; the state holds the last M + 1 frames.
 Limits: frames are taken to be CONSECUTIVE and IN ORDER (there are no time stamps); a track unseen for more than max_gap frames ends (with
 the default max_gap = 0: in the first frame that misses it); a cluster is looked for where it was last seen -- there is no motion
-prediction (no velocity term), only a gate that grows with the gap.
+prediction (no velocity term), only a gate that grows with the gap -- unless motion='velocity' is asked for:
+Motion (motion='velocity': csrc/identities_motion.cuh, THREE launches whatever max_gap is).  The levels, gates, masks, cost, mutual best,
+ties and id numbering are those of the gap rule, and two things are added.  Every cluster has a velocity, float64 [2] in ground-plane
+units per frame: (0, 0) without a predecessor; when cluster a of frame t is linked at level k to cluster b of frame t - 1 - k,
+vel(a) = (pos(a) - pos(b)) / float64(k + 1) per component -- one subtraction, one division, no smoothing.  And at level k cluster b is
+looked for at pred(b) = pos(b) + float64(k + 1) * vel(b) (one multiplication, one addition, no FMA): d is the distance from pos(a) to
+pred(b), admissible iff d <= gate_k = max_step * (k + 1), cost = d / gate_k + lam * dcos -- so max_step becomes the largest DEVIATION from
+the predicted position per frame, and may be smaller than the distance a person walks in one.  A non-finite prediction is admissible with
+nobody.  vel(b) is known only when b's frame has been through all its levels, so the frames go in order and the levels inside each frame
+(for zero velocities that order gives the gap rule's result): one workgroup walks the batch, and hands out the ids as it goes.  The rule
+is causal (the carried state holds the velocities of its M + 1 frames; it is a state of its own kind).  Tracks.velocity is float64 [N, 2].
+Limits: constant velocity from the LAST link only -- the prediction is wrong after a sharp turn, so a track can end there and restart;
+still no time stamps; matching='optimal' has no motion yet (the combination is refused).  DESIGN.md section 9 has what it does to identity switches on synthetic crossing walks.
 Optimal matching (matching='optimal': csrc/identities_assign.cuh, the same M + 4 launches, also with max_gap = 0).  Mutual best leaves a
 cluster unlinked whenever its best partner prefers somebody else, even when a second admissible partner is free.  In this mode the levels,
 gates, masks and cost stay as above and only the choice of pairs inside a (level, frame pair) table changes: with A the clusters of frame t
@@ -51,8 +64,8 @@ admissible pair can be.  The optimum's total is unique, its pairs need not be, s
 paths, rows inserted in ascending rank, ties to the smaller column (include/gnncca_mpn.h has it step by step, tests/tracking_assign_oracle.py
 as loops, and the kernel equals them bit for bit).  The table of a frame pair lives in LDS, so such a linker takes frames of at most
 MAX_OPTIMAL_FRAME_NODES = 128 detections (ValueError before any launch, for a frame of the batch or of the carried history).  The
-assignment is optimal per (level, frame pair), NOT over time: a shorter gap still wins over a longer one at any cost, there is still no
-motion prediction and there are still no time stamps.
+assignment is optimal per (level, frame pair), NOT over time: a shorter gap still wins over a longer one at any cost, this mode has no
+motion prediction (motion='velocity' above is mutual best only) and there are still no time stamps.
 Scores (csrc/track_score.cuh; per call one memset and two launches).  TrackScorer joins ids (batch.y), cam and Tracks.node_track over time.
 Detection i is VALID iff 0 <= ids[i] < max_ids, 0 <= cam[i] < max_cams and 0 <= node_track[i] < 2**40; it is SCORED iff it is valid and no
 valid detection j > i of its frame has the same (id, cam) (the largest node id wins a duplicate); every other detection is IGNORED (a
@@ -93,12 +106,14 @@ class Tracks:
     """Track ids of a batch (device tensors): cluster_track int64 [N] (row-aligned with the summaries, -1 beyond a frame's count),
     node_track int64 [N] (a detection's track), matched_prev int32 [N] (the rank of the cluster's predecessor in ITS OWN frame, or -1),
     matched_gap int32 [N] (-1: no predecessor; k: the predecessor is k + 1 frames back, k frames were skipped -- all 0 / -1 from a linker
-    without max_gap, where it is derived from matched_prev when first read), next_id int64 [1] (the first id nobody has yet)."""
-    __slots__ = ("cluster_track", "node_track", "matched_prev", "next_id", "_state", "_matched_gap")
+    without max_gap, where it is derived from matched_prev when first read), next_id int64 [1] (the first id nobody has yet), velocity
+    float64 [N, 2] (row-aligned with cluster_track: the displacement per frame since the predecessor, zero without one and beyond a
+    frame's count) from a linker with motion='velocity', None from any other."""
+    __slots__ = ("cluster_track", "node_track", "matched_prev", "next_id", "velocity", "_state", "_matched_gap")
 
-    def __init__(self, cluster_track, node_track, matched_prev, next_id, state, matched_gap=None):
+    def __init__(self, cluster_track, node_track, matched_prev, next_id, state, matched_gap=None, velocity=None):
         self.cluster_track, self.node_track, self.matched_prev, self.next_id, self._state = cluster_track, node_track, matched_prev, next_id, state
-        self._matched_gap = matched_gap
+        self._matched_gap, self.velocity = matched_gap, velocity
 
     @property
     def matched_gap(self):
@@ -202,12 +217,17 @@ class FrameLinker:
     min-cost assignment, where staying unlinked costs miss_cost: always the gap path, M + 4 launches also with max_gap = 0, and frames of
     at most MAX_OPTIMAL_FRAME_NODES = 128 detections).  miss_cost: None (1 + lam * (max_cos, or 2 without one): the dearest an admissible
     pair can be) or a finite number > 0; a pair dearer than it is never linked.  Only with matching='optimal'.
-    Frames are taken to be consecutive and in order (no time stamps); a track missing from more than max_gap frames ends; there is no
-    motion prediction (no velocity term); the assignment is optimal per (level, frame pair), not over time.  No counterpart in the
+    motion: 'none' (a cluster is looked for where it was last seen: the code paths above, untouched) or 'velocity' (it is looked for at
+    its last position plus its last displacement per frame times the frames gone by, and max_step bounds the deviation from there: three
+    launches whatever max_gap is, one workgroup walking the frames in order; Tracks.velocity).  Constant velocity from the last link only:
+    wrong after a sharp turn, where a track can end and restart.  Not with matching='optimal': the assignment kernel's frame-parallel
+    level launch cannot know the velocities; combining the two is left to a later change and refused until then.
+    Frames are taken to be consecutive and in order (no time stamps); a track missing from more than max_gap frames ends; without
+    motion='velocity' there is no motion prediction; the assignment is optimal per (level, frame pair), not over time.  No counterpart in the
     reference; what max_step, lam, max_cos, max_gap and matching do to tracking quality can be measured with TrackScorer wherever person
     ids exist (DESIGN.md section 9 has both matchings on synthetic sequences); with a trained model it has not been."""
 
-    def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0, matching="mutual", miss_cost=None):
+    def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0, matching="mutual", miss_cost=None, motion="none"):
         def real(v):
             return isinstance(v, numbers.Real) and not isinstance(v, bool)
         if not real(max_step) or not math.isfinite(max_step) or not max_step > 0:
@@ -226,14 +246,21 @@ class FrameLinker:
                 raise ValueError("miss_cost is the price of staying unlinked under matching='optimal'; matching='mutual' has no such price")
             if not real(miss_cost) or not math.isfinite(miss_cost) or not miss_cost > 0:
                 raise ValueError(f"miss_cost must be None or a finite number > 0, not {miss_cost!r}")
+        if not isinstance(motion, str) or motion not in nat.MOTION:
+            raise ValueError(f"motion must be 'none' or 'velocity', not {motion!r}")
+        if motion == "velocity" and matching == "optimal":
+            raise ValueError("motion='velocity' cannot be combined with matching='optimal' yet: the assignment kernel links all frames of a "
+                             "level at once and cannot know the velocities")
         self.max_gap = int(max_gap)
         self.matching = matching
+        self.motion = motion
         self.miss_cost = float(miss_cost) if miss_cost is not None else 1.0 + self.lam * (self.max_cos if self.max_cos is not None else 2.0)
         self.reset()
 
     def reset(self):
         """Forget the carried frames and the id counter."""
         self._state, self._cap, self._reid_dim = None, 0, None
+        self._state_motion = None   # the motion of the linker that wrote the state (only by changing `motion` can it differ from self.motion)
         self._frame_rows = []   # max_gap > 0: the node counts of the frames the state holds, oldest first (they bound the cluster counts)
 
     @property
@@ -262,6 +289,11 @@ class FrameLinker:
                 where = "the batch" if max_n > MAX_OPTIMAL_FRAME_NODES else "the carried history"
                 raise ValueError(f"a frame of {where} has {worst} detections; FrameLinker(matching='optimal') takes frames of at most "
                                  f"{MAX_OPTIMAL_FRAME_NODES} (reset() forgets the history)")
+        if self.motion not in nat.MOTION or (self.motion == "velocity" and self.matching == "optimal"):   # (changed after construction)
+            raise ValueError(f"motion={self.motion!r} with matching={self.matching!r} is not a linker this module has")
+        if self._state is not None and self._state_motion != self.motion:
+            raise ValueError(f"the carried state was written with motion={self._state_motion!r}, which motion={self.motion!r} cannot "
+                             "continue (the states differ in kind): reset() it first")
         dev = s.count.device
         self._reid_dim = r_all
         r = r_all if self.needs_embeddings else 0
@@ -270,7 +302,10 @@ class FrameLinker:
             if g == 0:   # nothing to link: the state stays
                 nid = self._state[:8].view(torch.int64) if self._state is not None else torch.zeros(1, dtype=torch.int64, device=dev)
                 e64, e32 = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
-                return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone())
+                vel = torch.empty((0, 2), dtype=torch.float64, device=dev) if self.motion == "velocity" else None
+                return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone(), vel)
+            if self.motion == "velocity":
+                return self._link_motion(lib, s, dev, sizes, g, n, max_n, r)
             if self.max_gap > 0 or self.matching == "optimal":
                 return self._link_gap(lib, s, dev, sizes, g, n, max_n, r)
             cap = int(sizes[-1])
@@ -288,7 +323,7 @@ class FrameLinker:
             if st:
                 nat.check(st, "gnncca_link_frames")
             # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
-        self._state, self._cap = state, cap
+        self._state, self._cap, self._state_motion = state, cap, self.motion
         return Tracks(tracks[0], tracks[1], matched, state[:8].view(torch.int64), state)
 
     def _link_gap(self, lib, s, dev, sizes, g, n, max_n, r):
@@ -315,8 +350,34 @@ class FrameLinker:
         if st:
             nat.check(st, "gnncca_link_frames_gap")
         # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
-        self._state, self._frame_rows = state, out_rows
+        self._state, self._frame_rows, self._state_motion = state, out_rows, self.motion
         return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1])
+
+    def _link_motion(self, lib, s, dev, sizes, g, n, max_n, r):
+        """The motion='velocity' call (inside _on(dev), g > 0), with any max_gap: like _link_gap everything is sized from host-known node
+        counts and nothing waits for the GPU; the state is of its own kind (it carries the velocities) and three launches do it all."""
+        in_rows = self._frame_rows
+        out_rows = (in_rows + [int(v) for v in sizes])[-(self.max_gap + 1):]
+        c_in, c_out = (C.c_int32 * max(len(in_rows), 1))(*in_rows), (C.c_int32 * len(out_rows))(*out_rows)
+        state = torch.empty(lib.gnncca_link_motion_state_bytes(sum(out_rows), len(out_rows), r), dtype=torch.uint8, device=dev)
+        tracks = torch.empty((2, n), dtype=torch.int64, device=dev)   # cluster_track | node_track
+        matched = torch.empty((2, n), dtype=torch.int32, device=dev)   # matched_prev | matched_gap
+        velocity = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        ws_bytes = lib.gnncca_link_motion_workspace_bytes(n, g, sum(in_rows))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        st = lib.gnncca_link_frames_motion(s.node_ptr_dev.data_ptr(), s.count.data_ptr(), s.rank.data_ptr() if n else None,
+                                           s.pos.data_ptr() if n else None, s.emb.data_ptr() if r and n else None, r, n, g, max_n, self.max_step,
+                                           self.lam, int(self.max_cos is not None), self.max_cos if self.max_cos is not None else 0.0,
+                                           self.max_gap, nat.MOTION[self.motion], self._state.data_ptr() if in_rows else None, c_in, len(in_rows),
+                                           state.data_ptr(), c_out, len(out_rows), tracks[0].data_ptr() if n else None,
+                                           tracks[1].data_ptr() if n else None, matched[0].data_ptr() if n else None,
+                                           matched[1].data_ptr() if n else None, velocity.data_ptr() if n else None, ws.data_ptr(), ws_bytes,
+                                           _raw_stream(dev))
+        if st:
+            nat.check(st, "gnncca_link_frames_motion")
+        # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
+        self._state, self._frame_rows, self._state_motion = state, out_rows, self.motion
+        return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1], velocity)
 
 
 class TrackScores:

@@ -799,6 +799,41 @@ GNNCCA_API int gnncca_link_frames_gap_ex(const int32_t* node_ptr_dev, const int3
                                          int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track, int32_t* matched_prev,
                                          int32_t* matched_gap, void* workspace, size_t workspace_bytes, gnncca_stream_t stream);
 
+/* gnncca_link_frames_motion: gnncca_link_frames_gap (mutual best) that looks for a cluster where it is HEADING.  motion must be 1 (constant
+ * velocity from the last link; 0 is gnncca_link_frames_gap itself and is not served here).  The levels, gates, masks, dcos, cost, mutual
+ * best, ties and id numbering are gnncca_link_frames_gap's, and so are the meaning of time, of n_frames = 0 and of the host arrays of frame
+ * capacities.  Two things are added, step by step:
+ *   1. Every cluster has a velocity vel fp64 [2], ground-plane units per frame.  A cluster without a predecessor has vel = (0, 0).  When
+ *      cluster a of frame t is linked at level k to cluster b of frame t - 1 - k:  vel(a) = (pos(a) - pos(b)) / (double)(k + 1)  per
+ *      component, one subtraction and one division.  No smoothing.
+ *   2. At level k the table of frame t uses, for cluster b of frame t - 1 - k,  pred(b) = pos(b) + (double)(k + 1) * vel(b)  per component,
+ *      one multiplication and one addition (no FMA);  dx = pos_x(a) - pred_x(b), dy likewise, d = sqrt(dx dx + dy dy);  admissible iff
+ *      d <= gate_k = max_step * (k + 1) (and dcos <= max_cos);  cost = d / gate_k + lam * dcos.  max_step is thus the largest deviation from
+ *      the predicted position, per frame.  A non-finite prediction gives a NaN or infinite d, which is admissible with nobody.
+ * vel(b) is known only when frame t - 1 - k has been through all its levels, so the order is frames outside, levels 0 .. max_gap inside;
+ * with every velocity zero that order gives gnncca_link_frames_gap's result (a table (k, t) depends only on tables (k' < k, t' < t) and
+ * (k' < k, t)).  The rule is causal: the result does not depend on how a sequence is cut into calls.
+ * Outputs: those of gnncca_link_frames_gap plus velocity fp64 [N][2], row-aligned with cluster_track, zero for a cluster without a
+ * predecessor and for rows at or beyond a frame's count.
+ * The state is of its OWN kind (a gap state is no valid state_in, and the other way round):  the 64-byte header of the gap state, then
+ * for C rows in all  pos fp64 [C][2], vel fp64 [C][2], track int64 [C], emb fp32 [C][R], succ int32 [C]  -- the 8-byte arrays first.
+ * state_out: gnncca_link_motion_state_bytes(C, n_frames_kept, R) bytes;  workspace: gnncca_link_motion_workspace_bytes(n_nodes, n_frames,
+ * state_rows).  Frames of up to GNNCCA_TRACK_MAX_FRAME_NODES detections: the predictions are computed on the fly, they need no LDS.
+ * THREE launches whatever max_gap is: a frame-parallel clear, ONE workgroup that walks the frames in order (levels, commits between
+ * barriers, ids from the running next_id; nothing waits for another workgroup), a frame-parallel launch for node_track and the new state.
+ * Deterministic, no host wait, no allocation: capturable.  GNNCCA_ERR_INVALID_ARG: motion != 1, the checks of gnncca_link_frames_gap.
+ * Limits: constant velocity from the LAST link only, so the prediction is wrong after a sharp turn and a track can end there and restart;
+ * no time stamps; the min-cost assignment (gnncca_link_frames_gap_ex, matching = 1) has no motion. */
+GNNCCA_API size_t gnncca_link_motion_state_bytes(int64_t capacity_rows, int32_t n_frames_kept, int32_t reid_dim);
+GNNCCA_API size_t gnncca_link_motion_workspace_bytes(int64_t n_nodes, int64_t n_frames, int64_t state_rows);
+GNNCCA_API int gnncca_link_frames_motion(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
+                                         const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                         double max_step, double lam, int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t motion,
+                                         const void* state_in, const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                                         const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track,
+                                         int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, double* velocity, void* workspace,
+                                         size_t workspace_bytes, gnncca_stream_t stream);
+
 /* ---- Identity-tracking scores over a sequence (csrc/track_score.cuh, included by csrc/identities.hip) --------------------------------
  * Joins ids int64 [N] (the caller's person id of every detection), cam int32 [N] and node_track int64 [N] (gnncca_link_frames*) over the
  * frames of a sequence, on the device and without a host wait.  No counterpart in the reference.  The rule:

@@ -3,6 +3,7 @@
 the person of every detection, tracks from FrameLinker on the ground-truth clusters of that batch.  Needs an MI355X.
 
     python tools/time_track_score.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3] [--max-gap 0] [--hide 0]
+                                     [--cross-only]
 
 Three forms, timed in alternating rounds in one process (host clock around repetitions that end in a device synchronise), the whole
 measurement run twice:
@@ -13,7 +14,11 @@ measurement run twice:
   copy     those device-to-host copies and their synchronisation alone: the floor under ANY host implementation
 and, for scale, `link`: FrameLinker's own call on the summaries of the same batch.  The two results are compared once (switched and
 counts exactly, result() by ==).  Prints one JSON line per run, then result() for max_gap 0, 1 and 3 and for both matchings on the
---hide 0.1 batch: SYNTHETIC data with ground-truth clusters, not a trained model."""
+--hide 0.1 batch: SYNTHETIC data with ground-truth clusters, not a trained model.  Last (--cross-only: nothing else), what motion='velocity'
+does to the scores where people cross each other: tests/tracking_motion_oracle.cross_sequence (12 frames, 70 and 25 people walking straight
+through a 6 x 6 arena at 0.3 .. 0.6 per frame, position noise 0.05, R = 16, seeds 0 .. 2), one JSON line per setting with the scores
+of motion none and velocity for max_step in {0.4, 1.0}, lam in {0, 1} and max_gap in {0, 2} (with max_gap 2 people are hidden with
+probability 0.12 per frame, for up to 3 frames)."""
 import argparse
 import json
 import os
@@ -28,8 +33,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import track_score_oracle as ts  # noqa: E402
+import tracking_motion_oracle as tm  # noqa: E402
 from time_tracking import make_batch  # noqa: E402
-from gnn_cca_amd.tracking import FrameLinker, TrackScorer, cluster_summaries_raw  # noqa: E402
+from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, TrackScorer, cluster_summaries_raw  # noqa: E402
 
 
 def on_device(b, a, max_gap, matching="mutual"):
@@ -98,6 +104,32 @@ def measure(a, b):
             "cap_after_a_round": score.cap, "detections_after_a_round": res["detections"], "IDSW_after_a_round": res["IDSW"]}
 
 
+def crossing_scores():
+    """TrackScorer's result for both motions on the crossing walks: one line per (persons, max_step, lam, max_gap, seed)."""
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    for persons in (70, 25):
+        for max_step in (0.4, 1.0):
+            for lam in (0.0, 1.0):
+                for gap in (0, 2):
+                    for seed in range(3):
+                        summ = tm.cross_sequence(np.random.default_rng(seed), 12, persons, 16, speed=(0.3, 0.6), noise=0.05,
+                                                 p_hide=0.12 if gap else 0.0, max_hide=gap + 1, arena=6.0)
+                        n, ptr = len(summ["rank"]), summ["node_ptr"]
+                        ones = t(np.ones(n, np.int32))
+                        s = ClusterSummaries(t(summ["count"]), t(summ["rank"]), ones, ones, t(summ["pos"]), t(summ["emb"]), ptr.tolist(),
+                                             t(ptr.astype(np.int32)))
+                        ids, cam = t(summ["person"]), t(np.zeros(n, np.int32))
+                        line = dict(persons=persons, max_step=max_step, lam=lam, max_gap=gap, seed=seed, synthetic=True)
+                        for motion in ("none", "velocity"):
+                            track = FrameLinker(max_step, lam=lam, max_gap=gap, motion=motion)(s).node_track
+                            score = TrackScorer(max_ids=1024, max_cams=8)
+                            score.add_raw(ids, cam, track, ptr.tolist(), node_ptr_dev=s.node_ptr_dev)
+                            res = score.result()
+                            line[motion] = {k: (round(res[k], 4) if isinstance(res[k], float) else res[k])
+                                            for k in ("IDSW", "IDF1", "AssA", "tracks", "tracks_per_id")}
+                        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", type=int, default=64)
@@ -109,9 +141,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--max-gap", type=int, default=0)
     ap.add_argument("--hide", type=float, default=0.0)
+    ap.add_argument("--cross-only", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_track_score.py measures on the GPU; no device is visible")
+    if a.cross_only:
+        return crossing_scores()
     b = make_batch(a.frames, a.cams, a.per, a.reid, hide=a.hide)
     for run in range(2):
         print(json.dumps(dict(measure(a, b), run=run)), flush=True)
@@ -122,6 +157,7 @@ def main():
             score = TrackScorer(max_ids=1024, max_cams=8)
             score.add_raw(ids, cam, track, hidden["node_ptr"].tolist(), node_ptr_dev=nptr)
             print(json.dumps(dict(score.result(), max_gap=gap, matching=matching, hide=0.1, synthetic=True)), flush=True)
+    crossing_scores()
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 (N = 2048, every person seen once per camera: 8 clusters of 4 per frame) with R = 2048 appearance columns.  Needs an MI355X.
 
     python tools/time_tracking.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3] [--max-gap 0] [--hide 0]
-                                  [--matching mutual|optimal] [--crowded]
+                                  [--matching mutual|optimal] [--crowded] [--motion none|velocity] [--drift 0]
 
 Two ways to the same result, timed in alternating rounds in one process (host clock around work that ends in a device synchronise):
   device   cluster summaries (2 launches) + FrameLinker (3 launches) on tensors that are already on the GPU, as a FramePipeline
@@ -17,7 +17,11 @@ frame, so that there is something to find again) against the numpy restatement o
 --matching optimal times FrameLinker(matching='optimal') (the gap path, M + 4 launches also at --max-gap 0) against
 tests/tracking_assign_oracle.py.  --crowded times, instead of all of the above, the linker's call alone on a crowded synthetic sequence
 (12 frames, 120 persons on 10 x 10, the first frame 102 single-node clusters, position only, --max-gap 1 unless given): both matchings in
-alternating rounds, each compared with its oracle once."""
+alternating rounds, each compared with its oracle once.
+--motion velocity times FrameLinker(motion='velocity') (three launches whatever --max-gap is, one workgroup walking the frames in order)
+against tests/tracking_motion_oracle.py; the ids AND the velocities are compared once per run.  --drift V selects a batch whose people
+move: every person walks a straight line at V units per frame in a direction of its own (the default batch only jitters around a point,
+so its velocities are noise)."""
 import argparse
 import json
 import os
@@ -32,11 +36,12 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import tracking_assign_oracle as ta  # noqa: E402
 import tracking_gap_oracle as tg  # noqa: E402
+import tracking_motion_oracle as tm  # noqa: E402
 import tracking_oracle as to  # noqa: E402
 from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, cluster_summaries_raw  # noqa: E402
 
 
-def make_batch(frames, cams, per, reid, seed=0, hide=0.0):
+def make_batch(frames, cams, per, reid, seed=0, hide=0.0, drift=0.0):
     rng = np.random.default_rng(seed)
     n_g = cams * per
     n = frames * n_g
@@ -44,6 +49,9 @@ def make_batch(frames, cams, per, reid, seed=0, hide=0.0):
     person = np.tile(np.tile(np.arange(per), cams), frames)
     frame_of = np.repeat(np.arange(frames), n_g)
     walk = rng.uniform(-8, 8, size=(1, per, 2)) + np.cumsum(rng.normal(0, 0.1, size=(frames, per, 2)), axis=0)
+    if drift > 0:   # (drawn only when asked for: the default batch keeps its numbers)
+        heading = rng.uniform(0, 2 * np.pi, size=per)
+        walk = walk + drift * np.arange(frames)[:, None, None] * np.stack([np.cos(heading), np.sin(heading)], -1)[None]
     xw = walk[frame_of, person, 0] + rng.normal(0, 0.05, n)
     yw = walk[frame_of, person, 1] + rng.normal(0, 0.05, n)
     look = rng.standard_normal((per, reid)).astype(np.float32)
@@ -107,17 +115,21 @@ def main():
     ap.add_argument("--hide", type=float, default=0.0)
     ap.add_argument("--matching", choices=("mutual", "optimal"), default="mutual")
     ap.add_argument("--crowded", action="store_true")
+    ap.add_argument("--motion", choices=("none", "velocity"), default="none")
+    ap.add_argument("--drift", type=float, default=0.0)
     a = ap.parse_args()
+    if a.motion == "velocity" and (a.matching == "optimal" or a.crowded):
+        raise SystemExit("--motion velocity goes with --matching mutual on the Terrace-shaped batch")
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_tracking.py measures on the GPU; no device is visible")
     if a.crowded:
         return crowded(a)
-    b = make_batch(a.frames, a.cams, a.per, a.reid, hide=a.hide)
+    b = make_batch(a.frames, a.cams, a.per, a.reid, hide=a.hide, drift=a.drift)
     dev = torch.device("cuda")
     d = {k: torch.from_numpy(b[k]).to(dev) for k in ("labels", "xw", "yw", "cam", "emb")}
     ptr_host = b["node_ptr"].tolist()
     max_step, lam = 1.0, 1.0
-    link = FrameLinker(max_step, lam=lam, max_gap=a.max_gap, matching=a.matching)
+    link = FrameLinker(max_step, lam=lam, max_gap=a.max_gap, matching=a.matching, motion=a.motion)
 
     def device_once():
         s = cluster_summaries_raw(d["labels"], ptr_host, d["xw"], d["yw"], d["cam"], d["emb"])
@@ -130,6 +142,8 @@ def main():
     def host_once(state):
         labels, xw, yw, cam, emb = copy_once()
         s = to.summaries(labels, b["node_ptr"], xw, yw, cam, emb)
+        if a.motion == "velocity":
+            return s, tm.link_motion(s, b["node_ptr"], max_step, lam, None, a.max_gap, state)
         if a.matching == "optimal":
             return s, ta.link_gap(s, b["node_ptr"], max_step, lam, None, a.max_gap, state, matching="optimal")
         if a.max_gap > 0:
@@ -143,8 +157,10 @@ def main():
     same = all(np.array_equal(getattr(s_dev, k).cpu().numpy(), s_host[k]) for k in ("count", "rank", "size", "n_cams", "pos", "emb"))
     same_ids = all(np.array_equal(getattr(t_dev, k).cpu().numpy(), t_host[k]) for k in ("cluster_track", "node_track", "matched_prev"))
     gaps = t_dev.matched_gap.cpu().numpy()
-    if a.max_gap > 0 or a.matching == "optimal":
+    if a.max_gap > 0 or a.matching == "optimal" or a.motion == "velocity":
         same_ids = same_ids and np.array_equal(gaps, t_host["matched_gap"])
+    if a.motion == "velocity":
+        same_ids = same_ids and np.array_equal(t_dev.velocity.cpu().numpy(), t_host["velocity"])
     for _ in range(10):   # warm-up: code objects, allocator
         device_once()
     torch.cuda.synchronize()
@@ -166,7 +182,7 @@ def main():
     print(json.dumps({"frames": a.frames, "cams": a.cams, "per_cam": a.per, "n_nodes": b["n"], "reid_dim": a.reid, "reps": a.reps,
                       "host_reps": a.host_reps, "device_ms": [round(v, 4) for v in dev_ms], "host_ms": [round(v, 2) for v in host_ms],
                       "copy_ms": [round(v, 4) for v in copy_ms], "summaries_equal": bool(same), "ids_equal": bool(same_ids),
-                      "tracks": int(t_dev.next_id.item()), "max_gap": a.max_gap, "hide": a.hide, "matching": a.matching,
+                      "tracks": int(t_dev.next_id.item()), "max_gap": a.max_gap, "hide": a.hide, "matching": a.matching, "motion": a.motion, "drift": a.drift,
                       "matches_per_gap": [int((gaps == k).sum()) for k in range(a.max_gap + 1)]}))
 
 
