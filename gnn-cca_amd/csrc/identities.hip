@@ -20,11 +20,14 @@
 //   3. one workgroup per frame: a matched cluster follows matched_prev back to the head of its chain (an unmatched cluster: next_id + the
 //      prefix of its frame + its rank among the unmatched; or a cluster of the carried state: its id), then node_track; the last frame's
 //      workgroup writes the new state.
+// The rule that decides a link -- distance, gate, whole-wave cosine, max_cos, cost, the tie -- is written ONCE, in link_common.cuh (included
+// below, after `fp contract(off)`), with the partner search, the ballot-scan numbering, the carried history state and the host-side checks
+// of the history entries; link_match_kernel above instantiates the search without masks, with one load per side in flight.
 // Gap-tolerant linking (gnncca_link_frames_gap: a track survives up to max_gap frames that miss it) is identities_gap.cuh, included at the
-// end of this file: its own kernels and state layout, the scan kernel shared.  Its level kernel has a second form that picks the pairs of a
+// end of this file: its level and ids kernels, the scan kernel shared.  Its level kernel has a second form that picks the pairs of a
 // frame pair by a min-cost assignment instead of mutual best (gnncca_link_frames_gap_ex, matching = 1): identities_assign.cuh, after it.
 // Scoring the track ids against ground-truth person ids over a sequence (gnncca_track_score_*) is track_score.cuh, included after it:
-// integer kernels of its own, nothing shared but this translation unit.
+// integer kernels of its own, nothing shared but this translation unit.  identities_motion.cuh (gnncca_link_frames_motion) comes last.
 // Deterministic: every fp sum has a fixed order, integer counts go through LDS atomics, no fp64 atomics.  No host wait, no allocation:
 // capturable.  The file is compiled without fp contraction: the sums, the divisions and the cost are the documented operations one by one.
 #include <hip/hip_runtime.h>
@@ -67,6 +70,12 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+}  // namespace gnncca
+
+#include "link_common.cuh"   // the pair rule, the partner search, numbering, the history state: what all linkers below share
+
+namespace gnncca {
+
 // ---- summaries, launch 1 ------------------------------------------------------------------------------------------------------------
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void summaries_kernel(const int* __restrict__ labels, int N_all, const int* __restrict__ node_ptr,
@@ -80,7 +89,7 @@ __global__ __launch_bounds__(BLOCK) void summaries_kernel(const int* __restrict_
     int* rk = s_dyn + P_lds;                                         // rank of a local root; after the sort: per cluster, start | n_cams << 12
     unsigned* keys = reinterpret_cast<unsigned*>(s_dyn + 2 * P_lds);   // rank << 12 | node, sorted
 
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int g = blockIdx.x, tid = threadIdx.x;
     int v0, n;
     if (!frame_range(node_ptr, g, N_all, v0, n)) {   // no rows to call this frame's
         if (tid == 0) count_out[g] = -1;
@@ -119,16 +128,8 @@ __global__ __launch_bounds__(BLOCK) void summaries_kernel(const int* __restrict_
 
     // ranks of the roots in ascending id
     if (tid < 64) {
-        const unsigned long long below = (1ull << lane) - 1;
-        int c = 0;
-        for (int base = 0; base < n; base += 64) {
-            const int v = base + lane;
-            const bool root = v < n && lab[v] == v;
-            const unsigned long long m = __ballot(root);
-            if (root) rk[v] = c + __popcll(m & below);
-            c += __popcll(m);
-        }
-        if (lane == 0) s_count = c;
+        const int c = wave_number(n, [&](int v) { return lab[v] == v; }, [&](int v, int k) { rk[v] = k; });
+        if (tid == 0) s_count = c;
     }
     __syncthreads();
     const int count = s_count;
@@ -224,72 +225,6 @@ __global__ __launch_bounds__(256) void summaries_emb_kernel(const float* __restr
 }
 
 // ---- linking, launch 1: mutual-best matches of a frame pair -----------------------------------------------------------------------
-struct LinkRule {
-    double max_step, lam, max_cos;
-    int need_emb, has_max_cos;
-};
-
-// out[r] = the admissible column of smallest cost for row r (ties: the smaller column), or -1.  A wave takes a row, its lanes the columns.
-template <int BLOCK>
-__device__ void best_partner(const double* __restrict__ rpos, const float* __restrict__ remb, int nr, const double* __restrict__ cpos,
-                             const float* __restrict__ cemb, int nc, int R, const LinkRule& rule, int* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int r = wave; r < nr; r += BLOCK / 64) {
-        const double rx = rpos[2 * (size_t)r], ry = rpos[2 * (size_t)r + 1];
-        double best = __builtin_inf();
-        int bi = INT_MAX;
-        for (int base = 0; base < nc; base += 64) {
-            const int c = base + lane;
-            bool cand = false;
-            double d = 0.0, dcos = 0.0;
-            if (c < nc) {
-                const double dx = rx - cpos[2 * (size_t)c], dy = ry - cpos[2 * (size_t)c + 1];
-                d = sqrt(dx * dx + dy * dy);
-                cand = d <= rule.max_step;
-            }
-            if (rule.need_emb) {
-                unsigned long long todo = __ballot(cand);   // (uniform) the pairs inside max_step: the whole wave computes each cosine
-                while (todo) {
-                    const int j = __ffsll((long long)todo) - 1;
-                    todo &= todo - 1;
-                    const float* er = remb + (size_t)r * R;
-                    const float* ec = cemb + (size_t)(base + j) * R;
-                    double dot = 0.0, na = 0.0, nb = 0.0;
-                    for (int k = lane; k < R; k += 64) {
-                        const double x = (double)er[k], y = (double)ec[k];
-                        dot += x * y;
-                        na += x * x;
-                        nb += y * y;
-                    }
-                    dot = wave_sum_f64(dot);
-                    na = wave_sum_f64(na);
-                    nb = wave_sum_f64(nb);
-                    const double v = (na == 0.0 || nb == 0.0) ? 1.0 : 1.0 - dot / (sqrt(na) * sqrt(nb));
-                    if (lane == j) dcos = v;
-                }
-                if (rule.has_max_cos) cand = cand && dcos <= rule.max_cos;
-            }
-            if (cand) {
-                const double cost = rule.need_emb ? d / rule.max_step + rule.lam * dcos : d / rule.max_step;
-                if (cost < best) best = cost, bi = c;   // (a lane's columns ascend: the smaller one stays on a tie)
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {   // lexicographic minimum of (cost, column): the same in every lane
-            const double ob = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bi, o);
-            if (ob < best || (ob == best && oi < bi)) best = ob, bi = oi;
-        }
-        if (lane == 0) out[r] = bi == INT_MAX ? -1 : bi;
-    }
-}
-
-// a frame's cluster count if the summaries hold one that fits (0 otherwise: such a frame links to nothing)
-__device__ __forceinline__ int usable_count(const int* __restrict__ count, int g, int n, int P_lds) {
-    const int c = count[g];
-    return (c >= 0 && c <= n && c <= P_lds) ? c : 0;
-}
-
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void link_match_kernel(const int* __restrict__ node_ptr, int N_all, const int* __restrict__ count,
                                                            const double* __restrict__ pos, const float* __restrict__ emb, int R, LinkRule rule,
@@ -299,34 +234,26 @@ __global__ __launch_bounds__(BLOCK) void link_match_kernel(const int* __restrict
     extern __shared__ int s_dyn[];
     int* fwd = s_dyn;           // [a] -> b, later the match itself
     int* bwd = s_dyn + P_lds;   // [b] -> a
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int g = blockIdx.x, tid = threadIdx.x;
     int v0, n;
     if (!frame_range(node_ptr, g, N_all, v0, n)) {
         if (tid == 0) n_new_ws[g] = 0;
         return;
     }
-    const int ca = usable_count(count, g, n, P_lds);
-    int cb = 0;
-    const double* ppos = nullptr;
-    const float* pemb = nullptr;
+    const LinkSide cur{pos + 2 * (size_t)v0, nullptr, emb + (size_t)v0 * R, nullptr, 0, usable_count(count, g, n, P_lds)};
+    const int ca = cur.n;
+    LinkSide prev{nullptr, nullptr, nullptr, nullptr, 0, 0};
     if (g > 0) {
-        int u0, m;
-        if (frame_range(node_ptr, g - 1, N_all, u0, m)) {
-            cb = usable_count(count, g - 1, m, P_lds);
-            ppos = pos + 2 * (size_t)u0;
-            pemb = emb + (size_t)u0 * R;
-        }
+        int row;
+        prev = side_b(g - 1, node_ptr, N_all, count, pos, nullptr, emb, R, nullptr, 0, nullptr, 0, false, P_lds, row);
     } else if (state_in) {
         const LinkHeader* h = reinterpret_cast<const LinkHeader*>(state_in);
         const int c = h->count;
-        cb = (c >= 0 && c <= state_in_cap && c <= P_lds) ? c : 0;
-        ppos = reinterpret_cast<const double*>(state_in + state_pos_off());
-        pemb = reinterpret_cast<const float*>(state_in + state_emb_off(state_in_cap));
+        prev.n = (c >= 0 && c <= state_in_cap && c <= P_lds) ? c : 0;
+        prev.pos = reinterpret_cast<const double*>(state_in + state_pos_off());
+        prev.emb = reinterpret_cast<const float*>(state_in + state_emb_off(state_in_cap));
     }
-    const double* cpos = pos + 2 * (size_t)v0;
-    const float* cemb = emb + (size_t)v0 * R;
-    best_partner<BLOCK>(cpos, cemb, ca, ppos, pemb, cb, R, rule, fwd);
-    best_partner<BLOCK>(ppos, pemb, cb, cpos, cemb, ca, R, rule, bwd);
+    mutual_best<BLOCK, 1, false>(cur, prev, 1.0, R, rule, fwd, bwd);
     __syncthreads();
     for (int a = tid; a < n; a += BLOCK) {
         int m = -1;
@@ -339,18 +266,7 @@ __global__ __launch_bounds__(BLOCK) void link_match_kernel(const int* __restrict
     __syncthreads();   // (fwd is overwritten only after every read of it above)
     for (int a = tid; a < ca; a += BLOCK) fwd[a] = matched_prev[v0 + a];   // each thread reads what it wrote itself
     __syncthreads();
-    if (tid < 64) {   // the unmatched clusters, numbered in rank order
-        const unsigned long long below = (1ull << lane) - 1;
-        int c = 0;
-        for (int base = 0; base < ca; base += 64) {
-            const int a = base + lane;
-            const bool fresh = a < ca && fwd[a] < 0;
-            const unsigned long long mk = __ballot(fresh);
-            if (fresh) new_rank_ws[v0 + a] = c + __popcll(mk & below);
-            c += __popcll(mk);
-        }
-        if (lane == 0) n_new_ws[g] = c;
-    }
+    number_fresh(fwd, ca, new_rank_ws + v0, n_new_ws + g);   // the unmatched clusters, numbered in rank order
 }
 
 // ---- linking, launch 2: base[g] = the unmatched clusters of the frames before g (base[G]: all of them) -------------------------------
@@ -411,10 +327,7 @@ __global__ __launch_bounds__(BLOCK) void link_ids_kernel(const int* __restrict__
     }
     for (int c = ca + tid; c < n; c += BLOCK) cluster_track[v0 + c] = -1;
     __syncthreads();
-    for (int v = tid; v < n; v += BLOCK) {
-        const int r = rank[v0 + v];
-        node_track[v0 + v] = (r >= 0 && r < ca) ? s_track[r] : -1;
-    }
+    write_node_tracks<BLOCK>(rank + v0, n, ca, s_track, node_track + v0);
     if (g != G - 1) return;
     const int cs = ca <= state_out_cap ? ca : 0;
     if (tid == 0) {
@@ -497,15 +410,11 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
     if (n_nodes < 0 || n_frames < 0 || reid_dim < 0 || state_in_capacity < 0 || state_out_capacity < 0) return GNNCCA_ERR_INVALID_ARG;
     if (max_frame_nodes < 0 || max_frame_nodes > kTrackMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
     if (state_in && state_in_capacity > kTrackMaxNodes) return GNNCCA_ERR_INVALID_ARG;
-    if (!(max_step > 0.0) || !(max_step < __builtin_inf()) || !(lam >= 0.0) || !(lam < __builtin_inf())) return GNNCCA_ERR_INVALID_ARG;
-    if (has_max_cos && !(max_cos >= 0.0 && max_cos <= 2.0)) return GNNCCA_ERR_INVALID_ARG;
+    LinkRule rule;
+    if (!link_rule(max_step, lam, has_max_cos, max_cos, rule)) return GNNCCA_ERR_INVALID_ARG;
     if (n_frames == 0) return GNNCCA_OK;   // nothing to link: the caller keeps its state
     if (!node_ptr_dev || !count || !state_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
     if (n_nodes > 0 && (!rank || !pos || !cluster_track || !node_track || !matched_prev)) return GNNCCA_ERR_INVALID_ARG;
-    LinkRule rule;
-    rule.max_step = max_step, rule.lam = lam, rule.max_cos = max_cos;
-    rule.has_max_cos = has_max_cos != 0;
-    rule.need_emb = lam != 0.0 || has_max_cos != 0;
     if (rule.need_emb && reid_dim > 0 && n_nodes > 0 && !emb) return GNNCCA_ERR_INVALID_ARG;
     if (workspace_bytes < gnncca_link_workspace_bytes(n_nodes, n_frames)) return GNNCCA_ERR_WORKSPACE;
     if (n_nodes >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
@@ -532,10 +441,10 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
 
 }  // extern "C"
 
-#include "identities_gap.cuh"   // gnncca_link_frames_gap: the gap-tolerant linker (its own kernels; nothing above changes)
+#include "identities_gap.cuh"   // gnncca_link_frames_gap: the gap-tolerant linker
 
 #include "identities_assign.cuh"   // gnncca_link_frames_gap_ex: the level kernel's min-cost-assignment form (matching = 1)
 
-#include "track_score.cuh"   // gnncca_track_score_*: identity-tracking scores over a sequence (its own kernels; nothing above changes)
+#include "track_score.cuh"   // gnncca_track_score_*: identity-tracking scores over a sequence (its own kernels)
 
 #include "identities_motion.cuh"   // gnncca_link_frames_motion: the gap-tolerant linker with a velocity prediction (one walking workgroup)

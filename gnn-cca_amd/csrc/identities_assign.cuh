@@ -1,6 +1,6 @@
 // identities_assign.cuh -- matching = 1 of gnncca_link_frames_gap_ex (FrameLinker(matching='optimal')), included by identities.hip after
-// identities_gap.cuh: the second form of the level kernel.  Levels, gates, masks, cost, the init / scan / ids kernels and the carried
-// state are identities_gap.cuh's, untouched; only the choice of pairs inside a workgroup's (A, B) table differs: the one-to-one set of
+// identities_gap.cuh: the second form of the level kernel.  Levels, gates, masks, the init / scan / ids kernels and the carried state are
+// identities_gap.cuh's, the cost of a pair is link_common.cuh's pair_rule (the one the mutual-best search calls); only the choice of pairs inside a workgroup's (A, B) table differs: the one-to-one set of
 // admissible pairs that minimises the sum of cost - miss_cost (leaving a pair's clusters unlinked is worth 0), found by shortest
 // augmenting paths in an order that is part of the contract (include/gnncca_mpn.h has it in full; tests/tracking_assign_oracle.py
 // restates it as loops and the kernel matches it bit for bit: every fp64 operation is elementwise, the file has `fp contract(off)`, and
@@ -8,7 +8,7 @@
 // One workgroup per frame, as in gap_level_kernel:
 //   1. wave 0 ranks the clusters of frame t without a predecessor (A, n of them), wave 1 those of frame t - 1 - k without a successor
 //      (B, m of them): ballot scans into LDS;
-//   2. all waves build W [n][m] in LDS, a wave per row, its lanes the columns, best_partner_masked's whole-wave cosine: W = cost -
+//   2. all waves build W [n][m] in LDS, a wave per row, its lanes the columns (through ib[]), pair_rule's whole-wave cosine: W = cost -
 //      miss_cost for an admissible pair whose cost is not NaN, +inf otherwise ((inf - u) - v = inf is never < minv: not an edge);
 //   3. wave 0 alone inserts the rows 0 .. n - 1 over m + n columns (column m + i: row i stays unlinked, 0 for row i, +inf for the
 //      others), columns over lanes, the duals and the tree in LDS, the minimum by shuffles: no workgroup barrier inside the loop.  LDS
@@ -17,7 +17,8 @@
 //      Every loop is bounded by numbers fixed at launch: n rows, at most min(n, m) + 1 tree steps per row (a step that does not end the
 //      row's search marks a matched REAL column, of which there are at most min(n - 1, m): an unlinked column is reached only from its
 //      own row and only while it is free), and a path of at most as many columns to flip;
-//   4. wave 0 writes the predecessor records and successor flags; then, at the last level, the numbering of gap_level_kernel.
+//   4. wave 0 writes the predecessor records and successor flags; then, at the last level, the numbering of gap_level_kernel
+//      (number_fresh).
 // LDS, from numbers the host knows (P = the power of two >= the largest frame of the batch and of the history, >= 64):  W 8 P^2, v and
 // minv 2 x 16 P, u 8 P, p / way / used 3 x 8 P, A / B ranks 2 x 4 P, the numbering's flags 4 P, two counts = 8 P^2 + 76 P + 16 bytes:
 // 37,648 at P = 64, 140,816 of the 163,840 at P = 128 = GNNCCA_TRACK_MAX_OPTIMAL_FRAME_NODES.  Rows of W are P * 8 bytes and every
@@ -31,21 +32,6 @@ __host__ __device__ inline size_t assign_lds_bytes(int P) { return (size_t)8 * P
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (no instruction: the compiler keeps LDS accesses on their side of it)
     __builtin_amdgcn_wave_barrier();
-}
-
-// ranks r < c with mask[r] == free, in ascending order -> list; returns their number (one wave, the same in every lane)
-__device__ __forceinline__ int wave_compact(const int* mask, int free, int c, int* list) {
-    const int lane = threadIdx.x & 63;
-    const unsigned long long below = (1ull << lane) - 1;
-    int k = 0;
-    for (int base = 0; base < c; base += 64) {
-        const int r = base + lane;
-        const bool on = r < c && mask[r] == free;
-        const unsigned long long mk = __ballot(on);
-        if (on) list[k + __popcll(mk & below)] = r;
-        k += __popcll(mk);
-    }
-    return k;
 }
 
 // `rule.max_step` is the gate of THIS level, as in gap_level_kernel.
@@ -70,32 +56,17 @@ __global__ __launch_bounds__(BLOCK) void gap_level_assign_kernel(const int* __re
     int* fwd = ib + P;                                 // [P] the frame's final gaps (last level)
     int* cnt = fwd + P;                                // n, m
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int S = in.off[in.n];
     int v0, nn;
     if (!frame_range(node_ptr, g, N_all, v0, nn)) {
         if (last_level && tid == 0) n_new_ws[g] = 0;
         return;
     }
     const int ca = usable_count(count, g, nn, P);
-    int cb = 0, brow = 0;   // brow: the combined row of B's rank 0
-    const double* ppos = nullptr;
-    const float* pemb = nullptr;
-    const int s = g - 1 - level;
-    if (s >= 0) {
-        int u0, mm;
-        if (frame_range(node_ptr, s, N_all, u0, mm)) {
-            cb = usable_count(count, s, mm, P);
-            ppos = pos + 2 * (size_t)u0;
-            pemb = emb + (size_t)u0 * R;
-            brow = S + u0;
-        }
-    } else if (state_in && in.n + s >= 0) {
-        const int f = in.n + s;
-        cb = gap_hist_count(state_in, in, f, P);
-        brow = in.off[f];
-        ppos = reinterpret_cast<const double*>(state_in + gap_pos_off()) + 2 * (size_t)brow;
-        pemb = reinterpret_cast<const float*>(state_in + gap_emb_off(S)) + (size_t)brow * R;
-    }
+    int brow;   // the combined row of B's rank 0
+    const LinkSide sb = side_b(g - 1 - level, node_ptr, N_all, count, pos, nullptr, emb, R, state_in, in.n, in.off, in.off[in.n], false, P, brow);
+    const int cb = sb.n;
+    const double* ppos = sb.pos;
+    const float* pemb = sb.emb;
     if (ca > 0 && cb > 0) {   // (uniform; ca, cb <= P)
         if (wave == 0) {
             const int k = wave_compact(matched_gap + v0, -1, ca, ia);
@@ -115,44 +86,13 @@ __global__ __launch_bounds__(BLOCK) void gap_level_assign_kernel(const int* __re
                 const double rx = cpos[2 * (size_t)a], ry = cpos[2 * (size_t)a + 1];
                 for (int base = 0; base < m; base += 64) {
                     const int j = base + lane;
-                    bool cand = false;
-                    double d = 0.0, dcos = 0.0;
-                    if (j < m) {
-                        const int b = ib[j];
-                        const double dx = rx - ppos[2 * (size_t)b], dy = ry - ppos[2 * (size_t)b + 1];
-                        d = sqrt(dx * dx + dy * dy);
-                        cand = d <= rule.max_step;
-                    }
-                    if (rule.need_emb) {
-                        unsigned long long todo = __ballot(cand);   // (uniform) the pairs inside the gate: the whole wave computes each cosine
-                        while (todo) {
-                            const int jj = __ffsll((long long)todo) - 1;
-                            todo &= todo - 1;
-                            const float* er = cemb + (size_t)a * R;
-                            const float* ec = pemb + (size_t)ib[base + jj] * R;
-                            double dot = 0.0, na = 0.0, nb = 0.0;
-                            for (int k = lane; k < R; k += 64) {
-                                const double x = (double)er[k], y = (double)ec[k];
-                                dot += x * y;
-                                na += x * x;
-                                nb += y * y;
-                            }
-                            dot = wave_sum_f64(dot);
-                            na = wave_sum_f64(na);
-                            nb = wave_sum_f64(nb);
-                            const double c = (na == 0.0 || nb == 0.0) ? 1.0 : 1.0 - dot / (sqrt(na) * sqrt(nb));
-                            if (lane == jj) dcos = c;
-                        }
-                        if (rule.has_max_cos) cand = cand && dcos <= rule.max_cos;
-                    }
-                    if (j < m) {
-                        double w = inf;
-                        if (cand) {
-                            const double cost = rule.need_emb ? d / rule.max_step + rule.lam * dcos : d / rule.max_step;
-                            if (cost == cost) w = cost - miss_cost;   // (a NaN cost: not admissible)
-                        }
-                        W[(size_t)i * P + j] = w;
-                    }
+                    double cx = 0.0, cy = 0.0, w = inf;
+                    if (j < m) cx = ppos[2 * (size_t)ib[j]], cy = ppos[2 * (size_t)ib[j] + 1];
+                    pair_rule<1>(j < m, rx, ry, cx, cy, cemb + (size_t)a * R, [&](int jj) { return pemb + (size_t)ib[base + jj] * R; }, R, rule,
+                                 [&](double cost) {
+                                     if (cost == cost) w = cost - miss_cost;   // (a NaN cost: not admissible)
+                                 });
+                    if (j < m) W[(size_t)i * P + j] = w;
                 }
             }
             __syncthreads();
@@ -182,15 +122,10 @@ __global__ __launch_bounds__(BLOCK) void gap_level_assign_kernel(const int* __re
                             }
                             if (mv < best) best = mv, bj = j;   // (a lane's columns ascend: the smaller one stays on a tie)
                         }
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) {   // lexicographic minimum of (minv, column): the same in every lane
-                            const double ob = __shfl_xor(best, o);
-                            const int oj = __shfl_xor(bj, o);
-                            if (ob < best || (ob == best && oj < bj)) best = ob, bj = oj;
-                        }
-                        if (bj == INT_MAX) break;   // (uniform; cannot be: row i0's own unlinked column is free)
-                        const double delta = best;
-                        j1 = bj;
+                        const ValueIndex least = wave_min_lex(best, bj);   // of (minv, column)
+                        if (least.i == INT_MAX) break;   // (uniform; cannot be: row i0's own unlinked column is free)
+                        const double delta = least.v;
+                        j1 = least.i;
                         wave_sync();
                         for (int j = lane; j < nc; j += 64) {
                             if (used[j]) {
@@ -243,18 +178,7 @@ __global__ __launch_bounds__(BLOCK) void gap_level_assign_kernel(const int* __re
     __syncthreads();   // (wave 0's records are visible to the workgroup)
     for (int a = tid; a < ca; a += BLOCK) fwd[a] = matched_gap[v0 + a];
     __syncthreads();
-    if (tid < 64) {   // the clusters without a predecessor, numbered in rank order
-        const unsigned long long below = (1ull << lane) - 1;
-        int c = 0;
-        for (int base = 0; base < ca; base += 64) {
-            const int a = base + lane;
-            const bool fresh = a < ca && fwd[a] < 0;
-            const unsigned long long mk = __ballot(fresh);
-            if (fresh) new_rank_ws[v0 + a] = c + __popcll(mk & below);
-            c += __popcll(mk);
-        }
-        if (lane == 0) n_new_ws[g] = c;
-    }
+    number_fresh(fwd, ca, new_rank_ws + v0, n_new_ws + g);   // the clusters without a predecessor, numbered in rank order
 }
 
 static int assign_level_launch(hipStream_t st, int n_frames, int P, const int* node_ptr_dev, int n_nodes, const int* count, const double* pos,

@@ -304,10 +304,8 @@ class FrameLinker:
                 e64, e32 = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
                 vel = torch.empty((0, 2), dtype=torch.float64, device=dev) if self.motion == "velocity" else None
                 return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone(), vel)
-            if self.motion == "velocity":
-                return self._link_motion(lib, s, dev, sizes, g, n, max_n, r)
-            if self.max_gap > 0 or self.matching == "optimal":
-                return self._link_gap(lib, s, dev, sizes, g, n, max_n, r)
+            if self.motion == "velocity" or self.max_gap > 0 or self.matching == "optimal":
+                return self._link_history(lib, s, dev, sizes, g, n, max_n, r)
             cap = int(sizes[-1])
             state = torch.empty(lib.gnncca_link_state_bytes(cap, r), dtype=torch.uint8, device=dev)
             tracks = torch.empty((2, n), dtype=torch.int64, device=dev)   # cluster_track | node_track
@@ -326,55 +324,40 @@ class FrameLinker:
         self._state, self._cap, self._state_motion = state, cap, self.motion
         return Tracks(tracks[0], tracks[1], matched, state[:8].view(torch.int64), state)
 
-    def _link_gap(self, lib, s, dev, sizes, g, n, max_n, r):
-        """The max_gap > 0 or matching='optimal' call (inside _on(dev), g > 0): everything is sized from host-known node counts, nothing
-        waits for the GPU."""
+    def _link_history(self, lib, s, dev, sizes, g, n, max_n, r):
+        """The call of every linker whose state is a history of frames (inside _on(dev), g > 0) -- max_gap > 0, matching='optimal',
+        motion='velocity': everything is sized from host-known node counts, nothing waits for the GPU.  The entries differ in the kind of
+        their state and workspace, and with motion (three launches do it all) a velocity per row comes back."""
+        moving = self.motion == "velocity"
+        state_bytes, workspace_bytes = ((lib.gnncca_link_motion_state_bytes, lib.gnncca_link_motion_workspace_bytes) if moving else
+                                        (lib.gnncca_link_gap_state_bytes, lib.gnncca_link_gap_workspace_bytes))
         in_rows = self._frame_rows
         out_rows = (in_rows + [int(v) for v in sizes])[-(self.max_gap + 1):]
         c_in, c_out = (C.c_int32 * max(len(in_rows), 1))(*in_rows), (C.c_int32 * len(out_rows))(*out_rows)
-        state = torch.empty(lib.gnncca_link_gap_state_bytes(sum(out_rows), len(out_rows), r), dtype=torch.uint8, device=dev)
+        state = torch.empty(state_bytes(sum(out_rows), len(out_rows), r), dtype=torch.uint8, device=dev)
         tracks = torch.empty((2, n), dtype=torch.int64, device=dev)   # cluster_track | node_track
         matched = torch.empty((2, n), dtype=torch.int32, device=dev)   # matched_prev | matched_gap
-        ws_bytes = lib.gnncca_link_gap_workspace_bytes(n, g, sum(in_rows))
+        velocity = torch.empty((n, 2), dtype=torch.float64, device=dev) if moving else None
+        ws_bytes = workspace_bytes(n, g, sum(in_rows))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         head = (s.node_ptr_dev.data_ptr(), s.count.data_ptr(), s.rank.data_ptr() if n else None, s.pos.data_ptr() if n else None,
                 s.emb.data_ptr() if r and n else None, r, n, g, max_n, self.max_step, self.lam, int(self.max_cos is not None),
                 self.max_cos if self.max_cos is not None else 0.0, self.max_gap)
         tail = (self._state.data_ptr() if in_rows else None, c_in, len(in_rows), state.data_ptr(), c_out, len(out_rows),
                 tracks[0].data_ptr() if n else None, tracks[1].data_ptr() if n else None, matched[0].data_ptr() if n else None,
-                matched[1].data_ptr() if n else None, ws.data_ptr(), ws_bytes, _raw_stream(dev))
-        if self.matching == "optimal":
-            st = lib.gnncca_link_frames_gap_ex(*head, nat.MATCHING[self.matching], self.miss_cost, *tail)
-        else:   # 'mutual': the entry, and with it the code, it has always run
-            st = lib.gnncca_link_frames_gap(*head, *tail)
+                matched[1].data_ptr() if n else None)
+        end = (ws.data_ptr(), ws_bytes, _raw_stream(dev))
+        if moving:
+            name = "gnncca_link_frames_motion"
+            st = lib.gnncca_link_frames_motion(*head, nat.MOTION[self.motion], *tail, velocity.data_ptr() if n else None, *end)
+        elif self.matching == "optimal":
+            name = "gnncca_link_frames_gap"
+            st = lib.gnncca_link_frames_gap_ex(*head, nat.MATCHING[self.matching], self.miss_cost, *tail, *end)
+        else:   # 'mutual': the entry it has always run
+            name = "gnncca_link_frames_gap"
+            st = lib.gnncca_link_frames_gap(*head, *tail, *end)
         if st:
-            nat.check(st, "gnncca_link_frames_gap")
-        # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
-        self._state, self._frame_rows, self._state_motion = state, out_rows, self.motion
-        return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1])
-
-    def _link_motion(self, lib, s, dev, sizes, g, n, max_n, r):
-        """The motion='velocity' call (inside _on(dev), g > 0), with any max_gap: like _link_gap everything is sized from host-known node
-        counts and nothing waits for the GPU; the state is of its own kind (it carries the velocities) and three launches do it all."""
-        in_rows = self._frame_rows
-        out_rows = (in_rows + [int(v) for v in sizes])[-(self.max_gap + 1):]
-        c_in, c_out = (C.c_int32 * max(len(in_rows), 1))(*in_rows), (C.c_int32 * len(out_rows))(*out_rows)
-        state = torch.empty(lib.gnncca_link_motion_state_bytes(sum(out_rows), len(out_rows), r), dtype=torch.uint8, device=dev)
-        tracks = torch.empty((2, n), dtype=torch.int64, device=dev)   # cluster_track | node_track
-        matched = torch.empty((2, n), dtype=torch.int32, device=dev)   # matched_prev | matched_gap
-        velocity = torch.empty((n, 2), dtype=torch.float64, device=dev)
-        ws_bytes = lib.gnncca_link_motion_workspace_bytes(n, g, sum(in_rows))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        st = lib.gnncca_link_frames_motion(s.node_ptr_dev.data_ptr(), s.count.data_ptr(), s.rank.data_ptr() if n else None,
-                                           s.pos.data_ptr() if n else None, s.emb.data_ptr() if r and n else None, r, n, g, max_n, self.max_step,
-                                           self.lam, int(self.max_cos is not None), self.max_cos if self.max_cos is not None else 0.0,
-                                           self.max_gap, nat.MOTION[self.motion], self._state.data_ptr() if in_rows else None, c_in, len(in_rows),
-                                           state.data_ptr(), c_out, len(out_rows), tracks[0].data_ptr() if n else None,
-                                           tracks[1].data_ptr() if n else None, matched[0].data_ptr() if n else None,
-                                           matched[1].data_ptr() if n else None, velocity.data_ptr() if n else None, ws.data_ptr(), ws_bytes,
-                                           _raw_stream(dev))
-        if st:
-            nat.check(st, "gnncca_link_frames_motion")
+            nat.check(st, name)
         # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
         self._state, self._frame_rows, self._state_motion = state, out_rows, self.motion
         return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1], velocity)
