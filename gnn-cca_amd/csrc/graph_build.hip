@@ -25,6 +25,7 @@
 
 #include "hip_try.h"
 #include "wave_reduce.cuh"
+#include "with_flag.h"
 
 namespace gnncca {
 
@@ -428,7 +429,7 @@ using namespace gnncca;
 
 // ---- what the host code of the edge entry points shares ----
 // The template arguments of a launch chosen at run time: f(std::integral_constant<int, MODE>) for the edge-attribute mode (the callers have
-// checked its range), f(std::true_type / std::false_type) for a flag.
+// checked its range), f(std::true_type / std::false_type) for a flag (with_flag.h).
 template <class F>
 static void with_mode(int32_t mode, F&& f) {
     switch (mode) {
@@ -437,8 +438,6 @@ static void with_mode(int32_t mode, F&& f) {
         default: f(std::integral_constant<int, GNNCCA_EDGE_ATTR_ONLY_DIST>{}); break;
     }
 }
-template <class F>
-static void with_flag(bool flag, F&& f) { flag ? f(std::true_type{}) : f(std::false_type{}); }
 template <class Ground>
 constexpr int rank_of(Ground) { return Ground::value ? GNNCCA_RANK_BY_GROUND : GNNCCA_RANK_BY_REID; }   // (the callers have checked rank_by)
 

@@ -1,5 +1,6 @@
-// internal.h -- layouts and host functions shared by the library's translation units: the host packer (pack.cpp), the inference
-// kernels (mpn_forward.hip), post-processing (mpn_post.hip), training (mpn_train.hip) and the smaller HIP units.  Plain C++, no HIP types.
+// internal.h -- layouts and host functions shared by the library's translation units: the host packer (pack.cpp), the node encoder's
+// route (enc_route.cpp), the inference kernels (mpn_forward.hip), post-processing (mpn_post.hip), training (mpn_train.hip) and the smaller
+// HIP units.  Plain C++, no HIP types.
 // Not part of the public ABI (include/gnncca_mpn.h is).
 #pragma once
 #include <stddef.h>
@@ -179,6 +180,76 @@ int ell_stride(const gnncca_mpn_dims* d, int64_t n, int64_t e);
 // partial slabs for the tail kernel.  One workgroup per CU (144 KB of LDS), so the cost is counted in ROUNDS of 256 workgroups.
 int enc_lds_ksplit(int64_t n_nodes, int K);
 Workspace carve(const gnncca_mpn_dims* d, int64_t n, int64_t e);
+
+// ---- the node encoder's route (enc_route.cpp) ------------------------------------------------------------------------------------
+// Which GEMM form every encoder layer but the last runs on, where the graph plan goes and which tail sums the slabs: decided ONCE
+// per forward by encoder_route(), a pure host function, and carried out by launch_node_encoder (mpn_forward.hip), which compares no
+// sizes.  tests/test_encoder_route.py pins the table; DESIGN.md 4.1 has it.
+enum EncForm : int {
+    kEncPlanGemm = 0,  // enc_gemm_plan_kernel: f32 MFMA GEMM, `slabs` k-slices of `kslice`; the plan rides on layer 0
+    kEncSlices,        // enc_gemm_f16_slices{8,4,2}_kernel: fp16-split, 32-row tiles x `slabs` slices `kslice` deep; the plan rides
+    kEncD128,          // enc_gemm_split_direct_kernel: split-bf16, 128-row workgroups x `slabs`; the plan rides
+    kEncR32Bf16,       // enc_gemm_rows32_fused_kernel<SPLIT3, nst>: 32-row workgroups, un-split, fused epilogue
+    kEncR32F16,        // enc_gemm_f16_rows32_kernel: the same on the fp16-split arithmetic
+    kEncLdsBf16,       // enc_gemm_split_lds_kernel<fused, SPLIT3>: 256-row workgroups; fused epilogue or `slabs` k-slices
+    kEncLdsF16,        // enc_gemm_f16_fused_kernel / enc_gemm_f16_split_kernel: the same on the fp16-split arithmetic
+};
+enum EncPlanPlace : int {
+    kPlanNone = 0,     // E == 0: no plan
+    kPlanRides,        // extra workgroups of the first GEMM launch
+    kPlanBefore,       // plan_only launch in front of a fused GEMM, whose last workgroup finishes the plan
+    kPlanAfter,        // plan_only launch behind the GEMM (256-row forms that are not fused); the tail finishes it
+};
+enum EncTail : int {
+    kTailNone = 0,     // the GEMM's fused epilogue wrote h0 and the step-1 projections
+    kTailFast,         // enc_tail_fast_kernel, `tail_npw` nodes per workgroup
+    kTailMfma,         // enc_tail_mfma_kernel, 32 nodes per workgroup
+    kTailLds,          // enc_tail_kernel with `tail_lds` bytes of dynamic LDS
+    kTailRefused,      // that kernel would need more than 160 KB: GNNCCA_ERR_UNSUPPORTED where the tail would have been launched
+};
+constexpr int kEncSliceMaxK = 256;   // deepest k-slice of kEncSlices: a workgroup's x tile is 32 rows x 256 floats = 32 KB of LDS
+// The measured thresholds of the route and the diagnostics that force an arm: the member initialisers are the defaults (the one place
+// they are written), enc_tuning() is the defaults overridden by the GNNCCA_* switches of DESIGN.md 11, read once per process.
+struct EncTuning {
+    int split_min = 384;                       // GNNCCA_GEMM_SPLIT_MIN: first node count of the split-bf16 forms
+    int lds_min = 6144;                        // GNNCCA_GEMM_LDS_MIN:   first node count of the 256-row forms
+    int r32f_min = 4096, r32f_max = 8192;      // GNNCCA_GEMM_R32F_MIN / _MAX: node range of kEncR32F16
+    int slices_min = 1, slices_max = 4095;     // GNNCCA_GEMM_SLICES_MIN / _MAX: node range of kEncSlices
+    int slices_nks = 16, slices_wgs = 256;     // GNNCCA_GEMM_SLICES_NKS / _WGS: cap of the slice count; workgroups one round may hold
+    int tail_mfma_min = 2560;                  // GNNCCA_TAIL_MFMA_MIN:  first node count of kTailMfma
+    bool gemm_bf16 = false;                    // GNNCCA_GEMM_BF16:      the bf16 forms as the A/B reference of the fp16-split GEMMs
+    int f16_force_arm = 0;                     // GNNCCA_GEMM_F16_ARM:   every tile / wave of the fp16-split GEMMs on its fallback arm (tests)
+    int f16_x_nt = -1;                         // GNNCCA_GEMM_F16_XNT:   0 / 1 forces the non-temporal x stream off / on
+};
+const EncTuning& enc_tuning();
+struct EncRouteIn {
+    const gnncca_mpn_dims* d;
+    const BlobHeader* hdr;
+    const Workspace* ws;
+    int N, E;
+    uint32_t options;
+    bool dropping;                    // train-mode Dropout active
+    bool trace_h;                     // the caller asked for the encoder output (gnncca_trace::h_enc)
+    bool x_aligned, ws_aligned;       // 16-byte alignment of x and of the workspace base
+    int plan_blocks, plan_span;       // plan.cuh: plan_num_blocks(E), plan_span(edge_index, E)
+};
+struct EncGemmRoute {
+    int form, K, O;
+    int slabs;     // k-slices the launch writes = slabs the following reduce / tail sums (<= Workspace::ksplit)
+    int kslice;    // depth of one slice
+    int nst;       // kEncR32Bf16: pipeline stages, 8 or 4
+    int vec_ok;    // kEncPlanGemm: rows allow 16-byte loads
+};
+struct EncRoute {
+    int n_gemm;
+    EncGemmRoute gemm[GNNCCA_MAX_LAYERS];
+    bool split3, fused;               // three of the six bf16 products; layer 0's epilogue finishes the encoder (tail == kTailNone)
+    int x_nt, force_arm;              // fp16-split forms: non-temporal x stream; EncTuning::f16_force_arm
+    int plan_place, plan_span, plan_wgs;   // plan_wgs: workgroups the plan adds to the GEMM launch / its own launch has
+    int tail, tail_npw, tail_vec;     // tail_vec: TailParams::vec_reduce
+    size_t tail_lds;
+};
+EncRoute encoder_route(const EncRouteIn& in, const EncTuning& t);
 
 // Workspace of the fused backward (gnncca_mpn_backward*, mpn_train.hip): byte offsets, all multiples of 256.  `d` must have passed
 // backward_ok (a two-layer node encoder); F1 is its first layer's width.

@@ -1,9 +1,10 @@
 """Node-encoder shapes of the fast family (csrc/pack.cpp: kFamilyMfma32x6) beyond the shipped `in -> 128 -> 32`.
 
-The family takes any node encoder of up to GNNCCA_MAX_LAYERS layers no wider than 1024 and any node_in_dim.  Its first layer has five
-GEMM forms in csrc/mpn_forward.hip, three of which split K into partial slabs summed by a later kernel (reduce_bias_act_kernel for
-encoders of three or more layers, the encoder tail otherwise); which form runs depends on N, K, the first layer's width, the depth
-and the options.  Every case here builds a model from torch.manual_seed and, on a sparse ring graph:
+The family takes any node encoder of up to GNNCCA_MAX_LAYERS layers no wider than 1024 and any node_in_dim.  Which GEMM form its
+first layer runs on, how many partial slabs that launch writes (summed by reduce_bias_act_kernel for encoders of three or more layers,
+by the encoder tail otherwise), where the graph plan goes and which tail follows is decided by encoder_route() (csrc/enc_route.cpp)
+from N, K, the first layer's width, the depth and the options; tests/test_encoder_route.py pins that table on the CPU.  Every case here builds a
+model from torch.manual_seed and, on a sparse ring graph:
 
   * asserts from the packed header that the model really is on the fast family;
   * judges the encoder output (trace['h_enc']) against an fp64 evaluation, within 4x the fp32 oracle's own error;
@@ -13,15 +14,13 @@ and the options.  Every case here builds a model from torch.manual_seed and, on 
   * checks the device-packed weight blob against the host packer's byte for byte (pack kinds 2 and 4, the split weight images of the
     first layer, included).
 
-Routes of the first encoder layer (mpn_forward.hip), by the case parameters:
-  PLAN    f32 plan GEMM (enc_gemm_plan_kernel), ws.ksplit slabs: below 384 nodes when K is not a power of two, or any N when the
-          shape has no split weights (first layer not 128 wide, K % 32 != 0, or a one-layer encoder);
-  SLICES  fp16-split slices (enc_f16_slices.cuh), nks <= ws.ksplit slabs: 128-wide first layer, K a power of two >= 64, N <= 4095;
-  D128    128-row split-bf16 GEMM (enc_gemm_split_direct_kernel): 384 ... 6143 nodes where SLICES does not apply;
-  R32     32-row un-split GEMM with the fused epilogue (fp16-split; bf16 under encoder_unsplit): 4096 ... 8192 nodes (any N >= 4096
-          under encoder_unsplit), two-layer encoder 128 -> 32 without reattach_initial_nodes, K % 256 == 0;
-  LDS256  256-row GEMM from 6144 nodes: split-K + a tail / reduce, or un-split with the fused epilogue (51233 nodes);
-and of the tail that sums the slabs: MFMA (from 2560 nodes, two-layer 128-wide encoder) or wave-per-node (everything else)."""
+The forms (csrc/internal.h: EncForm) as the docstrings below name them:
+  PLAN    kEncPlanGemm: the f32 plan GEMM in Workspace::ksplit slabs, and every GEMM layer behind the first;
+  SLICES  kEncSlices: fp16-split slices, nks <= Workspace::ksplit slabs;
+  D128    kEncD128: the 128-row split-bf16 GEMM;
+  R32     kEncR32F16 (kEncR32Bf16 under encoder_unsplit): 32-row un-split GEMM with the fused epilogue, no tail launch;
+  LDS256  kEncLdsF16 / kEncLdsBf16: the 256-row GEMM, split-K + a tail / reduce, or un-split with the fused epilogue;
+and the tails (EncTail): MFMA (kTailMfma), fast (kTailFast) or wave-per-node through LDS (kTailLds)."""
 import copy
 import os
 import struct
@@ -96,8 +95,8 @@ def _check(node_in, fc, n_nodes, reattach=False, products=6, unsplit=False):
     assert_poison_invariant(m, d, out)
 
 
-# The deep encoders of the slab-count fix: the first layer writes ks_split slabs (SLICES: nks, D128 / LDS256: the split its launch
-# picked) and reduce_bias_act_kernel must sum exactly those, not ws.ksplit.  With 2048 -> 128 -> 64 -> 32:
+# The deep encoders of the slab-count fix: the first layer writes EncGemmRoute::slabs slabs (SLICES: nks, D128 / LDS256: the split its
+# form picked) and reduce_bias_act_kernel must sum exactly those, not ws.ksplit.  With 2048 -> 128 -> 64 -> 32:
 #   64, 301 nodes    SLICES, 16 slabs written of ws.ksplit = 32
 #   1229             SLICES, 8 of 16
 #   3007             SLICES, 8 of 8
@@ -181,6 +180,40 @@ def test_profiled_kernel_sequence(fc, n_nodes, want):
         _, times = m.forward_profiled(d)
     kinds = [k for k, _ in times if not k.startswith("step")]
     assert kinds == want, kinds
+
+
+_G, _P, _R, _T = "enc_gemm", "plan", "enc_reduce", "enc_tail"
+
+
+@pytest.mark.parametrize("node_in,fc,n_nodes,unsplit,want", [
+    (2048, [128], 64, False, [_G, _T]),                       # SLICES, the plan riding; fast tail
+    (2048, [128], 2560, False, [_G, _T]),                     # SLICES; MFMA tail
+    (2048, [128], 4096, False, [_P, _G]),                     # R32_F16: the plan first, no tail
+    (2048, [128], 8192, False, [_P, _G]),
+    (2048, [128], 8193, False, [_G, _P, _T]),                 # LDS256_F16 split-K 4: the plan behind the GEMM, MFMA tail
+    (2048, [128], 4099, True, [_P, _G]),                      # encoder_unsplit: R32_BF16
+    (1536, [128], 301, False, [_G, _T]),                      # PLAN form (K not a power of two, below 384 nodes)
+    (1536, [128], 1229, False, [_G, _T]),                     # D128, the plan riding
+    (2048, [], 64, False, [_G, _T]),                          # one layer: PLAN form, the tail without a last layer
+    (2048, [128, 64], 4099, False, [_G, _R, _G, _T]),         # D128, reduce, 128 -> 64 PLAN form, LDS tail
+    (2048, [128, 64], 8197, False, [_G, _P, _R, _G, _T]),     # LDS256_F16 split-K (three layers: not fusable)
+    (2048, [128, 128, 64], 3007, False, [_G, _R, _G, _R, _G, _T])])
+def test_profiled_kinds_follow_the_route_table(node_in, fc, n_nodes, unsplit, want):
+    """The whole kind sequence of forward_profiled() -- encoder launches, then `step` for every message step but the last and `step_last` --
+    is the one encoder_route() implies (tests/test_encoder_route.py pins the routes themselves on the CPU): a riding plan has no launch
+    of its own, a fused GEMM has the plan in front and no tail, the other big-batch forms have the plan behind the GEMM, and every
+    GEMM but the last is followed by a reduce."""
+    _, _, _, m = _model(node_in, fc, seed=1)
+    m.encoder_unsplit = unsplit
+    d = to_device(*ring_graph(n_nodes, np.random.default_rng(3), node_in=node_in))
+    with torch.no_grad():
+        _, times = m.forward_profiled(d)
+    kinds = [k for k, _ in times]
+    enc = [k for k in kinds if not k.startswith("step")]
+    steps = kinds[len(enc):]
+    assert enc == want and kinds[:len(enc)] == enc, kinds
+    L = m.native_dims().num_enc_steps
+    assert L >= 1 and steps == ["step"] * (L - 1) + ["step_last"], kinds
 
 
 @pytest.mark.parametrize("cls,family", [([8], FAMILY_MFMA32X6), ([], FAMILY_MFMA32X6), ([1], 2)])
