@@ -12,7 +12,10 @@ the linker with max_gap=1 finds them again one frame later under the same id, th
 more linkers on the true partition show matching='optimal' and motion='velocity' (a cluster is looked for at its last position plus its
 last displacement per frame; these persons wander without a heading, so it has little to predict here: DESIGN.md section 9 has people
 crossing each other).  Four TrackScorers accumulate, on the device, the identity scores of the four linkers on the true partition
-against the person ids; their result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
+against the person ids.  Last, a DROPPED frame: the same batches without their frame 1, as a camera network that lost it would deliver
+them, go to two linkers with motion -- one is told nothing and takes the frames for consecutive, the other gets a time stamp per frame
+(linker(s, times=...)), so the hole is a gap of two periods: its velocities stay displacements per PERIOD and its gate and prediction
+cover the time that really passed.  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
 """
 import argparse
 import os
@@ -25,7 +28,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
 from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
-from gnn_cca_amd.tracking import FrameLinker, TrackScorer, cluster_summaries  # noqa: E402
+from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, TrackScorer, cluster_summaries  # noqa: E402
+
+
+def without_frame(s, q):
+    """The summaries of a batch without its frame q (rows are per frame, so the others move up as they are)."""
+    ptr = s.node_ptr
+    kept = [g for g in range(len(ptr) - 1) if g != q]
+    rows = torch.cat([torch.arange(ptr[g], ptr[g + 1]) for g in kept]).to(s.rank.device)
+    new_ptr = np.concatenate([[0], np.cumsum([ptr[g + 1] - ptr[g] for g in kept])])
+    return ClusterSummaries(s.count[kept], s.rank[rows], s.size[rows], s.n_cams[rows], s.pos[rows], s.emb[rows], new_ptr.tolist(),
+                            torch.from_numpy(new_ptr.astype(np.int32)).to(s.rank.device)), kept
 
 
 def main():
@@ -46,6 +59,7 @@ def main():
     score_opt = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     by_truth_vel = FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity")   # a cluster is looked for where it is heading
     score_vel = TrackScorer(max_ids=a.persons, max_cams=a.cams)
+    blind, timed = (FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity") for _ in range(2))   # for the batches that lost a frame
     where = rng.uniform(-8, 8, size=(a.persons, 2))
     look = rng.standard_normal((a.persons, 256)).astype(np.float32)
     id_cam = np.tile(np.repeat(np.arange(a.cams), a.persons), a.frames)
@@ -88,6 +102,14 @@ def main():
         print(f"  last frame, model partition: {k_model} clusters, sizes {s.size[last][:k_model].tolist()}")
         print(f"  last frame, true partition, motion='velocity': ids {tv.cluster_track[last][:k_truth].tolist()}, velocities "
               f"{[[round(v, 2) for v in p] for p in tv.velocity[last][:k_truth].tolist()]}")
+        if a.frames > 2:   # frame 1 never arrives: without time stamps the step over the hole passes for one period's
+            sd, kept = without_frame(st, 1)
+            tb = blind(sd)
+            tm = timed(sd, times=[k * a.frames + g for g in kept])   # (host numbers, checked before any launch; nothing waits for the GPU)
+            hole = slice(sd.node_ptr[1], sd.node_ptr[1] + int(sd.count[1].item()))   # the first frame after the hole
+            speed = lambda t: [round(float(v), 2) for v in t.velocity[hole].norm(dim=1).tolist()]
+            print(f"  frame 1 dropped: speeds in the frame after the hole {speed(tb)} taken for consecutive, {speed(tm)} per period with "
+                  f"times; tracks so far {int(tb.next_id.item())} against {int(tm.next_id.item())}")
         if a.frames > 2:   # person 0 is cluster 0 of every frame that shows them (their camera-0 detection is the frame's first node)
             before, after = r.batch.node_ptr[hidden - 1], r.batch.node_ptr[hidden + 1]
             print(f"  person 0, hidden in frame {hidden}: id {int(tt.cluster_track[before])} -> {int(tt.cluster_track[after])} without max_gap, "

@@ -236,6 +236,17 @@ _SIGNATURES = {
                                             C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
                                             C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # the two entries above plus frame_time_dev and max_dt
+    "gnncca_link_frames_gap_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
+                                               C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double,
+                                               C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                               C.c_double]),
+    "gnncca_link_frames_motion_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
+                                                  C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                  C.c_void_p, C.c_double]),
     "gnncca_track_score_table_bytes": (C.c_size_t, [C.c_int64]),
     "gnncca_track_score_reset": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gnncca_track_score_rehash": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

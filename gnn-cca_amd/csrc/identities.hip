@@ -28,6 +28,8 @@
 // frame pair by a min-cost assignment instead of mutual best (gnncca_link_frames_gap_ex, matching = 1): identities_assign.cuh, after it.
 // Scoring the track ids against ground-truth person ids over a sequence (gnncca_track_score_*) is track_score.cuh, included after it:
 // integer kernels of its own, nothing shared but this translation unit.  identities_motion.cuh (gnncca_link_frames_motion) comes last.
+// A time stamp per frame (gnncca_link_frames_gap_timed in identities_assign.cuh, gnncca_link_frames_motion_timed in identities_motion.cuh)
+// is an argument of the same level and walk kernels, not a kernel of its own: link_common.cuh's level_dt.
 // Deterministic: every fp sum has a fixed order, integer counts go through LDS atomics, no fp64 atomics.  No host wait, no allocation:
 // capturable.  The file is compiled without fp contraction: the sums, the divisions and the cost are the documented operations one by one.
 #include <hip/hip_runtime.h>

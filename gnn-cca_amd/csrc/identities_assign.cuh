@@ -34,14 +34,16 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// `rule.max_step` is the gate of THIS level, as in gap_level_kernel.
+// `rule.max_step` is the gate of THIS level, as in gap_level_kernel -- and with time stamps (frame_time != nullptr) the caller's max_step,
+// the gate max_step * dt worked out here and a table outside (0, max_dt] skipped whole, as there.
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void gap_level_assign_kernel(const int* __restrict__ node_ptr, int N_all, const int* __restrict__ count,
                                                                  const double* __restrict__ pos, const float* __restrict__ emb, int R,
                                                                  LinkRule rule, double miss_cost, int level, int last_level,
                                                                  const char* __restrict__ state_in, GapFrames in, int P_lds, int* succ_ws,
                                                                  int* matched_prev, int* matched_gap, int* __restrict__ new_rank_ws,
-                                                                 int* __restrict__ n_new_ws) {
+                                                                 int* __restrict__ n_new_ws, const double* __restrict__ frame_time,
+                                                                 double max_dt) {
     extern __shared__ __attribute__((aligned(16))) char s_assign[];
     const int P = P_lds;
     double* W = reinterpret_cast<double*>(s_assign);   // [P][P]: row i of A, column j of B
@@ -64,7 +66,12 @@ __global__ __launch_bounds__(BLOCK) void gap_level_assign_kernel(const int* __re
     const int ca = usable_count(count, g, nn, P);
     int brow;   // the combined row of B's rank 0
     const LinkSide sb = side_b(g - 1 - level, node_ptr, N_all, count, pos, nullptr, emb, R, state_in, in.n, in.off, in.off[in.n], false, P, brow);
-    const int cb = sb.n;
+    int cb = sb.n;
+    if (frame_time && ca > 0 && cb > 0) {   // (uniform; side B exists, so in.n + g - 1 - level >= 0)
+        double dt;
+        if (level_dt(frame_time, in.n + g, in.n + g - 1 - level, max_dt, dt)) rule.max_step = rule.max_step * dt;
+        else cb = 0;
+    }
     const double* ppos = sb.pos;
     const float* pemb = sb.emb;
     if (ca > 0 && cb > 0) {   // (uniform; ca, cb <= P)
@@ -184,7 +191,7 @@ __global__ __launch_bounds__(BLOCK) void gap_level_assign_kernel(const int* __re
 static int assign_level_launch(hipStream_t st, int n_frames, int P, const int* node_ptr_dev, int n_nodes, const int* count, const double* pos,
                                const float* emb, int R, const LinkRule& level_rule, int level, int last_level, const char* sin,
                                const GapFrames& in, int* succ_ws, int* matched_prev, int* matched_gap, int* new_rank_ws, int* n_new_ws,
-                               double miss_cost) {
+                               double miss_cost, const double* frame_time, double max_dt) {
     if (P > kTrackMaxOptimalNodes) return GNNCCA_ERR_INVALID_ARG;   // (the entry refused such a frame already)
     static thread_local int attr_dev = -1;   // above 64 KiB of dynamic LDS the function needs the attribute, once per device
     int dev = 0;
@@ -196,7 +203,7 @@ static int assign_level_launch(hipStream_t st, int n_frames, int P, const int* n
     }
     hipLaunchKernelGGL((gap_level_assign_kernel<256>), dim3((unsigned)n_frames), dim3(256), assign_lds_bytes(P), st, node_ptr_dev, n_nodes, count,
                        pos, emb, R, level_rule, miss_cost, level, last_level, sin, in, P, succ_ws, matched_prev, matched_gap, new_rank_ws,
-                       n_new_ws);
+                       n_new_ws, frame_time, max_dt);
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -216,7 +223,26 @@ int gnncca_link_frames_gap_ex(const int32_t* node_ptr_dev, const int32_t* count,
     return gnncca::link_frames_gap_run(node_ptr_dev, count, rank, pos, emb, reid_dim, n_nodes, n_frames, max_frame_nodes, max_step, lam, has_max_cos,
                                        max_cos, max_gap, matching, miss_cost, state_in, state_in_frame_rows, state_in_frames, state_out,
                                        state_out_frame_rows, state_out_frames, cluster_track, node_track, matched_prev, matched_gap, workspace,
-                                       workspace_bytes, stream);
+                                       workspace_bytes, stream, nullptr, 0.0);
+}
+
+/* gnncca_link_frames_gap_ex with a time stamp per frame (include/gnncca_mpn.h has the rule): the same run, the gate worked out per
+ * (frame, level) on the device from frame_time_dev, fp64 [state_in_frames + n_frames]. */
+int gnncca_link_frames_gap_timed(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
+                                 int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
+                                 int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t matching, double miss_cost, const void* state_in,
+                                 const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                                 const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track,
+                                 int32_t* matched_prev, int32_t* matched_gap, void* workspace, size_t workspace_bytes, gnncca_stream_t stream,
+                                 const double* frame_time_dev, double max_dt) {
+    if (matching != 0 && matching != 1) return GNNCCA_ERR_INVALID_ARG;
+    if (!(miss_cost > 0.0) || !(miss_cost < __builtin_inf())) return GNNCCA_ERR_INVALID_ARG;
+    if (!(max_dt > 0.0) || !(max_dt < __builtin_inf())) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames > 0 && !frame_time_dev) return GNNCCA_ERR_INVALID_ARG;
+    return gnncca::link_frames_gap_run(node_ptr_dev, count, rank, pos, emb, reid_dim, n_nodes, n_frames, max_frame_nodes, max_step, lam, has_max_cos,
+                                       max_cos, max_gap, matching, miss_cost, state_in, state_in_frame_rows, state_in_frames, state_out,
+                                       state_out_frame_rows, state_out_frames, cluster_track, node_track, matched_prev, matched_gap, workspace,
+                                       workspace_bytes, stream, frame_time_dev, max_dt);
 }
 
 }  // extern "C"

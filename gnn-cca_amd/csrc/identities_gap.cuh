@@ -22,13 +22,15 @@
 namespace gnncca {
 
 // ---- launch 2: one level ----------------------------------------------------------------------------------------------------------------
-// `rule.max_step` is the gate of THIS level, max_step * (k + 1), multiplied once on the host in fp64.
+// `rule.max_step` is the gate of THIS level, max_step * (k + 1), multiplied once on the host in fp64 -- unless the call has time stamps
+// (frame_time != nullptr, fp64 [history frames + G]): then it is the caller's max_step, dt = T[t] - T[t - 1 - k] is worked out here, the
+// gate is max_step * dt (one fp64 multiplication), and a table with !(dt > 0 && dt <= max_dt) is skipped whole.
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void gap_level_kernel(const int* __restrict__ node_ptr, int N_all, const int* __restrict__ count,
                                                           const double* __restrict__ pos, const float* __restrict__ emb, int R, LinkRule rule,
                                                           int level, int last_level, const char* __restrict__ state_in, GapFrames in, int P_lds,
                                                           int* succ_ws, int* matched_prev, int* matched_gap, int* __restrict__ new_rank_ws,
-                                                          int* __restrict__ n_new_ws) {
+                                                          int* __restrict__ n_new_ws, const double* __restrict__ frame_time, double max_dt) {
     extern __shared__ int s_dyn[];
     int* fwd = s_dyn;           // [a] -> b; at the last level then the frame's final gaps
     int* bwd = s_dyn + P_lds;   // [b] -> a
@@ -41,6 +43,11 @@ __global__ __launch_bounds__(BLOCK) void gap_level_kernel(const int* __restrict_
     const int ca = usable_count(count, g, n, P_lds);
     int brow;   // the combined row of B's rank 0
     LinkSide sb = side_b(g - 1 - level, node_ptr, N_all, count, pos, nullptr, emb, R, state_in, in.n, in.off, in.off[in.n], false, P_lds, brow);
+    if (frame_time && ca > 0 && sb.n > 0) {   // (uniform; side B exists, so in.n + g - 1 - level >= 0)
+        double dt;
+        if (level_dt(frame_time, in.n + g, in.n + g - 1 - level, max_dt, dt)) rule.max_step = rule.max_step * dt;
+        else sb.n = 0;
+    }
     if (ca > 0 && sb.n > 0) {   // (uniform)
         const LinkSide sa{pos + 2 * (size_t)v0, nullptr, emb + (size_t)v0 * R, matched_gap + v0, -1, ca};
         sb.mask = succ_ws + brow, sb.free = 0;
@@ -148,15 +155,17 @@ namespace gnncca {
 static int assign_level_launch(hipStream_t st, int n_frames, int P, const int* node_ptr_dev, int n_nodes, const int* count, const double* pos,
                                const float* emb, int R, const LinkRule& level_rule, int level, int last_level, const char* sin,
                                const GapFrames& in, int* succ_ws, int* matched_prev, int* matched_gap, int* new_rank_ws, int* n_new_ws,
-                               double miss_cost);
+                               double miss_cost, const double* frame_time, double max_dt);
 
-// gnncca_link_frames_gap (matching 0) and gnncca_link_frames_gap_ex: one body, the form of the level kernel chosen by `matching`
+// gnncca_link_frames_gap (matching 0), gnncca_link_frames_gap_ex and gnncca_link_frames_gap_timed: one body, the form of the level kernel
+// chosen by `matching`; frame_time nullptr (and max_dt unused) from the untimed entries, which multiply the gate here, on the host
 static int link_frames_gap_run(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
                                int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
                                int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t matching, double miss_cost, const void* state_in,
                                const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
                                const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track,
-                               int32_t* matched_prev, int32_t* matched_gap, void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
+                               int32_t* matched_prev, int32_t* matched_gap, void* workspace, size_t workspace_bytes, gnncca_stream_t stream,
+                               const double* frame_time, double max_dt) {
     HistoryPlan p;
     const int rc = plan_history(n_nodes, n_frames, reid_dim, max_frame_nodes, max_step, lam, has_max_cos, max_cos, max_gap, matching, state_in,
                                 state_in_frame_rows, state_in_frames, state_out, state_out_frame_rows, state_out_frames, node_ptr_dev, count, emb,
@@ -176,16 +185,16 @@ static int link_frames_gap_run(const int32_t* node_ptr_dev, const int32_t* count
     HIP_TRY(hipGetLastError());
     for (int k = 0; k <= max_gap; ++k) {
         LinkRule level_rule = rule;
-        level_rule.max_step = max_step * (double)(k + 1);   // gate_k: one fp64 multiplication
+        if (!frame_time) level_rule.max_step = max_step * (double)(k + 1);   // gate_k: one fp64 multiplication (timed: max_step * dt, in the kernel)
         if (matching) {
             const int rc = assign_level_launch(st, (int)n_frames, P, node_ptr_dev, (int)n_nodes, count, pos, emb, R, level_rule, k, (int)(k == max_gap),
-                                               sin, in, succ_ws, matched_prev, matched_gap, new_rank_ws, n_new_ws, miss_cost);
+                                               sin, in, succ_ws, matched_prev, matched_gap, new_rank_ws, n_new_ws, miss_cost, frame_time, max_dt);
             if (rc != GNNCCA_OK) return rc;
             continue;
         }
         hipLaunchKernelGGL((gap_level_kernel<256>), dim3((unsigned)n_frames), dim3(256), (size_t)2 * P * sizeof(int), st, node_ptr_dev, (int)n_nodes,
                            count, pos, emb, R, level_rule, k, (int)(k == max_gap), sin, in, P, succ_ws, matched_prev, matched_gap, new_rank_ws,
-                           n_new_ws);
+                           n_new_ws, frame_time, max_dt);
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(link_scan_kernel, dim3(1), dim3(64), 0, st, n_new_ws, (int)n_frames, base_ws);
@@ -210,7 +219,8 @@ int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t* count, co
                            size_t workspace_bytes, gnncca_stream_t stream) {
     return gnncca::link_frames_gap_run(node_ptr_dev, count, rank, pos, emb, reid_dim, n_nodes, n_frames, max_frame_nodes, max_step, lam, has_max_cos,
                                        max_cos, max_gap, 0, 0.0, state_in, state_in_frame_rows, state_in_frames, state_out, state_out_frame_rows,
-                                       state_out_frames, cluster_track, node_track, matched_prev, matched_gap, workspace, workspace_bytes, stream);
+                                       state_out_frames, cluster_track, node_track, matched_prev, matched_gap, workspace, workspace_bytes, stream,
+                                       nullptr, 0.0);
 }
 
 }  // extern "C"

@@ -40,12 +40,23 @@ struct WalkOutputs {
     const float* emb;         // the batch's appearance rows (never written)
 };
 
+// the same block for a call with time stamps: two more members, read where a level is set up
+struct TimedWalkOutputs : WalkOutputs {
+    const double* frame_time; // time stamps over the combined frames, fp64 [history frames + G] (never written)
+    double max_dt;            // a table whose dt is not in (0, max_dt] is skipped
+};
+
 // One workgroup, every frame of the batch in order.  `rule.max_step` is the caller's max_step; the gate of level k is max_step * (k + 1),
-// one fp64 multiplication.  Every loop is bounded by G, max_gap, P_lds (a count above it is taken as 0) or the 64 lanes of a wave.
-template <int BLOCK>
+// one fp64 multiplication; with time stamps (outs.frame_time) dt = T[t] - T[t - 1 - k], one fp64 subtraction, stands wherever k + 1 does,
+// and a table with !(dt > 0 && dt <= max_dt) is skipped whole.  Timed or not is the TYPE of the block (OUTS = WalkOutputs or
+// TimedWalkOutputs), not a null check: the untimed instantiation is the walk as it was, argument for argument (read at run time, the
+// pointer's round trip to LDS and back stood in front of every level's search and cost the untimed call 0.027 ms of 0.94 on 64 frames
+// x 3 levels, outside the run-to-run spread).  Every loop is bounded by G, max_gap, P_lds (a count above it is taken as 0) or the 64 lanes of a wave.
+template <int BLOCK, class OUTS>
 __global__ __launch_bounds__(BLOCK) void motion_walk_kernel(const int* __restrict__ node_ptr, int N_all, int G, const int* __restrict__ count,
                                                             const double* __restrict__ pos, int R, LinkRule rule,
-                                                            int max_gap, GapFrames in, int P_lds, WalkOutputs outs) {
+                                                            int max_gap, GapFrames in, int P_lds, OUTS outs) {
+    constexpr bool TIMED = std::is_same_v<OUTS, TimedWalkOutputs>;
     extern __shared__ int s_dyn[];
     __shared__ int s_fresh;
     int* fwd = s_dyn;                // [a] -> b; after the levels: a fresh cluster's rank among the frame's fresh ones
@@ -55,7 +66,7 @@ __global__ __launch_bounds__(BLOCK) void motion_walk_kernel(const int* __restric
     // What only the set-up of a level, the commit and the ids use is kept in LDS and read where it is used, not held in scalar registers
     // over the walk: the history's row offsets (s_off[HN] = S, the rows of the old state) and the output pointers.
     __shared__ int s_off[kGapMaxFrames + 1];
-    __shared__ WalkOutputs s_out;
+    __shared__ OUTS s_out;
     if (tid <= kGapMaxFrames) s_off[tid] = in.off[tid];
     if (tid == 0) s_out = outs;
     const int HN = in.n;
@@ -80,7 +91,11 @@ __global__ __launch_bounds__(BLOCK) void motion_walk_kernel(const int* __restric
             sb.mask = succ_ws + brow, sb.free = 0;
             const LinkSide sa{apos, nullptr, aemb, gap_a, -1, ca};
             const double* bpos = sb.pos;
-            const double steps = (double)(k + 1);
+            double steps = (double)(k + 1);
+            if constexpr (TIMED) {   // (uniform; side B exists, so HN + t - 1 - k >= 0.  The null check stays: without it this instantiation spilled 2 SGPRs)
+                const double* frame_time = s_out.frame_time;
+                if (frame_time && !level_dt(frame_time, HN + t, HN + t - 1 - k, s_out.max_dt, steps)) continue;
+            }
             const LinkRule level_rule{rule.max_step * steps, s_out.lam, s_out.max_cos, rule.need_emb, rule.has_max_cos};   // gate_k: one fp64 multiplication
             mutual_best<BLOCK, 4, true>(sa, sb, steps, R, level_rule, fwd, bwd);
             __syncthreads();   // (every read of the masks above comes before the writes below)
@@ -174,14 +189,18 @@ size_t gnncca_link_motion_workspace_bytes(int64_t n_nodes, int64_t n_frames, int
     return gnncca::round256(((size_t)state_rows + (size_t)n_nodes) * sizeof(int32_t));   // successor flags [S + N]
 }
 
-int gnncca_link_frames_motion(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
-                              int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
-                              int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t motion, const void* state_in,
-                              const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
-                              const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track,
-                              int32_t* matched_prev, int32_t* matched_gap, double* velocity, void* workspace, size_t workspace_bytes,
-                              gnncca_stream_t stream) {
-    using namespace gnncca;
+}  // extern "C"
+
+namespace gnncca {
+
+// gnncca_link_frames_motion and gnncca_link_frames_motion_timed: one body (frame_time nullptr from the untimed entry)
+static int link_frames_motion_run(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
+                                  int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
+                                  int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t motion, const void* state_in,
+                                  const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                                  const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track,
+                                  int32_t* matched_prev, int32_t* matched_gap, double* velocity, void* workspace, size_t workspace_bytes,
+                                  gnncca_stream_t stream, const double* frame_time, double max_dt) {
     if (motion != 1) return GNNCCA_ERR_INVALID_ARG;
     HistoryPlan p;
     const int rc = plan_history(n_nodes, n_frames, reid_dim, max_frame_nodes, max_step, lam, has_max_cos, max_cos, max_gap, 0, state_in,
@@ -194,16 +213,58 @@ int gnncca_link_frames_motion(const int32_t* node_ptr_dev, const int32_t* count,
     char* sout = static_cast<char*>(state_out);
     launch_link_init(st, p, true, n_nodes, succ_ws, matched_prev, matched_gap, velocity);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((motion_walk_kernel<kMotionWalkBlock>), dim3(1), dim3(kMotionWalkBlock), (size_t)3 * p.P * sizeof(int), st, node_ptr_dev,
-                       (int)n_nodes, (int)n_frames, count, pos, p.R, p.rule, (int)max_gap, p.in, p.P,
-                       WalkOutputs{matched_prev, matched_gap, velocity, reinterpret_cast<long long*>(cluster_track),
-                                   &reinterpret_cast<GapHeader*>(sout)->next_id, succ_ws, p.sin, lam, max_cos, emb});
+    const WalkOutputs outs{matched_prev, matched_gap, velocity, reinterpret_cast<long long*>(cluster_track),
+                           &reinterpret_cast<GapHeader*>(sout)->next_id, succ_ws, p.sin, lam, max_cos, emb};
+    if (!frame_time) {
+        hipLaunchKernelGGL((motion_walk_kernel<kMotionWalkBlock, WalkOutputs>), dim3(1), dim3(kMotionWalkBlock), (size_t)3 * p.P * sizeof(int), st,
+                           node_ptr_dev, (int)n_nodes, (int)n_frames, count, pos, p.R, p.rule, (int)max_gap, p.in, p.P, outs);
+    } else {
+        TimedWalkOutputs timed;
+        static_cast<WalkOutputs&>(timed) = outs;
+        timed.frame_time = frame_time, timed.max_dt = max_dt;
+        hipLaunchKernelGGL((motion_walk_kernel<kMotionWalkBlock, TimedWalkOutputs>), dim3(1), dim3(kMotionWalkBlock), (size_t)3 * p.P * sizeof(int),
+                           st, node_ptr_dev, (int)n_nodes, (int)n_frames, count, pos, p.R, p.rule, (int)max_gap, p.in, p.P, timed);
+    }
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL((motion_finish_kernel<256>), dim3((unsigned)(n_frames + p.carried)), dim3(256), 0, st, node_ptr_dev, (int)n_nodes, count, rank,
                        pos, emb, p.R, (int)n_frames, velocity, reinterpret_cast<const long long*>(cluster_track), succ_ws, p.sin, p.in, sout, p.out, p.P,
                        reinterpret_cast<long long*>(node_track));
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
+}
+
+}  // namespace gnncca
+
+extern "C" {
+
+int gnncca_link_frames_motion(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
+                              int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
+                              int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t motion, const void* state_in,
+                              const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                              const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track,
+                              int32_t* matched_prev, int32_t* matched_gap, double* velocity, void* workspace, size_t workspace_bytes,
+                              gnncca_stream_t stream) {
+    return gnncca::link_frames_motion_run(node_ptr_dev, count, rank, pos, emb, reid_dim, n_nodes, n_frames, max_frame_nodes, max_step, lam,
+                                          has_max_cos, max_cos, max_gap, motion, state_in, state_in_frame_rows, state_in_frames, state_out,
+                                          state_out_frame_rows, state_out_frames, cluster_track, node_track, matched_prev, matched_gap, velocity,
+                                          workspace, workspace_bytes, stream, nullptr, 0.0);
+}
+
+/* gnncca_link_frames_motion with a time stamp per frame (include/gnncca_mpn.h has the rule): the same run; dt from frame_time_dev, fp64
+ * [state_in_frames + n_frames], stands where k + 1 does in the gate, the prediction and the velocity. */
+int gnncca_link_frames_motion_timed(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
+                                    int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes, double max_step, double lam,
+                                    int32_t has_max_cos, double max_cos, int32_t max_gap, int32_t motion, const void* state_in,
+                                    const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                                    const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track,
+                                    int32_t* matched_prev, int32_t* matched_gap, double* velocity, void* workspace, size_t workspace_bytes,
+                                    gnncca_stream_t stream, const double* frame_time_dev, double max_dt) {
+    if (!(max_dt > 0.0) || !(max_dt < __builtin_inf())) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames > 0 && !frame_time_dev) return GNNCCA_ERR_INVALID_ARG;
+    return gnncca::link_frames_motion_run(node_ptr_dev, count, rank, pos, emb, reid_dim, n_nodes, n_frames, max_frame_nodes, max_step, lam,
+                                          has_max_cos, max_cos, max_gap, motion, state_in, state_in_frame_rows, state_in_frames, state_out,
+                                          state_out_frame_rows, state_out_frames, cluster_track, node_track, matched_prev, matched_gap, velocity,
+                                          workspace, workspace_bytes, stream, frame_time_dev, max_dt);
 }
 
 }  // extern "C"

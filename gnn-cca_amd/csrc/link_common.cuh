@@ -7,6 +7,7 @@
 //   wave_number     the ballot scan that numbers the entries where a predicate holds, in ascending order;
 //   side_b          where a frame's partners of level k are: an earlier frame of the batch, or a frame of the carried history;
 //   StateView       the arrays of a carried history state (with or without velocities), write_slot one frame's rows into it;
+//   level_dt        the time between the two frames of a (frame, level) table when the call has time stamps, and whether the table counts;
 //   write_node_tracks, link_init_kernel, and on the host plan_history: the checks and the numbers both history entries need.
 #pragma once
 
@@ -286,6 +287,15 @@ __device__ __forceinline__ LinkSide side_b(int s, const int* __restrict__ node_p
     return b;
 }
 
+// Time stamps (the _timed entries): frame_time is fp64 [history frames + G] over the COMBINED frame list, in units of the nominal frame
+// period.  dt = T[t] - T[s] (one fp64 subtraction) stands where the untimed rule has (double)(k + 1); a table with
+// !(dt > 0 && dt <= max_dt) has no admissible pair and is skipped whole -- which is also what a NaN or a disordered array gets.
+// t, s: indices into the combined list, s >= 0 (the caller has found side B there).
+__device__ __forceinline__ bool level_dt(const double* frame_time, int t, int s, double max_dt, double& dt) {
+    dt = frame_time[t] - frame_time[s];
+    return dt > 0.0 && dt <= max_dt;
+}
+
 // c rows of one frame -> slot j of the new state, whose rows start at orow: count, pos, vel (where the state has them), track, succ, emb
 template <int BLOCK>
 __device__ void write_slot(const StateView<char>& out, int j, int orow, int c, int R, const double* __restrict__ pos, const double* __restrict__ vel,
@@ -360,7 +370,7 @@ static bool gap_frames(const int32_t* rows, int n, GapFrames& f) {
     return true;
 }
 
-// what a history entry (gnncca_link_frames_gap / _gap_ex / _motion) works out before its first launch
+// what a history entry (gnncca_link_frames_gap / _gap_ex / _motion and their _timed forms) works out before its first launch
 struct HistoryPlan {
     bool nothing;          // n_frames == 0: no time passes, the caller keeps its state
     GapFrames in, out;     // the row offsets of the old and of the new state

@@ -10,6 +10,7 @@ over the frames of a batch and from one batch to the next.
     link = FrameLinker(max_step=0.8, max_gap=2)   # a track survives up to 2 frames that miss it; t.matched_gap [N]: frames skipped
     link = FrameLinker(max_step=0.8, matching='optimal')   # per frame pair the min-cost assignment instead of mutual best
     link = FrameLinker(max_step=0.4, max_gap=2, motion='velocity')   # look for a track where it is heading; t.velocity [N, 2]
+    t = link(r, times=[0.0, 1.0, 3.0, 4.1])       # any mode: one time per frame, in frame periods -- a dropped frame is a gap (max_dt)
     score = TrackScorer(max_ids=1024, max_cams=8) # identity-tracking scores against the caller's person ids, accumulated on the device
     score.add(r, t).switched                      # int32 [N]: -1 not scored, 0, 1 = this detection is an identity switch
     score.result()                                # IDSW, IDTP, IDF1, AssA, purity, coverage, MT / PT / ML ...: ONE synchronisation
@@ -39,7 +40,7 @@ gate_k = max_step * (k + 1): admissible iff d <= gate_k (and dcos <= max_cos), c
 ties to the smaller rank within the frame.  Level 0 is the rule above word for word, so a shorter gap always wins over a longer one, even
 at higher cost.  Time is the frame index over all calls since reset(): an empty or refused frame still counts as a frame, an empty batch
 passes no time.  The rule is causal, so the ids do not depend on how a sequence is cut into batches; the state holds the last M + 1 frames.
-Limits: frames are taken to be CONSECUTIVE and IN ORDER (there are no time stamps); a track unseen for more than max_gap frames ends (with
+Limits: without time stamps (below) frames are taken to be CONSECUTIVE and IN ORDER; a track unseen for more than max_gap frames ends (with
 the default max_gap = 0: in the first frame that misses it); a cluster is looked for where it was last seen -- there is no motion
 prediction (no velocity term), only a gate that grows with the gap -- unless motion='velocity' is asked for:
 Motion (motion='velocity': csrc/identities_motion.cuh, THREE launches whatever max_gap is).  The levels, gates, masks, cost, mutual best,
@@ -53,7 +54,7 @@ nobody.  vel(b) is known only when b's frame has been through all its levels, so
 (for zero velocities that order gives the gap rule's result): one workgroup walks the batch, and hands out the ids as it goes.  The rule
 is causal (the carried state holds the velocities of its M + 1 frames; it is a state of its own kind).  Tracks.velocity is float64 [N, 2].
 Limits: constant velocity from the LAST link only -- the prediction is wrong after a sharp turn, so a track can end there and restart;
-still no time stamps; matching='optimal' has no motion yet (the combination is refused).  DESIGN.md section 9 has what it does to identity switches on synthetic crossing walks.
+matching='optimal' has no motion yet (the combination is refused).  DESIGN.md section 9 has what it does to identity switches on synthetic crossing walks.
 Optimal matching (matching='optimal': csrc/identities_assign.cuh, the same M + 4 launches, also with max_gap = 0).  Mutual best leaves a
 cluster unlinked whenever its best partner prefers somebody else, even when a second admissible partner is free.  In this mode the levels,
 gates, masks and cost stay as above and only the choice of pairs inside a (level, frame pair) table changes: with A the clusters of frame t
@@ -65,7 +66,23 @@ paths, rows inserted in ascending rank, ties to the smaller column (include/gnnc
 as loops, and the kernel equals them bit for bit).  The table of a frame pair lives in LDS, so such a linker takes frames of at most
 MAX_OPTIMAL_FRAME_NODES = 128 detections (ValueError before any launch, for a frame of the batch or of the carried history).  The
 assignment is optimal per (level, frame pair), NOT over time: a shorter gap still wins over a longer one at any cost, this mode has no
-motion prediction (motion='velocity' above is mutual best only) and there are still no time stamps.
+motion prediction (motion='velocity' above is mutual best only).
+Time stamps (linker(x, times=...), every mode: gnncca_link_frames_gap_timed / gnncca_link_frames_motion_timed, the kernels and launches of
+the mode).  A timed call gives one fp64 time per frame of the batch, in units of the nominal frame period: finite, strictly increasing,
+the first strictly greater than the last time of the previous call.  T[f] is the time of frame f over the combined list (the carried
+history, then the batch).  Level order: for frame t at level k the other frame is still s = t - 1 - k, counted in frames PRESENT; a
+shorter gap still wins, and the history still holds the last max_gap + 1 frames.  Elapsed time: dt = T[t] - T[s], one fp64 subtraction,
+replaces float64(k + 1) everywhere: gate = max_step * dt; with motion pred(b) = pos(b) + dt * vel(b) and vel(a) = (pos(a) - pos(b)) / dt
+-- each one operation, in the order of the untimed code, no FMA.  Skipped tables: a table with not (dt > 0 and dt <= max_dt) has no
+admissible pair and is skipped whole (which also makes a bad device array harmless); max_dt defaults to max_gap + 1, so a hole of one
+frame period consumes one unit of max_gap.  Everything else is the mode's own rule, unchanged: masks, the cosine term, max_cos,
+cost = d / gate + lam * dcos, ties, mutual best or the assignment with miss_cost, the numbering of fresh ids, and matched_gap (still the
+level k).  Consequence: with T = 0, 1, 2, ... continuing across calls dt is exactly k + 1 and every output equals the untimed linker's bit
+for bit.  The times are checked on the host before any launch; the linker keeps the times of the frames its state holds on the host and
+sends the combined array through a fresh pinned buffer with one non-blocking copy on the current stream: still no wait for the GPU.  A
+timed linker with matching='mutual', max_gap=0, motion='none' runs the gap path with M = 0.  A state written with time stamps is not
+continued without them, nor the reverse (ValueError: reset() it first).  Limit: levels count frames present, so max_gap also bounds how
+many PRESENT frames a track may skip.
 Scores (csrc/track_score.cuh; per call one memset and two launches).  TrackScorer joins ids (batch.y), cam and Tracks.node_track over time.
 Detection i is VALID iff 0 <= ids[i] < max_ids, 0 <= cam[i] < max_cams and 0 <= node_track[i] < 2**40; it is SCORED iff it is valid and no
 valid detection j > i of its frame has the same (id, cam) (the largest node id wins a duplicate); every other detection is IGNORED (a
@@ -120,6 +137,10 @@ class Tracks:
         if self._matched_gap is None:   # the max_gap = 0 path launches nothing for it unless somebody asks: -1 stays, a rank becomes 0
             self._matched_gap = torch.clamp(self.matched_prev, max=0)
         return self._matched_gap
+
+
+def _real(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
 
 
 def _host_ptr(node_ptr):
@@ -222,14 +243,19 @@ class FrameLinker:
     launches whatever max_gap is, one workgroup walking the frames in order; Tracks.velocity).  Constant velocity from the last link only:
     wrong after a sharp turn, where a track can end and restart.  Not with matching='optimal': the assignment kernel's frame-parallel
     level launch cannot know the velocities; combining the two is left to a later change and refused until then.
-    Frames are taken to be consecutive and in order (no time stamps); a track missing from more than max_gap frames ends; without
+    max_dt: None (max_gap + 1) or a finite number > 0, read by calls with time stamps only: the longest time, in frame periods, over which
+    a track is continued.  `linker(x, times=seq)`: seq a host sequence or numpy array of one real, finite number per frame of the batch,
+    strictly increasing and after the previous call's last (ValueError before any launch otherwise, the state unmoved); the time between
+    two frames then stands where their distance in frames stood -- in the gate, the prediction and the velocity -- so a dropped frame is
+    a gap and jitter is accounted for.  A linker is timed or not from its first call to the next reset().
+    Without time stamps frames are taken to be consecutive and in order; a track missing from more than max_gap frames ends (levels
+    count frames present, so with time stamps max_gap also bounds how many present frames a track may skip); without
     motion='velocity' there is no motion prediction; the assignment is optimal per (level, frame pair), not over time.  No counterpart in the
     reference; what max_step, lam, max_cos, max_gap and matching do to tracking quality can be measured with TrackScorer wherever person
     ids exist (DESIGN.md section 9 has both matchings on synthetic sequences); with a trained model it has not been."""
 
-    def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0, matching="mutual", miss_cost=None, motion="none"):
-        def real(v):
-            return isinstance(v, numbers.Real) and not isinstance(v, bool)
+    def __init__(self, max_step, lam=1.0, max_cos=None, max_gap=0, matching="mutual", miss_cost=None, motion="none", max_dt=None):
+        real = _real
         if not real(max_step) or not math.isfinite(max_step) or not max_step > 0:
             raise ValueError(f"max_step must be a finite number > 0, not {max_step!r}")
         if not real(lam) or not math.isfinite(lam) or lam < 0:
@@ -251,7 +277,10 @@ class FrameLinker:
         if motion == "velocity" and matching == "optimal":
             raise ValueError("motion='velocity' cannot be combined with matching='optimal' yet: the assignment kernel links all frames of a "
                              "level at once and cannot know the velocities")
+        if max_dt is not None and (not real(max_dt) or not math.isfinite(max_dt) or not max_dt > 0):
+            raise ValueError(f"max_dt must be None or a finite number > 0, not {max_dt!r}")
         self.max_gap = int(max_gap)
+        self.max_dt = float(max_dt) if max_dt is not None else float(self.max_gap + 1)   # (read by timed calls only)
         self.matching = matching
         self.motion = motion
         self.miss_cost = float(miss_cost) if miss_cost is not None else 1.0 + self.lam * (self.max_cos if self.max_cos is not None else 2.0)
@@ -262,12 +291,33 @@ class FrameLinker:
         self._state, self._cap, self._reid_dim = None, 0, None
         self._state_motion = None   # the motion of the linker that wrote the state (only by changing `motion` can it differ from self.motion)
         self._frame_rows = []   # max_gap > 0: the node counts of the frames the state holds, oldest first (they bound the cluster counts)
+        self._frame_times = []  # timed calls: the times of those frames, beside _frame_rows (the state on the device does not hold them)
+        self._state_timed = None   # did the call that wrote the state have time stamps (a state continues only in kind)
 
     @property
     def needs_embeddings(self):
         return self.lam != 0.0 or self.max_cos is not None
 
-    def __call__(self, x):
+    def _host_times(self, times, g):
+        """The time stamps of a batch of g frames, checked on the host -> float64 [g].  ValueError: not a sequence of g real, finite,
+        strictly increasing numbers, or the first is not after the last time of the previous call."""
+        try:
+            seq = list(times)
+        except TypeError:
+            raise ValueError(f"times must be a sequence of {g} numbers, one per frame, not {times!r}") from None
+        if len(seq) != g:
+            raise ValueError(f"the batch has {g} frames, times has {len(seq)} entries")
+        for v in seq:
+            if not _real(v) or not math.isfinite(v):
+                raise ValueError(f"every time must be a finite real number, not {v!r}")
+        t = np.array([float(v) for v in seq], dtype=np.float64)
+        if g > 1 and not bool((np.diff(t) > 0).all()):
+            raise ValueError("times must be strictly increasing: frames come in order, one time stamp each")
+        if g > 0 and self._frame_times and not t[0] > self._frame_times[-1]:
+            raise ValueError(f"the first time, {t[0]!r}, is not after the last time of the previous call, {self._frame_times[-1]!r}")
+        return t
+
+    def __call__(self, x, times=None):
         s = x.identities() if hasattr(x, "identities") else x
         if not isinstance(s, ClusterSummaries):
             raise ValueError("FrameLinker takes a ClusterSummaries or a FrameResult")
@@ -294,6 +344,14 @@ class FrameLinker:
         if self._state is not None and self._state_motion != self.motion:
             raise ValueError(f"the carried state was written with motion={self._state_motion!r}, which motion={self.motion!r} cannot "
                              "continue (the states differ in kind): reset() it first")
+        timed = times is not None
+        if self._state is not None and self._state_timed != timed:
+            was, now = ("with", "without") if self._state_timed else ("without", "with")
+            raise ValueError(f"the carried state was written {was} time stamps, which a call {now} them cannot continue: reset() it first")
+        if timed:   # on the host, before any launch and before the state moves
+            if not _real(self.max_dt) or not math.isfinite(self.max_dt) or not self.max_dt > 0:   # (changed after construction)
+                raise ValueError(f"max_dt must be a finite number > 0, not {self.max_dt!r}")
+            times = self._host_times(times, g)
         dev = s.count.device
         self._reid_dim = r_all
         r = r_all if self.needs_embeddings else 0
@@ -304,8 +362,8 @@ class FrameLinker:
                 e64, e32 = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
                 vel = torch.empty((0, 2), dtype=torch.float64, device=dev) if self.motion == "velocity" else None
                 return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone(), vel)
-            if self.motion == "velocity" or self.max_gap > 0 or self.matching == "optimal":
-                return self._link_history(lib, s, dev, sizes, g, n, max_n, r)
+            if timed or self.motion == "velocity" or self.max_gap > 0 or self.matching == "optimal":
+                return self._link_history(lib, s, dev, sizes, g, n, max_n, r, times)
             cap = int(sizes[-1])
             state = torch.empty(lib.gnncca_link_state_bytes(cap, r), dtype=torch.uint8, device=dev)
             tracks = torch.empty((2, n), dtype=torch.int64, device=dev)   # cluster_track | node_track
@@ -321,13 +379,16 @@ class FrameLinker:
             if st:
                 nat.check(st, "gnncca_link_frames")
             # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
-        self._state, self._cap, self._state_motion = state, cap, self.motion
+        self._state, self._cap, self._state_motion, self._state_timed = state, cap, self.motion, False
         return Tracks(tracks[0], tracks[1], matched, state[:8].view(torch.int64), state)
 
-    def _link_history(self, lib, s, dev, sizes, g, n, max_n, r):
+    def _link_history(self, lib, s, dev, sizes, g, n, max_n, r, times=None):
         """The call of every linker whose state is a history of frames (inside _on(dev), g > 0) -- max_gap > 0, matching='optimal',
-        motion='velocity': everything is sized from host-known node counts, nothing waits for the GPU.  The entries differ in the kind of
-        their state and workspace, and with motion (three launches do it all) a velocity per row comes back."""
+        motion='velocity', and every call with time stamps: everything is sized from host-known node counts, nothing waits for the GPU.
+        The entries differ in the kind of their state and workspace, and with motion (three launches do it all) a velocity per row comes
+        back.  `times`: None, or the checked float64 [g] of the batch -- the times of the carried frames come before them, the whole goes
+        through a fresh pinned buffer (the host allocator hands its block out again only after the copy's event has passed) and one
+        non-blocking copy on the current stream, and the _timed form of the entry is called."""
         moving = self.motion == "velocity"
         state_bytes, workspace_bytes = ((lib.gnncca_link_motion_state_bytes, lib.gnncca_link_motion_workspace_bytes) if moving else
                                         (lib.gnncca_link_gap_state_bytes, lib.gnncca_link_gap_workspace_bytes))
@@ -347,7 +408,21 @@ class FrameLinker:
                 tracks[0].data_ptr() if n else None, tracks[1].data_ptr() if n else None, matched[0].data_ptr() if n else None,
                 matched[1].data_ptr() if n else None)
         end = (ws.data_ptr(), ws_bytes, _raw_stream(dev))
-        if moving:
+        if times is not None:
+            all_times = self._frame_times + times.tolist()   # (one time per carried frame: _frame_times moves with _frame_rows)
+            staged = torch.empty(len(all_times), dtype=torch.float64, pin_memory=True)
+            staged.copy_(torch.from_numpy(np.asarray(all_times, dtype=np.float64)))
+            times_dev = staged.to(dev, non_blocking=True)
+            if moving:
+                name = "gnncca_link_frames_motion_timed"
+                st = lib.gnncca_link_frames_motion_timed(*head, nat.MOTION[self.motion], *tail, velocity.data_ptr() if n else None, *end,
+                                                         times_dev.data_ptr(), self.max_dt)
+            else:
+                name = "gnncca_link_frames_gap_timed"
+                st = lib.gnncca_link_frames_gap_timed(*head, nat.MATCHING[self.matching], self.miss_cost, *tail, *end, times_dev.data_ptr(),
+                                                      self.max_dt)
+            # times_dev is freed in stream order like the workspace (allocated on this stream): the launches above still read it
+        elif moving:
             name = "gnncca_link_frames_motion"
             st = lib.gnncca_link_frames_motion(*head, nat.MOTION[self.motion], *tail, velocity.data_ptr() if n else None, *end)
         elif self.matching == "optimal":
@@ -359,7 +434,8 @@ class FrameLinker:
         if st:
             nat.check(st, name)
         # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
-        self._state, self._frame_rows, self._state_motion = state, out_rows, self.motion
+        self._state, self._frame_rows, self._state_motion, self._state_timed = state, out_rows, self.motion, times is not None
+        self._frame_times = all_times[-len(out_rows):] if times is not None else []
         return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1], velocity)
 
 

@@ -711,7 +711,7 @@ GNNCCA_API int gnncca_eval_frames_dense(const int64_t* edge_index, const float* 
  * written with the same reid_dim and its own capacity (<= GNNCCA_TRACK_MAX_FRAME_NODES); it is not modified.  n_frames = 0 launches
  * nothing and writes nothing.  Out of scope: re-identification after a frame in which a track was not seen (gnncca_link_frames_gap
  * below does that), an optimal assignment per frame pair in place of mutual best (gnncca_link_frames_gap_ex below does that), time
- * stamps.  Workspace: gnncca_link_workspace_bytes. */
+ * stamps (gnncca_link_frames_gap_timed below, with max_gap = 0, does that).  Workspace: gnncca_link_workspace_bytes. */
 #define GNNCCA_TRACK_MAX_FRAME_NODES 4096
 GNNCCA_API size_t gnncca_cluster_summaries_bytes(int64_t n_nodes, int64_t n_frames);
 GNNCCA_API int gnncca_cluster_summaries(const int32_t* labels, const int32_t* node_ptr_dev, const double* xw, const double* yw,
@@ -752,7 +752,7 @@ GNNCCA_API int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* co
  * max_gap + 1 frames; it is not modified.  state_out: gnncca_link_gap_state_bytes(C, n_frames_kept, R) bytes.  GNNCCA_ERR_INVALID_ARG:
  * max_gap outside [0, GNNCCA_TRACK_MAX_GAP], a frame capacity above GNNCCA_TRACK_MAX_FRAME_NODES, the checks of gnncca_link_frames.
  * max_gap + 4 launches; deterministic (integer flags, fixed sum orders, no atomics), no host wait, no allocation: capturable.
- * Out of scope: motion prediction (a velocity term), time stamps; the pairs of a (level, frame pair) table are chosen by mutual best
+ * Out of scope: motion prediction (a velocity term); time stamps are gnncca_link_frames_gap_timed's, below; the pairs of a (level, frame pair) table are chosen by mutual best
  * here and by a min-cost assignment in gnncca_link_frames_gap_ex below, in both cases per table, never over time.
  * Workspace: gnncca_link_gap_workspace_bytes(n_nodes, n_frames, state_rows = the sum of state_in_frame_rows). */
 #define GNNCCA_TRACK_MAX_GAP 8
@@ -789,7 +789,7 @@ GNNCCA_API int gnncca_link_frames_gap(const int32_t* node_ptr_dev, const int32_t
  * matching = 1 max_frame_nodes and every state_in_frame_rows entry are at most GNNCCA_TRACK_MAX_OPTIMAL_FRAME_NODES.
  * GNNCCA_ERR_INVALID_ARG, before any launch: a matching other than 0 or 1, a miss_cost that is not finite and > 0, a frame of the batch
  * or of the history above that limit with matching = 1, the checks of gnncca_link_frames_gap.  max_gap + 4 launches; deterministic, no
- * host wait, no allocation: capturable.  Out of scope: an assignment over time (across levels or frames), motion prediction, time stamps. */
+ * host wait, no allocation: capturable.  Out of scope: an assignment over time (across levels or frames), motion prediction.  Time stamps: gnncca_link_frames_gap_timed. */
 #define GNNCCA_TRACK_MAX_OPTIMAL_FRAME_NODES 128
 GNNCCA_API int gnncca_link_frames_gap_ex(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
                                          const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
@@ -823,7 +823,7 @@ GNNCCA_API int gnncca_link_frames_gap_ex(const int32_t* node_ptr_dev, const int3
  * barriers, ids from the running next_id; nothing waits for another workgroup), a frame-parallel launch for node_track and the new state.
  * Deterministic, no host wait, no allocation: capturable.  GNNCCA_ERR_INVALID_ARG: motion != 1, the checks of gnncca_link_frames_gap.
  * Limits: constant velocity from the LAST link only, so the prediction is wrong after a sharp turn and a track can end there and restart;
- * no time stamps; the min-cost assignment (gnncca_link_frames_gap_ex, matching = 1) has no motion. */
+ * the min-cost assignment (gnncca_link_frames_gap_ex, matching = 1) has no motion.  Time stamps: gnncca_link_frames_motion_timed. */
 GNNCCA_API size_t gnncca_link_motion_state_bytes(int64_t capacity_rows, int32_t n_frames_kept, int32_t reid_dim);
 GNNCCA_API size_t gnncca_link_motion_workspace_bytes(int64_t n_nodes, int64_t n_frames, int64_t state_rows);
 GNNCCA_API int gnncca_link_frames_motion(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
@@ -833,6 +833,47 @@ GNNCCA_API int gnncca_link_frames_motion(const int32_t* node_ptr_dev, const int3
                                          const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track,
                                          int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, double* velocity, void* workspace,
                                          size_t workspace_bytes, gnncca_stream_t stream);
+
+/* gnncca_link_frames_gap_timed, gnncca_link_frames_motion_timed: gnncca_link_frames_gap_ex and gnncca_link_frames_motion with a TIME
+ * STAMP per frame, so that a dropped frame is a gap and not a silent error.  The arguments are those entries', then frame_time_dev and
+ * max_dt; the run is the same one (the untimed entries pass NULL, their launches and their bits are as they were); states, their
+ * layouts, the workspaces and the launch counts do not change.  The rule:
+ *   Time stamps.  A timed call gives one fp64 time per frame of the batch, in units of the nominal frame period: finite, strictly
+ *     increasing, the first strictly greater than the last time of the previous call.  T[f] is the time of frame f over the combined
+ *     list (the carried history, then the batch).
+ *   Level order.  For frame t at level k the other frame is still s = t - 1 - k, counted in frames PRESENT; a shorter gap still wins, and
+ *     the history still holds the last max_gap + 1 frames.
+ *   Elapsed time.  dt = T[t] - T[s], one fp64 subtraction, replaces (double)(k + 1) everywhere:  gate = max_step * dt;  with motion
+ *     pred(b) = pos(b) + dt * vel(b)  and  vel(a) = (pos(a) - pos(b)) / dt  -- each one operation, in the order of the untimed code, no FMA.
+ *   Skipped tables.  A table with !(dt > 0 && dt <= max_dt) has no admissible pair and is skipped whole (which also makes a bad device
+ *     array harmless).  max_dt is finite and > 0; FrameLinker's default is max_gap + 1, so a hole of one frame period consumes one unit
+ *     of max_gap.
+ *   Everything else is the mode's own rule, unchanged: masks, the cosine term, max_cos, cost = d / gate + lam * dcos, ties, mutual best
+ *     or the assignment with miss_cost, the numbering of fresh ids, and matched_gap (still the level k).
+ *   Consequence.  With T = 0, 1, 2, ... continuing across calls dt is exactly k + 1 and every output equals the untimed entry's bit
+ *     for bit.
+ * frame_time_dev is a DEVICE array, fp64 [state_in_frames + n_frames]: the times of the frames state_in holds, oldest first, then the
+ * batch's.  The CALLER keeps the times of the carried frames (the state does not hold them) and checks the order on the host; the
+ * kernels derive dt and the gate per (frame, level) and never loop over the array.  GNNCCA_ERR_INVALID_ARG, before any launch: max_dt
+ * not finite and > 0, frame_time_dev NULL with n_frames > 0, the checks of the untimed entry.  A state written by a timed call continued
+ * by an untimed one (or the reverse) is valid as far as the layout goes, but the ids then follow neither rule: FrameLinker refuses it.
+ * Limit: levels count frames present, so max_gap also bounds how many PRESENT frames a track may skip. */
+GNNCCA_API int gnncca_link_frames_gap_timed(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
+                                            const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                            double max_step, double lam, int32_t has_max_cos, double max_cos, int32_t max_gap,
+                                            int32_t matching, double miss_cost, const void* state_in, const int32_t* state_in_frame_rows,
+                                            int32_t state_in_frames, void* state_out, const int32_t* state_out_frame_rows,
+                                            int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track, int32_t* matched_prev,
+                                            int32_t* matched_gap, void* workspace, size_t workspace_bytes, gnncca_stream_t stream,
+                                            const double* frame_time_dev, double max_dt);
+GNNCCA_API int gnncca_link_frames_motion_timed(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
+                                               const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                               double max_step, double lam, int32_t has_max_cos, double max_cos, int32_t max_gap,
+                                               int32_t motion, const void* state_in, const int32_t* state_in_frame_rows,
+                                               int32_t state_in_frames, void* state_out, const int32_t* state_out_frame_rows,
+                                               int32_t state_out_frames, int64_t* cluster_track, int64_t* node_track, int32_t* matched_prev,
+                                               int32_t* matched_gap, double* velocity, void* workspace, size_t workspace_bytes,
+                                               gnncca_stream_t stream, const double* frame_time_dev, double max_dt);
 
 /* ---- Identity-tracking scores over a sequence (csrc/track_score.cuh, included by csrc/identities.hip) --------------------------------
  * Joins ids int64 [N] (the caller's person id of every detection), cam int32 [N] and node_track int64 [N] (gnncca_link_frames*) over the

@@ -3,7 +3,7 @@
 (N = 2048, every person seen once per camera: 8 clusters of 4 per frame) with R = 2048 appearance columns.  Needs an MI355X.
 
     python tools/time_tracking.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3] [--max-gap 0] [--hide 0]
-                                  [--matching mutual|optimal] [--crowded] [--motion none|velocity] [--drift 0]
+                                  [--matching mutual|optimal] [--crowded] [--motion none|velocity] [--drift 0] [--times drop:P|jitter:S]
 
 Two ways to the same result, timed in alternating rounds in one process (host clock around work that ends in a device synchronise):
   device   cluster summaries (2 launches) + FrameLinker (3 launches) on tensors that are already on the GPU, as a FramePipeline
@@ -21,7 +21,11 @@ alternating rounds, each compared with its oracle once.
 --motion velocity times FrameLinker(motion='velocity') (three launches whatever --max-gap is, one workgroup walking the frames in order)
 against tests/tracking_motion_oracle.py; the ids AND the velocities are compared once per run.  --drift V selects a batch whose people
 move: every person walks a straight line at V units per frame in a direction of its own (the default batch only jitters around a point,
-so its velocities are noise)."""
+so its velocities are noise).
+--times times the call WITH time stamps (linker(s, times=...), the _timed entries; the adjacent linker then runs the gap path with
+M = 0) against tests/tracking_time_oracle.py: drop:P removes every frame but the first with probability P and stamps the survivors with
+their indices, jitter:S (S < 0.5) keeps every frame and perturbs its index by uniform +-S.  Every repetition continues the times of the
+one before it (the state carries), so a repetition is a batch of a running sequence.  Without --times the call has no time stamps."""
 import argparse
 import json
 import os
@@ -38,6 +42,7 @@ import tracking_assign_oracle as ta  # noqa: E402
 import tracking_gap_oracle as tg  # noqa: E402
 import tracking_motion_oracle as tm  # noqa: E402
 import tracking_oracle as to  # noqa: E402
+import tracking_time_oracle as tt  # noqa: E402
 from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, cluster_summaries_raw  # noqa: E402
 
 
@@ -67,6 +72,32 @@ def make_batch(frames, cams, per, reid, seed=0, hide=0.0, drift=0.0):
         xw[out] += 1000.0 + 50.0 * np.arange(n)[out]
     node_ptr = (np.arange(frames + 1) * n_g).astype(np.int64)
     return dict(labels=labels, node_ptr=node_ptr, xw=xw, yw=yw, cam=cam, emb=emb.astype(np.float32), n=n)
+
+
+def stamp(b, spec, n_g, seed=1):
+    """--times: -> (the batch, without its dropped frames; the time of every remaining frame, float64).  Labels point inside a node's own
+    frame, so they move with their frame."""
+    kind, _, value = spec.partition(":")
+    try:
+        value = float(value)
+    except ValueError:
+        value = -1.0
+    frames = len(b["node_ptr"]) - 1
+    rng = np.random.default_rng(seed)
+    if kind == "jitter" and 0 <= value < 0.5:
+        return b, np.arange(frames, dtype=np.float64) + rng.uniform(-value, value, size=frames)
+    if kind != "drop" or not 0 <= value < 1:
+        raise SystemExit("--times takes drop:P with 0 <= P < 1 or jitter:S with 0 <= S < 0.5")
+    keep = rng.random(frames) >= value
+    keep[0] = True
+    rows = np.flatnonzero(np.repeat(keep, n_g))
+    new_row = np.full(b["n"], -1, np.int64)
+    new_row[rows] = np.arange(len(rows))
+    out = {k: b[k][rows] for k in ("xw", "yw", "cam", "emb")}
+    out["labels"] = new_row[b["labels"][rows]].astype(np.int32)
+    out["node_ptr"] = (np.arange(int(keep.sum()) + 1) * n_g).astype(np.int64)
+    out["n"] = len(rows)
+    return out, np.flatnonzero(keep).astype(np.float64)
 
 
 def crowded(a):
@@ -117,7 +148,10 @@ def main():
     ap.add_argument("--crowded", action="store_true")
     ap.add_argument("--motion", choices=("none", "velocity"), default="none")
     ap.add_argument("--drift", type=float, default=0.0)
+    ap.add_argument("--times", default=None, metavar="drop:P|jitter:S")
     a = ap.parse_args()
+    if a.times and a.crowded:
+        raise SystemExit("--times goes with the Terrace-shaped batch")
     if a.motion == "velocity" and (a.matching == "optimal" or a.crowded):
         raise SystemExit("--motion velocity goes with --matching mutual on the Terrace-shaped batch")
     if not torch.cuda.is_available():
@@ -125,6 +159,10 @@ def main():
     if a.crowded:
         return crowded(a)
     b = make_batch(a.frames, a.cams, a.per, a.reid, hide=a.hide, drift=a.drift)
+    times = None
+    if a.times:
+        b, times = stamp(b, a.times, a.cams * a.per)
+    calls = [0]   # timed: every call continues the times of the one before it, a.frames periods later
     dev = torch.device("cuda")
     d = {k: torch.from_numpy(b[k]).to(dev) for k in ("labels", "xw", "yw", "cam", "emb")}
     ptr_host = b["node_ptr"].tolist()
@@ -133,7 +171,10 @@ def main():
 
     def device_once():
         s = cluster_summaries_raw(d["labels"], ptr_host, d["xw"], d["yw"], d["cam"], d["emb"])
-        return s, link(s)
+        if times is None:
+            return s, link(s)
+        calls[0] += 1
+        return s, link(s, times=times + float((calls[0] - 1) * a.frames))
 
     def copy_once():
         out = [d[k].cpu() for k in ("labels", "xw", "yw", "cam", "emb")]   # (.cpu() of a device tensor synchronises)
@@ -142,6 +183,9 @@ def main():
     def host_once(state):
         labels, xw, yw, cam, emb = copy_once()
         s = to.summaries(labels, b["node_ptr"], xw, yw, cam, emb)
+        if times is not None:
+            return s, tt.link_timed(s, b["node_ptr"], times, max_step, lam, None, a.max_gap, state, matching=a.matching,
+                                    motion=a.motion == "velocity")
         if a.motion == "velocity":
             return s, tm.link_motion(s, b["node_ptr"], max_step, lam, None, a.max_gap, state)
         if a.matching == "optimal":
@@ -157,7 +201,7 @@ def main():
     same = all(np.array_equal(getattr(s_dev, k).cpu().numpy(), s_host[k]) for k in ("count", "rank", "size", "n_cams", "pos", "emb"))
     same_ids = all(np.array_equal(getattr(t_dev, k).cpu().numpy(), t_host[k]) for k in ("cluster_track", "node_track", "matched_prev"))
     gaps = t_dev.matched_gap.cpu().numpy()
-    if a.max_gap > 0 or a.matching == "optimal" or a.motion == "velocity":
+    if a.max_gap > 0 or a.matching == "optimal" or a.motion == "velocity" or times is not None:
         same_ids = same_ids and np.array_equal(gaps, t_host["matched_gap"])
     if a.motion == "velocity":
         same_ids = same_ids and np.array_equal(t_dev.velocity.cpu().numpy(), t_host["velocity"])
@@ -183,6 +227,7 @@ def main():
                       "host_reps": a.host_reps, "device_ms": [round(v, 4) for v in dev_ms], "host_ms": [round(v, 2) for v in host_ms],
                       "copy_ms": [round(v, 4) for v in copy_ms], "summaries_equal": bool(same), "ids_equal": bool(same_ids),
                       "tracks": int(t_dev.next_id.item()), "max_gap": a.max_gap, "hide": a.hide, "matching": a.matching, "motion": a.motion, "drift": a.drift,
+                      "times": a.times, "frames_kept": len(b["node_ptr"]) - 1,
                       "matches_per_gap": [int((gaps == k).sum()) for k in range(a.max_gap + 1)]}))
 
 
