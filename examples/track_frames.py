@@ -15,7 +15,9 @@ crossing each other).  Four TrackScorers accumulate, on the device, the identity
 against the person ids.  Last, a DROPPED frame: the same batches without their frame 1, as a camera network that lost it would deliver
 them, go to two linkers with motion -- one is told nothing and takes the frames for consecutive, the other gets a time stamp per frame
 (linker(s, times=...)), so the hole is a gap of two periods: its velocities stay displacements per PERIOD and its gate and prediction
-cover the time that really passed.  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
+cover the time that really passed.  A TrackGallery (gnn_cca_amd.reentry) stands behind the linker WITHOUT max_gap: it cannot bridge the
+hidden frame, so person 0 comes back as a new track, and the gallery gives that track the old identity back by appearance; its
+identities are scored like track ids.  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
 """
 import argparse
 import os
@@ -28,7 +30,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
 from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
-from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, TrackScorer, cluster_summaries  # noqa: E402
+from gnn_cca_amd.reentry import TrackGallery  # noqa: E402
+from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, Tracks, TrackScorer, cluster_summaries  # noqa: E402
 
 
 def without_frame(s, q):
@@ -59,6 +62,8 @@ def main():
     score_opt = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     by_truth_vel = FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity")   # a cluster is looked for where it is heading
     score_vel = TrackScorer(max_ids=a.persons, max_cams=a.cams)
+    gallery = TrackGallery(by_truth, max_cos=0.3)   # ended tracks, matched against newly born ones by appearance
+    score_back = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     blind, timed = (FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity") for _ in range(2))   # for the batches that lost a frame
     where = rng.uniform(-8, 8, size=(a.persons, 2))
     look = rng.standard_normal((a.persons, 256)).astype(np.float32)
@@ -87,6 +92,8 @@ def main():
         st = cluster_summaries(r.batch, truth)   # any partition of the batch's detections can be summarised
         tt = by_truth(st)
         tg = by_truth_gap(st)                    # tg.matched_gap: 1 where a cluster continues one that was last seen two frames ago
+        back = gallery(st, tt)                   # identities: a track born after an absence too long for the linker takes an ended track's
+        score_back.add(r, Tracks(back.cluster_identity, back.node_identity, tt.matched_prev, tt.next_id, None))   # scored where tracks stood
         score.add(r, tt)                         # ids (batch.y), cameras and node tracks joined over time: nothing waits for the GPU
         score_gap.add(r, tg)
         score_opt.add(r, by_truth_opt(st))
@@ -115,8 +122,10 @@ def main():
             print(f"  person 0, hidden in frame {hidden}: id {int(tt.cluster_track[before])} -> {int(tt.cluster_track[after])} without max_gap, "
                   f"{int(tg.cluster_track[before])} -> {int(tg.cluster_track[after])} with max_gap=1 "
                   f"(matched_gap {int(tg.matched_gap[after])}); tracks so far {int(tt.next_id.item())} against {int(tg.next_id.item())}")
+            print(f"  ... and behind the linker without max_gap the gallery: identity {int(back.cluster_identity[before])} -> "
+                  f"{int(back.cluster_identity[after])} (re-entered from track {int(back.reentered_from[after])})")
     print("random weights: the model's clusters are meaningless, the plumbing is what is shown; on the true partition a person keeps its id")
-    for name, sc in (("without max_gap", score), ("with max_gap=1", score_gap), ("with max_gap=1, matching='optimal'", score_opt),
+    for name, sc in (("without max_gap", score), ("without max_gap, identities of the re-entry gallery", score_back), ("with max_gap=1", score_gap), ("with max_gap=1, matching='optimal'", score_opt),
                      ("with max_gap=1, motion='velocity'", score_vel)):   # result(): the one synchronisation of a scorer
         res = sc.result()
         print(f"true partition {name}: " + ", ".join(f"{q} {v:.3f}" if isinstance(v, float) else f"{q} {v}" for q, v in res.items()))

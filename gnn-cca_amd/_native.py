@@ -19,6 +19,7 @@ MATCHING = {"mutual": 0, "optimal": 1}   # gnncca_link_frames_gap_ex
 MOTION = {"none": 0, "velocity": 1}      # gnncca_link_frames_motion takes 1; "none" is the entries above
 SCORE_MAX_IDS, SCORE_MAX_CAMS, SCORE_MAX_STREAMS, SCORE_MAX_SLOTS = 65536, 64, 1 << 20, 1 << 22   # gnncca_track_score_add
 SCORE_MIN_CAP, SCORE_HEADER_LEN = 1024, 8
+REENTRY_MAX_WINDOW = 4096            # gnncca_reentry_update: the walking workgroup keeps a frame's candidate tracks in LDS
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
 
 
@@ -252,6 +253,12 @@ _SIGNATURES = {
     "gnncca_track_score_rehash": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gnncca_track_score_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_reentry_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gnncca_reentry_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gnncca_reentry_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                        C.c_int32, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
+                                        C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnncca_edge_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "gnncca_edge_loss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -913,6 +913,58 @@ GNNCCA_API int gnncca_track_score_add(const int64_t* ids, const int32_t* cam, co
                                       int64_t node_base, int64_t n_nodes, int32_t n_frames, int32_t max_ids, int32_t max_cams, void* table,
                                       int64_t cap, int64_t* last, int32_t* slot, int32_t* switched, gnncca_stream_t stream);
 
+/* ---- Re-entry gallery (csrc/identities_reentry.cuh, included by csrc/identities.hip) ---------------------------------------------------
+ * A second stage behind gnncca_link_frames*: a track born after an absence longer than the linker bridges gets the IDENTITY of the ended
+ * track it looks like.  Track ids stay as the linker gave them; identities are what a consumer scores.  No counterpart in the reference.
+ * Notation: M = max_gap (the linker's), W = window, S = W + max_batch ring slots, f = frames_seen + the frame's index in the call (the
+ * caller counts the frames of all calls; an empty or refused frame counts).  A BIRTH is a usable cluster (rank < the frame's count) with
+ * matched_prev == -1; b is its cluster_track.  The inputs cluster_track, matched_prev, matched_gap are the linker's outputs for the SAME
+ * summaries (matched_gap of gnncca_link_frames: 0 where matched_prev >= 0, else -1).
+ * State.  ring_state, gnncca_reentry_state_bytes(S, R) bytes, updated IN PLACE: owner int64 [S] (-1: empty), identity int64 [S], last
+ *   int64 [S], pos fp64 [S][2], continued int32 [S], then from the next 256-byte boundary sum fp32 [S][R].  Track j lives in slot j mod S.
+ *   A fresh ring has owner = -1 and everything else 0 (the caller fills it).  And the identities of the rows of the last M + 1 frames,
+ *   hist_in -> hist_out int64, frame after frame, each frame with the row capacity the caller gives in hist_*_frame_rows (host arrays, as
+ *   the state_*_frame_rows of gnncca_link_frames_gap: per frame its node count; hist_out_frames = min(hist_in_frames + n_frames, M + 1)).
+ * Frames in order; for frame f:
+ *   1. a continued cluster (matched_prev = m >= 0, matched_gap = k) takes the identity of row m of frame f - 1 - k, from this call's
+ *      cluster_identity or from hist_in -- never through the ring, so a track may live longer than S births;
+ *   2. track j is eligible for birth b iff  b - W <= j < b and owner[j mod S] == j;  continued[j] == 0;  f - last[j] >= M + 2;  max_age
+ *      absent or f - last[j] <= max_age;  max_speed absent or d <= max_speed * (double)(f - last[j]) with d = sqrt(dx dx + dy dy) between
+ *      the birth's pos and pos[j];  dcos <= max_cos, where dcos = 1 - <e, sum[j]> / (|e| |sum[j]|) in fp64 over the birth's emb row e
+ *      (1 if a norm is 0; a NaN is admissible with nobody).  cost = dcos;
+ *   3. mutual best among the births of the frame: b's best j has the smallest cost, ties to the smaller j; j's best birth the smallest
+ *      cost, ties to the smaller rank.  Mutual: identity(b) = identity[j], continued[j] = 1, reentered_from = j.  Else identity(b) = b;
+ *   4. a birth takes slot b mod S whatever it held: owner = b, sum = 0, continued = 0, identity = identity(b);
+ *   5. every usable cluster whose track t has owner[t mod S] == t: sum += emb row (fp32, one addition per column, in frame order),
+ *      last = f, pos = its pos.  A cluster whose slot was taken by a younger track is skipped.
+ * Consequences: the result does not depend on how a sequence is cut into calls; with n_nodes <= max_batch an eligible track's slot cannot
+ * have been taken by a birth of the same call; an eligible track can no longer be continued by the linker, so its sum / last / pos are
+ * final -- the kernels accumulate them for the whole call first.  The dot product is a chain of fp64 fused multiply-adds in ascending
+ * column order, the norms lane-strided fp64 sums: decisions equal the numpy restatement's wherever no comparison hangs on the last bits.
+ * The births of a call must carry consecutive track ids in row order (every gnncca_link_frames* numbers fresh ids so); otherwise
+ * nobody re-enters in that call.
+ * Outputs: cluster_identity int64 [N] (row-aligned with cluster_track, -1 beyond a frame's count), node_identity int64 [N] (through
+ * rank), reentered_from int64 [N] (the old TRACK id a born cluster was attached to, else -1).
+ * workspace: gnncca_reentry_workspace_bytes(n_nodes, window, max_batch) bytes: the cost table fp64 [n_nodes][W] and O(n_nodes + S) more.
+ * Six launches (prep, mark, accumulate, norms, the tiled cosine table, one walking workgroup); deterministic, no host wait, no
+ * allocation: capturable.  n_frames = 0 launches nothing.  GNNCCA_ERR_INVALID_ARG before any launch: max_cos outside [0, 2], window
+ * outside [1, GNNCCA_REENTRY_MAX_WINDOW], max_batch < 1, n_nodes > max_batch, max_age < M + 2, max_speed not finite and > 0, reid_dim < 1,
+ * max_gap outside [0, GNNCCA_TRACK_MAX_GAP], a frame above GNNCCA_TRACK_MAX_FRAME_NODES, inconsistent history frames, a NULL array.
+ * Limits: appearance decides (max_speed is the only use of position); chains are one-to-one, an ended track is continued once; a person
+ * absent while more than W other tracks are born is forgotten; n_nodes <= max_batch per call. */
+#define GNNCCA_REENTRY_MAX_WINDOW 4096
+GNNCCA_API size_t gnncca_reentry_state_bytes(int64_t n_slots, int32_t reid_dim);
+GNNCCA_API size_t gnncca_reentry_workspace_bytes(int64_t n_nodes, int32_t window, int32_t max_batch);
+GNNCCA_API int gnncca_reentry_update(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos, const float* emb,
+                                     int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                     const int64_t* cluster_track, const int32_t* matched_prev, const int32_t* matched_gap, int32_t max_gap,
+                                     double max_cos, int32_t window, int32_t max_batch, int32_t has_max_age, int64_t max_age,
+                                     int32_t has_max_speed, double max_speed, int64_t frames_seen, void* ring_state, const int64_t* hist_in,
+                                     const int32_t* hist_in_frame_rows, int32_t hist_in_frames, int64_t* hist_out,
+                                     const int32_t* hist_out_frame_rows, int32_t hist_out_frames, int64_t* cluster_identity,
+                                     int64_t* node_identity, int64_t* reentered_from, void* workspace, size_t workspace_bytes,
+                                     gnncca_stream_t stream);
+
 /* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
  * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).
  * criterion: GNNCCA_LOSS_BCE, GNNCCA_LOSS_BCE_WEIGHTED (pos_weight > 0) or GNNCCA_LOSS_FOCAL (utils.FocalLoss_binary: focusing_param,
