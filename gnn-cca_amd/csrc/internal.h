@@ -1,5 +1,5 @@
 // internal.h -- layouts and host functions shared by the library's translation units: the host packer (pack.cpp), the node encoder's
-// route (enc_route.cpp), the inference kernels (mpn_forward.hip), post-processing (mpn_post.hip), training (mpn_train.hip) and the smaller
+// route (enc_route.cpp), the message steps' route (step_route.cpp), the inference kernels (mpn_forward.hip), post-processing (mpn_post.hip), training (mpn_train.hip) and the smaller
 // HIP units.  Plain C++, no HIP types.
 // Not part of the public ABI (include/gnncca_mpn.h is).
 #pragma once
@@ -250,6 +250,99 @@ struct EncRoute {
     size_t tail_lds;
 };
 EncRoute encoder_route(const EncRouteIn& in, const EncTuning& t);
+
+// ---- the message steps' route (step_route.cpp) -----------------------------------------------------------------------------------
+// Which instantiation of which step kernel every step launches, on what grid and into which logit slots: step_plan() decides once per
+// forward what does not change from step to step, step_launch() names one step's kernel; both are pure host functions.
+// launch_step_variant (mpn_forward.hip) carries a StepLaunch out and compares no sizes.  tests/test_step_route.py pins the table;
+// DESIGN.md 4.2 has it.
+enum StepFamily : int {
+    kStepGeneral = 0,  // mpn_step_kernel<RE, MSG, MX> (step_general.cuh): any dims of the family, traces, dropout, 'max'
+    kStepFast,         // mpn_step_fast_kernel<FIRST, CLS, MSG, PDL, EB, NT> (step_fast.cuh): the shipped shape, f32 message
+    kStepPipe,         // mpn_step_pipe_kernel<FIRST, CLS, MSG, PDL, EB, NT, RNG, NPW, CIN> (step_pipe.cuh): the same, bf16-split message
+};
+#ifndef GNNCCA_NPW2_CLS
+#define GNNCCA_NPW2_CLS 0         // 1: instantiate the two-nodes-per-wave form for the classifying steps as well (diagnostic builds)
+#endif
+// THE statement of which instantiations the library has: step_launch() never names another one, launch_step_variant instantiates
+// these and no others (if constexpr).  The kernels' static_asserts are the wider, necessary conditions.
+constexpr bool step_variant_exists(int family, bool FIRST, bool CLS, bool MSG, bool PDL, bool EB, int NT, bool RNG, int NPW, bool CIN) {
+    if (family == kStepGeneral) return true;                    // every <RE, MSG, MX>; the other arguments are not its own
+    if (NT < 0 || NT > 2 || (NT != 0 && PDL)) return false;     // non-temporal streams only without the LDS-resident gather table
+    if (family == kStepFast) return !RNG && NPW == 1 && !CIN;   // no range, two-node or deferred forms
+    // the nine forms that classify their input state: a message step (one or two nodes per wave), or the last step classifying both
+    if (CIN) return !FIRST && !PDL && !EB && !RNG && (MSG ? !CLS && (NPW == 1 || NPW == 2) : CLS && NPW == 1);
+    // column ranges: default cache policy, one node per wave (also compiled for FIRST && !MSG, where they would do nothing and the
+    // route never takes them: step_launch)
+    if (RNG) return NT == 0 && NPW == 1;
+    // two nodes per wave: message steps without the table; the classifying ones need 143-155 VGPRs (step_pipe.cuh) and are a build option
+    if (NPW == 2) return MSG && !PDL && (!CLS || GNNCCA_NPW2_CLS);
+    return NPW == 1;
+}
+// mpn_step_pipe_kernel's eligibility: every buffer it addresses with 32-bit offsets stays below 2^31 bytes
+inline bool step_pipe_fits(long long N, long long E, long long e_stride, unsigned long long ws_bytes) {
+    const long long lim = 1ll << 31;
+    // (the whole workspace is addressed through one descriptor: it must end below the out-of-range offset 2^31 of a dead lane, and
+    // below 2^31 - 4 so that "the slot before slot 0" of DERIVE's predecessor load is out of range too)
+    return 6 * e_stride * 4 <= lim && E * 16 <= lim && N * 32 <= lim && ws_bytes <= (unsigned long long)lim - 4096;
+}
+// The measured thresholds of the step route and the diagnostics that force a choice: the member initialisers are the defaults (the one
+// place they are written), step_tuning() is the defaults overridden by the GNNCCA_* switches of DESIGN.md 11, read once per process.
+// step_route.cpp has the measurements beside the rules.
+struct StepTuning {
+    int msg_f32_max_n = 512;                         // last node count of the f32 message (kStepFast)
+    int fill_waves = 4096, fill_waves_long = 16384;  // waves that fill the chip; the same for graphs whose nodes average >= long_chunks chunks
+    int long_chunks = 32;
+    int npw_min_n = 16384;                           // GNNCCA_NPW_MIN_N:       first node count of two nodes per wave (steps 2 ... L)
+    int npw_min_n_first = 16384;                     // GNNCCA_NPW_MIN_N_FIRST: the same for step 1
+    int pd_lds_min = 0x7FFFFFFF, pd_lds_max = 1024;  // GNNCCA_PD_LDS_MIN / _MAX: node range that stages the P_dst table in LDS (default: none)
+    double nt_store_bytes = 150e6;                   // edge state beyond which its stores (and the edge_attr loads) are non-temporal
+    double nt_load_bytes = 256e6;                    // ... and its loads as well
+    int force_wps = 0;                               // GNNCCA_WPS:     1 / 2 / 4 waves per node (capped by the chunk count)
+    int force_npw = 0;                               // GNNCCA_NPW:     1 / 2 = two nodes per wave never / whenever eligible
+    int force_nt = -1;                               // GNNCCA_STEP_NT: 0 / 1 / 2 = default policy / nt stores / nt loads too
+};
+const StepTuning& step_tuning();
+struct StepRouteIn {
+    const gnncca_mpn_dims* d;
+    const BlobHeader* hdr;
+    const Workspace* ws;
+    int N, E;
+    uint32_t options;
+    bool dropping;                    // train-mode Dropout active
+    bool traced, trace_h_steps;       // a gnncca_trace was passed; it asks for the node states of every step (so the last step sends messages)
+    bool attr_aligned;                // 16-byte alignment of edge_attr
+};
+struct StepPlan {                     // what does not change from step to step
+    int launches;                     // 0: no edges, the forward ends behind the encoder; 1 for L == 0 (classify only); else L
+    int family;                       // StepFamily (kStepGeneral for L == 0)
+    bool RE, MX;                      // kStepGeneral: reattach_edges, 'max' aggregation
+    int N, hin;
+    int msg_f32, attr_vec, wps, npw_first, npw_later, pd_lds, e_bf16;
+    int nt;                           // 0 / 1 / 2: the policy (StepParams::nt_store, nt_load); the template argument where a variant has it
+    bool ranges;                      // StepParams::rng is set
+    int ell_S;                        // padded edge-state layout as USED (0: compact)
+    bool defer;                       // deferred classification (step_pipe.cuh: CIN)
+    bool trace_h_steps;
+    int first_cls, L, cls_layers;
+};
+struct StepLaunch {
+    // the instantiation: kStepGeneral <RE, MSG, MX>, kStepFast <FIRST ... NT>, kStepPipe all nine
+    int family;
+    bool RE, MX, FIRST, CLS, MSG, PDL, EB;
+    int NT;
+    bool RNG;
+    int NPW;
+    bool CIN;
+    unsigned blocks;                  // workgroups of 256 threads
+    size_t lds;                       // dynamic LDS bytes
+    // the per-step scalars of StepParams (npw: the forward's choice for this step, whatever NPW the variant has)
+    int first, update, store_e, npw, cls_layers, cls_no, stamp_slot;
+    int slot_out, slot_in;            // logit slot this step writes / classifies from its input state; -1: none
+    int buf_in, buf_out;              // index of the pd / psq table read / written; -1: none
+};
+StepPlan step_plan(const StepRouteIn& in, const StepTuning& t);
+StepLaunch step_launch(const StepPlan& p, int step);   // step 1 ... L; 0: the L == 0 launch
 
 // Workspace of the fused backward (gnncca_mpn_backward*, mpn_train.hip): byte offsets, all multiples of 256.  `d` must have passed
 // backward_ok (a two-layer node encoder); F1 is its first layer's width.

@@ -18,7 +18,8 @@
 // no atomics and is bitwise reproducible.
 //
 // This translation unit is INFERENCE: the graph plan, the node encoder's GEMM forms, the message-passing step kernels, the generic family
-// and the forward itself (forward_impl: checks, carve-up, the node encoder as encoder_route() of enc_route.cpp decided it, the steps).
+// and the forward itself (forward_impl: checks, carve-up, the node encoder as encoder_route() of enc_route.cpp decided it, every step as
+// step_plan() / step_launch() of step_route.cpp named it: launch_step_variant).
 // Post-processing and the one-call frame pipeline are mpn_post.hip, training (fused backward, layer-by-layer engine, device packer) is
 // mpn_train.hip; every __global__ kernel is compiled in exactly one of the three, and the few that
 // another unit launches too have host launchers (internal.h).
@@ -265,20 +266,12 @@ static int launch_node_encoder(const EncRoute& r, const gnncca_mpn_dims* d, cons
     return GNNCCA_OK;
 }
 
-// The message steps' set-up: everything of StepParams that does not change from step to step, and the nodes-per-wave of step 1 / of
-// the later steps (step_pipe.cuh: NPW).
-struct StepSetup {
+// The message steps' set-up: everything of StepParams that does not change from step to step, the decided part from the plan
+// (step_route.cpp).  Every field is filled whichever kernel the steps run on, also where that kernel ignores it.
+static StepParams step_setup(const StepPlan& plan, const gnncca_mpn_dims* d, const BlobHeader& hdr, const Workspace& ws, const FwdBuffers& b,
+                             const float* blob, const float* edge_attr, int N, int E, const DropCfg& drop) {
     StepParams sp;
-    int npw_first, npw_later;
-};
-static StepSetup step_setup(const gnncca_mpn_dims* d, const BlobHeader& hdr, const Workspace& ws, const FwdBuffers& b, const float* blob,
-                            const float* edge_attr, int N, int E, uint32_t options, bool use_ell, const DropCfg& drop) {
-    const int L = d->num_enc_steps;
-    const long long avg_deg = (E + (long long)N - 1) / N;
-    const int chunks = (int)((avg_deg + 63) / 64);
-    StepSetup out;
-    StepParams& sp = out.sp;
-    std::memset(&sp, 0, sizeof(sp));
+    std::memset(&sp, 0, sizeof(sp));   // (diag stays 0: nothing sets its bits any more; the step kernels keep the field, StepParams::diag)
     sp.blob = blob;
     sp.seg_ptr = b.seg_ptr;
     sp.col32 = b.col32;
@@ -301,71 +294,64 @@ static StepSetup step_setup(const gnncca_mpn_dims* d, const BlobHeader& hdr, con
     sp.off_cb2 = hdr.cls_b2;
     sp.off_fast = hdr.fast_consts;
     sp.off_wnebf = hdr.wne_bf16;
-    // which arithmetic the node message uses (StepParams::msg_f32): the traced (general) and the fast kernels follow ONE rule
-    sp.msg_f32 = (N <= 512 || !step_pipe_fits(N, E, ws.e_stride, ws.total)) ? 1 : 0;
     sp.cls_hidden = hdr.cls_hidden;
     sp.N = N;
     sp.E = E;
     sp.edge_in = d->edge_in;
-    sp.attr_vec = d->edge_in == 4 && (reinterpret_cast<uintptr_t>(edge_attr) & 15) == 0;
     sp.agg = d->agg;
     sp.reatt_n = d->reattach_nodes;
-    // waves per source-node segment: split a segment over 2 or 4 waves only while that is needed to put ~4 waves on
-    // every SIMD (small graphs are latency-bound); big batches keep one wave per node, which amortises the
-    // per-node prologue / projection epilogue over all of the node's chunks
-    {
-        // waves per node that would fill the chip; graphs whose nodes average >= 32 chunks (degree ~2000+) get four times that: the
-        // tail of a launch is then a few long segments (dense3000: 0.4315 -> 0.4039 ms with four waves per node, dense2048 equal;
-        // profiles/r03_logs/r3_wps1.log)
-        const long long want = (chunks >= 32 ? 16384 : 4096) / (long long)N;
-        int wps = chunks >= 4 ? 4 : (chunks >= 2 ? 2 : 1);
-        while (wps > 1 && wps > want) wps >>= 1;
-        // GNNCCA_OPT_ENC_UNSPLIT promises logits that do not depend on the batch around a graph for batches of >= 4096 nodes: the
-        // cross-wave combine sums in another order with another wave count, and `want` above depends on N (a shard of 2 x dense2048
-        // would get four waves per node, the union of 8 one), so the option pins one wave per node there, the rule of every round
-        // before the four-wave one (tests/test_gpu_sharded.py: dense2048 shard against its union, bitwise)
-        if ((options & GNNCCA_OPT_ENC_UNSPLIT) != 0 && N >= 4096) wps = 1;
-        static const int force_wps = diag_env_int("GNNCCA_WPS", 0, 1, 4);  // diagnostics
-        if (force_wps == 1 || force_wps == 2 || force_wps == 4) wps = std::min(force_wps, chunks >= 4 ? 4 : (chunks >= 2 ? 2 : 1));
-        sp.wps = wps;
-        // two nodes per wave (step_pipe.cuh: NPW): batches whose nodes average one round (<= 128 edges) and that still fill the chip with
-        // half as many waves
-        static const int force_npw = diag_env_int("GNNCCA_NPW", 0, 1, 2);   // diagnostics: 1 / 2 = never / whenever eligible
-        // thresholds: from 16 384 nodes (step 1 at 8192: 14.9 -> 15.7 us; at 16 384: 29.8 -> 28.2).  The later steps alone from 8192 nodes, with
-        // the classification deferred, move 64 x dense128 from 17.2 / 15.3 / 6.4 to 14.5 / 14.6 / 8.9 us per step: a tie per forward
-        // (profiles/r04_logs/ab_npw{6,7}.log), so one threshold serves both
-        static const int npw_min_n = diag_env_int("GNNCCA_NPW_MIN_N", 16384, 0, 0x7FFFFFFF);
-        static const int npw_min_n_first = diag_env_int("GNNCCA_NPW_MIN_N_FIRST", 16384, 0, 0x7FFFFFFF);
-        out.npw_later = (wps == 1 && chunks <= 2 && (force_npw == 2 || (force_npw == 0 && N >= npw_min_n))) ? 2 : 1;
-        out.npw_first = (out.npw_later == 2 && (force_npw == 2 || N >= npw_min_n_first)) ? 2 : 1;
-        sp.npw = out.npw_later;
-    }
-    sp.hin = (d->reattach_nodes ? 2 : 1) * kH;
-    // column ranges instead of the col32 stream on steps 2 ... L of the specialised kernels (StepParams::rng)
-    sp.rng = (L >= 2 && (options & GNNCCA_OPT_COLUMN_RANGES) != 0) ? reinterpret_cast<int*>(b.base + ws.rng) : nullptr;
+    sp.hin = plan.hin;
+    sp.msg_f32 = plan.msg_f32;
+    sp.attr_vec = plan.attr_vec;
+    sp.wps = plan.wps;
+    sp.npw = plan.npw_later;
+    sp.pd_lds = plan.pd_lds;
+    sp.e_bf16 = plan.e_bf16;
+    sp.ell_S = plan.ell_S;
+    sp.nt_store = plan.nt >= 1, sp.nt_load = plan.nt >= 2;
+    sp.rng = plan.ranges ? reinterpret_cast<int*>(b.base + ws.rng) : nullptr;
     sp.ws_base = b.base;
     sp.ws_bytes = ws.total;
     sp.so_e = (unsigned)ws.e, sp.so_col = (unsigned)ws.col32, sp.so_perm = (unsigned)ws.perm;
-    // The P_dst gather table staged whole in LDS: OFF by default since round 4.  Rounds 1-2 staged it for every N <= 1024; round 3 found
-    // gathers straight from L2 ahead below 801 nodes (dense32 ... dense768 -1.3 ... -4 % per forward, r3_pdlds2.log, r3_pdlds3.log) and
-    // kept it for 801 ... 1024; with four waves per node and the kernels as they are now the table loses there as well -- dense1024,
-    // L = 8 (BASELINE config 5): 120.4 -> 118.3 us per forward with the fp32 edge state, 112.8 -> 110.1 with bf16
-    // (profiles/r04_logs/ab_config5.log; with ONE wave per node the table still wins, 141 vs 151 us, but that form is slower anyway).
-    // The switches keep the variant reachable for A/B runs: GNNCCA_PD_LDS_MIN / _MAX name the node range that stages it.
-    static const int pd_lds_max = diag_env_int("GNNCCA_PD_LDS_MAX", 1024, 0, 1024);   // diagnostics
-    static const int pd_lds_min = diag_env_int("GNNCCA_PD_LDS_MIN", 0x7FFFFFFF, 0, 0x7FFFFFFF);
-    sp.pd_lds = (N >= pd_lds_min && N <= pd_lds_max) && d->num_enc_steps > 0;
-    sp.e_bf16 = (options & GNNCCA_OPT_EDGE_STATE_BF16) != 0;  // honoured by the specialised kernels only
-    sp.ell_S = use_ell ? ws.ell_S : 0;
     sp.drop = drop;
-    {
-        const double state_bytes = (double)(sp.e_bf16 ? kEF / 2 : kEF) * (double)ws.e_stride * 4.0;
-        sp.nt_store = state_bytes > 150e6;
-        sp.nt_load = state_bytes > 256e6;
-        static const int force_nt = diag_env_int("GNNCCA_STEP_NT", -1, -1, 2);   // diagnostics: 0 / 1 / 2 = default policy / nt stores / nt loads too
-        if (force_nt >= 0) sp.nt_store = force_nt >= 1, sp.nt_load = force_nt >= 2;
+    return sp;
+}
+
+// One step as step_launch() (step_route.cpp) named it: the ladders turn the run-time names into template arguments, `if constexpr` keeps
+// them to the instantiations the library has (step_variant_exists: internal.h).  Compares no sizes; the grid and the LDS are the route's.
+// A name the library does not have launches nothing and is hipErrorInvalidValue (step_launch never produces one: tests/test_step_route.py).
+static hipError_t launch_step_variant(const StepLaunch& l, const StepParams& sp, hipStream_t st) {
+    const dim3 grid(l.blocks), block(256);
+    bool launched = false;
+    auto with_nt = [&](auto&& f) {
+        l.NT == 2 ? f(std::integral_constant<int, 2>{}) : l.NT == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+    };
+    if (l.family == kStepGeneral) {
+        with_flag(l.RE, [&](auto RE) { with_flag(l.MSG, [&](auto MSG) { with_flag(l.MX, [&](auto MX) {
+            GNNCCA_LAUNCH((mpn_step_kernel<RE(), MSG(), MX()>), grid, block, l.lds, st, sp);
+            launched = true;
+        }); }); });
+    } else {
+        with_flag(l.FIRST, [&](auto FIRST) { with_flag(l.CLS, [&](auto CLS) { with_flag(l.MSG, [&](auto MSG) { with_flag(l.PDL, [&](auto PDL) {
+        with_nt([&](auto NT) { with_flag(l.EB, [&](auto EB) {
+            if (l.family == kStepFast) {
+                if constexpr (step_variant_exists(kStepFast, FIRST(), CLS(), MSG(), PDL(), EB(), NT(), false, 1, false)) {
+                    GNNCCA_LAUNCH((mpn_step_fast_kernel<FIRST(), CLS(), MSG(), PDL(), EB(), NT()>), grid, block, l.lds, st, sp);
+                    launched = true;
+                }
+                return;
+            }
+            with_flag(l.RNG, [&](auto RNG) { with_flag(l.NPW == 2, [&](auto TWO) { with_flag(l.CIN, [&](auto CIN) {
+                constexpr int NPW = TWO() ? 2 : 1;
+                if constexpr (step_variant_exists(kStepPipe, FIRST(), CLS(), MSG(), PDL(), EB(), NT(), RNG(), NPW, CIN())) {
+                    GNNCCA_LAUNCH((mpn_step_pipe_kernel<FIRST(), CLS(), MSG(), PDL(), EB(), NT(), RNG(), NPW, CIN()>), grid, block, l.lds, st, sp);
+                    launched = true;
+                }
+            }); }); });
+        }); });
+        }); }); }); });
     }
-    return out;
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const float* x, const int64_t* edge_index,
@@ -407,84 +393,41 @@ static int forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const 
     const FwdBuffers b = carve_pointers(workspace, ws);
     auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
 
-    // big, nearly regular batches keep the edge state in the padded layout (StepParams::ell_S); the decision is a pure
-    // function of (dims, N, E) made in carve(); the plan validates the degrees against it on the device
-    const bool use_ell = ws.ell_S > 0 && hdr.fast_consts != 0 && d->edge_in == 4 && !trace && d->agg != GNNCCA_AGG_MAX && aligned16(edge_attr) && E > 0;
-
-    // ---- node encoder: the route decided once (enc_route.cpp), then launched ---------------------------------------
+    // ---- the routes: decided once (enc_route.cpp, step_route.cpp), then launched ----------------------------------
     float* trace_h = trace ? trace->h_enc : nullptr;
+    const StepRouteIn sin{d, &hdr, &ws, N, E, options, dropping, trace != nullptr, trace && trace->h_steps, aligned16(edge_attr)};
+    const StepPlan plan = step_plan(sin, step_tuning());
     const EncRouteIn rin{d, &hdr, &ws, N, E, options, dropping, trace_h != nullptr, aligned16(x), aligned16(workspace),
                          E > 0 ? plan_num_blocks(E) : 0, E > 0 ? plan_span(edge_index, E) : 0};
     const EncRoute route = encoder_route(rin, enc_tuning());
-    int s = launch_node_encoder(route, d, hdr, blob, x, edge_index, N, E, use_ell ? ws.ell_S : 0, b, trace_h, drop, st, prof);
-    if (s != GNNCCA_OK || E == 0) return s;
+    int s = launch_node_encoder(route, d, hdr, blob, x, edge_index, N, E, plan.ell_S, b, trace_h, drop, st, prof);
+    if (s != GNNCCA_OK || plan.launches == 0) return s;
 
-    // ---- message passing steps ----------------------------------------------------------------------------
-    const int L = d->num_enc_steps;
-    const int first_cls = L - d->num_class_steps + 1;  // models/mpn.py:277
-    StepSetup setup = step_setup(d, hdr, ws, b, blob, edge_attr, N, E, options, use_ell, drop);
-    StepParams& sp = setup.sp;
-    const int npw_first = setup.npw_first, npw_later = setup.npw_later;
-    const bool re = d->reattach_edges != 0;
-    int out_idx = 0;
-    if (L == 0) {  // models/mpn.py:295-297: classify the encoded edge features once
-        sp.first = 1;
-        sp.update = 0;
-        sp.cls_layers = hdr.cls_layers;
-        sp.logits = logits_out;
-        sp.trace_e_enc = trace ? trace->e_enc : nullptr;
-        HIP_TRY(re ? (launch_step<true, false>(sp, st)) : (launch_step<false, false>(sp, st)));
-        PROF_MARK(GNNCCA_K_STEP_LAST);
-        return GNNCCA_OK;
-    }
-    // DEFERRED classification (step_pipe.cuh: CIN): a message step that produces a classified state does not classify it; the step that reads
-    // the state back does (the last step: its input and its output).  The classifying message steps then run the variant without the
-    // classifier -- lighter, and eligible for two nodes per wave.  Where it pays: forwards whose message steps run two nodes per wave
-    // (sp.npw == 2); fp32 edge state only (the bf16 state is rounded after its step classified it); logits bit for bit the same.
-    const bool can_defer = hdr.fast_consts != 0 && sp.attr_vec && !trace && d->agg != GNNCCA_AGG_MAX && !sp.msg_f32 && !sp.e_bf16 && !sp.pd_lds &&
-                           sp.rng == nullptr && first_cls < L && !dropping;
-    const bool defer = can_defer && npw_later == 2;
-    for (int step = 1; step <= L; ++step) {
-        const bool want_h = trace && trace->h_steps;
-        const bool msg = step < L || want_h;
-        sp.first = step == 1;
-        sp.npw = step == 1 ? npw_first : npw_later;
+    // ---- message passing steps (L == 0: one launch, step 0, that classifies the encoded edge features; models/mpn.py:295-297) ----
+    StepParams sp = step_setup(plan, d, hdr, ws, b, blob, edge_attr, N, E, drop);
+    for (int i = 0; i < plan.launches; ++i) {
+        const int step = plan.L == 0 ? 0 : i + 1;
+        const StepLaunch l = step_launch(plan, step);
+        sp.first = l.first;
+        sp.update = l.update;
+        sp.store_e = l.store_e;
+        sp.npw = l.npw;
         sp.step_no = step;
-        sp.cls_no = out_idx;
-        sp.stamp_slot = 2 + (step - 1 < 6 ? step - 1 : 5);
-        sp.update = 1;
-        sp.store_e = step < L;
-        if (defer) {   // slot of step s: s - first_cls
-            sp.cls_layers = step == L ? hdr.cls_layers : 0;
-            sp.logits = step == L ? logits_out + (size_t)(L - first_cls) * E : nullptr;
-            sp.logits_in = step - 1 >= first_cls ? logits_out + (size_t)(step - 1 - first_cls) * E : nullptr;
-        } else {
-            sp.cls_layers = step >= first_cls ? hdr.cls_layers : 0;
-            sp.logits = step >= first_cls ? logits_out + (size_t)(out_idx++) * E : nullptr;
-            sp.logits_in = nullptr;
-        }
-        sp.pd_in = b.pd[(step - 1) & 1];
-        sp.so_pd = (unsigned)ws.pd[(step - 1) & 1];
-        sp.psq_in = b.psq[(step - 1) & 1];
-        sp.pd_out = step < L ? b.pd[step & 1] : nullptr;
-        sp.psq_out = step < L ? b.psq[step & 1] : nullptr;
-        sp.trace_e_enc = (trace && step == 1) ? trace->e_enc : nullptr;
-        sp.trace_e = (trace && trace->e_steps) ? trace->e_steps + (size_t)(step - 1) * E * kEF : nullptr;
-        sp.trace_h = want_h ? trace->h_steps + (size_t)(step - 1) * N * kH : nullptr;
-        hipError_t err;
-        const bool fast = hdr.fast_consts != 0 && sp.attr_vec && !trace && d->agg != GNNCCA_AGG_MAX;
-        sp.diag = 0;   // nothing sets its bits any more; the step kernels keep the field for their register allocation (StepParams::diag)
-        const bool pipe_ok = fast && !sp.msg_f32;
-        if (pipe_ok)
-            err = launch_pipe_dispatch(sp, msg, st);
-        else if (fast)
-            err = launch_fast_dispatch(sp, msg, st);
-        else if (re)
-            err = msg ? launch_step<true, true>(sp, st) : launch_step<true, false>(sp, st);
-        else
-            err = msg ? launch_step<false, true>(sp, st) : launch_step<false, false>(sp, st);
-        HIP_TRY(err);
-        PROF_MARK(msg ? GNNCCA_K_STEP : GNNCCA_K_STEP_LAST);
+        sp.cls_no = l.cls_no;
+        sp.stamp_slot = l.stamp_slot;
+        sp.cls_layers = l.cls_layers;
+        sp.logits = l.slot_out >= 0 ? logits_out + (size_t)l.slot_out * E : nullptr;
+        sp.logits_in = l.slot_in >= 0 ? logits_out + (size_t)l.slot_in * E : nullptr;
+        sp.pd_in = l.buf_in >= 0 ? b.pd[l.buf_in] : nullptr;
+        sp.so_pd = l.buf_in >= 0 ? (unsigned)ws.pd[l.buf_in] : 0u;
+        sp.psq_in = l.buf_in >= 0 ? b.psq[l.buf_in] : nullptr;
+        sp.pd_out = l.buf_out >= 0 ? b.pd[l.buf_out] : nullptr;
+        sp.psq_out = l.buf_out >= 0 ? b.psq[l.buf_out] : nullptr;
+        sp.trace_e_enc = (trace && l.first) ? trace->e_enc : nullptr;
+        sp.trace_e = (trace && trace->e_steps && l.update) ? trace->e_steps + (size_t)(step - 1) * E * kEF : nullptr;
+        sp.trace_h = (plan.trace_h_steps && l.update) ? trace->h_steps + (size_t)(step - 1) * N * kH : nullptr;
+        HIP_TRY(launch_step_variant(l, sp, st));
+        PROF_MARK(l.MSG ? GNNCCA_K_STEP : GNNCCA_K_STEP_LAST);
     }
     return GNNCCA_OK;
 }

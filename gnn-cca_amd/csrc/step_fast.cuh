@@ -1,6 +1,6 @@
 #pragma once
-// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers and the launch code
-// below instantiates their templates); see that file for the overall picture.
+// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers; launch_step_variant there
+// instantiates the templates); see that file for the overall picture.
 namespace gnncca {
 
 // ------------------------------------------------------------------------------------------------------------
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) GNNCCA_FAST_ATTR void mpn_step_fast_kernel(con
     const int ktouch = touch_kernargs(sizeof(StepParams));
     const unsigned gflags = p.flags[0];
     const unsigned rbad = p.flags[1];
-    const int wps = p.wps;         // 1, 2 or 4 (mpn_forward.hip): shifts, not the 40-instruction software division of round 1-4
+    const int wps = p.wps;         // 1, 2 or 4 (step_route.cpp): shifts, not the 40-instruction software division of round 1-4
     const int wl = wps >> 1;       // log2(wps)
     const int node = (int)(blockIdx.x << (2 - wl)) + (wave >> wl);
     const int sub = wave & (wps - 1);
@@ -443,52 +443,6 @@ __global__ __launch_bounds__(256) GNNCCA_FAST_ATTR void mpn_step_fast_kernel(con
     GNNCCA_STAMP(p.stamp_slot, 7);
 }
 
-template <bool FIRST, bool CLS, bool MSG, bool PDL, bool EB, int NT>
-static hipError_t launch_fast_t(const StepParams& sp, hipStream_t st) {
-    const int npg = 4 / sp.wps;
-    const unsigned blocks = (unsigned)((sp.N + npg - 1) / npg);
-    const size_t lds = ((MSG ? (size_t)kH * kProjOut : 0) + 4 * kH + 16 + (PDL ? (size_t)sp.N * kPdStride : 0)) * sizeof(float);
-    GNNCCA_LAUNCH((mpn_step_fast_kernel<FIRST, CLS, MSG, PDL, EB, NT>), dim3(blocks), dim3(256), lds, st, sp);
-    return hipGetLastError();
-}
-
-template <bool FIRST, bool CLS, bool MSG, bool PDL>
-static hipError_t launch_fast(const StepParams& sp, hipStream_t st) {
-    if (!PDL) {   // the non-temporal variants only exist beyond the LDS-resident gather table (N > 1024): big batches
-        const int nt = sp.nt_load ? 2 : (sp.nt_store ? 1 : 0);
-        if (nt == 2) return sp.e_bf16 ? launch_fast_t<FIRST, CLS, MSG, false, true, 2>(sp, st) : launch_fast_t<FIRST, CLS, MSG, false, false, 2>(sp, st);
-        if (nt == 1) return sp.e_bf16 ? launch_fast_t<FIRST, CLS, MSG, false, true, 1>(sp, st) : launch_fast_t<FIRST, CLS, MSG, false, false, 1>(sp, st);
-    }
-    return sp.e_bf16 ? launch_fast_t<FIRST, CLS, MSG, PDL, true, 0>(sp, st) : launch_fast_t<FIRST, CLS, MSG, PDL, false, 0>(sp, st);
-}
-
-#ifndef GNNCCA_KERNELS_ONLY   // (tools: compile-only probes of single instantiations skip the dispatch tables)
-static hipError_t launch_fast_dispatch(const StepParams& sp, bool msg, hipStream_t st) {
-    const int key = (sp.first ? 8 : 0) | (sp.cls_layers ? 4 : 0) | (msg ? 2 : 0) | (sp.pd_lds ? 1 : 0);
-    switch (key) {
-#define GNNCCA_FAST_CASE(K, A, B, C, D) \
-    case K: return launch_fast<A, B, C, D>(sp, st);
-        GNNCCA_FAST_CASE(0, false, false, false, false)
-        GNNCCA_FAST_CASE(1, false, false, false, true)
-        GNNCCA_FAST_CASE(2, false, false, true, false)
-        GNNCCA_FAST_CASE(3, false, false, true, true)
-        GNNCCA_FAST_CASE(4, false, true, false, false)
-        GNNCCA_FAST_CASE(5, false, true, false, true)
-        GNNCCA_FAST_CASE(6, false, true, true, false)
-        GNNCCA_FAST_CASE(7, false, true, true, true)
-        GNNCCA_FAST_CASE(8, true, false, false, false)
-        GNNCCA_FAST_CASE(9, true, false, false, true)
-        GNNCCA_FAST_CASE(10, true, false, true, false)
-        GNNCCA_FAST_CASE(11, true, false, true, true)
-        GNNCCA_FAST_CASE(12, true, true, false, false)
-        GNNCCA_FAST_CASE(13, true, true, false, true)
-        GNNCCA_FAST_CASE(14, true, true, true, false)
-        GNNCCA_FAST_CASE(15, true, true, true, true)
-#undef GNNCCA_FAST_CASE
-    }
-    return hipErrorInvalidValue;
-}
-#endif
-
+// Which instantiations exist: step_variant_exists (internal.h); the launch is launch_step_variant (mpn_forward.hip).
 
 }  // namespace gnncca

@@ -1,6 +1,6 @@
 #pragma once
-// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers and the launch code
-// below instantiates their templates); see that file for the overall picture.
+// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers; launch_step_variant there
+// instantiates the templates); see that file for the overall picture.
 namespace gnncca {
 
 // ------------------------------------------------------------------------------------------------------------
@@ -342,23 +342,5 @@ __global__ __launch_bounds__(256) void mpn_step_kernel(const StepParams p) {
         }
     }
 }
-
-// ------------------------------------------------------------------------------------------------------------
-
-template <bool RE, bool MSG, bool MX>
-static hipError_t launch_step_t(const StepParams& sp, hipStream_t st) {
-    const int npg = 4 / sp.wps;
-    const unsigned blocks = (unsigned)((sp.N + npg - 1) / npg);
-    const size_t lds = ((MSG ? (size_t)sp.hin * kProjOut : 0) + 4 * kH + (sp.pd_lds ? (size_t)sp.N * kPdStride : 0)) * sizeof(float);
-    GNNCCA_LAUNCH((mpn_step_kernel<RE, MSG, MX>), dim3(blocks), dim3(256), lds, st, sp);
-    return hipGetLastError();
-}
-
-template <bool RE, bool MSG>
-static hipError_t launch_step(const StepParams& sp, hipStream_t st) {
-    return sp.agg == GNNCCA_AGG_MAX ? launch_step_t<RE, MSG, true>(sp, st) : launch_step_t<RE, MSG, false>(sp, st);
-}
-
-
 
 }  // namespace gnncca

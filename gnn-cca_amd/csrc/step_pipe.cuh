@@ -1,6 +1,6 @@
 #pragma once
-// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers and the launch code
-// below instantiates their templates); see that file for the overall picture.
+// Part of the translation unit mpn_forward.hip, and included by it alone (kernels share device helpers; launch_step_variant there
+// instantiates the templates); see that file for the overall picture.
 namespace gnncca {
 
 // ------------------------------------------------------------------------------------------------------------
@@ -32,26 +32,15 @@ __device__ __forceinline__ float buf_load_f32(rsrc_t r, unsigned voff, unsigned 
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, AUX));
 }
 
-// host-side eligibility: every buffer this kernel addresses with 32-bit offsets stays below 2^31 bytes
-static inline bool step_pipe_fits(long long N, long long E, long long e_stride, unsigned long long ws_bytes) {
-    const long long lim = 1ll << 31;
-    // (the whole workspace is addressed through one descriptor: it must end below the out-of-range offset 2^31 of a dead lane, and
-    // below 2^31 - 4 so that "the slot before slot 0" of DERIVE's predecessor load is out of range too)
-    return 6 * e_stride * 4 <= lim && E * 16 <= lim && N * 32 <= lim && ws_bytes <= (unsigned long long)lim - 4096;
-}
-
 #define GNNCCA_SB() __builtin_amdgcn_sched_barrier(0)
-#ifndef GNNCCA_NPW2_CLS
-#define GNNCCA_NPW2_CLS 0         // 1: instantiate the two-nodes-per-wave form for the classifying steps as well (diagnostic builds)
-#endif
 #ifndef GNNCCA_NPW2_CLS_WAVES
 #define GNNCCA_NPW2_CLS_WAVES 3   // waves per SIMD the CLASSIFYING two-nodes-per-wave variants are compiled for (143-155 VGPRs; the others fit four)
 #endif
 
 // RNG: the column-range code is compiled in (StepParams::rng) -- step 1 derives the ranges, later steps compute target ids from them.  A
 // template parameter and not only a run-time switch because this kernel's scalar register file is full: the few SGPRs the ranges need
-// turn into v_readlane / v_writelane spill traffic on the VALU, which is what the issue-bound big batches are short of; the host
-// instantiates RNG for the latency-bound regime only (mpn_forward.hip).
+// turn into v_readlane / v_writelane spill traffic on the VALU, which is what the issue-bound big batches are short of; the route
+// takes RNG on request only (GNNCCA_OPT_COLUMN_RANGES; step_route.cpp).
 // NPW = 2 (round 4): a wave owns TWO consecutive nodes (one wave per node only; message steps; no LDS table, no range code).  Batches of
 // small dense graphs give a wave ONE round (<= 128 edges) per node: its whole life is the chain seg_ptr -> ids + state -> gather ->
 // arithmetic -> epilogue with nothing to overlap but the other three waves of the SIMD, and 64 x dense256 (two rounds per wave, the second
@@ -85,7 +74,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSG ? (NPW 
     const int ktouch = NPW == 1 ? touch_kernargs(sizeof(StepParams)) : 0;   // (common.cuh; the two-node forms have no SGPRs to spare)
     const unsigned gflags = p.flags[0];
     const unsigned rbad = p.flags[1];
-    const int wps = NPW == 2 ? 1 : p.wps;   // 1, 2 or 4 (mpn_forward.hip): shifts, not a software division
+    const int wps = NPW == 2 ? 1 : p.wps;   // 1, 2 or 4 (step_route.cpp): shifts, not a software division
     const int wl = wps >> 1;                // log2(wps)
     int node = NPW == 2 ? (blockIdx.x * 4 + wave) * 2 : (int)(blockIdx.x << (2 - wl)) + (wave >> wl);
     const int sub = NPW == 2 ? 0 : wave & (wps - 1);
@@ -396,87 +385,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSG ? (NPW 
     GNNCCA_STAMP(p.stamp_slot, 7);
 }
 
-template <bool FIRST, bool CLS, bool MSG, bool PDL, bool EB, int NT, bool RNG = false, int NPW = 1, bool CIN = false>
-static hipError_t launch_pipe_t(const StepParams& sp, hipStream_t st) {
-    const int npg = NPW == 2 ? 8 : 4 / sp.wps;
-    const unsigned blocks = (unsigned)((sp.N + npg - 1) / npg);
-    const size_t lds = ((MSG ? (size_t)kH * kProjOut : 0) + 4 * kH + 16 + (PDL ? ((size_t)sp.N + 1) * kPdStride : 0)) * sizeof(float);
-    GNNCCA_LAUNCH((mpn_step_pipe_kernel<FIRST, CLS, MSG, PDL, EB, NT, RNG, NPW, CIN>), dim3(blocks), dim3(256), lds, st, sp);
-    return hipGetLastError();
-}
-
-// A step of a forward with DEFERRED classification (forward_impl: StepParams::logits_in != nullptr) that classifies its input state:
-// a message step (never classifies its own output in that scheme) or the last step (classifies both).  fp32 state, no LDS table, no ranges.
-static hipError_t launch_pipe_cin(const StepParams& sp, bool msg, hipStream_t st) {
-    const int nt = sp.nt_load ? 2 : (sp.nt_store ? 1 : 0);
-    if (msg) {
-        if (sp.npw == 2 && sp.wps == 1) {   // two nodes per wave; the second node's ids early, its state and gather after the hand-over (registers)
-            if (nt == 2) return launch_pipe_t<false, false, true, false, false, 2, false, 2, true>(sp, st);
-            if (nt == 1) return launch_pipe_t<false, false, true, false, false, 1, false, 2, true>(sp, st);
-            return launch_pipe_t<false, false, true, false, false, 0, false, 2, true>(sp, st);
-        }
-        if (nt == 2) return launch_pipe_t<false, false, true, false, false, 2, false, 1, true>(sp, st);
-        if (nt == 1) return launch_pipe_t<false, false, true, false, false, 1, false, 1, true>(sp, st);
-        return launch_pipe_t<false, false, true, false, false, 0, false, 1, true>(sp, st);
-    }
-    if (nt == 2) return launch_pipe_t<false, true, false, false, false, 2, false, 1, true>(sp, st);
-    if (nt == 1) return launch_pipe_t<false, true, false, false, false, 1, false, 1, true>(sp, st);
-    return launch_pipe_t<false, true, false, false, false, 0, false, 1, true>(sp, st);
-}
-
-// two nodes per wave (StepParams::npw == 2: the host's choice, mpn_forward.hip): message steps, one wave per node, no LDS table, no range code.
-// Only the steps that do not classify are instantiated: their two-node form fits four waves per SIMD (115-128 VGPRs) and gains 11-16 % on
+// Which instantiations exist: step_variant_exists (internal.h).  Two nodes per wave (StepParams::npw == 2: the host's choice, step_route.cpp):
+// only the steps that do not classify are instantiated: their two-node form fits four waves per SIMD (115-128 VGPRs) and gains 11-16 % on
 // batches of >= 32 768 nodes (512 x dense128 step 1: 117.7 -> 105.2 us; 1000 x dense64: 88.6 -> 74.3); the classifying variants need 143-155
 // registers, i.e. three waves per SIMD (or scratch: 2x slower), and come out at -7 ... +3 % (profiles/r04_logs/ab_npw{1,2,3,4}.log).
-template <bool FIRST, bool CLS, bool MSG, bool PDL, bool EB, int NT>
-static hipError_t launch_pipe_npw(const StepParams& sp, hipStream_t st) {
-    if constexpr (MSG && !PDL && (!CLS || GNNCCA_NPW2_CLS)) {
-        if (sp.npw == 2 && sp.wps == 1 && sp.rng == nullptr) return launch_pipe_t<FIRST, CLS, MSG, PDL, EB, NT, false, 2>(sp, st);
-    }
-    return launch_pipe_t<FIRST, CLS, MSG, PDL, EB, NT>(sp, st);
-}
-
-template <bool FIRST, bool CLS, bool MSG, bool PDL>
-static hipError_t launch_pipe(const StepParams& sp, hipStream_t st) {
-    if (!PDL) {   // the non-temporal variants only exist beyond the LDS-resident gather table (N > 1024): big batches
-        const int nt = sp.nt_load ? 2 : (sp.nt_store ? 1 : 0);
-        if (nt == 2) return sp.e_bf16 ? launch_pipe_npw<FIRST, CLS, MSG, false, true, 2>(sp, st) : launch_pipe_npw<FIRST, CLS, MSG, false, false, 2>(sp, st);
-        if (nt == 1) return sp.e_bf16 ? launch_pipe_npw<FIRST, CLS, MSG, false, true, 1>(sp, st) : launch_pipe_npw<FIRST, CLS, MSG, false, false, 1>(sp, st);
-    }
-    // the column-range variants (StepParams::rng != nullptr: the host's choice) exist for the default cache policy and where they do
-    // something: step 1 when it derives (FIRST && MSG), every later step
-    if (sp.rng != nullptr && (!FIRST || MSG))
-        return sp.e_bf16 ? launch_pipe_t<FIRST, CLS, MSG, PDL, true, 0, true>(sp, st) : launch_pipe_t<FIRST, CLS, MSG, PDL, false, 0, true>(sp, st);
-    return sp.e_bf16 ? launch_pipe_npw<FIRST, CLS, MSG, PDL, true, 0>(sp, st) : launch_pipe_npw<FIRST, CLS, MSG, PDL, false, 0>(sp, st);
-}
-
-#ifndef GNNCCA_KERNELS_ONLY   // (tools: compile-only probes of single instantiations skip the dispatch tables)
-static hipError_t launch_pipe_dispatch(const StepParams& sp, bool msg, hipStream_t st) {
-    if (sp.logits_in != nullptr) return launch_pipe_cin(sp, msg, st);
-    const int key = (sp.first ? 8 : 0) | (sp.cls_layers ? 4 : 0) | (msg ? 2 : 0) | (sp.pd_lds ? 1 : 0);
-    switch (key) {
-#define GNNCCA_PIPE_CASE(K, A, B, C, D) \
-    case K: return launch_pipe<A, B, C, D>(sp, st);
-        GNNCCA_PIPE_CASE(0, false, false, false, false)
-        GNNCCA_PIPE_CASE(1, false, false, false, true)
-        GNNCCA_PIPE_CASE(2, false, false, true, false)
-        GNNCCA_PIPE_CASE(3, false, false, true, true)
-        GNNCCA_PIPE_CASE(4, false, true, false, false)
-        GNNCCA_PIPE_CASE(5, false, true, false, true)
-        GNNCCA_PIPE_CASE(6, false, true, true, false)
-        GNNCCA_PIPE_CASE(7, false, true, true, true)
-        GNNCCA_PIPE_CASE(8, true, false, false, false)
-        GNNCCA_PIPE_CASE(9, true, false, false, true)
-        GNNCCA_PIPE_CASE(10, true, false, true, false)
-        GNNCCA_PIPE_CASE(11, true, false, true, true)
-        GNNCCA_PIPE_CASE(12, true, true, false, false)
-        GNNCCA_PIPE_CASE(13, true, true, false, true)
-        GNNCCA_PIPE_CASE(14, true, true, true, false)
-        GNNCCA_PIPE_CASE(15, true, true, true, true)
-#undef GNNCCA_PIPE_CASE
-    }
-    return hipErrorInvalidValue;
-}
-#endif
+// The launch is launch_step_variant (mpn_forward.hip).
 
 }  // namespace gnncca

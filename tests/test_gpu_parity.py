@@ -113,6 +113,29 @@ def test_dense_graphs_vs_oracle(n):
         assert err <= TOL
 
 
+@pytest.mark.parametrize("n,deg,cls", [(512, 3, 2), (513, 3, 2), (600, 65, 2), (600, 193, 2), (16384, 3, 1), (16384, 3, 2), (16384, 3, 3)])
+def test_step_route_rows_vs_oracle(n, deg, cls):
+    """Rows of the message steps' route table (tests/test_step_route.py) at their smallest shapes, on rings of `deg` edges per node: the
+    f32 message at 512 nodes and the bf16-split one at 513, two and four waves per node (600 nodes, degree 65 / 193), and 16 384 nodes --
+    two nodes per wave -- with 1 / 2 / 3 classifying steps: no deferral, the last step classifying its input and its output, and a message
+    step that classifies its input on top."""
+    params, arch, sd = _default_model(1.0 / deg, num_enc_steps=4, num_class_steps=cls)
+    rng = np.random.default_rng(n + deg)
+    x = rng.standard_normal((n, 2048)).astype(np.float32)
+    x /= np.linalg.norm(x, axis=0, keepdims=True)
+    src = np.repeat(np.arange(n), deg)
+    ei = np.stack([src, (src + np.tile(np.arange(1, deg + 1), n)) % n]).astype(np.int64)
+    ea = rng.random((ei.shape[1], 4)).astype(np.float32)
+    ref = NumpyOracle(params, arch, sd, np.float32).forward(x, ei, ea)
+    m = build(params, arch, sd)
+    with torch.no_grad():
+        out = m(Data(torch.from_numpy(x).cuda(), torch.from_numpy(ei).cuda(), torch.from_numpy(ea).cuda()))["classified_edges"]
+    assert len(out) == len(ref) == cls
+    for o, r in zip(out, ref):
+        err = np.abs(o.cpu().numpy() - r).max()
+        assert err <= TOL_TIGHT * 4, (n, deg, cls, err)
+
+
 def test_batch_of_graphs_equals_per_graph():
     """Disjoint union (Batch.from_data_list, inference.py:279) == each graph alone, bit for bit."""
     params, arch, sd = _default_model(1.0 / 40)
