@@ -23,6 +23,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
+from gnn_cca_amd.calibration import SweepAccumulator  # noqa: E402
 from gnn_cca_amd.evaluation import EvalAccumulator, evaluate_frames  # noqa: E402
 from gnn_cca_amd.graph_build import build_graph_batch  # noqa: E402
 from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
@@ -99,7 +100,16 @@ def main():
     if a.top_k:   # a capped graph: the same predictions scored as the dense graph would have been, dropped edges predicted 0
         acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"], against="dense"))
         print("against the dense truth:   ", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))
-    print("random weights / random embeddings: the cluster structure is meaningless, the plumbing is what is shown")
+    # which threshold?  every operating point of the batch in one pass (gnn_cca_amd.calibration), the best one applied
+    ths = np.arange(0.05, 1.0, 0.05)
+    sweep = SweepAccumulator(ths).add(r.sweep(ths))                      # float64 [T, G, 16] on the device; add() does not wait
+    best = sweep.best("F_micro")                                         # every threshold of maximal F over the whole batch
+    th = float(sweep.thresholds[best[0]])
+    tuned = FramePipeline(model, threshold=th, **cap)(xw, yw, ids, id_cam, [n_g] * frames, max_dist, node_embeds, reid_embeds)
+    at = EvalAccumulator().add(tuned.evaluate(final=False)).result()
+    print(f"threshold sweep: F_micro is maximal ({sweep.result()['F_micro'][best[0]]:.4g}) at {sweep.thresholds[best].round(2).tolist()}; "
+          f"FramePipeline(threshold={th:.2f}): TP {at['TP']} FP {at['FP']} FN {at['FN']}, F per frame {at['F']:.4g}")
+    print("random weights / random embeddings: the cluster structure and the chosen threshold are meaningless, the plumbing is what is shown")
 
 
 if __name__ == "__main__":

@@ -19,8 +19,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 
 #include "hip_try.h"
+#include "plan.cuh"   // plan_num_blocks: the sweep builds the graph plan through internal.h's launchers
 
 #pragma clang fp contract(off)
 
@@ -63,12 +65,25 @@ __device__ __forceinline__ int lds_load(const int* p) { return __hip_atomic_load
 // dense graph's label-1 edges join all its detections: any two on one camera meet through one on another), and v's dense out-degree per
 // class, whose sums minus the kept edges of the class are the dropped pairs: FN += D1 - C1, TN += D0 - C0.  n^2 / BLOCK LDS reads per
 // thread (64 k at 4096 nodes).  person / cam are null otherwise and nothing of this runs: the instantiation is the kernel as it was.
-template <int BLOCK, bool DENSE>
-__global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __restrict__ ei, long long E, const float* __restrict__ elab,
-                                                            const long long* __restrict__ pred, const int* __restrict__ labels, int N_all,
-                                                            const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int P_lds,
-                                                            int* __restrict__ gt_out, double* __restrict__ out, double* __restrict__ lf_ws,
-                                                            const int* __restrict__ person, const int* __restrict__ cam) {
+// The body is written once for every caller (eval_frame_body): it asks "is edge k predicted" (`pred(k)`: 1 / 0, as the int64 prediction)
+// and "the label of the frame's node v" (`label(v0, v)`: a batch-global node id) through two small functors, so that the kernels below read
+// them from two global arrays and the threshold sweep (eval_sweep.cuh) from scores and LDS -- the arithmetic is the same text.
+// FILL_LF: the workgroup writes its frame's lgamma table itself (false: an earlier launch did, with the same expression).
+struct GlobalPred {
+    const long long* __restrict__ pred;
+    __device__ __forceinline__ long long operator()(long long k) const { return pred[k]; }
+};
+struct GlobalLabel {
+    const int* __restrict__ labels;
+    __device__ __forceinline__ int operator()(int v0, int v) const { return labels[v0 + v]; }
+};
+
+template <int BLOCK, bool DENSE, bool FILL_LF, class PredF, class LabelF>
+__device__ __forceinline__ void eval_frame_body(const int g, double* __restrict__ row, const long long* __restrict__ ei, long long E,
+                                                const float* __restrict__ elab, const PredF pred, const LabelF label, int N_all,
+                                                const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int P_lds,
+                                                int* __restrict__ gt_out, double* __restrict__ lf_ws, const int* __restrict__ person,
+                                                const int* __restrict__ cam) {
     extern __shared__ int s_dyn[];
     __shared__ unsigned long long s_int[I_COUNT];
     __shared__ double s_red[BLOCK / 64];
@@ -78,11 +93,10 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
     unsigned* cnt = reinterpret_cast<unsigned*>(s_dyn + P_lds);       // per local root: a (bits 0-15) | b (bits 16-31)
     unsigned* keys = reinterpret_cast<unsigned*>(s_dyn + 2 * P_lds);  // contingency keys, sorted
 
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int v0 = node_ptr[g], v1 = node_ptr[g + 1];
     const long long k0 = edge_ptr[g], k1 = edge_ptr[g + 1];
     const int n = v1 - v0;
-    double* row = out + (size_t)g * 16;
     if (v0 < 0 || n < 0 || n > P_lds || v1 > N_all || k0 < 0 || k1 < k0 || k1 > E) {
         if (tid < 16) row[tid] = __builtin_nan("");
         return;
@@ -93,7 +107,8 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
         cnt[v] = DENSE ? (unsigned)cam[v0 + v] : 0u;
         if (DENSE) keys[v] = (unsigned)person[v0 + v];
     }
-    for (int k = tid; k <= n; k += BLOCK) lf[k] = lgamma((double)k + 1.0);   // read only after the barriers below
+    if (FILL_LF)
+        for (int k = tid; k <= n; k += BLOCK) lf[k] = lgamma((double)k + 1.0);   // read only after the barriers below
     if (tid < I_COUNT) s_int[tid] = 0;
     __syncthreads();
     if (DENSE) {
@@ -129,7 +144,7 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
             const long long a = ei[k] - v0, b = ei[E + k] - v0;
             if (a < 0 || a >= n || b < 0 || b >= n) continue;   // an edge that leaves its frame: ignored
             const float l = elab[k];
-            const long long p = pred[k];
+            const long long p = pred(k);
             if (l == 1.f) {
                 ++c1;
                 tp += p == 1;
@@ -174,7 +189,7 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
         unsigned ngt = 0, npred = 0;
         for (int v = tid; v < n; v += BLOCK) {
             const int r = parent[v];
-            const int lab = labels[v0 + v];
+            const int lab = label(v0, v);
             int lp = lab - v0;
             if (lp < 0 || lp >= n) lp = v;   // outside the frame: the node's own cluster
             atomicAdd(&cnt[r], 1u);
@@ -360,7 +375,20 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
     for (int q = 0; q < 16; ++q) row[q] = vals[q];
 }
 
+template <int BLOCK, bool DENSE>
+__global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __restrict__ ei, long long E, const float* __restrict__ elab,
+                                                            const long long* __restrict__ pred, const int* __restrict__ labels, int N_all,
+                                                            const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int P_lds,
+                                                            int* __restrict__ gt_out, double* __restrict__ out, double* __restrict__ lf_ws,
+                                                            const int* __restrict__ person, const int* __restrict__ cam) {
+    const int g = blockIdx.x;
+    eval_frame_body<BLOCK, DENSE, true>(g, out + (size_t)g * 16, ei, E, elab, GlobalPred{pred}, GlobalLabel{labels}, N_all, node_ptr, edge_ptr,
+                                        P_lds, gt_out, lf_ws, person, cam);
+}
+
 }  // namespace gnncca
+
+#include "eval_sweep.cuh"   // the threshold sweep: its kernels call eval_frame_body
 
 using namespace gnncca;
 
@@ -419,6 +447,76 @@ int gnncca_eval_frames_dense(const int64_t* edge_index, const float* edge_labels
                              void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
     return eval_frames(edge_index, edge_labels, predictions, labels, person_id, cam, true, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev,
                        n_frames, max_frame_nodes, gt_labels_out, out, workspace, workspace_bytes, stream);
+}
+
+// ---- the threshold sweep (eval_sweep.cuh) ---------------------------------------------------------------------------------------------
+// workspace: [the graph plan, as gnncca_post_workspace_bytes lays it out | rev int32 [E] | lgamma tables fp64 [N + G]] -- O(E + N); the
+// only thing of size T x N is the caller's labels_out
+struct SweepWorkspace { PostWorkspace plan; size_t rev, lf, total; };
+static SweepWorkspace carve_sweep(int64_t n, int64_t e, int64_t g) {
+    SweepWorkspace w;
+    w.plan = carve_post(n, e);
+    size_t off = w.plan.total;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    w.rev = take((size_t)e * 4), w.lf = take(((size_t)n + (size_t)g) * sizeof(double)), w.total = off;
+    return w;
+}
+
+size_t gnncca_eval_sweep_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames, int64_t n_thresholds) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0 || n_thresholds < 0) return 0;
+    return carve_sweep(n_nodes, n_edges, n_frames).total;
+}
+
+int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_labels, const float* scores, int64_t n_nodes, int64_t n_edges,
+                      const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes,
+                      const double* thresholds_dev, int32_t n_thresholds, int32_t keep_le, double* rows_out, int32_t* labels_out,
+                      void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_thresholds < 1 || n_thresholds > GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > kEvalMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if (!thresholds_dev) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames == 0) return GNNCCA_OK;
+    if (!node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !edge_labels || !scores)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    const SweepWorkspace ws = carve_sweep(n_nodes, n_edges, n_frames);
+    if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int N = (int)n_nodes, E = (int)n_edges;
+    char* base = static_cast<char*>(workspace);
+    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
+    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
+    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
+    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
+    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
+    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
+    int* rev = reinterpret_cast<int*>(base + ws.rev);
+    double* lf = reinterpret_cast<double*>(base + ws.lf);
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    if (E > 0) {   // the plan of gnncca_post_prune_cluster (no padded layout to validate)
+        EncPlanParams ep;
+        std::memset(&ep, 0, sizeof(ep));
+        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
+        launch_plan_only(ep, plan_num_blocks(E), st);
+        HIP_TRY(hipGetLastError());
+        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
+        HIP_TRY(hipGetLastError());
+    }
+    const int edge_blocks = (E + 255) / 256;
+    hipLaunchKernelGGL(eval_sweep_prepare_kernel, dim3((unsigned)edge_blocks + (unsigned)n_frames), dim3(256), 0, st, ei, (long long)E,
+                       (const int*)seg_ptr, (const int*)col32, (const int*)perm, (const unsigned*)flags, rev, edge_blocks, node_ptr_dev, N, lf);
+    HIP_TRY(hipGetLastError());
+    int P = 1;
+    while (P < max_frame_nodes) P <<= 1;
+    const size_t lds = (size_t)3 * P * sizeof(int) + (size_t)P * sizeof(unsigned short);
+    const dim3 grid((unsigned)n_frames, (unsigned)n_thresholds);
+#define GNNCCA_SWEEP(B)                                                                                                                  \
+    hipLaunchKernelGGL((eval_sweep_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, scores, (const int*)rev, thresholds_dev, \
+                       (int)keep_le, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
+    if (P <= 64) GNNCCA_SWEEP(64); else GNNCCA_SWEEP(256);   // (eval_frames' choice)
+#undef GNNCCA_SWEEP
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
 }
 
 }  // extern "C"

@@ -41,6 +41,18 @@ int gnncca_post_threshold(const float* logits, int64_t n_edges, float* probs_out
     return GNNCCA_OK;
 }
 
+int gnncca_post_threshold_at(const float* logits, int64_t n_edges, double at, float* probs_out, int64_t* predictions_out,
+                             gnncca_stream_t stream) {
+    if (n_edges < 0 || at != at) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges == 0) return GNNCCA_OK;
+    if (!logits || !probs_out || !predictions_out) return GNNCCA_ERR_INVALID_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(post_threshold_at_kernel, grid1((size_t)n_edges, 256), dim3(256), 0, st, logits, (long long)n_edges, at, probs_out,
+                       reinterpret_cast<long long*>(predictions_out));
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
 int gnncca_post_prune_cluster(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
                               void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
                               int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out, gnncca_stream_t stream) {

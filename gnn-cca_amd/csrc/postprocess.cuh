@@ -16,6 +16,17 @@ __global__ __launch_bounds__(256) void post_threshold_kernel(const float* __rest
     preds[k] = p >= 0.5f ? 1 : 0;                    // (preds_prob >= 0.5) * 1
 }
 
+// The threshold at another operating point (gnncca_post_threshold_at): the same probability; the comparison in fp64 against the widened
+// fp32 value, so that `at` is not rounded to fp32 first (0.5 is exact either way: the bits of the kernel above).
+__global__ __launch_bounds__(256) void post_threshold_at_kernel(const float* __restrict__ logits, long long E, double at,
+                                                                float* __restrict__ probs, long long* __restrict__ preds) {
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= E) return;
+    const float p = 1.f / (1.f + expf(-logits[k]));  // torch.nn.Sigmoid
+    probs[k] = p;
+    preds[k] = (double)p >= at ? 1 : 0;
+}
+
 // out[k] = pred[k] && the reverse edge (col k, row k) exists and is active too.  The reverse edge is searched in the
 // CSR segment of node col[k] (plan of the MPN forward: seg_ptr / col32 / perm), any column order.
 // FUSED_THRESHOLD (gnncca_frames_forward): `logits` instead of `pred` -- the thread computes its edge's probability and prediction with

@@ -104,6 +104,20 @@ def evaluate_frames(batch, predictions, labels, gt_labels=False, against="kept")
     return (out, gt) if gt_labels else out
 
 
+def _reduce_rows(allr):
+    """The ONE definition of main.py:335-348's reduction of float64 [F, 16] rows: sums of the count columns, means of the others, in
+    float64 and in a fixed order (torch's sum over one contiguous tensor) -> float64 [16] on the device, no synchronisation.
+    EvalAccumulator and calibration.SweepAccumulator both reduce with it."""
+    sums = allr.sum(dim=0)
+    return torch.where(torch.tensor([0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 1, 1], dtype=torch.bool, device=allr.device),
+                       sums, sums / allr.shape[0])
+
+
+def _aggregates(host):
+    """A reduced row on the host -> {'P': ..., 'TP': ...} as main.py prints them."""
+    return {name: (int(host[col]) if how == "sum" else float(host[col])) for name, col, how in AGGREGATES}
+
+
 class EvalAccumulator:
     """Collects the device rows of many batches (`add`, no synchronisation) and reduces them ONCE (`result`): the aggregates main.py:335-348
     prints -- means of P, R, F, RI, MI, hom, com, v, prec0, prec1 and sums of TP, FP, FN, TN over all frames -- in float64, in a fixed
@@ -125,11 +139,8 @@ class EvalAccumulator:
         if not self._rows:
             raise ValueError("EvalAccumulator.result: no rows were added")
         allr = torch.cat(self._rows) if len(self._rows) > 1 else self._rows[0]
-        sums = allr.sum(dim=0)
-        red = torch.where(torch.tensor([0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 1, 1], dtype=torch.bool, device=allr.device),
-                          sums, sums / allr.shape[0])
-        host = red.cpu().numpy()       # the one synchronisation
-        return {name: (int(host[col]) if how == "sum" else float(host[col])) for name, col, how in AGGREGATES}
+        host = _reduce_rows(allr).cpu().numpy()       # the one synchronisation
+        return _aggregates(host)
 
 
 __all__ = ["METRICS", "MAX_FRAME_NODES", "evaluate_frames", "EvalAccumulator"]

@@ -39,6 +39,9 @@ dense graph with every dropped edge predicted 0.  top_k=None (the default) is th
 no counterpart in the reference either): every kept edge then has its reverse.  E depends on the data, so such a pipeline takes the
 step-by-step path below and waits once per batch for its edge count; the one-call entry is not extended.
 
+`FramePipeline(model, threshold=th)` decides at sigmoid(logit) >= th instead of the reference's 0.5; `r.sweep(thresholds)` scores every
+candidate th of a batch in one pass (gnn_cca_amd.calibration).  Any th other than 0.5 takes the step-by-step path too.
+
 Batches of more than 4096 detections, train mode and forward hooks take the step-by-step path (same results; a capped pipeline passes its
 cap on to build_graph_batch, whose limit of 4096 candidates per detection then raises NotImplementedError).  No CPU fallback."""
 import ctypes as C
@@ -49,7 +52,7 @@ import torch
 from . import _native as nat
 from .frames import StagedFrames, _on, _raw_stream, attach, check_cap
 from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, build_graph_batch
-from .postprocess import finalize, prune_and_cluster, threshold
+from .postprocess import check_threshold, finalize, prune_and_cluster, threshold
 from .sharding import GraphBatch
 
 MAX_NODES = 4096
@@ -164,6 +167,12 @@ class FrameResult:
                 cache[key] = evaluate_frames(self.batch, self.pruned, self.labels, against=against)
         return cache[key]
 
+    def sweep(self, thresholds):
+        """Every operating point of this batch in one pass: calibration.sweep_thresholds(self.batch, self.probs, thresholds, 'ge') ->
+        float64 [T, G, 16] on the device; rows[t] is what evaluate(final=False) returns for a pipeline run at threshold thresholds[t]."""
+        from .calibration import sweep_thresholds
+        return sweep_thresholds(self.batch, self.probs, thresholds, "ge")
+
     def identities(self, final=True):
         """The per-cluster summaries of this batch (gnn_cca_amd.tracking.cluster_summaries: fused position, mean appearance, size and
         camera count of every identity cluster, as device tensors; no counterpart in the reference).  final=True summarises final()'s
@@ -196,8 +205,11 @@ class _Finished:
 
 class FramePipeline:
     def __init__(self, model, only_appearance=False, only_dist=False, normalize=True, rounding=True, pruning=True, splitting=True, top_k=None,
-                 rank_by="ground", symmetric=None):
+                 rank_by="ground", symmetric=None, threshold=0.5):
         self.model = model
+        # the decision threshold on the edge probabilities: 0.5 is the reference's (inference.py:286-291) and every path below as it
+        # always was; any other value in (0, 1) -- one chosen with r.sweep(...) -- takes the step-by-step path
+        self.threshold = check_threshold(threshold)
         if not pruning:
             raise ValueError("FramePipeline prunes on the device (PRUNING = True, as config_inference.yaml:7 ships it)")
         # the cap: build_graph_batch's arguments and its refusals, here before any batch (or the GPU) is touched
@@ -282,7 +294,7 @@ class FramePipeline:
             out = self.model(b)
         r = FrameResult()
         r.batch, r.outputs = b, out
-        r.probs, r.preds = threshold(out["classified_edges"][-1])
+        r.probs, r.preds = threshold(out["classified_edges"][-1], at=self.threshold)
         post = prune_and_cluster(b.edge_index, r.preds, b.x.shape[0], b.node_ptr_dev, b.edge_ptr_dev)
         r.pruned, r.flow_out, r.flow_in, r.labels, r.n_clusters = post["pruned"], post["flow_out"], post["flow_in"], post["labels"], post["n_clusters"]
         r.triggers, r._switches, r._final = post["triggers"], self.switches, None
@@ -295,7 +307,7 @@ class FramePipeline:
         if not (node_embeds.is_cuda and reid_embeds.is_cuda):
             raise RuntimeError("gnn_cca_amd.pipeline runs on MI355X only (no CPU fallback)")
         n = int(node_embeds.shape[0])
-        if m.training or n > MAX_NODES or n == 0 or self.symmetric is not None or m._containers_hooked():
+        if m.training or n > MAX_NODES or n == 0 or self.symmetric is not None or self.threshold != 0.5 or m._containers_hooked():
             return self._slow(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds)
         dev = reid_embeds.device
         lib = nat.lib()

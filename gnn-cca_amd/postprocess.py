@@ -11,6 +11,7 @@ raised a bit: native host code (csrc/post_host.cpp; SURVEY.md 8f keeps the bridg
 as the reference does.  A frame with no bit set already has its final partition.
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 import torch
@@ -21,8 +22,21 @@ from . import _native as nat
 from .frames import _on, _raw_stream as _stream   # the lean device guard / raw stream handle (host time matters here: ~6 launches)
 
 
-def threshold(logits):
-    """logits: Tensor[E] or [E,1] on the GPU -> (probs float32 [E], predictions int64 [E])."""
+def check_threshold(at):
+    """A decision threshold on a probability: a real number strictly between 0 and 1 -> float (ValueError otherwise)."""
+    if isinstance(at, bool) or not isinstance(at, numbers.Real):
+        raise ValueError(f"the threshold must be a real number in (0, 1), not {at!r}")
+    th = float(at)
+    if not 0.0 < th < 1.0:
+        raise ValueError(f"the threshold must lie strictly between 0 and 1, not {at!r}")
+    return th
+
+
+def threshold(logits, at=0.5):
+    """logits: Tensor[E] or [E,1] on the GPU -> (probs float32 [E], predictions int64 [E]): probs = sigmoid(logits), predictions =
+    (probs >= at).  at=0.5 is the reference's threshold (inference.py:286-291) and the launch this function has always made; any other
+    value in (0, 1) -- one chosen with calibration.sweep_thresholds -- is compared in float64 against the widened float32 probability."""
+    at = check_threshold(at)
     if not logits.is_cuda:
         raise RuntimeError("gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)")
     x = logits.reshape(-1)
@@ -31,7 +45,10 @@ def threshold(logits):
     probs = torch.empty_like(x)
     preds = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
     with _on(x.device):
-        st = nat.lib().gnncca_post_threshold(x.data_ptr(), x.shape[0], probs.data_ptr(), preds.data_ptr(), _stream(x.device))
+        if at == 0.5:
+            st = nat.lib().gnncca_post_threshold(x.data_ptr(), x.shape[0], probs.data_ptr(), preds.data_ptr(), _stream(x.device))
+        else:
+            st = nat.lib().gnncca_post_threshold_at(x.data_ptr(), x.shape[0], at, probs.data_ptr(), preds.data_ptr(), _stream(x.device))
     if st:
         nat.check(st, "gnncca_post_threshold")
     return probs, preds

@@ -374,6 +374,11 @@ GNNCCA_API int gnncca_normalize_columns_backward2(const float* x0, const float* 
  * probs = sigmoid(logits), predictions = (probs >= 0.5) as int64 0/1 (inference.py:286-291). */
 GNNCCA_API int gnncca_post_threshold(const float* logits, int64_t n_edges, float* probs_out,
                                      int64_t* predictions_out, gnncca_stream_t stream);
+/* The same at another operating point (one chosen with gnncca_eval_sweep): probs as above, predictions = ((double)probs >= at).  The
+ * comparison is made in fp64 against the widened fp32 probability; with at = 0.5 both outputs are gnncca_post_threshold's bit for bit.
+ * `at` must be a number (a NaN is GNNCCA_ERR_INVALID_ARG). */
+GNNCCA_API int gnncca_post_threshold_at(const float* logits, int64_t n_edges, double at, float* probs_out, int64_t* predictions_out,
+                                        gnncca_stream_t stream);
 GNNCCA_API size_t gnncca_post_workspace_bytes(int64_t n_nodes, int64_t n_edges);
 /* pruned_out[k] = predictions[k] && the reverse edge is active too (utils.remove_edges_single_direction,
  * libs/utils.py:387-404); flow_out / flow_in [N] int32 = active pruned edges leaving / entering each node
@@ -674,6 +679,33 @@ GNNCCA_API int gnncca_eval_frames_dense(const int64_t* edge_index, const float* 
                                         int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
                                         int32_t max_frame_nodes, int32_t* gt_labels_out, double* out, void* workspace,
                                         size_t workspace_bytes, gnncca_stream_t stream);
+
+/* ---- Threshold sweep: every operating point of a batch in one pass (csrc/eval_sweep.cuh) -------------------------------------------
+ * What the reference's calibration does one threshold at a time on the host (main.py:124-319, MODE REID: 100 thresholds over a per-edge
+ * score, compute_P_R_F at each, the threshold of maximal F; the OPT_TH / GEOM_TH tables of config_inference.yaml are such results).
+ * `scores` fp32 [E] is ANY per-edge score (a probability, a distance: normalising it is the caller's business -- main.py:141 divides by
+ * the dataset's maximum); thresholds_dev fp64 [n_thresholds] in DEVICE memory, any order, duplicates allowed.  The rule for threshold t
+ * and frame g, which is exactly what gnncca_post_threshold_at -> gnncca_post_prune_cluster_frames -> gnncca_eval_frames compute one
+ * threshold at a time:
+ *   activity   edge k is active iff (double)scores[k] >= thresholds[t] (keep_le != 0: <=).  The comparison is made in fp64 against the
+ *              widened fp32 score; a NaN score is never active.
+ *   pruning    edge k is kept iff it is active and an edge (dst k, src k) of the same frame exists and is active.
+ *   partition  labels_out[t] (int32 [n_thresholds][N], nullable) = the connected components of the kept edges inside the frame; a
+ *              node's label is the smallest batch-global id of its component.
+ *   scores     rows_out[t][g] (fp64 [n_thresholds][n_frames][16]) = the 16 columns of gnncca_eval_frames (GNNCCA_EVAL_COLUMNS) for
+ *              those kept predictions and that partition, bit for bit: the scoring arithmetic is the same code.
+ * Edge lists with duplicate ordered pairs are unspecified (gnncca_build_edges and its capped forms make none).  A capped batch is swept
+ * against its kept edges only (no counterpart of gnncca_eval_frames_dense).  A frame whose ranges do not fit gets a NaN row, as above.
+ * Four launches whatever n_thresholds is (graph plan, plan finish, reverse edges + lgamma tables, one launch of n_frames x n_thresholds
+ * workgroups); no prediction vector is materialised; the workspace (gnncca_eval_sweep_workspace_bytes) is O(E + N); no host
+ * synchronisation, no allocation: capturable.  GNNCCA_ERR_INVALID_ARG: n_thresholds < 1 or > GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS, a null
+ * pointer where the count is positive, max_frame_nodes above GNNCCA_EVAL_MAX_FRAME_NODES. */
+#define GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS 1024
+GNNCCA_API size_t gnncca_eval_sweep_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames, int64_t n_thresholds);
+GNNCCA_API int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_labels, const float* scores, int64_t n_nodes,
+                                 int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                 int32_t max_frame_nodes, const double* thresholds_dev, int32_t n_thresholds, int32_t keep_le,
+                                 double* rows_out, int32_t* labels_out, void* workspace, size_t workspace_bytes, gnncca_stream_t stream);
 
 /* ---- Cluster summaries and frame-to-frame track ids (csrc/identities.hip) -----------------------------------------------------------
  * No counterpart in the reference, which scores single frames (inference.py:349-371) and neither fuses a cluster nor links two frames.

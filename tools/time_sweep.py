@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Time calibration.sweep_thresholds against the loop it replaces; prints ONE JSON line.
+
+The loop is what a user had before: per threshold, the predictions at the threshold, `prune_and_cluster`, `evaluate_frames` -- the
+functions the sweep's results are defined by, which the sweep did not change, so the loop is the yardstick.  Two forms of it are timed:
+`loop_at` makes the predictions with `postprocess.threshold(logits, at=t)` (one launch; only a tree that has the switch), `loop_torch`
+with `(probs.double() >= t)` in torch (what a tree without the switch can do).  With `--parent PATH` (a checkout of the parent commit
+with its library built) a child process times `loop_torch` there too, before and after this tree's rounds.
+
+Batch: 64 frames of 4 cameras x 8 detections, every cross-camera pair an edge (graph_build.build_graph_batch); the scores are the
+sigmoid of seeded random logits; thresholds np.arange(0.01, 1.01, 0.01), as main.py:143 sweeps them.  Method: every side is warmed up,
+then timed as `reps` back-to-back repetitions that end in ONE device synchronise, host clock around them; the sides alternate inside a
+round, several rounds; the line carries every round's figure, the median and the spread (max - min over the rounds).
+
+    python tools/time_sweep.py [--rounds 7] [--reps 20] [--loop-reps 3] [--parent PATH]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def make_batch(torch, frames, cams, per_cam):
+    from gnn_cca_amd.graph_build import build_graph_batch
+    rng = np.random.default_rng(0)
+    n = frames * cams * per_cam
+    sizes = np.full(frames, cams * per_cam)
+    id_cam = np.tile(np.repeat(np.arange(cams), per_cam), frames)
+    ids = rng.integers(0, per_cam + 2, size=n)
+    node = torch.from_numpy(rng.standard_normal((n, 32)).astype(np.float32)).cuda()
+    reid = torch.from_numpy(rng.standard_normal((n, 32)).astype(np.float32)).cuda()
+    b = build_graph_batch(rng.uniform(-10, 10, n), rng.uniform(-10, 10, n), ids, id_cam, sizes, rng.uniform(10, 90, frames), node, reid)
+    logits = torch.randn(b.edge_index.shape[1], generator=torch.Generator().manual_seed(0)).cuda()
+    return b, logits
+
+
+def timed(torch, fn, reps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / reps
+
+
+def summary(vals):
+    return {"rounds_ms": [round(v, 4) for v in vals], "median_ms": round(float(np.median(vals)), 4),
+            "spread_ms": round(float(max(vals) - min(vals)), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=20, help="sweeps per timed window")
+    ap.add_argument("--loop-reps", type=int, default=3, help="whole loops (100 thresholds each) per timed window")
+    ap.add_argument("--root", default=os.path.dirname(HERE), help="the tree whose gnn_cca_amd is timed")
+    ap.add_argument("--loop-only", action="store_true", help="time loop_torch alone (what a child run in the parent's tree does)")
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: its loop_torch is timed in a child process")
+    args = ap.parse_args()
+    sys.path.insert(0, args.root)
+    import torch
+    from gnn_cca_amd.evaluation import evaluate_frames
+    from gnn_cca_amd.postprocess import prune_and_cluster, threshold
+
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/time_sweep.py measures on the GPU; no device found")
+    ths = np.arange(0.01, 1.01, 0.01)
+    b, logits = make_batch(torch, 64, 4, 8)
+    n = int(b.node_ptr[-1])
+    probs, _ = threshold(logits)
+
+    def one(preds):
+        post = prune_and_cluster(b.edge_index, preds, n, b.node_ptr_dev, b.edge_ptr_dev)
+        return evaluate_frames(b, post["pruned"], post["labels"])
+
+    def loop_torch():
+        return [one((probs.double() >= float(t)).to(torch.int64)) for t in ths]
+
+    sides = {"loop_torch": (loop_torch, args.loop_reps)}
+    if not args.loop_only:
+        from gnn_cca_amd.calibration import sweep_thresholds
+
+        def loop_at():
+            return [one(threshold(logits, at=float(t))[1]) for t in ths]
+
+        sides = {"sweep": (lambda: sweep_thresholds(b, probs, ths), args.reps), "loop_at": (loop_at, args.loop_reps), **sides}
+        rows = sweep_thresholds(b, probs, ths)
+        want = torch.stack(loop_at())
+        if not (torch.equal(rows, want) and torch.equal(want, torch.stack(loop_torch()))):   # (no NaN rows in this batch)
+            raise SystemExit("the sweep and the loop disagree: nothing to time")
+
+    def parent_run():
+        if not args.parent:
+            return None
+        cmd = [sys.executable, os.path.abspath(__file__), "--root", args.parent, "--loop-only", "--rounds", str(max(args.rounds // 2, 2)),
+               "--loop-reps", str(args.loop_reps)]
+        return json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().splitlines()[-1])["loop_torch"]
+
+    before = parent_run()
+    for fn, _ in sides.values():   # warm-up: every shape and kernel of the timed windows
+        fn()
+        fn()
+    got = {k: [] for k in sides}
+    for _ in range(args.rounds):
+        for k, (fn, reps) in sides.items():
+            got[k].append(timed(torch, fn, reps))
+    after = parent_run()
+    res = {"metric": "threshold sweep, ms per 100 thresholds", "frames": 64, "nodes": n, "edges": int(b.edge_index.shape[1]),
+           "thresholds": len(ths), "rounds": args.rounds, "root": "parent" if args.loop_only else "this tree"}
+    res.update({k: summary(v) for k, v in got.items()})
+    if before is not None:
+        res["parent_loop_torch_before"], res["parent_loop_torch_after"] = before, after
+    if "sweep" in got:
+        res["loop_at_over_sweep"] = round(float(np.median(got["loop_at"]) / np.median(got["sweep"])), 1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
