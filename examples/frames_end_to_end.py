@@ -2,7 +2,8 @@
 """End-to-end walk through the reference's per-batch inference flow (inference.py:173-345) on synthetic frames, with
 every GPU-side step taken by this repository: graph construction + edge attributes (row N1), the MPN forward (the hot
 path), threshold / pruning / identity clusters (row N2), and the per-frame scores of inference.py:349-371 aggregated as main.py:335-348
-does (gnn_cca_amd.evaluation).  Needs an MI355X.
+does (gnn_cca_amd.evaluation), next to the baseline the GNN has to beat: rank-1 ReID links with and without k-reciprocal re-ranking
+(MODE eval_RANK, gnn_cca_amd.rerank), same batch, same scorer.  Needs an MI355X.
 
     python examples/frames_end_to_end.py [frames] [cams] [detections_per_cam] [--top-k K] [--rank-by ground|reid] [--symmetric union|mutual]
 
@@ -28,6 +29,7 @@ from gnn_cca_amd.evaluation import EvalAccumulator, evaluate_frames  # noqa: E40
 from gnn_cca_amd.graph_build import build_graph_batch  # noqa: E402
 from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
 from gnn_cca_amd.postprocess import prune_and_cluster, threshold  # noqa: E402
+from gnn_cca_amd.rerank import MAX_FRAME_NODES as RERANK_MAX_FRAME_NODES, rank_baseline  # noqa: E402
 
 
 def main():
@@ -109,6 +111,13 @@ def main():
     at = EvalAccumulator().add(tuned.evaluate(final=False)).result()
     print(f"threshold sweep: F_micro is maximal ({sweep.result()['F_micro'][best[0]]:.4g}) at {sweep.thresholds[best].round(2).tolist()}; "
           f"FramePipeline(threshold={th:.2f}): TP {at['TP']} FP {at['FP']} FN {at['FN']}, F per frame {at['F']:.4g}")
+    # the baseline the GNN has to beat (MODE eval_RANK with RERANK): rank-1 ReID links after k-reciprocal re-ranking, same batch, same scorer
+    if n_g <= RERANK_MAX_FRAME_NODES:
+        for name, kw in (("rank-1 + re-ranking", dict(rank=1)), ("rank-1, plain distances", dict(rank=1, rerank=False))):
+            base = EvalAccumulator().add(rank_baseline(batch, **kw)).result()
+            print(f"{name}: " + ", ".join(f"{k} {base[k]:.4g}" for k in ("RI", "MI", "hom", "com", "v")))
+        gnn = acc.result() if not a.top_k else EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"])).result()
+        print("the GNN on the same frames: " + ", ".join(f"{k} {gnn[k]:.4g}" for k in ("RI", "MI", "hom", "com", "v")))
     print("random weights / random embeddings: the cluster structure and the chosen threshold are meaningless, the plumbing is what is shown")
 
 

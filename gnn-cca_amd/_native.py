@@ -22,6 +22,7 @@ SCORE_MIN_CAP, SCORE_HEADER_LEN = 1024, 8
 REENTRY_MAX_WINDOW = 4096            # gnncca_reentry_update: the walking workgroup keeps a frame's candidate tracks in LDS
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
 SWEEP_MAX_THRESHOLDS = 1024          # gnncca_eval_sweep
+RERANK_MAX_FRAME_NODES, RERANK_MAX_K1 = 128, 64   # gnncca_rerank_frames, gnncca_rank_predictions: a frame's tables and masks live in LDS
 
 
 class Layer(C.Structure):
@@ -217,6 +218,12 @@ _SIGNATURES = {
     "gnncca_eval_sweep_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "gnncca_eval_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnncca_frame_distances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gnncca_rerank_lds_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "gnncca_rerank_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gnncca_rank_predictions": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gnncca_cluster_summaries_bytes":(C.c_size_t, [C.c_int64, C.c_int64]),
     "gnncca_cluster_summaries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgnncca_mpn.so")
 SOURCES = ["pack.cpp", "enc_route.cpp", "step_route.cpp", "post_host.cpp", "mpn_forward.hip", "mpn_post.hip", "mpn_train.hip", "graph_build.hip", "evaluate.hip", "identities.hip", "loss.hip",
-           "optim.hip"]
+           "optim.hip", "rerank.hip"]
 HEADERS = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".cuh", ".inc"))] + [os.path.join(ROOT, "include", "gnncca_mpn.h")]
 
 

@@ -707,6 +707,51 @@ GNNCCA_API int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_la
                                  int32_t max_frame_nodes, const double* thresholds_dev, int32_t n_thresholds, int32_t keep_le,
                                  double* rows_out, int32_t* labels_out, void* workspace, size_t workspace_bytes, gnncca_stream_t stream);
 
+/* ---- Rank-R ReID baseline with k-reciprocal re-ranking (csrc/rerank.cuh) -----------------------------------------------------------
+ * The reference's MODE eval_RANK (inference.py:388-511) with RERANK (libs/utils.py:578-644, Zhong et al.): the baseline the GNN has to
+ * beat.  A batch's per-frame matrices lie back to back, frame g's n_g x n_g row-major fp32 matrix at element sum_{q<g} n_q^2; `total` is
+ * the number of elements the caller allocated (sum_g n_g^2 by its host copy of node_ptr).  The kernels derive every offset from
+ * node_ptr_dev (int32 [n_frames + 1] in DEVICE memory) and skip a frame whose matrix would not fit into `total`.  `max_frame_nodes` is
+ * the largest frame as the caller's host copy of node_ptr knows it.  One launch per entry, on the caller's stream; no host
+ * synchronisation, no allocation: capturable.  Deterministic: every floating-point sum has a fixed order, no float atomics.
+ *
+ * gnncca_frame_distances: out[g][i][j] = sqrt(sum_k (x_i[k] - x_j[k])^2) over the rows embeds fp32 [N][dim] of frame g, the sum of
+ *   squared DIFFERENCES in fp32 over k ascending (torch.cdist(p=2) of inference.py:416 without the |a|^2 + |b|^2 - 2ab form).  The
+ *   diagonal is exactly 0, the matrix exactly symmetric, the relative error at most (dim + 2) 2^-24.  Any dim >= 1, any frame size.
+ * gnncca_rerank_frames: out = re_ranking(D, D, D, k1, k2, lam) per frame, the whole n x n matrix (the reference returns the block
+ *   [:nq, nq:] of a query / gallery split, which does not depend on where the split is).  In fp32 like the reference, per frame with
+ *   D = dist's matrix:
+ *     1. O[i][j] = fl(D[j][i]^2) / max_k fl(D[k][i]^2), division correctly rounded; a zero maximum gives O[i][:] = 0 (the reference: NaN).
+ *     2. rank[i] = the columns of O[i] ascending, ties to the smaller index (the reference's argsort is unstable).
+ *     3. F_m(i) = the first min(m, n) entries of rank[i]; R_m(i) = {j in F_m(i) : i in F_m(j)}; K = k1 + 1; h = round-half-even(k1 / 2) + 1.
+ *     4. X(i) = R_K(i) | OR { R_h(c) : c in R_K(i), 3 |R_h(c) & R_K(i)| > 2 |R_h(c)| }.
+ *     5. V[i][j] = exp(-O[i][j]) / sum_{m in X(i)} exp(-O[i][m]) for j in X(i) (summed over m ascending), 0 elsewhere.
+ *     6. k2 != 1: V'[i] = (sum of V[m] over the first min(k2, n) entries m of rank[i], in rank order) / their number; else V' = V.
+ *     7. S(i, j) = sum_c min(V'[i][c], V'[j][c]) over c ascending; J = 1 - S / (2 - S).
+ *     8. out[i][j] = J (1 - lam) + O[i][j] lam, with (float)(1 - lam) and (float)lam.
+ *   eval_RANK passes one matrix three times, so that every distance has an exact twin and its result depends on the unstable sort's tie
+ *   order: that is NOT reproduced.  One workgroup per frame, V and V' in LDS (sized by max_frame_nodes: gnncca_rerank_lds_bytes).
+ *   GNNCCA_ERR_UNSUPPORTED: max_frame_nodes above GNNCCA_RERANK_MAX_FRAME_NODES.  GNNCCA_ERR_INVALID_ARG: k1 outside
+ *   [1, GNNCCA_RERANK_MAX_K1], k2 outside [1, k1], lam outside [0, 1].  Debug outputs (nullable): rank_out int32 [N][rank_cols], row v =
+ *   the first min(rank_cols, max(k1 + 1, k2), n) entries of v's ranking as frame-local ids, -1 after; mask_out uint64 [N][4], row v =
+ *   X(v) (two words, bit j = frame-local id j) and the columns where V'[v] is not zero (two words).
+ * gnncca_rank_predictions: predictions int64 [E] on the batch's edge list (edge_index int64 [2][E], edge_ptr_dev int32 [n_frames + 1]):
+ *   edge (i, j) is 1 iff j is among the min(rank, deg_i) detections of i's frame on another camera (cam int32 [N]) with the smallest
+ *   dist[i][.], ties to the smaller id, or i is among j's (inference.py:454-481).  Where the reference goes on to same-camera detections
+ *   once rank exceeds deg_i, this stops.  An edge missing from a capped list is simply not predicted; an edge that leaves its frame is 0.
+ *   Frames of at most GNNCCA_RERANK_MAX_FRAME_NODES (GNNCCA_ERR_UNSUPPORTED); rank < 1 is GNNCCA_ERR_INVALID_ARG. */
+#define GNNCCA_RERANK_MAX_FRAME_NODES 128
+#define GNNCCA_RERANK_MAX_K1 64
+GNNCCA_API int gnncca_frame_distances(const float* embeds, int32_t dim, int64_t n_nodes, const int32_t* node_ptr_dev, int32_t n_frames,
+                                      int32_t max_frame_nodes, int64_t total, float* out, gnncca_stream_t stream);
+GNNCCA_API size_t gnncca_rerank_lds_bytes(int32_t max_frame_nodes, int32_t k1, int32_t k2);
+GNNCCA_API int gnncca_rerank_frames(const float* dist, int64_t total, int64_t n_nodes, const int32_t* node_ptr_dev, int32_t n_frames,
+                                    int32_t max_frame_nodes, int32_t k1, int32_t k2, double lam, float* out, int32_t* rank_out,
+                                    int32_t rank_cols, uint64_t* mask_out, gnncca_stream_t stream);
+GNNCCA_API int gnncca_rank_predictions(const float* dist, int64_t total, const int32_t* cam, int64_t n_nodes, const int64_t* edge_index,
+                                       int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                       int32_t max_frame_nodes, int32_t rank, int64_t* predictions, gnncca_stream_t stream);
+
 /* ---- Cluster summaries and frame-to-frame track ids (csrc/identities.hip) -----------------------------------------------------------
  * No counterpart in the reference, which scores single frames (inference.py:349-371) and neither fuses a cluster nor links two frames.
  * Both stages take a batch laid out as above (node_ptr_dev: int32 [n_frames + 1] in DEVICE memory) and `max_frame_nodes`, the largest
