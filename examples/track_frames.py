@@ -3,7 +3,7 @@
 camera count) -> persistent track ids across frames and batches (gnn_cca_amd.tracking).  Everything stays on the GPU until the final
 print.  The reference has no counterpart of this stage: it scores single frames (inference.py:349-371).  Needs an MI355X.
 
-    python examples/track_frames.py [batches] [frames_per_batch] [cams] [persons]
+    python examples/track_frames.py [batches] [frames_per_batch] [cams] [persons] [--exclusive]
 
 Persons walk on the ground plane; every camera sees every person, with noise on the position.  The model has random weights, so its
 clusters mean nothing: the ids are shown for the model's partition AND for the ground-truth partition of the same detections, where a
@@ -17,7 +17,9 @@ them, go to two linkers with motion -- one is told nothing and takes the frames 
 (linker(s, times=...)), so the hole is a gap of two periods: its velocities stay displacements per PERIOD and its gate and prediction
 cover the time that really passed.  A TrackGallery (gnn_cca_amd.reentry) stands behind the linker WITHOUT max_gap: it cannot bridge the
 hidden frame, so person 0 comes back as a new track, and the gallery gives that track the old identity back by appearance; its
-identities are scored like track ids.  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
+identities are scored like track ids.  With --exclusive one more linker runs the WAITING-FREE loop on a partition that is legal by
+construction: r.exclusive() (no cluster holds two detections of one camera, whatever the number of cameras; no wait for the host
+heuristics of final()) -> cluster_summaries -> FrameLinker, one extra line per batch.  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
 """
 import argparse
 import os
@@ -50,12 +52,14 @@ def main():
     ap.add_argument("frames", nargs="?", type=int, default=8, metavar="frames_per_batch")
     ap.add_argument("cams", nargs="?", type=int, default=4)
     ap.add_argument("persons", nargs="?", type=int, default=6)
+    ap.add_argument("--exclusive", action="store_true", help="also link the camera-exclusive clusters of r.exclusive(): the loop that never waits")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     n_g = a.cams * a.persons
     model = bench.build_model(bench.graph_net_params(), n_g).cuda().eval()
     pipe = FramePipeline(model)
     by_model, by_truth = FrameLinker(max_step=1.0, lam=1.0), FrameLinker(max_step=1.0, lam=1.0)
+    by_exclusive = FrameLinker(max_step=1.0, lam=1.0)              # --exclusive: the model's probabilities, at most one detection per camera
     by_truth_gap = FrameLinker(max_step=1.0, lam=1.0, max_gap=1)   # a track survives one frame that misses it
     by_truth_opt = FrameLinker(max_step=1.0, lam=1.0, max_gap=1, matching="optimal")   # per frame pair the min-cost assignment, not mutual best
     score, score_gap = TrackScorer(max_ids=a.persons, max_cams=a.cams), TrackScorer(max_ids=a.persons, max_cams=a.cams)
@@ -99,6 +103,10 @@ def main():
         score_opt.add(r, by_truth_opt(st))
         tv = by_truth_vel(st)                    # tv.velocity: float64 [N, 2], the displacement per frame since the predecessor
         score_vel.add(r, tv)
+        if a.exclusive:   # exclusive() -> cluster_summaries -> FrameLinker: device work only, legal clusters without final()'s wait
+            ex = r.exclusive()
+            se = cluster_summaries(r.batch, ex["labels"])
+            te = by_exclusive(se)
         # ---- only the printing below waits for the GPU ----
         last = slice(r.batch.node_ptr[-2], r.batch.node_ptr[-1])
         k_model, k_truth = int(s.count[-1].item()), int(st.count[-1].item())
@@ -109,6 +117,10 @@ def main():
         print(f"  last frame, model partition: {k_model} clusters, sizes {s.size[last][:k_model].tolist()}")
         print(f"  last frame, true partition, motion='velocity': ids {tv.cluster_track[last][:k_truth].tolist()}, velocities "
               f"{[[round(v, 2) for v in p] for p in tv.velocity[last][:k_truth].tolist()]}")
+        if a.exclusive:
+            print(f"  exclusive partition: {int(ex['n_clusters'].item())} clusters, every one with size == cameras: "
+                  f"{bool((se.size == se.n_cams).all().item())} (model partition: {bool((s.size == s.n_cams).all().item())}); candidate pairs cut "
+                  f"{int(ex['cut'].sum().item())}, tracks so far {int(te.next_id.item())}")
         if a.frames > 2:   # frame 1 never arrives: without time stamps the step over the hole passes for one period's
             sd, kept = without_frame(st, 1)
             tb = blind(sd)

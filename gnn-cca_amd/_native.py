@@ -22,7 +22,9 @@ SCORE_MIN_CAP, SCORE_HEADER_LEN = 1024, 8
 REENTRY_MAX_WINDOW = 4096            # gnncca_reentry_update: the walking workgroup keeps a frame's candidate tracks in LDS
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
 SWEEP_MAX_THRESHOLDS = 1024          # gnncca_eval_sweep
-RERANK_MAX_FRAME_NODES, RERANK_MAX_K1 = 128, 64   # gnncca_rerank_frames, gnncca_rank_predictions: a frame's tables and masks live in LDS
+EXCLUSIVE_MAX_FRAME_NODES, EXCLUSIVE_MAX_CAMERAS = 4096, 64   # gnncca_post_exclusive_frames: 12-bit local ids, one 64-bit camera mask
+EXCLUSIVE_BAD_CAMERA, EXCLUSIVE_BAD_RANGE = 1, 2              # its flags_out[g]
+RERANK_MAX_FRAME_NODES, RERANK_MAX_K1 = 128, 64  # gnncca_rerank_frames, gnncca_rank_predictions: a frame's tables and masks live in LDS
 
 
 class Layer(C.Structure):
@@ -147,6 +149,10 @@ _SIGNATURES = {
     "gnncca_post_prune_cluster_frames_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_post_exclusive_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "gnncca_post_exclusive_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                               C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_size_t, C.c_void_p]),
     "gnncca_post_finalize_frame_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnncca_post_finalize_frames_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,

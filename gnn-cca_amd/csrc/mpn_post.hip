@@ -1,9 +1,11 @@
 // mpn_post.hip -- post-processing on the device (threshold, pruning, flow counters, connected components; kernels in
-// postprocess.cuh) and the one-call frame pipeline gnncca_frames_forward, which chains graph build, forward and post stage on one stream.
+// postprocess.cuh), the camera-exclusive clusters (exclusive.cuh) and the one-call frame pipeline gnncca_frames_forward, which chains graph
+// build, forward and post stage on one stream.
 // The graph-plan kernels it needs are compiled in mpn_forward.hip and reached through their launchers (internal.h).
 #include "common.cuh"
 #include "plan.cuh"
 #include "postprocess.cuh"
+#include "exclusive.cuh"
 
 using namespace gnncca;
 
@@ -182,6 +184,94 @@ static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* pre
     hipLaunchKernelGGL(post_cc_kernel, dim3(node_ptr_dev ? (unsigned)n_frames : 1u), dim3(1024), 0, st, ei,
                        (const long long*)pruned, (long long)E, N, node_ptr_dev, edge_ptr_dev, labels_out, n_clusters_out,
                        (const int*)flow_out, (const int*)flow_in, sizes_scratch, triggers_out);
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- camera-exclusive identity clusters (exclusive.cuh) -----------------------------------------------------------------------------------
+// workspace: [the graph plan, as gnncca_post_workspace_bytes lays it out | rev int32 [E] | candidate keys u64 [E]]
+struct ExclWorkspace { PostWorkspace plan; size_t rev, cand, total; };
+static ExclWorkspace carve_excl(int64_t n, int64_t e, int64_t g) {
+    ExclWorkspace w;
+    w.plan = carve_post(n, e);
+    size_t off = w.plan.total;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t E = (size_t)(e > 0 ? e : 0);
+    w.rev = take(E * 4), w.cand = take(E * 8), w.total = off;
+    return w;
+}
+
+size_t gnncca_post_exclusive_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return 0;
+    return carve_excl(n_nodes, n_edges, n_frames).total;
+}
+
+int gnncca_post_exclusive_frames(const int64_t* edge_index, const float* scores, int64_t n_nodes, int64_t n_edges, const int32_t* cam,
+                                 const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes,
+                                 double threshold, int64_t* predictions_out, int32_t* labels_out, int32_t* n_clusters_out, int32_t* cut_out,
+                                 uint32_t* flags_out, void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (!(threshold > 0.0 && threshold < 1.0)) return GNNCCA_ERR_INVALID_ARG;   // (a NaN included)
+    if (max_frame_nodes < 0 || max_frame_nodes > kExclMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if (!n_clusters_out) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames == 0 && n_nodes > 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_frames == 0) {   // nothing to cluster: the zero alone
+        hipLaunchKernelGGL(excl_prepare_kernel, dim3(1), dim3(256), 0, st, (const long long*)nullptr, 0ll, (const int*)nullptr, (const int*)nullptr,
+                           (const int*)nullptr, (const unsigned*)nullptr, (int*)nullptr, n_clusters_out);
+        HIP_TRY(hipGetLastError());
+        return GNNCCA_OK;
+    }
+    if (!node_ptr_dev || !edge_ptr_dev || !cut_out || !flags_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes > 0 && (!cam || !labels_out)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !scores || !predictions_out)) return GNNCCA_ERR_INVALID_ARG;
+    const ExclWorkspace ws = carve_excl(n_nodes, n_edges, n_frames);
+    if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    const int N = (int)n_nodes, E = (int)n_edges;
+    char* base = static_cast<char*>(workspace);
+    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
+    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
+    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
+    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
+    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
+    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
+    int* rev = reinterpret_cast<int*>(base + ws.rev);
+    excl_u64* cand = reinterpret_cast<excl_u64*>(base + ws.cand);
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    int P = 1;
+    while (P < max_frame_nodes) P <<= 1;
+    const size_t lds = (size_t)P * (2 * sizeof(excl_u64) + sizeof(int)) + 8 * sizeof(int);
+    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (rerank.hip)
+        static thread_local int attr_dev = -1;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if (attr_dev != dev) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(excl_cluster_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)((size_t)kExclMaxNodes * (2 * sizeof(excl_u64) + sizeof(int)) + 8 * sizeof(int))));
+            attr_dev = dev;
+        }
+    }
+    if (E > 0) {   // the plan of gnncca_post_prune_cluster (no padded layout to validate)
+        EncPlanParams ep;
+        std::memset(&ep, 0, sizeof(ep));
+        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
+        launch_plan_only(ep, plan_num_blocks(E), st);
+        HIP_TRY(hipGetLastError());
+        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
+        HIP_TRY(hipGetLastError());
+    }
+    // the reverse edges, and *n_clusters_out = 0 (kernels only on the stream: no memset)
+    hipLaunchKernelGGL(excl_prepare_kernel, grid1((size_t)std::max(E, 1), 256), dim3(256), 0, st, ei, (long long)E, (const int*)seg_ptr,
+                       (const int*)col32, (const int*)perm, (const unsigned*)flags, rev, n_clusters_out);
+    HIP_TRY(hipGetLastError());
+    long long* preds = reinterpret_cast<long long*>(predictions_out);
+#define GNNCCA_EXCL(B)                                                                                                                      \
+    hipLaunchKernelGGL((excl_cluster_kernel<B>), dim3((unsigned)n_frames), dim3(B), lds, st, ei, (long long)E, scores, threshold, cam,         \
+                       (const int*)rev, cand, N, node_ptr_dev, edge_ptr_dev, P, preds, labels_out, n_clusters_out, cut_out, \
+                       flags_out)
+    if (P <= 64) GNNCCA_EXCL(64); else GNNCCA_EXCL(256);   // (eval_frames' choice: a Terrace frame has ~20 detections, one wave per frame)
+#undef GNNCCA_EXCL
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

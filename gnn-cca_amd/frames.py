@@ -178,8 +178,11 @@ class StagedFrames:
         self._event.record(_current_stream(dst.device))
 
 
-def attach(batch, staged, layout):
+def attach(batch, staged, layout, cam_host=None):
     """The device views a GraphBatch carries of its staging image: node_ptr_dev / edge_ptr_dev (int32 [G + 1], for the per-frame
-    post-processing), y (the int64 person ids) and the image itself, which batch.person_dev / batch.cam_dev slice when asked for."""
+    post-processing), y (the int64 person ids) and the image itself, which batch.person_dev / batch.cam_dev slice when asked for.
+    `cam_host`: the host camera ids the image was planned from (StagedFrames.arrays[3]; kept by reference, so that a consumer with a
+    limit on them -- FrameResult.exclusive -- can refuse a batch without waiting for the device)."""
     batch.node_ptr_dev, batch.edge_ptr_dev = layout.view(staged, "graph_ptr"), layout.view(staged, "edge_ptr_g")
     batch.y, batch._frames = layout.view(staged, "ids"), (staged, layout)
+    batch.cam_host = cam_host

@@ -371,7 +371,7 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
     node_ptr, edge_ptr = frames.layout.host_ptrs(frames.pinned)
     # (a symmetric build: the offsets its count read back; the device image holds the same, the pinned one still the plan's)
     batch = GraphBatch(node_embeds, edge_index, edge_attr, job.edge_ptr_g if sym else edge_ptr, node_ptr)
-    attach(batch, staged, frames.layout)
+    attach(batch, staged, frames.layout, frames.arrays[3])
     batch.edge_labels = edge_labels
     batch.reid_embeds = reid_embeds
     return batch

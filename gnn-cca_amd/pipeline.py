@@ -52,7 +52,8 @@ import torch
 from . import _native as nat
 from .frames import StagedFrames, _on, _raw_stream, attach, check_cap
 from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, build_graph_batch
-from .postprocess import check_threshold, finalize, prune_and_cluster, threshold
+from .postprocess import MAX_FRAME_NODES as EXCLUSIVE_MAX_FRAME_NODES
+from .postprocess import check_cameras, check_threshold, exclusive_clusters, finalize, prune_and_cluster, threshold
 from .sharding import GraphBatch
 
 MAX_NODES = 4096
@@ -109,7 +110,7 @@ class PendingFinal:
 class FrameResult:
     """Outputs of one batch; tensors are views of ONE device buffer owned by this object."""
     __slots__ = ("batch", "outputs", "probs", "preds", "pruned", "flow_out", "flow_in", "labels", "n_clusters", "triggers", "_switches", "_final", "_keep",
-                 "_pipe", "_d2h", "_pending", "_eval", "_ident")
+                 "_pipe", "_d2h", "_pending", "_eval", "_ident", "_excl")
 
     def final_async(self):
         """Hand this batch to the pipeline's pool of host threads (no synchronisation) -> PendingFinal.  Results that did not come from the
@@ -186,6 +187,28 @@ class FrameResult:
         if key not in cache:
             cache[key] = cluster_summaries(self.batch, self.final()["labels"] if final else self.labels)
         return cache[key]
+
+    def exclusive(self):
+        """Camera-exclusive identity clusters of this batch (postprocess.exclusive_clusters on self.probs, the batch's device camera ids
+        and the pipeline's threshold): dict(predictions, labels, n_clusters, cut, flags) on the device, no cluster holding two detections of
+        one camera whatever the number of cameras, WITHOUT the wait final() needs.  Computed once; nothing else of this result changes.
+        On a capped batch the candidates are the mutual pairs, as pruning has it.  Compose: evaluate_frames(r.batch, ex['predictions'],
+        ex['labels']), cluster_summaries(r.batch, ex['labels']) -> FrameLinker.  ValueError before any launch if the batch's camera ids
+        leave [0, 64)."""
+        ex = getattr(self, "_excl", None)
+        if ex is None:
+            b = self.batch
+            if getattr(b, "cam_host", None) is None:
+                raise ValueError("exclusive() needs a batch of build_graph_batch / FramePipeline (its host camera ids are judged before any launch)")
+            check_cameras(b.cam_host)
+            n = int(b.x.shape[0])
+            sizes = np.diff(np.asarray(b.node_ptr, dtype=np.int64))
+            widest = int(sizes.max()) if sizes.size else 0
+            if widest > EXCLUSIVE_MAX_FRAME_NODES:
+                raise ValueError(f"a frame has {widest} detections; exclusive() takes frames of at most {EXCLUSIVE_MAX_FRAME_NODES}")
+            ex = self._excl = exclusive_clusters(b.edge_index, self.probs, b.cam_dev, n, b.node_ptr_dev, b.edge_ptr_dev, at=self._pipe.threshold,
+                                                 max_frame_nodes=widest)
+        return ex
 
 
 class _Finished:
@@ -394,7 +417,7 @@ class FramePipeline:
         reid_n = f32[o_reid:o_reid + n * r_dim].view(n, r_dim) if self.normalize else reid_embeds
         node_ptr, edge_ptr = layout.host_ptrs(frames.pinned)
         batch = GraphBatch(x, i64[o_ei:o_ei + 2 * e].view(2, e), f32[o_attr:o_attr + e * n_attr].view(e, n_attr), edge_ptr, node_ptr)
-        attach(batch, staged, layout)
+        attach(batch, staged, layout, frames.arrays[3])
         batch.edge_labels = f32[o_lab:o_lab + e]
         batch.reid_embeds = reid_n
         r = FrameResult()

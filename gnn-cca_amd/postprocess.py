@@ -9,6 +9,9 @@ utils.disjoint_big_clusters has, libs/utils.py:321-322).  `finalize` runs those 
 configuration (config_inference.yaml:6-8 ROUNDING / PRUNING / SPLITTING = True; inference.py:306-345), for the frames that
 raised a bit: native host code (csrc/post_host.cpp; SURVEY.md 8f keeps the bridge searches on the CPU), one frame at a time
 as the reference does.  A frame with no bit set already has its final partition.
+
+`exclusive_clusters` has no counterpart in the reference: a partition in which no cluster holds two detections of one camera, for any
+number of cameras, computed on the device without a wait (csrc/exclusive.cuh).
 """
 import ctypes as C
 import numbers
@@ -105,6 +108,114 @@ def prune_and_cluster(edge_index, predictions, n_nodes, node_ptr=None, edge_ptr=
         nat.check(st, "gnncca_post_prune_cluster")
     out["_workspace"] = (ws, np_dev, ep_dev)
     return out
+
+
+MAX_FRAME_NODES = nat.EXCLUSIVE_MAX_FRAME_NODES
+MAX_CAMERAS = nat.EXCLUSIVE_MAX_CAMERAS
+
+
+def check_cameras(cam):
+    """HOST camera ids (any integer sequence or array) must lie in [0, 64) for exclusive_clusters: a cluster's cameras are one 64-bit
+    mask.  ValueError otherwise; nothing is launched."""
+    cam = np.asarray(cam)
+    if cam.size and (cam.dtype.kind not in "iu" or int(cam.min()) < 0 or int(cam.max()) >= MAX_CAMERAS):
+        raise ValueError(f"camera ids must be integers in [0, {MAX_CAMERAS}) for the camera-exclusive clusters "
+                         f"(found {cam.min()!r} .. {cam.max()!r})")
+
+
+def _host_ptr(v, name):
+    """A frame-offset sequence as a host int64 array, or None for a device tensor (whose values are not read: no synchronisation)."""
+    if torch.is_tensor(v):
+        if v.is_cuda:
+            return None
+        v = v.numpy()
+    a = np.asarray(v)
+    if a.ndim != 1 or a.size < 2 or a.dtype.kind not in "iu":
+        raise ValueError(f"{name} must hold G + 1 integer offsets")
+    return a.astype(np.int64)
+
+
+def exclusive_clusters(edge_index, probs, cam, n_nodes, node_ptr, edge_ptr, at=0.5, max_frame_nodes=None):
+    """Camera-exclusive identity clusters: a partition of every frame in which no cluster holds two detections of one camera, for any
+    number of cameras, on the device and without a synchronisation (csrc/exclusive.cuh; no counterpart in the reference).  The rule
+    (include/gnncca_mpn.h has it in full, tests/exclusive_oracle.py in numpy): an edge is active iff float64(probs[k]) >= at; a pair
+    {i, j} is a candidate iff both of its edges exist in the frame and are active (the pruning rule); its weight is the smaller of the two
+    probabilities; candidates are walked by descending weight (ties: smaller min(i, j), then smaller max) and a candidate's two clusters
+    merge iff they differ and share no camera.  Where a frame's plain connected components are already legal the result is
+    prune_and_cluster's, exactly.
+
+    edge_index int64 [2, E], probs float32 [E] or [E, 1], cam int32 [N] camera ids in [0, 64): device tensors.  node_ptr / edge_ptr: the
+    frame ranges as prune_and_cluster takes them (sequences of G + 1 ints, or int32 device tensors).  With device tensors the largest
+    frame is not known on the host: pass max_frame_nodes (default: min(n_nodes, 4096), which sizes the kernel's LDS for the worst case).
+
+    -> dict(predictions int64 [E]: 1 iff the edge belongs to a candidate pair inside one cluster; labels int32 [N]: the smallest node
+    id of the node's cluster; n_clusters int32 [1]; cut int32 [G]: candidate pairs of the frame that ended up between two clusters;
+    flags uint32-valued int32 [G]: 0, 1 = a camera id outside [0, 64) reached the device, 2 = the frame's ranges do not fit -- every node
+    of such a frame is its own cluster with predictions 0), all on the device.  ValueError before any launch: a threshold outside (0, 1),
+    mismatched lengths, a frame of more than 4096 detections (where the host knows the sizes)."""
+    at = check_threshold(at)
+    if node_ptr is None or edge_ptr is None:
+        raise ValueError("exclusive_clusters works frame by frame: node_ptr and edge_ptr are required")
+    n_nodes = int(n_nodes)
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError(f"edge_index must be [2, E], not {tuple(edge_index.shape)}")
+    e = int(edge_index.shape[1])
+    if probs.numel() != e:
+        raise ValueError(f"probs [{probs.numel()}] does not match edge_index (E={e})")
+    if cam.numel() != n_nodes:
+        raise ValueError(f"cam [{cam.numel()}] does not match n_nodes ({n_nodes})")
+    if not cam.is_cuda:   # a host array can be judged here (the batch-level entry points do; a device tensor is judged by the kernel)
+        check_cameras(cam.numpy())
+    np_h, ep_h = _host_ptr(node_ptr, "node_ptr"), _host_ptr(edge_ptr, "edge_ptr")
+    g = (np_h.size if np_h is not None else node_ptr.numel()) - 1
+    if (ep_h.size if ep_h is not None else edge_ptr.numel()) != g + 1 or g < 1:
+        raise ValueError("node_ptr / edge_ptr must both have G + 1 entries")
+    if np_h is not None:
+        if int(np_h[0]) != 0 or int(np_h[-1]) != n_nodes or (np.diff(np_h) < 0).any():
+            raise ValueError("node_ptr must ascend from 0 to n_nodes")
+        widest = int(np.diff(np_h).max())
+        if widest > MAX_FRAME_NODES:
+            raise ValueError(f"a frame has {widest} detections; exclusive_clusters takes frames of at most {MAX_FRAME_NODES}")
+        max_frame_nodes = widest if max_frame_nodes is None else max_frame_nodes
+    if ep_h is not None and (int(ep_h[0]) != 0 or int(ep_h[-1]) != e or (np.diff(ep_h) < 0).any()):
+        raise ValueError("edge_ptr must ascend from 0 to E")
+    if max_frame_nodes is None:
+        max_frame_nodes = min(n_nodes, MAX_FRAME_NODES)
+    max_frame_nodes = int(max_frame_nodes)
+    if not 0 <= max_frame_nodes <= MAX_FRAME_NODES:
+        raise ValueError(f"max_frame_nodes must lie in [0, {MAX_FRAME_NODES}], not {max_frame_nodes}")
+    max_frame_nodes = min(max_frame_nodes, n_nodes)
+    if not (edge_index.is_cuda and probs.is_cuda and cam.is_cuda):
+        raise RuntimeError("gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)")
+    dev = edge_index.device
+    lib = nat.lib()
+    with _on(dev):
+        ei = edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.long().contiguous()
+        pr = probs.reshape(-1)
+        if pr.dtype != torch.float32 or not pr.is_contiguous():
+            pr = pr.float().contiguous()
+
+        def as_dev(v):
+            if torch.is_tensor(v):
+                if v.dtype == torch.int32 and v.device == dev and v.is_contiguous():
+                    return v
+                return v.to(device=dev, dtype=torch.int32).contiguous()
+            return torch.tensor([int(q) for q in v], dtype=torch.int32).to(dev)
+        cm, np_dev, ep_dev = as_dev(cam), as_dev(node_ptr), as_dev(edge_ptr)
+        ws_bytes = lib.gnncca_post_exclusive_workspace_bytes(n_nodes, e, g)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        preds = torch.empty(e, dtype=torch.int64, device=dev)
+        ints = torch.empty(n_nodes + 1 + 2 * g, dtype=torch.int32, device=dev)   # labels | n_clusters | cut | flags
+        ip = ints.data_ptr()
+        st = lib.gnncca_post_exclusive_frames(ei.data_ptr() if e else None, pr.data_ptr() if e else None, n_nodes, e,
+                                              cm.data_ptr() if n_nodes else None, np_dev.data_ptr(), ep_dev.data_ptr(), g, max_frame_nodes, at,
+                                              preds.data_ptr() if e else None, ip if n_nodes else None, ip + 4 * n_nodes, ip + 4 * (n_nodes + 1),
+                                              ip + 4 * (n_nodes + 1 + g), ws.data_ptr(), ws_bytes, _stream(dev))
+    if st:
+        nat.check(st, "gnncca_post_exclusive_frames")
+    # (the workspace is freed by the caching allocator in stream order: nothing to keep)
+    return {"predictions": preds, "labels": ints[:n_nodes], "n_clusters": ints[n_nodes:n_nodes + 1],
+            "cut": ints[n_nodes + 1:n_nodes + 1 + g], "flags": ints[n_nodes + 1 + g:]}
 
 
 def finalize(edge_index, probs, pruned, labels, n_clusters, triggers, node_ptr=None, edge_ptr=None, rounding=True, pruning=True,

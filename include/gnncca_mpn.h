@@ -416,6 +416,51 @@ GNNCCA_API int gnncca_post_prune_cluster_frames_ex(const int64_t* edge_index, co
                                                    int32_t* labels_out, int32_t* n_clusters_out, int32_t* sizes_scratch,
                                                    int32_t* triggers_out, gnncca_stream_t stream);
 
+/* ---- Camera-exclusive identity clusters (csrc/exclusive.cuh): a partition that is legal by construction ------------------------------
+ * A connected component of the pruned edges can hold two detections of one camera, which cannot be one person.  This entry computes,
+ * on the device and without a host wait, a partition of every frame in which NO cluster holds two detections of one camera, for any
+ * number of cameras with ids in [0, GNNCCA_EXCLUSIVE_MAX_CAMERAS).  No counterpart in the reference (its repair, the ROUNDING /
+ * SPLITTING heuristics of gnncca_post_finalize_frame_host below, is tied to four cameras and runs on the host); nothing else changes.
+ * Inputs: `scores` fp32 [E] per-edge probabilities, `threshold` in (0, 1), `cam` int32 [N] camera ids in DEVICE memory, the frame ranges
+ * node_ptr_dev / edge_ptr_dev (int32 [n_frames + 1], DEVICE memory) as gnncca_post_prune_cluster_frames takes them, `max_frame_nodes`
+ * the largest frame as the caller's host copy of node_ptr knows it (at most GNNCCA_EXCLUSIVE_MAX_FRAME_NODES).  The rule for frame g:
+ *   active      edge k is active iff (double)scores[k] >= threshold: the comparison gnncca_eval_sweep makes, in fp64 against the widened
+ *               fp32 score; a NaN score is never active.
+ *   candidates  the unordered pair {i, j} is a candidate iff the edges (i, j) and (j, i) both exist in the frame and both are active:
+ *               exactly the pruning rule.  On a directed capped list the candidates are the mutual pairs.
+ *   weight      w = min(scores[i -> j], scores[j -> i]), an exact fp32.
+ *   order       candidates by descending w; ties go to the smaller lo = min(i, j), then to the smaller hi.  A strict total order.
+ *   clustering  every node starts as its own cluster with camera mask 1 << cam.  Walk the candidates in that order and merge the two
+ *               clusters of a candidate iff they differ and their camera masks are disjoint; the merged mask is the OR.
+ *   outputs     labels_out[v] (int32 [N]) = the smallest batch-global node id of v's cluster (gnncca_post_prune_cluster's convention);
+ *               predictions_out[k] (int64 [E]) = 1 iff k belongs to a candidate pair and labels[src k] == labels[dst k];
+ *               *n_clusters_out (int32) = the batch total; cut_out[g] (int32 [n_frames]) = the candidate pairs of frame g whose ends
+ *               lie in different clusters; flags_out[g] (uint32 [n_frames]) = 0, or one of the two refusals below.
+ * Where a frame's plain connected components already hold every camera at most once, labels and predictions are
+ * gnncca_post_prune_cluster_frames' labels and pruned predictions for that frame exactly, and cut_out[g] = 0.  Same-camera edges are
+ * never admissible; edge lists with duplicate ordered pairs are unspecified, as in the sweep.  The kernel runs mutual-best rounds (each
+ * cluster takes its first admissible candidate, pairs that chose each other merge), which give the walk's partition; every comparison
+ * is an integer maximum on 64-bit keys, there are no float atomics: two runs give the same bits, and a frame's result does not depend
+ * on the rest of the batch.
+ * flags_out[g] = GNNCCA_EXCLUSIVE_BAD_CAMERA: a camera id of the frame lies outside [0, 64); GNNCCA_EXCLUSIVE_BAD_RANGE: the frame's
+ * ranges do not fit (gnncca_eval_sweep's test; a frame larger than max_frame_nodes rounded up to a power of two included).  Either way every node of the frame is its own
+ * cluster, its predictions are 0 and cut_out[g] = 0 (as far as the ranges allow writing at all); other frames are unaffected.
+ * Launches: the graph plan (plan + plan finish), the prepare kernel (reverse edges; it also zeroes *n_clusters_out), one workgroup per
+ * frame (candidate keys, rounds, outputs); with n_edges == 0 only the last two.  Kernels only: no memset on the stream.  LDS: 20 bytes
+ * per node of the largest frame, rounded up to a power of two (80 KiB at 4096).  Workspace: gnncca_post_exclusive_workspace_bytes,
+ * O(E + N).  No host synchronisation, no allocation: capturable.  GNNCCA_ERR_INVALID_ARG: a threshold outside (0, 1), max_frame_nodes above 4096 or
+ * above n_nodes, a null pointer where the count is positive. */
+#define GNNCCA_EXCLUSIVE_MAX_FRAME_NODES 4096
+#define GNNCCA_EXCLUSIVE_MAX_CAMERAS 64
+#define GNNCCA_EXCLUSIVE_BAD_CAMERA 1u
+#define GNNCCA_EXCLUSIVE_BAD_RANGE 2u
+GNNCCA_API size_t gnncca_post_exclusive_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames);
+GNNCCA_API int gnncca_post_exclusive_frames(const int64_t* edge_index, const float* scores, int64_t n_nodes, int64_t n_edges,
+                                            const int32_t* cam, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                            int32_t max_frame_nodes, double threshold, int64_t* predictions_out, int32_t* labels_out,
+                                            int32_t* n_clusters_out, int32_t* cut_out, uint32_t* flags_out, void* workspace,
+                                            size_t workspace_bytes, gnncca_stream_t stream);
+
 /* Row N2, second half, for ONE frame on the HOST ("bridges-based heuristics stay on CPU"): the reference's call sequence
  * inference.py:306-345 after the threshold -- by the three switches of config_inference.yaml:6-8 (all True as shipped):
  * utils.remove_edges_single_direction (libs/utils.py:387-404) -> utils.compute_rounding (25-173) -> remove_edges_single_direction ->
