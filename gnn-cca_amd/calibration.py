@@ -8,6 +8,7 @@ launches and one int64 [E] prediction vector per threshold; `sweep_thresholds` i
 
     rows = sweep_thresholds(batch, scores, thresholds)             # float64 [T, G, 16] on the device, columns evaluation.METRICS
     rows = r.sweep(thresholds)                                     # r: a pipeline.FrameResult, its probabilities, keep='ge'
+    rows = r.sweep(thresholds, partition='exclusive')              # the operating points of r.exclusive(), not of the components
     acc = SweepAccumulator(thresholds); acc.add(rows) ...          # no synchronisation
     res = acc.result()                                             # one synchronisation
     th = acc.thresholds[acc.best('F_micro')]                       # every threshold of maximal F (main.py:190)
@@ -15,7 +16,9 @@ launches and one int64 [E] prediction vector per threshold; `sweep_thresholds` i
 
 The rule for threshold t (include/gnncca_mpn.h has it in full): an edge is active iff its score >= thresholds[t] (keep='le': <=, for
 distances); it is kept iff its reverse edge is active too; the partition is the connected components of the kept edges; the row is
-evaluate_frames' for those predictions and that partition.
+evaluate_frames' for those predictions and that partition.  With partition='exclusive' the partition is the camera-exclusive one of
+postprocess.exclusive_clusters at thresholds[t] and the predictions are its predictions (one pass as well: a pair's place in the rule's
+order does not depend on the threshold).
 
 * A threshold is compared in float64 against the float32 score widened to float64.  `scores <= t` in numpy or torch may round t to
   float32 first: only at a threshold that lies within a float32 rounding of a score can the two differ.
@@ -30,9 +33,11 @@ import torch
 from . import _native as nat
 from .evaluation import MAX_FRAME_NODES, METRICS, _aggregates, _dev_i32, _reduce_rows
 from .frames import _on, _raw_stream
+from .postprocess import check_cameras, check_threshold
 
 MAX_THRESHOLDS = nat.SWEEP_MAX_THRESHOLDS
 KEEP = ("ge", "le")
+PARTITIONS = ("components", "exclusive")
 MICRO = ("P_micro", "R_micro", "F_micro")
 
 
@@ -50,16 +55,31 @@ def _thresholds(thresholds):
     return th
 
 
-def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False):
+def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False, partition="components", cam=None):
     """Scores every frame of `batch` (a GraphBatch as evaluate_frames takes it) at every threshold: `scores` float32 [E] or [E, 1] on the
     device, any per-edge score; `thresholds` a host sequence of finite reals (at most 1024; any order, duplicates allowed); keep='ge'
     keeps score >= t (probabilities), keep='le' keeps score <= t (distances).  Enqueued on the current stream without a wait (the
     thresholds go up through pinned memory); returns float64 [T, G, 16] on the device, rows[t] bit for bit
     evaluate_frames(batch, post['pruned'], post['labels']) with post = prune_and_cluster(..., predictions at thresholds[t], ...), and with
-    return_labels=True also int32 [T, N], the partitions (a node's label the smallest node id of its cluster)."""
+    return_labels=True also int32 [T, N], the partitions (a node's label the smallest node id of its cluster).
+
+    partition='exclusive' sweeps the CAMERA-EXCLUSIVE partition instead (csrc/eval_sweep_exclusive.cuh): rows[t] bit for bit
+    evaluate_frames(batch, ex['predictions'], ex['labels']) with ex = postprocess.exclusive_clusters(..., at=thresholds[t]), the labels
+    ex['labels'] -- the threshold of FrameResult.exclusive() is calibrated on this partition, not on the components.  `cam`: int32 [N]
+    camera ids on the device (default: batch.cam_dev).  Its domain is exclusive_clusters': every threshold strictly inside (0, 1),
+    keep='ge' only (the rule needs positive weights), camera ids in [0, 64) (judged on the host where batch.cam_host or a host `cam`
+    exists; an id that reaches the device makes its frame "every node its own cluster"), frames of at most 4096 detections."""
     if keep not in KEEP:
         raise ValueError(f"keep must be 'ge' or 'le', not {keep!r}")
+    if not isinstance(partition, str) or partition not in PARTITIONS:
+        raise ValueError(f"partition must be 'components' or 'exclusive', not {partition!r}")
+    exclusive = partition == "exclusive"
+    if exclusive and keep != "ge":
+        raise ValueError("partition='exclusive' takes keep='ge' only: the camera-exclusive rule orders pairs by a positive weight")
     th = _thresholds(thresholds)
+    if exclusive:
+        for v in th.tolist():
+            check_threshold(v)
     node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
     g = len(node_ptr) - 1
     n = int(node_ptr[-1]) if g > 0 else 0
@@ -69,7 +89,18 @@ def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False):
         raise ValueError(f"a frame has {max_n} detections; sweep_thresholds scores frames of at most {MAX_FRAME_NODES}")
     if scores.numel() != e or batch.edge_labels.numel() != e:
         raise ValueError(f"scores [{scores.numel()}] / edge_labels [{batch.edge_labels.numel()}] do not match the batch (E={e})")
-    if not scores.is_cuda:
+    if exclusive:
+        if cam is None:
+            cam = getattr(batch, "cam_dev", None)
+            if cam is None:
+                raise ValueError("partition='exclusive' needs camera ids: pass cam (int32 [N] on the device) or a batch with cam_dev")
+            if getattr(batch, "cam_host", None) is not None:
+                check_cameras(batch.cam_host)
+        if not torch.is_tensor(cam) or cam.numel() != n:
+            raise ValueError(f"cam [{cam.numel() if torch.is_tensor(cam) else type(cam).__name__}] does not match the batch (N={n})")
+        if not cam.is_cuda:   # a host tensor can be judged here; it is refused below like any other host input
+            check_cameras(cam.numpy())
+    if not scores.is_cuda or (exclusive and not cam.is_cuda):
         raise RuntimeError("gnn_cca_amd.calibration runs on MI355X only (no CPU fallback)")
     dev = scores.device
     t = int(th.size)
@@ -87,13 +118,24 @@ def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False):
             staged = torch.empty(t, dtype=torch.float64, pin_memory=True)
             staged.copy_(torch.from_numpy(th))
             th_dev = staged.to(dev, non_blocking=True)
-            ws_bytes = lib.gnncca_eval_sweep_workspace_bytes(n, e, g, t)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            st = lib.gnncca_eval_sweep(ei.data_ptr() if e else None, el.data_ptr() if e else None, sc.data_ptr() if e else None, n, e,
-                                       nptr.data_ptr(), eptr.data_ptr(), g, max_n, th_dev.data_ptr(), t, int(keep == "le"), rows.data_ptr(),
-                                       labels.data_ptr() if return_labels and n else None, ws.data_ptr(), ws_bytes, _raw_stream(dev))
-            if st:
-                nat.check(st, "gnncca_eval_sweep")
+            lab_ptr = labels.data_ptr() if return_labels and n else None
+            if exclusive:
+                cm = _dev_i32(cam.reshape(-1), sc)
+                ws_bytes = lib.gnncca_eval_sweep_exclusive_workspace_bytes(n, e, g, t)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+                st = lib.gnncca_eval_sweep_exclusive(ei.data_ptr() if e else None, el.data_ptr() if e else None, sc.data_ptr() if e else None,
+                                                     cm.data_ptr() if n else None, n, e, nptr.data_ptr(), eptr.data_ptr(), g, max_n,
+                                                     th_dev.data_ptr(), t, rows.data_ptr(), lab_ptr, ws.data_ptr(), ws_bytes, _raw_stream(dev))
+                if st:
+                    nat.check(st, "gnncca_eval_sweep_exclusive")
+            else:
+                ws_bytes = lib.gnncca_eval_sweep_workspace_bytes(n, e, g, t)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+                st = lib.gnncca_eval_sweep(ei.data_ptr() if e else None, el.data_ptr() if e else None, sc.data_ptr() if e else None, n, e,
+                                           nptr.data_ptr(), eptr.data_ptr(), g, max_n, th_dev.data_ptr(), t, int(keep == "le"), rows.data_ptr(),
+                                           lab_ptr, ws.data_ptr(), ws_bytes, _raw_stream(dev))
+                if st:
+                    nat.check(st, "gnncca_eval_sweep")
             # workspace and thresholds are freed by the caching allocator in stream order (allocated on this stream): nothing to keep
     return (rows, labels) if return_labels else rows
 

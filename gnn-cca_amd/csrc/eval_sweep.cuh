@@ -31,19 +31,7 @@ __global__ __launch_bounds__(256) void eval_sweep_prepare_kernel(const long long
     if ((int)blockIdx.x < edge_blocks) {
         const long long k = (long long)blockIdx.x * 256 + tid;
         if (k >= E) return;
-        const unsigned fl = flags[0];
-        int r = -1;
-        if (!(fl & GNNCCA_GRAPH_BAD_INDEX)) {   // (every index is in [0, N_all) then)
-            const bool unsorted = (fl & GNNCCA_GRAPH_UNSORTED) != 0;
-            const int i = (int)ei[k], j = (int)ei[E + k];
-            for (int q = seg_ptr[j]; q < seg_ptr[j + 1]; ++q) {
-                if (col32[q] == i) {
-                    r = unsorted ? perm[q] : q;
-                    break;
-                }
-            }
-        }
-        rev[k] = r;
+        rev[k] = excl_reverse_edge(ei, E, k, seg_ptr, col32, perm, flags[0]);   // (excl_common.cuh: one search for every prepare kernel)
         return;
     }
     const int g = (int)blockIdx.x - edge_blocks;

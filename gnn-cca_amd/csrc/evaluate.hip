@@ -388,7 +388,9 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
 
 }  // namespace gnncca
 
-#include "eval_sweep.cuh"   // the threshold sweep: its kernels call eval_frame_body
+#include "excl_common.cuh"           // the camera-exclusive rule's shared pieces (also part of mpn_post.hip through exclusive.cuh)
+#include "eval_sweep.cuh"            // the threshold sweep: its kernels call eval_frame_body
+#include "eval_sweep_exclusive.cuh"  // the same sweep over the camera-exclusive partition
 
 using namespace gnncca;
 
@@ -515,6 +517,88 @@ int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_labels, const
                        (int)keep_le, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
     if (P <= 64) GNNCCA_SWEEP(64); else GNNCCA_SWEEP(256);   // (eval_frames' choice)
 #undef GNNCCA_SWEEP
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- the threshold sweep over the camera-exclusive partition (eval_sweep_exclusive.cuh) ------------------------------------------------
+// workspace: [the graph plan | rev int32 [E] | pair keys u64 [E] | lgamma tables fp64 [N + G]] -- O(E + N) whatever T is
+struct SweepExclWorkspace { PostWorkspace plan; size_t rev, keys, lf, total; };
+static SweepExclWorkspace carve_sweep_excl(int64_t n, int64_t e, int64_t g) {
+    SweepExclWorkspace w;
+    w.plan = carve_post(n, e);
+    size_t off = w.plan.total;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    w.rev = take((size_t)e * 4), w.keys = take((size_t)e * 8), w.lf = take(((size_t)n + (size_t)g) * sizeof(double)), w.total = off;
+    return w;
+}
+
+size_t gnncca_eval_sweep_exclusive_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames, int64_t n_thresholds) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0 || n_thresholds < 0) return 0;
+    return carve_sweep_excl(n_nodes, n_edges, n_frames).total;
+}
+
+int gnncca_eval_sweep_exclusive(const int64_t* edge_index, const float* edge_labels, const float* scores, const int32_t* cam, int64_t n_nodes,
+                                int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                int32_t max_frame_nodes, const double* thresholds_dev, int32_t n_thresholds, double* rows_out,
+                                int32_t* labels_out, void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_thresholds < 1 || n_thresholds > GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > kExclMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if (!thresholds_dev) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames == 0) return GNNCCA_OK;
+    if (!node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes > 0 && !cam) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !edge_labels || !scores)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    const SweepExclWorkspace ws = carve_sweep_excl(n_nodes, n_edges, n_frames);
+    if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int N = (int)n_nodes, E = (int)n_edges;
+    int P = 1;
+    while (P < max_frame_nodes) P <<= 1;
+    const size_t lds = (size_t)20 * P;   // best u64 | mask u64 | parent int; the scoring's 14 P lie inside (eval_sweep_exclusive.cuh)
+    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (exclusive.cuh's entry, rerank.hip)
+        static thread_local int attr_dev = -1;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if (attr_dev != dev) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_sweep_excl_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)((size_t)20 * kExclMaxNodes)));
+            attr_dev = dev;
+        }
+    }
+    char* base = static_cast<char*>(workspace);
+    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
+    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
+    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
+    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
+    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
+    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
+    int* rev = reinterpret_cast<int*>(base + ws.rev);
+    excl_u64* keys = reinterpret_cast<excl_u64*>(base + ws.keys);
+    double* lf = reinterpret_cast<double*>(base + ws.lf);
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    if (E > 0) {   // the plan of gnncca_post_prune_cluster (no padded layout to validate)
+        EncPlanParams ep;
+        std::memset(&ep, 0, sizeof(ep));
+        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
+        launch_plan_only(ep, plan_num_blocks(E), st);
+        HIP_TRY(hipGetLastError());
+        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
+        HIP_TRY(hipGetLastError());
+    }
+    const int edge_blocks = (E + 255) / 256;
+    hipLaunchKernelGGL(eval_sweep_excl_prepare_kernel, dim3((unsigned)edge_blocks + (unsigned)n_frames), dim3(256), 0, st, ei, (long long)E,
+                       (const int*)seg_ptr, (const int*)col32, (const int*)perm, (const unsigned*)flags, scores, rev, keys, edge_blocks,
+                       node_ptr_dev, edge_ptr_dev, (int)n_frames, N, P, lf);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid((unsigned)n_frames, (unsigned)n_thresholds);
+#define GNNCCA_SWEEP_EXCL(B)                                                                                                                \
+    hipLaunchKernelGGL((eval_sweep_excl_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, scores, cam, (const int*)rev,    \
+                       (const excl_u64*)keys, thresholds_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
+    if (P <= 64) GNNCCA_SWEEP_EXCL(64); else GNNCCA_SWEEP_EXCL(256);   // (gnncca_eval_sweep's choice, which is eval_frames')
+#undef GNNCCA_SWEEP_EXCL
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

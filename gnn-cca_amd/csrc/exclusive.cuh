@@ -23,22 +23,9 @@
 // floats order as their bits do: the LARGEST key is the FIRST candidate, the key alone names the pair, and 0 is no key.  Every use of the
 // keys is an integer maximum (LDS atomicMax on 64-bit words): neither the order in which a frame's keys are appended to its list nor the
 // order in which lanes arrive changes a bit of the result.  No float atomics anywhere.
+#include "excl_common.cuh"   // the activity test, the key codec, the reverse-edge search, the merge and compress phases: shared with the sweep
+
 namespace gnncca {
-
-constexpr int kExclMaxNodes = GNNCCA_EXCLUSIVE_MAX_FRAME_NODES;   // 12-bit frame-local ids in the keys
-constexpr int kExclMaxCams = GNNCCA_EXCLUSIVE_MAX_CAMERAS;        // one 64-bit mask word
-
-typedef unsigned long long excl_u64;
-
-__device__ __forceinline__ int excl_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void excl_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ bool excl_active(float s, double th) { return (double)s >= th; }   // (false for a NaN)
-
-// eval_sweep_kernel's test of a frame's ranges, with the LDS regions' size in the place of P_lds
-__device__ __forceinline__ bool excl_frame_ok(int v0, int v1, long long k0, long long k1, int N_all, long long E, int P) {
-    const int n = v1 - v0;
-    return !(v0 < 0 || n < 0 || n > P || v1 > N_all || k0 < 0 || k1 < k0 || k1 > E);
-}
 
 // One thread per edge: rev[k] = the edge (dst k, src k) or -1, searched in the CSR segment of dst k as post_prune_kernel and
 // eval_sweep_prepare_kernel search it (a plan with GNNCCA_GRAPH_BAD_INDEX gives no edge a reverse).  Thread 0 of the launch also zeroes
@@ -51,19 +38,7 @@ __global__ __launch_bounds__(256) void excl_prepare_kernel(const long long* __re
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
     if (k == 0) *n_clusters = 0;
     if (k >= E) return;
-    const unsigned fl = flags[0];
-    int r = -1;
-    if (!(fl & GNNCCA_GRAPH_BAD_INDEX)) {   // (every index is in [0, N_all) then)
-        const bool unsorted = (fl & GNNCCA_GRAPH_UNSORTED) != 0;
-        const int i = (int)ei[k], j = (int)ei[E + k];
-        for (int q = seg_ptr[j]; q < seg_ptr[j + 1]; ++q) {
-            if (col32[q] == i) {
-                r = unsorted ? perm[q] : q;
-                break;
-            }
-        }
-    }
-    rev[k] = r;
+    rev[k] = excl_reverse_edge(ei, E, k, seg_ptr, col32, perm, flags[0]);
 }
 
 // Workgroup g: frame g.  Dynamic LDS: best u64 [P] | mask u64 [P] | parent int [P] | 8 ints (20 P + 32 bytes: 80 KiB at 4096 nodes).
@@ -128,8 +103,7 @@ __global__ __launch_bounds__(BLOCK) void excl_cluster_kernel(const long long* __
         if (a < 0 || a >= b || b >= n) continue;            // one thread per pair; an edge that leaves its frame: ignored (post_cc_kernel)
         const float sk = scores[k], sr = scores[r];
         if (!excl_active(sk, th) || !excl_active(sr, th)) continue;
-        const excl_u64 key = ((excl_u64)__float_as_uint(fminf(sk, sr)) << 24) | ((excl_u64)(4095 - (int)a) << 12) | (excl_u64)(4095 - (int)b);
-        mine[atomicAdd(&s_misc[4], 1)] = key;               // (one append per edge of the frame at most: the slot is below k1 - k0)
+        mine[atomicAdd(&s_misc[4], 1)] = excl_key(fminf(sk, sr), (int)a, (int)b);   // (one append per edge of the frame at most: the slot is below k1 - k0)
     }
     __syncthreads();
     const int n_cand = s_misc[4];
@@ -139,7 +113,7 @@ __global__ __launch_bounds__(BLOCK) void excl_cluster_kernel(const long long* __
         for (int c = tid; c < n_cand; c += BLOCK) {
             const excl_u64 key = mine[c];
             if (key == 0) continue;             // dropped in an earlier round
-            const int lo = 4095 - (int)((key >> 12) & 4095), hi = 4095 - (int)(key & 4095);   // (both below n: written above)
+            const int lo = excl_key_lo(key), hi = excl_key_hi(key);   // (both below n: written above)
             const int ra = parent[lo], rb = parent[hi];   // roots: nothing writes `parent` in this phase
             if (ra != rb && (mask[ra] & mask[rb]) == 0) {
                 atomicMax(&best[ra], key);
@@ -149,32 +123,9 @@ __global__ __launch_bounds__(BLOCK) void excl_cluster_kernel(const long long* __
             }
         }
         __syncthreads();
-        // merge the mutual choices.  Only the LARGER root of a pair acts: it hooks itself under the smaller and ORs its mask in.  Its reads are
-        // clean -- nobody else writes parent[x], and its partner, matched with x alone, is not hooked this round.  A smaller or unmatched root
-        // may read a `parent` word that is being written: it then sees x itself or a third root t, and best[t] cannot be x's key (the key
-        // names a pair between x's cluster and its partner's), so it does nothing, as it should.
-        for (int x = tid; x < n; x += BLOCK) {
-            if (excl_ld(&parent[x]) != x) continue;
-            const excl_u64 key = best[x];
-            if (key == 0) continue;
-            const int lo = 4095 - (int)((key >> 12) & 4095), hi = 4095 - (int)(key & 4095);
-            const int ra = excl_ld(&parent[lo]), rb = excl_ld(&parent[hi]);
-            const int other = ra == x ? rb : ra;
-            if (other < x && best[other] == key) {
-                excl_st(&parent[x], other);
-                atomicOr(&mask[other], mask[x]);
-                s_misc[0] = 1;
-            }
-        }
+        excl_merge_phase<BLOCK>(parent, best, mask, n, tid, &s_misc[0]);   // the mutual choices merge (excl_common.cuh)
         __syncthreads();
-        // back to depth one (a node hangs at most two below its new root: old root -> new root, and a new root was not hooked this round;
-        // a word read while it is written holds its old root or its new one, and both lead to the same root), and `best` cleared
-        for (int v = tid; v < n; v += BLOCK) {
-            int r = excl_ld(&parent[v]);
-            for (int q = excl_ld(&parent[r]); q != r; q = excl_ld(&parent[r])) r = q;
-            excl_st(&parent[v], r);
-            best[v] = 0;
-        }
+        excl_compress_phase<BLOCK>(parent, best, n, tid);                  // `parent` back to depth one, `best` cleared
         const int merged = s_misc[0];
         __syncthreads();
         if (!merged) break;

@@ -168,11 +168,19 @@ class FrameResult:
                 cache[key] = evaluate_frames(self.batch, self.pruned, self.labels, against=against)
         return cache[key]
 
-    def sweep(self, thresholds):
+    def sweep(self, thresholds, partition="components"):
         """Every operating point of this batch in one pass: calibration.sweep_thresholds(self.batch, self.probs, thresholds, 'ge') ->
-        float64 [T, G, 16] on the device; rows[t] is what evaluate(final=False) returns for a pipeline run at threshold thresholds[t]."""
+        float64 [T, G, 16] on the device; rows[t] is what evaluate(final=False) returns for a pipeline run at threshold thresholds[t].
+        partition='exclusive': the operating points of exclusive() instead -- rows[t] is evaluate_frames(batch, ex['predictions'],
+        ex['labels']) of a pipeline run at thresholds[t]; like exclusive() it judges the batch's host camera ids before any launch."""
         from .calibration import sweep_thresholds
-        return sweep_thresholds(self.batch, self.probs, thresholds, "ge")
+        if partition == "exclusive":
+            b = self.batch
+            if getattr(b, "cam_host", None) is None:
+                raise ValueError("sweep(partition='exclusive') needs a batch of build_graph_batch / FramePipeline (its host camera ids are "
+                                 "judged before any launch)")
+            check_cameras(b.cam_host)
+        return sweep_thresholds(self.batch, self.probs, thresholds, "ge", partition=partition)
 
     def identities(self, final=True):
         """The per-cluster summaries of this batch (gnn_cca_amd.tracking.cluster_summaries: fused position, mean appearance, size and

@@ -752,6 +752,45 @@ GNNCCA_API int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_la
                                  int32_t max_frame_nodes, const double* thresholds_dev, int32_t n_thresholds, int32_t keep_le,
                                  double* rows_out, int32_t* labels_out, void* workspace, size_t workspace_bytes, gnncca_stream_t stream);
 
+/* ---- Threshold sweep over the CAMERA-EXCLUSIVE partition (csrc/eval_sweep_exclusive.cuh) --------------------------------------------
+ * gnncca_eval_sweep scores the connected components of the pruned edges.  Whoever ships gnncca_post_exclusive_frames' clusters needs the
+ * sweep of THAT partition: the two differ wherever a component holds a camera twice, and a threshold chosen on one says nothing about
+ * the other.  Arguments: gnncca_eval_sweep's, plus `cam` int32 [N] camera ids in DEVICE memory, without keep_le (the rule needs
+ * positive weights: probabilities, not distances).  The rule for threshold t (thresholds_dev[t] strictly inside (0, 1)) and frame g
+ * defines nothing new:
+ *   rows        rows_out[t][g] (fp64 [n_thresholds][n_frames][16]) = the 16 columns of gnncca_eval_frames for the predictions_out and
+ *               labels_out of gnncca_post_exclusive_frames(..., threshold = thresholds_dev[t]), bit for bit.
+ *   labels      labels_out[t] (int32 [n_thresholds][N], nullable) = that call's labels_out, exactly.
+ * Activity ((double)scores[k] >= threshold, a NaN score is never active), candidates (both edges of a pair exist in the frame and are
+ * active), weight (the smaller of the two scores, an exact fp32), order (descending weight, ties to the smaller lo, then the smaller hi),
+ * clustering (merge iff the clusters differ and their camera masks are disjoint), labels (the smallest batch-global node id of the
+ * cluster) and predictions (1 iff the edge belongs to a candidate pair inside one cluster) are the exclusive entry's, stated there in
+ * full; the scoring is gnncca_eval_frames' code.
+ * How one pass does it: a pair's 64-bit key -- (fp32 bits of the weight) << 24 | (4095 - lo) << 12 | (4095 - hi) -- does not depend on
+ * the threshold, and the candidates at a threshold are exactly the pairs whose weight is >= it (the weight IS one of the two scores).
+ * One read-only key array per batch (slot k for the edge k of a pair with src < dst, 0 elsewhere) serves all thresholds; workgroup
+ * (g, t) runs the exclusive entry's mutual-best rounds over frame g's slots with the weight test in front.  Integer maxima and ORs in
+ * LDS only, no float atomics: two runs give the same bits, and a frame's rows do not depend on the rest of the batch.  The partitions
+ * nest: a lower threshold continues the walk of a higher one, so its clusters are unions of the higher one's.
+ * Refusals as in the two parents: a frame whose ranges do not fit (gnncca_eval_sweep's test) gets a NaN row; a frame with a camera id
+ * outside [0, 64) gets the row of "every node its own cluster, predictions 0"; other frames are unaffected; edge lists with duplicate
+ * ordered pairs are unspecified.  Thresholds outside (0, 1) are the caller's to refuse: on the device a threshold <= 0 behaves as the
+ * comparisons say -- every edge with a score >= it counts as active for the predictions, while only pairs of positive weight carry a
+ * key and can merge.
+ * Four launches whatever n_thresholds is (graph plan, plan finish, one prepare kernel: reverse edges + pair keys + lgamma tables, one
+ * launch of n_frames x n_thresholds workgroups), kernels only (no memset on the stream); LDS 20 bytes per node of the largest frame
+ * rounded up to a power of two (80 KiB at 4096); the workspace (gnncca_eval_sweep_exclusive_workspace_bytes: plan, rev int32 [E], keys
+ * u64 [E], lgamma tables) is O(E + N) and does not depend on n_thresholds; no host synchronisation, no allocation: capturable.
+ * GNNCCA_ERR_INVALID_ARG before any launch: n_thresholds < 1 or > GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS, max_frame_nodes outside
+ * [0, GNNCCA_EXCLUSIVE_MAX_FRAME_NODES] or above n_nodes, a negative size, a null thresholds_dev, a null pointer where the count is
+ * positive; GNNCCA_ERR_WORKSPACE: a short workspace.  n_frames == 0 returns GNNCCA_OK and launches nothing. */
+GNNCCA_API size_t gnncca_eval_sweep_exclusive_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames, int64_t n_thresholds);
+GNNCCA_API int gnncca_eval_sweep_exclusive(const int64_t* edge_index, const float* edge_labels, const float* scores, const int32_t* cam,
+                                           int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev,
+                                           int32_t n_frames, int32_t max_frame_nodes, const double* thresholds_dev, int32_t n_thresholds,
+                                           double* rows_out, int32_t* labels_out, void* workspace, size_t workspace_bytes,
+                                           gnncca_stream_t stream);
+
 /* ---- Rank-R ReID baseline with k-reciprocal re-ranking (csrc/rerank.cuh) -----------------------------------------------------------
  * The reference's MODE eval_RANK (inference.py:388-511) with RERANK (libs/utils.py:578-644, Zhong et al.): the baseline the GNN has to
  * beat.  A batch's per-frame matrices lie back to back, frame g's n_g x n_g row-major fp32 matrix at element sum_{q<g} n_q^2; `total` is

@@ -13,6 +13,11 @@ then timed as `reps` back-to-back repetitions that end in ONE device synchronise
 round, several rounds; the line carries every round's figure, the median and the spread (max - min over the rounds).
 
     python tools/time_sweep.py [--rounds 7] [--reps 20] [--loop-reps 3] [--parent PATH]
+
+`--partition exclusive` times the sweep of the camera-exclusive partition (sweep_thresholds(partition='exclusive')) the same way, on the
+same batch, against ITS loop: per threshold `postprocess.exclusive_clusters(at=t)` and `evaluate_frames` of its predictions and labels,
+over np.arange(0.01, 1.00, 0.01) (the rule's thresholds lie strictly inside (0, 1)).  Both functions of that loop are older than the
+sweep and untouched by it.
 """
 import argparse
 import json
@@ -54,6 +59,40 @@ def summary(vals):
             "spread_ms": round(float(max(vals) - min(vals)), 4)}
 
 
+def time_exclusive(torch, args, b, probs):
+    from gnn_cca_amd.calibration import sweep_thresholds
+    from gnn_cca_amd.evaluation import evaluate_frames
+    from gnn_cca_amd.postprocess import exclusive_clusters
+    ths = np.arange(0.01, 1.00, 0.01)
+    n, widest = int(b.node_ptr[-1]), int(np.diff(b.node_ptr).max())
+
+    def loop():
+        rows = []
+        for t in ths:
+            ex = exclusive_clusters(b.edge_index, probs, b.cam_dev, n, b.node_ptr_dev, b.edge_ptr_dev, at=float(t), max_frame_nodes=widest)
+            rows.append(evaluate_frames(b, ex["predictions"], ex["labels"]))
+        return rows
+
+    def sweep():
+        return sweep_thresholds(b, probs, ths, partition="exclusive")
+
+    if not torch.equal(sweep(), torch.stack(loop())):   # (no NaN rows in this batch)
+        raise SystemExit("the exclusive sweep and its loop disagree: nothing to time")
+    sides = {"sweep_exclusive": (sweep, args.reps), "loop_exclusive": (loop, args.loop_reps)}
+    for fn, _ in sides.values():   # warm-up: every shape and kernel of the timed windows
+        fn()
+        fn()
+    got = {k: [] for k in sides}
+    for _ in range(args.rounds):
+        for k, (fn, reps) in sides.items():   # the sides alternate inside a round
+            got[k].append(timed(torch, fn, reps))
+    res = {"metric": "threshold sweep of the camera-exclusive partition, ms per 99 thresholds", "frames": len(b.node_ptr) - 1, "nodes": n,
+           "edges": int(b.edge_index.shape[1]), "thresholds": len(ths), "rounds": args.rounds}
+    res.update({k: summary(v) for k, v in got.items()})
+    res["loop_over_sweep"] = round(float(np.median(got["loop_exclusive"]) / np.median(got["sweep_exclusive"])), 1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -62,6 +101,7 @@ def main():
     ap.add_argument("--root", default=os.path.dirname(HERE), help="the tree whose gnn_cca_amd is timed")
     ap.add_argument("--loop-only", action="store_true", help="time loop_torch alone (what a child run in the parent's tree does)")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: its loop_torch is timed in a child process")
+    ap.add_argument("--partition", choices=("components", "exclusive"), default="components", help="which partition's sweep is timed")
     args = ap.parse_args()
     sys.path.insert(0, args.root)
     import torch
@@ -74,6 +114,8 @@ def main():
     b, logits = make_batch(torch, 64, 4, 8)
     n = int(b.node_ptr[-1])
     probs, _ = threshold(logits)
+    if args.partition == "exclusive":
+        return time_exclusive(torch, args, b, probs)
 
     def one(preds):
         post = prune_and_cluster(b.edge_index, preds, n, b.node_ptr_dev, b.edge_ptr_dev)
