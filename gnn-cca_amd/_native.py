@@ -22,6 +22,9 @@ SCORE_MIN_CAP, SCORE_HEADER_LEN = 1024, 8
 REENTRY_MAX_WINDOW = 4096            # gnncca_reentry_update: the walking workgroup keeps a frame's candidate tracks in LDS
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
 SWEEP_MAX_THRESHOLDS = 1024          # gnncca_eval_sweep
+JOINT_MAX_SCORES = 4                 # gnncca_eval_sweep_joint
+JOINT_MAX_POINTS = 16384
+CMP = {"ge": 0, "gt": 1, "le": 2, "lt": 3}   # GNNCCA_CMP_*
 EXCLUSIVE_MAX_FRAME_NODES, EXCLUSIVE_MAX_CAMERAS = 4096, 64   # gnncca_post_exclusive_frames: 12-bit local ids, one 64-bit camera mask
 EXCLUSIVE_BAD_CAMERA, EXCLUSIVE_BAD_RANGE = 1, 2              # its flags_out[g]
 RERANK_MAX_FRAME_NODES, RERANK_MAX_K1 = 128, 64  # gnncca_rerank_frames, gnncca_rank_predictions: a frame's tables and masks live in LDS
@@ -228,6 +231,11 @@ _SIGNATURES = {
     "gnncca_eval_sweep_exclusive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                               C.c_void_p]),
+    "gnncca_eval_sweep_joint_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "gnncca_eval_sweep_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
+                                          C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnncca_eval_rows_accumulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnncca_frame_distances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "gnncca_rerank_lds_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gnncca_rerank_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,

@@ -16,7 +16,8 @@
 // Launches (their number does not depend on T): the graph plan (plan_only + plan finish, as gnncca_post_prune_cluster makes it without
 // a handed-over plan), eval_sweep_prepare_kernel (the reverse edge of every edge from the plan's CSR, and the per-frame lgamma tables
 // the scoring reads), eval_sweep_kernel with grid (G, T).  No prediction vector exists anywhere: a workgroup judges an edge from its
-// score and its reverse edge's score when it needs it.
+// score and its reverse edge's score when it needs it.  The workgroup's work is written for any such judgement (eval_sweep_frame,
+// eval_sweep_body<BLOCK, PredF>): eval_sweep_joint.cuh runs it with a conjunction of conditions.
 namespace gnncca {
 
 // rev[k] = the edge (dst k, src k), or -1.  Blocks [0, edge_blocks): one edge per thread, searched in the CSR segment of dst k as
@@ -65,34 +66,46 @@ struct SweepLabel {
     __device__ __forceinline__ int operator()(int v0, int v) const { return v0 + (int)lab16[v]; }
 };
 
-// Workgroup (g, t): frame g at thresholds[t].  The partition first -- union-find over the kept edges in eval_frame_body's `parent`
-// region (which the body initialises again), the larger root hooked under the smaller by compare-and-swap, so that a component's
-// root is its smallest node, then every node's root into a fourth LDS region of P_lds 16-bit words -- then the scoring body.
-// LDS: 3.5 x P_lds ints (56 KiB at 4096 nodes) + the body's ~2 KiB.  labels_out (nullable): int32 [T][N_all].
+// The part of a sweep workgroup that comes before the predicate exists: the frame's ranges.  A frame whose ranges do not fit
+// (eval_frame_body's test) gets a NaN row and identity labels, and the workgroup is done (false).
+struct SweepFrame {
+    int v0, n;
+    long long k0, k1;
+};
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void eval_sweep_kernel(const long long* __restrict__ ei, long long E, const float* __restrict__ elab,
-                                                           const float* __restrict__ scores, const int* __restrict__ rev,
-                                                           const double* __restrict__ thresholds, int keep_le, int N_all,
-                                                           const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int P_lds,
-                                                           double* __restrict__ rows_out, int* __restrict__ labels_out,
-                                                           double* __restrict__ lf_ws) {
-    extern __shared__ int s_dyn[];
-    int* parent = s_dyn;
-    unsigned short* lab16 = reinterpret_cast<unsigned short*>(s_dyn + 3 * P_lds);
-    const int g = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
-    const int n_frames = gridDim.x;
-    double* row = rows_out + ((size_t)t * n_frames + g) * 16;
-    int* lab_t = labels_out ? labels_out + (size_t)t * N_all : nullptr;
+__device__ __forceinline__ bool eval_sweep_frame(int g, int N_all, long long E, const int* __restrict__ node_ptr,
+                                                 const int* __restrict__ edge_ptr, int P_lds, double* __restrict__ row, int* __restrict__ lab_t,
+                                                 SweepFrame& f) {
+    const int tid = threadIdx.x;
     const int v0 = node_ptr[g], v1 = node_ptr[g + 1];
     const long long k0 = edge_ptr[g], k1 = edge_ptr[g + 1];
     const int n = v1 - v0;
+    f = SweepFrame{v0, n, k0, k1};
     if (v0 < 0 || n < 0 || n > P_lds || v1 > N_all || k0 < 0 || k1 < k0 || k1 > E) {   // eval_frame_body's test: a NaN row
         if (tid < 16) row[tid] = __builtin_nan("");
         if (lab_t && v0 >= 0 && v1 <= N_all)
             for (int v = v0 + tid; v < v1; v += BLOCK) lab_t[v] = v;
-        return;
+        return false;
     }
-    const SweepPred pred{scores, rev, thresholds[t], k0, k1, keep_le != 0};
+    return true;
+}
+
+// The workgroup body of every sweep over the connected components, written once for every predicate (`pred(k)`: 1 iff edge k is kept at
+// this workgroup's operating point -- SweepPred here, SweepJointPred in eval_sweep_joint.cuh).  The partition first -- union-find over
+// the kept edges in eval_frame_body's `parent` region (which the body initialises again), the larger root hooked under the smaller by
+// compare-and-swap, so that a component's root is its smallest node, then every node's root into a fourth LDS region of P_lds 16-bit
+// words -- then the scoring body.  LDS: 3.5 x P_lds ints (56 KiB at 4096 nodes) + the body's ~2 KiB.
+template <int BLOCK, class PredF>
+__device__ __forceinline__ void eval_sweep_body(int g, const SweepFrame f, const PredF pred, const long long* __restrict__ ei, long long E,
+                                                const float* __restrict__ elab, int N_all, const int* __restrict__ node_ptr,
+                                                const int* __restrict__ edge_ptr, int P_lds, double* __restrict__ row,
+                                                int* __restrict__ lab_t, double* __restrict__ lf_ws) {
+    extern __shared__ int s_dyn[];
+    int* parent = s_dyn;
+    unsigned short* lab16 = reinterpret_cast<unsigned short*>(s_dyn + 3 * P_lds);
+    const int tid = threadIdx.x;
+    const int v0 = f.v0, n = f.n;
+    const long long k0 = f.k0, k1 = f.k1;
     for (int v = tid; v < n; v += BLOCK) parent[v] = v;
     __syncthreads();
     for (long long k = k0 + tid; k < k1; k += BLOCK) {
@@ -118,6 +131,24 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_kernel(const long long* __re
     __syncthreads();
     eval_frame_body<BLOCK, false, false>(g, row, ei, E, elab, pred, SweepLabel{lab16}, N_all, node_ptr, edge_ptr, P_lds, nullptr, lf_ws,
                                          nullptr, nullptr);
+}
+
+// Workgroup (g, t): frame g at thresholds[t].  labels_out (nullable): int32 [T][N_all].
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void eval_sweep_kernel(const long long* __restrict__ ei, long long E, const float* __restrict__ elab,
+                                                           const float* __restrict__ scores, const int* __restrict__ rev,
+                                                           const double* __restrict__ thresholds, int keep_le, int N_all,
+                                                           const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int P_lds,
+                                                           double* __restrict__ rows_out, int* __restrict__ labels_out,
+                                                           double* __restrict__ lf_ws) {
+    const int g = blockIdx.x, t = blockIdx.y;
+    const int n_frames = gridDim.x;
+    double* row = rows_out + ((size_t)t * n_frames + g) * 16;
+    int* lab_t = labels_out ? labels_out + (size_t)t * N_all : nullptr;
+    SweepFrame f;
+    if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, P_lds, row, lab_t, f)) return;
+    const SweepPred pred{scores, rev, thresholds[t], f.k0, f.k1, keep_le != 0};
+    eval_sweep_body<BLOCK>(g, f, pred, ei, E, elab, N_all, node_ptr, edge_ptr, P_lds, row, lab_t, lf_ws);
 }
 
 }  // namespace gnncca

@@ -391,6 +391,7 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
 #include "excl_common.cuh"           // the camera-exclusive rule's shared pieces (also part of mpn_post.hip through exclusive.cuh)
 #include "eval_sweep.cuh"            // the threshold sweep: its kernels call eval_frame_body
 #include "eval_sweep_exclusive.cuh"  // the same sweep over the camera-exclusive partition
+#include "eval_sweep_joint.cuh"      // the sweep of a conjunction of conditions: eval_sweep.cuh's workgroup body, another predicate
 
 using namespace gnncca;
 
@@ -469,6 +470,36 @@ size_t gnncca_eval_sweep_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64
     return carve_sweep(n_nodes, n_edges, n_frames).total;
 }
 
+// The three launches every sweep over the connected components starts with: the plan of gnncca_post_prune_cluster (no padded layout to
+// validate), its finish, and eval_sweep_prepare_kernel (rev and the lgamma tables, handed back as pointers into the workspace).
+static int sweep_prepare(const SweepWorkspace& ws, void* workspace, const long long* ei, int E, int N, const int32_t* node_ptr_dev,
+                         int32_t n_frames, hipStream_t st, int** rev_out, double** lf_out) {
+    char* base = static_cast<char*>(workspace);
+    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
+    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
+    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
+    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
+    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
+    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
+    int* rev = reinterpret_cast<int*>(base + ws.rev);
+    double* lf = reinterpret_cast<double*>(base + ws.lf);
+    if (E > 0) {
+        EncPlanParams ep;
+        std::memset(&ep, 0, sizeof(ep));
+        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
+        launch_plan_only(ep, plan_num_blocks(E), st);
+        HIP_TRY(hipGetLastError());
+        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
+        HIP_TRY(hipGetLastError());
+    }
+    const int edge_blocks = (E + 255) / 256;
+    hipLaunchKernelGGL(eval_sweep_prepare_kernel, dim3((unsigned)edge_blocks + (unsigned)n_frames), dim3(256), 0, st, ei, (long long)E,
+                       (const int*)seg_ptr, (const int*)col32, (const int*)perm, (const unsigned*)flags, rev, edge_blocks, node_ptr_dev, N, lf);
+    HIP_TRY(hipGetLastError());
+    *rev_out = rev, *lf_out = lf;
+    return GNNCCA_OK;
+}
+
 int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_labels, const float* scores, int64_t n_nodes, int64_t n_edges,
                       const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes,
                       const double* thresholds_dev, int32_t n_thresholds, int32_t keep_le, double* rows_out, int32_t* labels_out,
@@ -485,29 +516,10 @@ int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_labels, const
     if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = (int)n_nodes, E = (int)n_edges;
-    char* base = static_cast<char*>(workspace);
-    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
-    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
-    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
-    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
-    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
-    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
-    int* rev = reinterpret_cast<int*>(base + ws.rev);
-    double* lf = reinterpret_cast<double*>(base + ws.lf);
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
-    if (E > 0) {   // the plan of gnncca_post_prune_cluster (no padded layout to validate)
-        EncPlanParams ep;
-        std::memset(&ep, 0, sizeof(ep));
-        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
-        launch_plan_only(ep, plan_num_blocks(E), st);
-        HIP_TRY(hipGetLastError());
-        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
-        HIP_TRY(hipGetLastError());
-    }
-    const int edge_blocks = (E + 255) / 256;
-    hipLaunchKernelGGL(eval_sweep_prepare_kernel, dim3((unsigned)edge_blocks + (unsigned)n_frames), dim3(256), 0, st, ei, (long long)E,
-                       (const int*)seg_ptr, (const int*)col32, (const int*)perm, (const unsigned*)flags, rev, edge_blocks, node_ptr_dev, N, lf);
-    HIP_TRY(hipGetLastError());
+    int* rev = nullptr;
+    double* lf = nullptr;
+    if (const int rc = sweep_prepare(ws, workspace, ei, E, N, node_ptr_dev, n_frames, st, &rev, &lf)) return rc;
     int P = 1;
     while (P < max_frame_nodes) P <<= 1;
     const size_t lds = (size_t)3 * P * sizeof(int) + (size_t)P * sizeof(unsigned short);
@@ -599,6 +611,67 @@ int gnncca_eval_sweep_exclusive(const int64_t* edge_index, const float* edge_lab
                        (const excl_u64*)keys, thresholds_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
     if (P <= 64) GNNCCA_SWEEP_EXCL(64); else GNNCCA_SWEEP_EXCL(256);   // (gnncca_eval_sweep's choice, which is eval_frames')
 #undef GNNCCA_SWEEP_EXCL
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- the sweep of a conjunction of conditions (eval_sweep_joint.cuh) ------------------------------------------------------------------
+// workspace: gnncca_eval_sweep's, whatever the numbers of points and scores are
+size_t gnncca_eval_sweep_joint_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return 0;
+    return carve_sweep(n_nodes, n_edges, n_frames).total;
+}
+
+int gnncca_eval_sweep_joint(const int64_t* edge_index, const float* edge_labels, const float* const* scores, const int64_t* score_strides,
+                            const int32_t* comparators, int32_t n_scores, int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev,
+                            const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes, const double* points_dev,
+                            int32_t n_points, const double* frame_div_dev, double* rows_out, int32_t* labels_out, void* workspace,
+                            size_t workspace_bytes, gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_scores < 1 || n_scores > GNNCCA_EVAL_JOINT_MAX_SCORES) return GNNCCA_ERR_INVALID_ARG;
+    if (n_points < 1 || n_points > GNNCCA_EVAL_JOINT_MAX_POINTS) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > kEvalMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if (!points_dev || !scores || !score_strides || !comparators) return GNNCCA_ERR_INVALID_ARG;
+    JointScores sc;
+    std::memset(&sc, 0, sizeof(sc));
+    sc.K = n_scores;
+    for (int k = 0; k < n_scores; ++k) {
+        if (comparators[k] < GNNCCA_CMP_GE || comparators[k] > GNNCCA_CMP_LT || score_strides[k] < 1) return GNNCCA_ERR_INVALID_ARG;
+        if (n_edges > 0 && !scores[k]) return GNNCCA_ERR_INVALID_ARG;
+        sc.p[k] = scores[k], sc.stride[k] = score_strides[k], sc.cmp[k] = comparators[k];
+    }
+    if (n_frames == 0) return GNNCCA_OK;
+    if (!node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !edge_labels)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    const SweepWorkspace ws = carve_sweep(n_nodes, n_edges, n_frames);
+    if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int N = (int)n_nodes, E = (int)n_edges;
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    int* rev = nullptr;
+    double* lf = nullptr;
+    if (const int rc = sweep_prepare(ws, workspace, ei, E, N, node_ptr_dev, n_frames, st, &rev, &lf)) return rc;
+    int P = 1;
+    while (P < max_frame_nodes) P <<= 1;
+    const size_t lds = (size_t)3 * P * sizeof(int) + (size_t)P * sizeof(unsigned short);   // (gnncca_eval_sweep's: the body is the same)
+    const dim3 grid((unsigned)n_frames, (unsigned)n_points);
+#define GNNCCA_SWEEP_JOINT(B)                                                                                                               \
+    hipLaunchKernelGGL((eval_sweep_joint_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, sc, (const int*)rev, points_dev, \
+                       frame_div_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
+    if (P <= 64) GNNCCA_SWEEP_JOINT(64); else GNNCCA_SWEEP_JOINT(256);   // (eval_frames' choice)
+#undef GNNCCA_SWEEP_JOINT
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_eval_rows_accumulate(const double* rows, int32_t n_points, int32_t n_frames, double* sums, int64_t* frames,
+                                gnncca_stream_t stream) {
+    if (n_points < 1 || n_points > GNNCCA_EVAL_JOINT_MAX_POINTS || n_frames < 0 || !sums) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames == 0) return GNNCCA_OK;
+    if (!rows) return GNNCCA_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(eval_rows_accumulate_kernel, dim3((unsigned)(n_points * 16 + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       rows, (int)n_points, (int)n_frames, sums, reinterpret_cast<long long*>(frames));
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

@@ -791,6 +791,54 @@ GNNCCA_API int gnncca_eval_sweep_exclusive(const int64_t* edge_index, const floa
                                            double* rows_out, int32_t* labels_out, void* workspace, size_t workspace_bytes,
                                            gnncca_stream_t stream);
 
+/* ---- Joint sweep: every operating point of a CONJUNCTION of conditions in one pass (csrc/eval_sweep_joint.cuh) -----------------------
+ * The reference's position baselines keep an edge iff several scores pass at once: geometrical_association iff the ground distance
+ * < GEOM_TH / max_dist (inference.py:722-724), geometrical_appearance_association iff that holds AND the ReID distance < th
+ * (inference.py:896); the GEOM_TH / OPT_TH tables of config_inference.yaml were swept by hand, one axis at a time.  Arguments beyond
+ * gnncca_eval_sweep's: `scores` a HOST array of n_scores DEVICE pointers to fp32 scores, `score_strides` a host array of their element
+ * strides (element e of score k is scores[k][e * score_strides[k]]: the columns of an edge_attr [E][4] are swept in place with stride
+ * 4), `comparators` a host array of GNNCCA_CMP_* codes, one per condition (1 <= n_scores <= GNNCCA_EVAL_JOINT_MAX_SCORES);
+ * points_dev fp64 [n_points][n_scores] in DEVICE memory (1 <= n_points <= GNNCCA_EVAL_JOINT_MAX_POINTS; any order, duplicates allowed);
+ * frame_div_dev fp64 [n_scores][n_frames] in DEVICE memory, nullable.  The rule for point t and frame g:
+ *   threshold  th[k] = points_dev[t][k] / frame_div_dev[k][g], one IEEE fp64 division; points_dev[t][k] itself when frame_div_dev is
+ *              null (GEOM_TH / max_dist[g]: the table value is in metres, the attribute was divided by the frame's max_dist).
+ *   activity   edge e is active iff for EVERY k: (double)scores[k][e] cmp_k th[k].  The comparison is made in fp64 against the widened
+ *              fp32 score; a NaN score is never active under any comparator.
+ *   pruning, partition, scores   exactly gnncca_eval_sweep's: an edge is kept iff its reverse edge of the same frame is active too;
+ *              labels_out[t] (int32 [n_points][N], nullable) = the connected components of the kept edges, a node's label the smallest
+ *              batch-global id of its component; rows_out[t][g] (fp64 [n_points][n_frames][16]) = the 16 columns of
+ *              gnncca_eval_frames.  The workgroup body is gnncca_eval_sweep's own code with another predicate: with one score, no
+ *              divisor and GNNCCA_CMP_GE / GNNCCA_CMP_LE the rows and labels are that entry's bit for bit.
+ * NOT reproduced: the reference clusters with the strongly connected components of the digraph of active edges and does not prune; with
+ * a score that is not symmetric (F.pairwise_distance adds eps to a - b) a directed cycle without a mutual pair joins nodes there, here
+ * only mutual pairs join.  inference.py:892,896 use the last graph's labels and max_dist[0] for a whole batch; here every frame has its
+ * own.  A frame whose ranges do not fit gets a NaN row; edge lists with duplicate ordered pairs are unspecified (as above).
+ * Four launches whatever n_points and n_scores are (graph plan, plan finish, gnncca_eval_sweep's prepare kernel unchanged, one launch of
+ * n_frames x n_points workgroups); the workspace (gnncca_eval_sweep_joint_workspace_bytes) is gnncca_eval_sweep's, O(E + N); no host
+ * synchronisation, no allocation: capturable.  GNNCCA_ERR_INVALID_ARG before any launch: n_scores or n_points out of range, an unknown
+ * comparator code, a stride < 1, a negative size, max_frame_nodes above GNNCCA_EVAL_MAX_FRAME_NODES or n_nodes, a null array, a null
+ * pointer where its count is positive; GNNCCA_ERR_WORKSPACE: a short workspace.  n_frames == 0 returns GNNCCA_OK and launches nothing.
+ *
+ * gnncca_eval_rows_accumulate folds the rows fp64 [n_points][n_frames][16] of one batch into running sums fp64 [n_points][16] and a
+ * frame count (int64 [1], nullable; both in DEVICE memory, zeroed by the caller before the first batch) in ONE launch:
+ * sums[t][c] = ((sums[t][c] + rows[t][0][c]) + rows[t][1][c]) + ... -- the frames in ascending g, plain fp64 adds, an order that is part
+ * of the contract; no atomics, no reduction tree: two runs give the same bits.  A NaN row makes its sums NaN.  *frames += n_frames. */
+#define GNNCCA_EVAL_JOINT_MAX_SCORES 4
+#define GNNCCA_EVAL_JOINT_MAX_POINTS 16384
+#define GNNCCA_CMP_GE 0
+#define GNNCCA_CMP_GT 1
+#define GNNCCA_CMP_LE 2
+#define GNNCCA_CMP_LT 3
+GNNCCA_API size_t gnncca_eval_sweep_joint_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames);
+GNNCCA_API int gnncca_eval_sweep_joint(const int64_t* edge_index, const float* edge_labels, const float* const* scores,
+                                       const int64_t* score_strides, const int32_t* comparators, int32_t n_scores, int64_t n_nodes,
+                                       int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                       int32_t max_frame_nodes, const double* points_dev, int32_t n_points, const double* frame_div_dev,
+                                       double* rows_out, int32_t* labels_out, void* workspace, size_t workspace_bytes,
+                                       gnncca_stream_t stream);
+GNNCCA_API int gnncca_eval_rows_accumulate(const double* rows, int32_t n_points, int32_t n_frames, double* sums, int64_t* frames,
+                                           gnncca_stream_t stream);
+
 /* ---- Rank-R ReID baseline with k-reciprocal re-ranking (csrc/rerank.cuh) -----------------------------------------------------------
  * The reference's MODE eval_RANK (inference.py:388-511) with RERANK (libs/utils.py:578-644, Zhong et al.): the baseline the GNN has to
  * beat.  A batch's per-frame matrices lie back to back, frame g's n_g x n_g row-major fp32 matrix at element sum_{q<g} n_q^2; `total` is

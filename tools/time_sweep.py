@@ -18,6 +18,14 @@ round, several rounds; the line carries every round's figure, the median and the
 same batch, against ITS loop: per threshold `postprocess.exclusive_clusters(at=t)` and `evaluate_frames` of its predictions and labels,
 over np.arange(0.01, 1.00, 0.01) (the rule's thresholds lie strictly inside (0, 1)).  Both functions of that loop are older than the
 sweep and untouched by it.
+
+`--joint TAxTB` (say 100x100, main.py's own 0.01 step on two axes) times calibration.sweep_grid over a TA x TB grid on the same batch --
+edge_attr[:, 0] < a AND edge_attr[:, 2] < b, the axes spread evenly over each column's range -- against ITS loop: per point the two
+float64 comparisons in torch, `prune_and_cluster`, `evaluate_frames`, all older than the joint sweep and untouched by it.  A whole
+loop is TA * TB points: --loop-reps 1 is plenty.  It also times folding `--acc-batches` such row sets into a JointSweepAccumulator
+(`accumulate`: one add per batch) against keeping a copy of each and reducing them once with torch (`keep_rows`: clone, cat, sum),
+both on the device alone; prints the bytes each way holds there; and times one result() (`result_ms`: the synchronisation, the copy
+and the host's T dicts).
 """
 import argparse
 import json
@@ -93,6 +101,65 @@ def time_exclusive(torch, args, b, probs):
     print(json.dumps(res))
 
 
+def time_joint(torch, args, b):
+    from gnn_cca_amd.calibration import JointSweepAccumulator, grid_points, sweep_grid
+    from gnn_cca_amd.evaluation import evaluate_frames
+    from gnn_cca_amd.postprocess import prune_and_cluster
+    try:
+        ta, tb = (int(v) for v in args.joint.lower().split("x"))
+    except ValueError:
+        raise SystemExit("--joint takes TAxTB, such as 100x100") from None
+    n, g = int(b.node_ptr[-1]), len(b.node_ptr) - 1
+    s0, s1 = b.edge_attr[:, 0], b.edge_attr[:, 2]
+    axes = [np.linspace(float(s.min()), float(s.max()), t + 1)[1:] for s, t in ((s0, ta), (s1, tb))]
+    pts, shape = grid_points(axes)
+    d0, d1 = s0.double(), s1.double()
+
+    def loop():
+        rows = []
+        for a, c in pts:
+            preds = ((d0 < float(a)) & (d1 < float(c))).to(torch.int64)
+            post = prune_and_cluster(b.edge_index, preds, n, b.node_ptr_dev, b.edge_ptr_dev)
+            rows.append(evaluate_frames(b, post["pruned"], post["labels"]))
+        return rows
+
+    def grid():
+        return sweep_grid(b, [s0, s1], axes, ["lt", "lt"])
+
+    rows = grid()
+    if not torch.equal(rows.reshape(len(pts), g, 16), torch.stack(loop())):   # (no NaN rows in this batch)
+        raise SystemExit("the joint sweep and its loop disagree: nothing to time")
+    flat = rows.reshape(len(pts), g, 16)
+
+    acc = JointSweepAccumulator(pts)
+
+    def accumulate():   # the device side of a data set: one launch per batch, nothing of the batch kept
+        for _ in range(args.acc_batches):
+            acc.add(flat)
+
+    def keep_rows():    # (a data set's batches are distinct tensors: each one is held until the reduction)
+        kept = [flat.clone() for _ in range(args.acc_batches)]
+        return torch.cat(kept, dim=1).sum(dim=1)
+
+    sides = {"grid": (grid, args.reps), "loop": (loop, args.loop_reps), "accumulate": (accumulate, args.acc_reps),
+             "keep_rows": (keep_rows, args.acc_reps)}
+    for fn, _ in sides.values():   # warm-up: every shape and kernel of the timed windows (the loop ran once above)
+        fn()
+    got = {k: [] for k in sides}
+    for _ in range(args.rounds):
+        for k, (fn, reps) in sides.items():   # the sides alternate inside a round
+            got[k].append(timed(torch, fn, reps))
+    res = {"metric": f"joint sweep, ms per {ta} x {tb} grid", "frames": g, "nodes": n, "edges": int(b.edge_index.shape[1]), "points": len(pts),
+           "rounds": args.rounds, "acc_batches": args.acc_batches, "accumulator_device_bytes": (len(pts) * 16 + 1) * 8,
+           "kept_rows_device_bytes": args.acc_batches * len(pts) * g * 16 * 8}
+    res.update({k: summary(v) for k, v in got.items()})
+    t0 = time.perf_counter()
+    acc.result()   # one synchronisation, one copy, then the host's part: T dicts of aggregates and the micro scores
+    res["result_ms"] = round((time.perf_counter() - t0) * 1e3, 4)
+    res["loop_over_grid"] = round(float(np.median(got["loop"]) / np.median(got["grid"])), 1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -102,6 +169,9 @@ def main():
     ap.add_argument("--loop-only", action="store_true", help="time loop_torch alone (what a child run in the parent's tree does)")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: its loop_torch is timed in a child process")
     ap.add_argument("--partition", choices=("components", "exclusive"), default="components", help="which partition's sweep is timed")
+    ap.add_argument("--joint", default=None, metavar="TAxTB", help="time sweep_grid over a TA x TB grid against its per-point loop")
+    ap.add_argument("--acc-reps", type=int, default=200, help="--joint: accumulate / keep_rows calls per timed window (a call is well under 1 ms)")
+    ap.add_argument("--acc-batches", type=int, default=8, help="--joint: row sets folded into the accumulator / kept, per timed call")
     args = ap.parse_args()
     sys.path.insert(0, args.root)
     import torch
@@ -114,6 +184,8 @@ def main():
     b, logits = make_batch(torch, 64, 4, 8)
     n = int(b.node_ptr[-1])
     probs, _ = threshold(logits)
+    if args.joint:
+        return time_joint(torch, args, b)
     if args.partition == "exclusive":
         return time_exclusive(torch, args, b, probs)
 
