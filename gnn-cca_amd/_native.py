@@ -25,6 +25,7 @@ SWEEP_MAX_THRESHOLDS = 1024          # gnncca_eval_sweep
 JOINT_MAX_SCORES = 4                 # gnncca_eval_sweep_joint
 JOINT_MAX_POINTS = 16384
 CMP = {"ge": 0, "gt": 1, "le": 2, "lt": 3}   # GNNCCA_CMP_*
+RANK_MAX_SCORES, RANK_MAX_FRAME_EDGES, RANK_POOL_MAX_THRESHOLDS = 4, 16384, 65536   # gnncca_rank_metrics, gnncca_rank_pool_add
 EXCLUSIVE_MAX_FRAME_NODES, EXCLUSIVE_MAX_CAMERAS = 4096, 64   # gnncca_post_exclusive_frames: 12-bit local ids, one 64-bit camera mask
 EXCLUSIVE_BAD_CAMERA, EXCLUSIVE_BAD_RANGE = 1, 2              # its flags_out[g]
 RERANK_MAX_FRAME_NODES, RERANK_MAX_K1 = 128, 64  # gnncca_rerank_frames, gnncca_rank_predictions: a frame's tables and masks live in LDS
@@ -236,6 +237,12 @@ _SIGNATURES = {
                                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnncca_eval_rows_accumulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_rank_metrics_lds_bytes": (C.c_size_t, [C.c_int32]),
+    "gnncca_rank_metrics": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_int64,
+                                      C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gnncca_rank_rows_accumulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_rank_pool_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "gnncca_frame_distances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "gnncca_rerank_lds_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gnncca_rerank_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,

@@ -392,6 +392,7 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
 #include "eval_sweep.cuh"            // the threshold sweep: its kernels call eval_frame_body
 #include "eval_sweep_exclusive.cuh"  // the same sweep over the camera-exclusive partition
 #include "eval_sweep_joint.cuh"      // the sweep of a conjunction of conditions: eval_sweep.cuh's workgroup body, another predicate
+#include "rank_metrics.cuh"          // threshold-free ranking scores per frame (AUROC, AP, best F) and the pooled curve's histograms
 
 using namespace gnncca;
 
@@ -672,6 +673,84 @@ int gnncca_eval_rows_accumulate(const double* rows, int32_t n_points, int32_t n_
     if (!rows) return GNNCCA_ERR_INVALID_ARG;
     hipLaunchKernelGGL(eval_rows_accumulate_kernel, dim3((unsigned)(n_points * 16 + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
                        rows, (int)n_points, (int)n_frames, sums, reinterpret_cast<long long*>(frames));
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- ranking scores without a threshold (rank_metrics.cuh) ------------------------------------------------------------------------------
+// bytes of dynamic LDS for a batch whose largest frame has max_frame_edges edges: 8 per word of the next power of two (at least 64 words)
+size_t gnncca_rank_metrics_lds_bytes(int32_t max_frame_edges) {
+    if (max_frame_edges < 0 || max_frame_edges > kRankMaxEdges) return 0;
+    size_t words = 64;
+    while (words < (size_t)max_frame_edges) words <<= 1;
+    return words * sizeof(rank_u64);
+}
+
+int gnncca_rank_metrics(const float* edge_labels, const float* const* scores, const int64_t* score_strides, const int32_t* positive_low,
+                        int32_t n_scores, int64_t n_edges, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_edges,
+                        double* rows_out, gnncca_stream_t stream) {
+    if (n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_scores < 1 || n_scores > kRankMaxScores || !scores || !score_strides || !positive_low) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_edges < 0 || max_frame_edges > kRankMaxEdges || max_frame_edges > n_edges) return GNNCCA_ERR_INVALID_ARG;
+    RankScores sc;
+    std::memset(&sc, 0, sizeof(sc));
+    for (int k = 0; k < n_scores; ++k) {
+        if (score_strides[k] < 1 || (positive_low[k] != 0 && positive_low[k] != 1)) return GNNCCA_ERR_INVALID_ARG;
+        if (n_edges > 0 && !scores[k]) return GNNCCA_ERR_INVALID_ARG;
+        sc.p[k] = scores[k], sc.stride[k] = score_strides[k], sc.low[k] = positive_low[k];
+    }
+    if (n_frames == 0) return GNNCCA_OK;
+    if (!edge_ptr_dev || !rows_out || (n_edges > 0 && !edge_labels)) return GNNCCA_ERR_INVALID_ARG;
+    const size_t lds = gnncca_rank_metrics_lds_bytes(max_frame_edges);
+    const int cap = (int)(lds / sizeof(rank_u64));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)n_frames, (unsigned)n_scores);
+    if (cap > 4096) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (gnncca_eval_sweep_exclusive's way)
+        static thread_local int attr_dev = -1;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if (attr_dev != dev) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_metrics_kernel<1024>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kRankMaxEdges * sizeof(rank_u64))));
+            attr_dev = dev;
+        }
+    }
+#define GNNCCA_RANK(B)                                                                                                             \
+    hipLaunchKernelGGL((rank_metrics_kernel<B>), grid, dim3(B), lds, st, edge_labels, (long long)n_edges, sc, edge_ptr_dev, cap, rows_out)
+    if (cap <= 1024) GNNCCA_RANK(256);   // threads by capacity: at most 16 words of the image per thread
+    else if (cap <= 4096) GNNCCA_RANK(512);
+    else GNNCCA_RANK(1024);
+#undef GNNCCA_RANK
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_rank_rows_accumulate(const double* rows, int32_t n_scores, int32_t n_frames, double* sums, int64_t* counts, gnncca_stream_t stream) {
+    if (n_scores < 1 || n_scores > kRankMaxScores || n_frames < 0 || !sums || !counts) return GNNCCA_ERR_INVALID_ARG;
+    if (n_frames == 0) return GNNCCA_OK;
+    if (!rows) return GNNCCA_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(rank_rows_accumulate_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), rows, (int)n_scores, (int)n_frames,
+                       sums, reinterpret_cast<long long*>(counts));
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_rank_pool_add(const float* scores, int64_t score_stride, const float* labels, int64_t n_samples, const double* thresholds_dev,
+                         int32_t n_thresholds, int32_t keep_le, int64_t* hist, int64_t* nan_count, gnncca_stream_t stream) {
+    if (n_samples < 0 || score_stride < 1) return GNNCCA_ERR_INVALID_ARG;
+    if (n_thresholds < 1 || n_thresholds > GNNCCA_RANK_POOL_MAX_THRESHOLDS || !thresholds_dev || !hist || !nan_count) return GNNCCA_ERR_INVALID_ARG;
+    if (n_samples == 0) return GNNCCA_OK;
+    if (!scores || !labels) return GNNCCA_ERR_INVALID_ARG;
+    const long long per_block = 256 * kPoolPerThread;
+    const long long blocks = (n_samples + per_block - 1) / per_block;
+    if (blocks >= (1ll << 31)) return GNNCCA_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define GNNCCA_POOL(L)                                                                                                                   \
+    hipLaunchKernelGGL((rank_pool_add_kernel<L>), dim3((unsigned)blocks), dim3(256), 0, st, scores, (long long)score_stride, labels,     \
+                       (long long)n_samples, thresholds_dev, (int)n_thresholds, (int)keep_le, reinterpret_cast<rank_u64*>(hist),         \
+                       reinterpret_cast<rank_u64*>(nan_count))
+    if (n_thresholds + 1 <= kPoolLdsBuckets) GNNCCA_POOL(true); else GNNCCA_POOL(false);
+#undef GNNCCA_POOL
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

@@ -182,6 +182,12 @@ class FrameResult:
             check_cameras(b.cam_host)
         return sweep_thresholds(self.batch, self.probs, thresholds, "ge", partition=partition)
 
+    def rank_metrics(self):
+        """How well this batch's probabilities ORDER its edges, without a threshold: ranking.rank_metrics(self.batch, self.probs, 'high') ->
+        float64 [1, G, 8] on the device, columns ranking.RANK_COLUMNS (AUROC, AP, best F per frame)."""
+        from .ranking import rank_metrics
+        return rank_metrics(self.batch, self.probs, "high")
+
     def identities(self, final=True):
         """The per-cluster summaries of this batch (gnn_cca_amd.tracking.cluster_summaries: fused position, mean appearance, size and
         camera count of every identity cluster, as device tensors; no counterpart in the reference).  final=True summarises final()'s

@@ -839,6 +839,72 @@ GNNCCA_API int gnncca_eval_sweep_joint(const int64_t* edge_index, const float* e
 GNNCCA_API int gnncca_eval_rows_accumulate(const double* rows, int32_t n_points, int32_t n_frames, double* sums, int64_t* frames,
                                            gnncca_stream_t stream);
 
+/* ---- Ranking scores without a threshold: AUROC, average precision, best F per frame; the pooled curve (csrc/rank_metrics.cuh) --------
+ * Every entry above judges a score AT a threshold.  gnncca_rank_metrics says how well a score ORDERS a frame's edges: one launch of
+ * n_frames x n_scores workgroups, no workspace (a frame is sorted in LDS), no host synchronisation, no allocation: capturable.
+ * `scores`, `score_strides`: as gnncca_eval_sweep_joint takes them (host arrays of n_scores device pointers and element strides,
+ * 1 <= n_scores <= GNNCCA_RANK_MAX_SCORES); `positive_low`: a host array, 0 = a HIGH score speaks for label 1 (probabilities), 1 = a LOW
+ * one does (distances); max_frame_edges: the batch's largest frame as the caller's host copy of edge_ptr knows it.  rows_out fp64
+ * [n_scores][n_frames][8], columns GNNCCA_RANK_COLUMNS.  The rule for frame g and score k:
+ *   samples    the frame's directed edges e in [edge_ptr[g], edge_ptr[g + 1]) whose label is exactly 1.0f (positive) or 0.0f (negative),
+ *              the two values gnncca_eval_frames counts; an edge with any other label is no sample.  n_pos, n_neg count them (a NaN score
+ *              included).  A capped batch is ranked on its kept edges.
+ *   key        s = the fp32 score, exactly negated when positive_low; -0 is taken as +0; the 32 bits u of s become
+ *              key = u | 0x80000000 for s >= 0 and ~u for s < 0: a larger s has a larger key, +-inf are ordinary values.  A NaN score
+ *              is counted in n_nan, takes no part in the ranking, and makes the frame's four real-valued columns NaN.
+ *   groups     samples with equal keys are ONE tie group; n_distinct is the number of groups.  The groups are visited from the largest
+ *              key (the most positive) to the smallest with running TP, FP = the positives, negatives of the groups visited so far, the
+ *              current one included; p, n = the current group's positives and negatives.
+ *   AUROC      (sum over groups of p (2 neg_ranked_below + n)) / (2 n_pos n_neg), neg_ranked_below = n_neg - FP: the numerator and the
+ *              denominator exact integers, converted to fp64, ONE division.  NaN if n_pos == 0 or n_neg == 0.
+ *   AP         sum over groups with p > 0 of ((double)p / (double)n_pos) * ((double)TP / (double)(TP + FP)): two divisions and one
+ *              multiplication per term, never fused with the additions.  Order of the additions: sort the samples by key descending; a
+ *              group's term stands at the position (from 0) of the group's LAST sample, every other position holds +0; lane q of 256
+ *              adds the positions q, q + 256, q + 512, ... ascending onto +0; within each block of 64 lanes six butterfly steps
+ *              v[q] = v[q] + v[q ^ o], o = 32, 16, 8, 4, 2, 1 (all lanes at once); AP = ((v[0] + v[64]) + v[128]) + v[192].  Nothing in
+ *              it depends on the batch, the block size or the LDS capacity.  NaN if n_pos == 0.
+ *   best_F     the maximum over the n_distinct cuts (a cut predicts 1 for every group visited so far) of compute_P_R_F's F
+ *              (inference.py:53-66): P = TP / (TP + FP), R = TP / (TP + FN) with FN = n_pos - TP, F = 2 * (P * R) / (P + R), 0 when
+ *              P + R == 0 -- `score >= cut` (positive_low: `score <= cut`).  NaN if n_pos == 0.
+ *   best_cut   the score of the FIRST cut in visiting order that reaches best_F: the key mapped back to fp32, negated back when
+ *              positive_low, widened to fp64; a zero is +0.  NaN if n_pos == 0.
+ *   empty      a frame without samples: the four counts 0, the four real-valued columns NaN.
+ * A frame whose edge range lies outside [0, n_edges] or holds more than max_frame_edges rounded up to a power of two gets eight NaNs.
+ * LDS: gnncca_rank_metrics_lds_bytes(max_frame_edges) = 8 bytes per edge of the largest frame rounded up to a power of two (at least
+ * 64): 8 KiB for a Terrace frame of 768 edges, 128 KiB at GNNCCA_RANK_MAX_FRAME_EDGES; 0 for a size out of range.
+ * GNNCCA_ERR_INVALID_ARG before any launch: n_scores out of range, a stride < 1, a positive_low other than 0 / 1, max_frame_edges outside
+ * [0, GNNCCA_RANK_MAX_FRAME_EDGES] or above n_edges, a negative size, a null array, a null pointer where its count is positive.
+ * n_frames == 0 returns GNNCCA_OK and launches nothing.
+ *
+ * gnncca_rank_rows_accumulate folds rows fp64 [n_scores][n_frames][8] into sums fp64 [n_scores][8] and counts int64 [n_scores][8] (DEVICE
+ * memory, zeroed by the caller before the first batch) in one launch: per score and column the frames in ascending g; a NaN is skipped,
+ * every other value is added onto the running sum (a plain fp64 add) and counted.  No atomics, no tree: the order is the contract.
+ *
+ * gnncca_rank_pool_add is the reference's own sweep (main.py:124-319, MODE REID): every raw edge distance of the data set pooled,
+ * `preds = dist <= t` at each threshold, compute_P_R_F on the pooled vector -- no pruning, no clustering -- kept as two histograms, so
+ * that nothing of a batch has to stay.  thresholds_dev: fp64 [n_thresholds] in DEVICE memory, strictly increasing (the caller's to
+ * ensure), 1 <= n_thresholds <= GNNCCA_RANK_POOL_MAX_THRESHOLDS.  hist: int64 [2][n_thresholds + 1], row 0 the negatives (label 0.0f),
+ * row 1 the positives (label 1.0f); nan_count: int64 [2] likewise; both in DEVICE memory, zeroed by the caller before the first call.
+ * Sample e (scores[e * score_stride], labels[e]; any other label is no sample) adds 1 to bucket b(e) of its label's row:
+ *   keep_le = 1   b = the number of thresholds <  (double)score: `score <= thresholds[t]` holds exactly for t >= b;
+ *   keep_le = 0   b = the number of thresholds <= (double)score: `score >= thresholds[t]` holds exactly for t <  b;
+ * compared in fp64 against the widened fp32 score, as everywhere above; +-inf are ordinary values; a NaN score adds 1 to nan_count
+ * instead.  TP[t] is then the sum of row 1 over the buckets <= t (keep_le = 0: > t), FP[t] the same of row 0.  Integer atomics only: any
+ * split of a data set into calls leaves the same state.  One launch, no frame size limit, no host synchronisation: capturable. */
+#define GNNCCA_RANK_MAX_SCORES 4
+#define GNNCCA_RANK_MAX_FRAME_EDGES 16384
+#define GNNCCA_RANK_POOL_MAX_THRESHOLDS 65536
+#define GNNCCA_RANK_COLUMNS "n_pos,n_neg,n_distinct,n_nan,AUROC,AP,best_F,best_cut"
+GNNCCA_API size_t gnncca_rank_metrics_lds_bytes(int32_t max_frame_edges);
+GNNCCA_API int gnncca_rank_metrics(const float* edge_labels, const float* const* scores, const int64_t* score_strides,
+                                   const int32_t* positive_low, int32_t n_scores, int64_t n_edges, const int32_t* edge_ptr_dev,
+                                   int32_t n_frames, int32_t max_frame_edges, double* rows_out, gnncca_stream_t stream);
+GNNCCA_API int gnncca_rank_rows_accumulate(const double* rows, int32_t n_scores, int32_t n_frames, double* sums, int64_t* counts,
+                                           gnncca_stream_t stream);
+GNNCCA_API int gnncca_rank_pool_add(const float* scores, int64_t score_stride, const float* labels, int64_t n_samples,
+                                    const double* thresholds_dev, int32_t n_thresholds, int32_t keep_le, int64_t* hist,
+                                    int64_t* nan_count, gnncca_stream_t stream);
+
 /* ---- Rank-R ReID baseline with k-reciprocal re-ranking (csrc/rerank.cuh) -----------------------------------------------------------
  * The reference's MODE eval_RANK (inference.py:388-511) with RERANK (libs/utils.py:578-644, Zhong et al.): the baseline the GNN has to
  * beat.  A batch's per-frame matrices lie back to back, frame g's n_g x n_g row-major fp32 matrix at element sum_{q<g} n_q^2; `total` is
