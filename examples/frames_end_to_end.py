@@ -6,12 +6,16 @@ does (gnn_cca_amd.evaluation), next to the baseline the GNN has to beat: rank-1 
 (MODE eval_RANK, gnn_cca_amd.rerank), same batch, same scorer.  Needs an MI355X.
 
     python examples/frames_end_to_end.py [frames] [cams] [detections_per_cam] [--top-k K] [--rank-by ground|reid] [--symmetric union|mutual]
+                                         [--radius R] [--radius-unit ground|max_dist]
 
 --top-k K keeps every detection's K nearest cross-camera candidates (build_graph_batch(top_k=K); the graph is then directed and the
 pruning keeps mutual pairs only); the same batch also goes through the one-call form, FramePipeline(model, top_k=K).
 --symmetric union|mutual (with --top-k) closes that list under reversal: an edge is kept if either / both of its endpoints selected the
 other.  The build then waits once for its edge count, and the pipeline takes its step-by-step path.  With --top-k the scores are also
 printed against the dense truth (evaluate_frames(against='dense'): every dropped edge counts as predicted 0).
+--radius R keeps a cross-camera pair only if the two detections are within R on the ground plane (build_graph_batch(radius=R); in the
+units of the positions, or of max_dist with --radius-unit max_dist).  The list is closed under reversal and its size is known on the host,
+so the pipeline keeps its one-call form; the scores are printed against the dense truth as well.  Not together with --top-k.
 """
 import argparse
 import os
@@ -41,11 +45,16 @@ def main():
     ap.add_argument("--rank-by", choices=("ground", "reid"), default="ground", help="what 'nearest' means for --top-k")
     ap.add_argument("--symmetric", choices=("union", "mutual"), default=None,
                     help="close the --top-k list under reversal: keep an edge if either (union) / both (mutual) endpoints selected the other")
+    ap.add_argument("--radius", type=float, default=None, metavar="R", help="keep a cross-camera pair only within R on the ground plane (default: all)")
+    ap.add_argument("--radius-unit", choices=("ground", "max_dist"), default="ground", help="R in the units of the positions, or of each frame's max_dist")
     a = ap.parse_args()
     if a.symmetric and not a.top_k:
         ap.error("--symmetric needs --top-k")
+    if a.radius is not None and a.top_k:
+        ap.error("--radius and --top-k exclude each other")
     frames, cams, per = a.frames, a.cams, a.per
-    cap = dict(top_k=a.top_k, rank_by=a.rank_by, symmetric=a.symmetric)
+    cap = dict(top_k=a.top_k, rank_by=a.rank_by, symmetric=a.symmetric, radius=a.radius, radius_unit=a.radius_unit)
+    pruned_graph = bool(a.top_k) or a.radius is not None
     rng = np.random.default_rng(0)
     n_g = cams * per
     n = frames * n_g
@@ -86,7 +95,8 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / reps
     e = batch.edge_index.shape[1]
-    print(f"{frames} frames x {cams} cameras x {per} detections: N={n} E={e}" + (f" (top_k={a.top_k} by {a.rank_by}" + (f", {a.symmetric}" if a.symmetric else "") + ")" if a.top_k else ""))
+    print(f"{frames} frames x {cams} cameras x {per} detections: N={n} E={e}" + (f" (top_k={a.top_k} by {a.rank_by}" + (f", {a.symmetric}" if a.symmetric else "") + ")" if a.top_k else "")
+          + (f" (radius={a.radius} {a.radius_unit})" if a.radius is not None else ""))
     print(f"graph build + MPN (L=4) + threshold/prune/cluster: {dt * 1e3:.3f} ms per batch "
           f"({e / dt / 1e6:.1f} M edges/s end to end, host planning included)")
     print(f"active edges after pruning: {int(post['pruned'].sum())}, identity clusters: {int(post['n_clusters'].item())}, "
@@ -99,7 +109,7 @@ def main():
     # per-frame metrics against the ground truth the graph build wrote (batch.edge_labels: same person id), then main.py's aggregates
     acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"]))
     print("aggregates over the frames:", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))
-    if a.top_k:   # a capped graph: the same predictions scored as the dense graph would have been, dropped edges predicted 0
+    if pruned_graph:   # a capped or gated graph: the same predictions scored as the dense graph would have been, dropped edges predicted 0
         acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"], against="dense"))
         print("against the dense truth:   ", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))
     # which threshold?  every operating point of the batch in one pass (gnn_cca_amd.calibration), the best one applied
@@ -116,7 +126,7 @@ def main():
         for name, kw in (("rank-1 + re-ranking", dict(rank=1)), ("rank-1, plain distances", dict(rank=1, rerank=False))):
             base = EvalAccumulator().add(rank_baseline(batch, **kw)).result()
             print(f"{name}: " + ", ".join(f"{k} {base[k]:.4g}" for k in ("RI", "MI", "hom", "com", "v")))
-        gnn = acc.result() if not a.top_k else EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"])).result()
+        gnn = acc.result() if not pruned_graph else EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"])).result()
         print("the GNN on the same frames: " + ", ".join(f"{k} {gnn[k]:.4g}" for k in ("RI", "MI", "hom", "com", "v")))
     print("random weights / random embeddings: the cluster structure and the chosen threshold are meaningless, the plumbing is what is shown")
 

@@ -21,6 +21,7 @@ SCORE_MAX_IDS, SCORE_MAX_CAMS, SCORE_MAX_STREAMS, SCORE_MAX_SLOTS = 65536, 64, 1
 SCORE_MIN_CAP, SCORE_HEADER_LEN = 1024, 8
 REENTRY_MAX_WINDOW = 4096            # gnncca_reentry_update: the walking workgroup keeps a frame's candidate tracks in LDS
 SYMMETRIC = {"union": 1, "mutual": 2}   # gnncca_build_edges_topk_sym_count
+RADIUS_UNIT = {"ground": 0, "max_dist": 1}   # GNNCCA_RADIUS_UNIT_*: gnncca_plan_frames_radius, gnncca_build_edges_radius, gnncca_frames_forward_radius
 SWEEP_MAX_THRESHOLDS = 1024          # gnncca_eval_sweep
 JOINT_MAX_SCORES = 4                 # gnncca_eval_sweep_joint
 JOINT_MAX_POINTS = 16384
@@ -129,6 +130,8 @@ _SIGNATURES = {
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gnncca_build_edges_topk": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnncca_build_edges_radius": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnncca_build_edges_topk_sym_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
     "gnncca_build_edges_topk_sym_count": (C.c_int, [C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                                     C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -211,11 +214,15 @@ _SIGNATURES = {
     "gnncca_frames_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "gnncca_frames_forward_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_void_p]),
+    "gnncca_frames_forward_radius": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                               C.c_double, C.c_int32, C.c_void_p]),
     "gnncca_plan_frames_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "gnncca_plan_frames": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_size_t]),
     "gnncca_plan_frames_ex": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]),
+    "gnncca_plan_frames_radius": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_double, C.c_int32, C.c_void_p, C.c_size_t]),
     "gnncca_pad_frame": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "gnncca_read_graph_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),

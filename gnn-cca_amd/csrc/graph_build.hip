@@ -424,6 +424,7 @@ __global__ __launch_bounds__(256) void colnorm_fused_lds_kernel(const ColnormJob
 #include "graph_grads.cuh"
 #include "graph_topk.cuh"
 #include "graph_topk_sym.cuh"
+#include "graph_radius.cuh"
 
 using namespace gnncca;
 
@@ -459,6 +460,11 @@ static bool edge_sizes_invalid(const gnncca_frames* fr, int64_t n_nodes, int64_t
 static bool edge_pointers_null(const gnncca_frames* fr, const void* edge_index_out, const void* edge_attr_out, const void* edge_labels_out) {
     return !fr->xw || !fr->yw || !fr->max_dist || !fr->person_id || !fr->cam || !fr->graph_of || !fr->graph_ptr || !fr->src_order ||
            !fr->edge_ptr || !edge_index_out || !edge_attr_out || !edge_labels_out;
+}
+
+// radius: a number >= 0 or +inf (a NaN fails the comparison); unit: one of GNNCCA_RADIUS_UNIT_*
+static bool radius_invalid(double radius, int32_t unit) {
+    return !(radius >= 0.0) || (unit != GNNCCA_RADIUS_UNIT_GROUND && unit != GNNCCA_RADIUS_UNIT_MAX_DIST);
 }
 
 extern "C" {
@@ -580,6 +586,14 @@ int gnncca_build_edges_topk(const gnncca_frames* fr, const float* reid, int32_t 
                             float* edge_labels_out, gnncca_stream_t stream) {
     return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, true, top_k, rank_by, max_deg, edge_index_out, edge_attr_out,
                                        edge_labels_out, nullptr, 0, stream);
+}
+
+// ---- row N1 with a ground-plane gate (graph_radius.cuh) ----
+int gnncca_build_edges_radius(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                              double radius, int32_t unit, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                              gnncca_stream_t stream) {
+    return gnncca::build_edges_radius_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, radius, unit, edge_index_out, edge_attr_out,
+                                              edge_labels_out, nullptr, 0, stream);
 }
 
 // ---- the capped neighbourhood closed under reversal (graph_topk_sym.cuh) ----
@@ -756,6 +770,29 @@ int gnncca::build_edges_zeroing(const gnncca_frames* fr, const float* reid, int3
     return GNNCCA_OK;
 }
 
+// gnncca_build_edges_radius, and the build of gnncca_frames_forward_radius (zero_ptr: the post stage's counters).  The gate's own refusals
+// come first, as the capped entry's do: before the early return for an empty batch.
+int gnncca::build_edges_radius_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                                       double radius, int32_t unit, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                                       int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream) {
+    if (edge_sizes_invalid(fr, n_nodes, n_edges, reid_dim, mode) || radius_invalid(radius, unit)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (edge_pointers_null(fr, edge_index_out, edge_attr_out, edge_labels_out)) return GNNCCA_ERR_INVALID_ARG;
+    if (mode != GNNCCA_EDGE_ATTR_ONLY_DIST && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
+    // few sources: the dense launch's split of a source's candidate chunks over up to 16 waves
+    unsigned slices = 1;
+    while (slices < 16 && (long long)n_nodes * slices < 4096) slices *= 2;
+    const dim3 grid((unsigned)((n_nodes + 3) / 4), slices), block(256);
+    with_mode(mode, [&](auto M) {
+        hipLaunchKernelGGL((build_edges_radius_kernel<M()>), grid, block, 0, static_cast<hipStream_t>(stream), *fr, reid, (int)reid_dim, (int)n_nodes,
+                           (long long)n_edges, radius, (int)unit, reinterpret_cast<long long*>(edge_index_out), edge_attr_out, edge_labels_out,
+                           zero_ptr, (int)zero_n);
+    });
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
 extern "C" {
 
 // ---- host side of row N1: the edge enumeration of a batch of frames (inference.py:207-212), written straight into the staging image ----
@@ -846,6 +883,55 @@ int64_t gnncca_plan_frames_ex(const double* xw, const double* yw, const int64_t*
     img.edge_ptr[n] = (int32_t)e;
     for (int64_t q = 0; q <= g; ++q) img.edge_ptr_g[q] = img.edge_ptr[img.graph_ptr[q]];   // edges are emitted frame by frame
     if (max_deg_out) *max_deg_out = (int32_t)max_deg;
+    return (int64_t)e;
+}
+
+// The gate of graph_radius.cuh on the host: the identical IEEE sequence (two products and one sum, each rounded once; contraction off).
+static inline bool within_radius_host(double xi, double yi, double xj, double yj, double t2) {
+#pragma clang fp contract(off)
+    const double dx = xi - xj, dy = yi - yj;
+    const double a = dx * dx, b = dy * dy;
+    const double s = a + b;
+    return s <= t2;
+}
+static inline double radius_gate_t2_host(double radius, int32_t unit, double md) {
+#pragma clang fp contract(off)
+    const double t = unit == GNNCCA_RADIUS_UNIT_MAX_DIST ? radius * md : radius;
+    return t * t;
+}
+
+// gnncca_plan_frames' image with edge_ptr / edge_ptr_g counting the candidates within the radius.  Every unordered pair of a frame is
+// evaluated once (s(i, j) == s(j, i) bit for bit) and counted for both of its sources.
+int64_t gnncca_plan_frames_radius(const double* xw, const double* yw, const int64_t* ids, const int64_t* id_cam, int64_t n,
+                                  const int64_t* graph_sizes, const double* max_dist, int64_t g, double radius, int32_t unit, void* staging,
+                                  size_t staging_bytes) {
+    if (radius_invalid(radius, unit)) return -(int64_t)GNNCCA_ERR_INVALID_ARG;
+    const int64_t dense = gnncca_plan_frames_ex(xw, yw, ids, id_cam, n, graph_sizes, max_dist, g, 0, staging, staging_bytes, nullptr);
+    if (dense < 0) return dense;
+    const StagingImage img = staging_image(staging, n, g);
+    std::vector<int32_t> kept((size_t)n, 0);
+    for (int64_t q = 0; q < g; ++q) {
+        const int32_t gs = img.graph_ptr[q], ge = img.graph_ptr[q + 1];
+        const double t2 = radius_gate_t2_host(radius, unit, max_dist[q]);
+        for (int32_t a = gs; a < ge; ++a) {
+            const double xa = xw[a], ya = yw[a];
+            const int32_t ca = img.cam[a];
+            int32_t mine = 0;
+            for (int32_t b = a + 1; b < ge; ++b) {
+                const int32_t hit = (img.cam[b] != ca) & (int32_t)within_radius_host(xa, ya, xw[b], yw[b], t2);
+                mine += hit;
+                kept[(size_t)b] += hit;
+            }
+            kept[(size_t)a] += mine;
+        }
+    }
+    long long e = 0;
+    for (int64_t pos = 0; pos < n; ++pos) {
+        img.edge_ptr[pos] = (int32_t)e;
+        e += kept[(size_t)img.src_order[pos]];   // (<= the dense count, which the plan above bounded by 2^31 - 64)
+    }
+    img.edge_ptr[n] = (int32_t)e;
+    for (int64_t q = 0; q <= g; ++q) img.edge_ptr_g[q] = img.edge_ptr[img.graph_ptr[q]];
     return (int64_t)e;
 }
 

@@ -161,6 +161,11 @@ int build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid
                         int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                         int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream);
 
+// gnncca_build_edges_radius with the same zeroing (graph_build.hip, graph_radius.cuh; gnncca_frames_forward_radius hands it the counters)
+int build_edges_radius_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                               double radius, int32_t unit, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                               int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream);
+
 Family classify(const gnncca_mpn_dims* d);
 bool blob_header(const gnncca_mpn_dims* d, BlobHeader* out);  // false if unsupported
 bool dims_valid(const gnncca_mpn_dims* d);

@@ -277,10 +277,12 @@ int gnncca_post_exclusive_frames(const int64_t* edge_index, const float* scores,
 }
 
 // The one-call chain of gnncca_frames_forward (top_k == 0: the complete graph) and gnncca_frames_forward_topk (top_k >= 1: the staging image
-// and n_edges are gnncca_plan_frames_ex(top_k)'s, the build is the capped kernel).  Everything after the build sees an ordinary edge list.
+// and n_edges are gnncca_plan_frames_ex(top_k)'s, the build is the capped kernel) and gnncca_frames_forward_radius (gate != nullptr: the image
+// and n_edges are gnncca_plan_frames_radius', the build is the gated kernel).  Everything after the build sees an ordinary edge list.
+struct RadiusGate { double radius; int32_t unit; };
 static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
                                size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
-                               int32_t top_k, int32_t rank_by, int32_t max_deg, gnncca_stream_t stream) {
+                               int32_t top_k, int32_t rank_by, int32_t max_deg, const RadiusGate* gate, gnncca_stream_t stream) {
     if (!d || !io || !io->staged_dev) return GNNCCA_ERR_INVALID_ARG;
     const int64_t n = io->n_nodes, g = io->n_frames, e = io->n_edges;
     if (n < 1 || g < 1 || e < 0) return GNNCCA_ERR_INVALID_ARG;
@@ -290,7 +292,7 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
         return GNNCCA_ERR_INVALID_ARG;
     if (io->counters_len < 3 * n + 1 + g) return GNNCCA_ERR_INVALID_ARG;   // flow_out | flow_in | n_clusters | sizes | triggers (ABI 2: stated, not assumed)
     // (what gnncca_build_edges_topk would refuse, refused here: before the normalisation's launch)
-    if (top_k > 0 && (io->mode < GNNCCA_EDGE_ATTR_FULL || io->mode > GNNCCA_EDGE_ATTR_ONLY_DIST)) return GNNCCA_ERR_INVALID_ARG;
+    if ((top_k > 0 || gate) && (io->mode < GNNCCA_EDGE_ATTR_FULL || io->mode > GNNCCA_EDGE_ATTR_ONLY_DIST)) return GNNCCA_ERR_INVALID_ARG;
     if (top_k > 0 && rank_by == GNNCCA_RANK_BY_REID && io->reid_dim <= 0) return GNNCCA_ERR_INVALID_ARG;   // the ranking reads the table in every mode
     const StagingImage img = staging_image(io->staged_dev, n, g);
     const gnncca_frames fr = img.frames();
@@ -306,8 +308,12 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
     const bool zero_here = e > 0 && mpn_workspace != nullptr;
     int32_t* zero_ptr = zero_here ? io->counters : nullptr;
     const int64_t zero_n = zero_here ? 3 * n + 1 + g : 0;
-    st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, top_k > 0, top_k, rank_by, max_deg, io->edge_index, io->edge_attr,
-                             io->edge_labels, zero_ptr, zero_n, stream);
+    if (gate)
+        st = build_edges_radius_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, gate->radius, gate->unit, io->edge_index, io->edge_attr,
+                                        io->edge_labels, zero_ptr, zero_n, stream);
+    else
+        st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, top_k > 0, top_k, rank_by, max_deg, io->edge_index, io->edge_attr,
+                                 io->edge_labels, zero_ptr, zero_n, stream);
     if (st != GNNCCA_OK) return st;
     const int n_out = gnncca_num_outputs(d);
     if (n_out < 1) return GNNCCA_ERR_UNSUPPORTED;
@@ -347,7 +353,7 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
 int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
                           size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
                           gnncca_stream_t stream) {
-    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, 0, 0, 0, stream);
+    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, 0, 0, 0, nullptr, stream);
 }
 
 int gnncca_frames_forward_topk(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
@@ -356,7 +362,16 @@ int gnncca_frames_forward_topk(const gnncca_mpn_dims* d, const void* packed_dev,
     if (top_k < 1 || max_deg < 0 || (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID)) return GNNCCA_ERR_INVALID_ARG;
     if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
     return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, top_k,
-                               rank_by, max_deg, stream);
+                               rank_by, max_deg, nullptr, stream);
+}
+
+int gnncca_frames_forward_radius(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
+                                 size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
+                                 double radius, int32_t unit, gnncca_stream_t stream) {
+    if (!(radius >= 0.0) || (unit != GNNCCA_RADIUS_UNIT_GROUND && unit != GNNCCA_RADIUS_UNIT_MAX_DIST)) return GNNCCA_ERR_INVALID_ARG;
+    const RadiusGate gate{radius, unit};
+    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, 0, 0, 0,
+                               &gate, stream);
 }
 
 }  // extern "C"

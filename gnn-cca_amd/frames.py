@@ -134,6 +134,23 @@ def check_cap(top_k, rank_by, symmetric):
     return top_k, nat.RANK_BY[rank_by], nat.SYMMETRIC[symmetric] if symmetric else 0
 
 
+def check_radius(radius, radius_unit, top_k=None, symmetric=None):
+    """The arguments of a radius-gated graph (build_graph_batch has their meaning) -> (radius as a float or None, unit code), or ValueError:
+    radius is None, a finite number >= 0 or inf (no bool, no NaN); the unit 'ground' or 'max_dist'; no top_k / symmetric next to a radius."""
+    if not isinstance(radius_unit, str) or radius_unit not in nat.RADIUS_UNIT:
+        raise ValueError(f"radius_unit must be 'ground' or 'max_dist', not {radius_unit!r}")
+    if radius is None:
+        return None, nat.RADIUS_UNIT[radius_unit]
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
+        raise ValueError(f"radius must be None, a number >= 0 or inf, not {radius!r}")
+    radius = float(radius)
+    if not radius >= 0.0:   # (a NaN fails the comparison too)
+        raise ValueError(f"radius must be None, a number >= 0 or inf, not {radius!r}")
+    if top_k is not None or symmetric is not None:
+        raise ValueError("radius together with top_k / symmetric is not supported: a radius-gated k-nearest list has no definition here yet")
+    return radius, nat.RADIUS_UNIT[radius_unit]
+
+
 class StagedFrames:
     """The host side of one batch of frames.  The constructor converts the six host arrays (`arrays`: xw, yw, ids, id_cam, graph_sizes,
     max_dist as contiguous float64 / int64) and checks their lengths; nothing else is touched, so the caller can still refuse the batch.
@@ -149,8 +166,9 @@ class StagedFrames:
             raise ValueError(self.LENGTHS_DISAGREE)
         self.arrays, self.n, self.g, self.layout = (xw, yw, ids64, cam64, sizes, md), n, g, FrameLayout(n, g)
 
-    def plan(self, dev, top_k=None):
-        """gnncca_plan_frames (top_k=None) or gnncca_plan_frames_ex into the ring's next slot; waits only if that slot's upload is still queued."""
+    def plan(self, dev, top_k=None, radius=None, unit=0):
+        """gnncca_plan_frames (top_k=None, radius=None), gnncca_plan_frames_ex or gnncca_plan_frames_radius into the ring's next slot; waits only
+        if that slot's upload is still queued."""
         lib = nat.lib()
         nbytes = lib.gnncca_plan_frames_bytes(self.n, self.g)
         assert nbytes == self.layout.nbytes   # the library's StagingImage and FrameLayout agree
@@ -159,7 +177,9 @@ class StagedFrames:
         xw, yw, ids64, cam64, sizes, md = self.arrays
         args = (xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, self.n, sizes.ctypes.data, md.ctypes.data, self.g)
         max_deg = C.c_int32(0)
-        if top_k is None:
+        if radius is not None:
+            e = lib.gnncca_plan_frames_radius(*args, radius, unit, pinned.data_ptr(), nbytes)
+        elif top_k is None:
             e = lib.gnncca_plan_frames(*args, pinned.data_ptr(), nbytes)
         else:
             e = lib.gnncca_plan_frames_ex(*args, top_k, pinned.data_ptr(), nbytes, C.byref(max_deg))

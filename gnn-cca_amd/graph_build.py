@@ -14,7 +14,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native as nat
-from .frames import StagedFrames, _current_stream, _f32c, _on, _raw_stream, attach, check_cap  # noqa: F401  (the lean device helpers live there)
+from .frames import StagedFrames, _current_stream, _f32c, _on, _raw_stream, attach, check_cap, check_radius  # noqa: F401  (the lean device helpers live there)
 from .sharding import GraphBatch
 
 MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST = 0, 1, 2
@@ -153,13 +153,20 @@ def normalize_columns(x, other=None):
 class _EdgeJob:
     """What the edge kernels of one batch need besides the reid table: the staged frame image and its layout; for a capped build
     (top_k is not None) also the cap, the ranking key and the batch's largest uncapped degree; for a symmetric one (sym != 0) the host
-    array of frame sizes too -- and `e` / `edge_ptr_g` are what its count read back, set by _edges_launch."""
-    __slots__ = ("staged", "layout", "n", "g", "e", "mode", "top_k", "rank", "max_deg", "sym", "sizes", "edge_ptr_g")
+    array of frame sizes too -- and `e` / `edge_ptr_g` are what its count read back, set by _edges_launch; for a radius-gated build
+    (radius is not None) the radius and its unit code.  `pruned`: the edge list is a proper subsequence of the dense one, which the
+    backward then looks its edges up in."""
+    __slots__ = ("staged", "layout", "n", "g", "e", "mode", "top_k", "rank", "max_deg", "sym", "sizes", "edge_ptr_g", "radius", "unit")
 
-    def __init__(self, staged, layout, e, mode, top_k=None, rank=0, max_deg=0, sym=0, sizes=None):
+    def __init__(self, staged, layout, e, mode, top_k=None, rank=0, max_deg=0, sym=0, sizes=None, radius=None, unit=0):
         self.staged, self.layout, self.n, self.g, self.e, self.mode = staged, layout, layout.n, layout.g, e, mode
         self.top_k, self.rank, self.max_deg = top_k, rank, max_deg
         self.sym, self.sizes, self.edge_ptr_g = sym, sizes, None
+        self.radius, self.unit = radius, unit
+
+    @property
+    def pruned(self):
+        return self.top_k is not None or self.radius is not None
 
 
 _readback = {}   # device index -> (pinned int32 buffer, event) of the symmetric build's one read-back
@@ -204,8 +211,8 @@ def _sym_edges_launch(job, reid_embeds):
 
 
 def _edges_launch(job, reid_embeds):
-    """gnncca_build_edges (gnncca_build_edges_topk for a capped job, the two ..._topk_sym_* calls for a symmetric one) on the current
-    stream: (edge_index, edge_attr, edge_labels), new tensors."""
+    """gnncca_build_edges (gnncca_build_edges_topk for a capped job, the two ..._topk_sym_* calls for a symmetric one,
+    gnncca_build_edges_radius for a gated one) on the current stream: (edge_index, edge_attr, edge_labels), new tensors."""
     if job.sym:
         return _sym_edges_launch(job, reid_embeds)
     dev, n, e = reid_embeds.device, job.n, job.e
@@ -214,7 +221,13 @@ def _edges_launch(job, reid_embeds):
     edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
     edge_attr = torch.empty((e, n_attr), dtype=torch.float32, device=dev)
     edge_labels = torch.empty(e, dtype=torch.float32, device=dev)
-    if job.top_k is not None:
+    if job.radius is not None:
+        # (called with E == 0 too, as the capped entry is: it checks its arguments before it looks at the sizes, and launches nothing then)
+        st = nat.lib().gnncca_build_edges_radius(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode, job.radius, job.unit,
+                                                 edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
+        if st:
+            nat.check(st, "gnncca_build_edges_radius")
+    elif job.top_k is not None:
         # (called with E == 0 too: the entry point checks its arguments, the degree limit among them, before it looks at the sizes)
         st = nat.lib().gnncca_build_edges_topk(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode, job.top_k, job.rank,
                                                job.max_deg, edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
@@ -234,7 +247,8 @@ class _GraphBuildFunction(torch.autograd.Function):
     the raw embeddings through them).  forward(node_raw | None, reid, job): with node_raw the embeddings are normalised here and the
     outputs are (x, edge_attr, reid_normalised, edge_index, edge_labels); with None (normalize=False) `reid` is used as given and the
     outputs are (edge_attr, edge_index, edge_labels).  backward: gnncca_build_edges_backward (gnncca_build_edges_topk_backward for a
-    capped build: the selection is piecewise constant, the gradient flows through the kept edges) on grad_edge_attr, plus whatever arrives
+    capped or radius-gated build: the selection is piecewise constant, the gradient flows through the kept edges; that entry serves any
+    subsequence of the dense list whose runs ascend in the destination) on grad_edge_attr, plus whatever arrives
     on the normalised reid table directly, then gnncca_normalize_columns_backward per matrix; an input that does not require grad
     costs no launch and no allocation.  The ground-plane attributes, edge_index and edge_labels carry no gradient.  Differentiable
     once (double backward raises torch's error)."""
@@ -249,7 +263,7 @@ class _GraphBuildFunction(torch.autograd.Function):
             reid_n, x = reid, None
         edge_index, edge_attr, edge_labels = _edges_launch(job, reid_n)
         ctx.mark_non_differentiable(edge_index, edge_labels)
-        pruned = (edge_index,) if job.top_k is not None else ()   # the capped backward looks its edges up in the forward's edge list
+        pruned = (edge_index,) if job.pruned else ()   # the capped / gated backward looks its edges up in the forward's edge list
         if ctx.normalized:
             ctx.save_for_backward(node_raw, reid, reid_n, edge_attr, *pruned)
             return x, edge_attr, reid_n, edge_index, edge_labels
@@ -261,7 +275,7 @@ class _GraphBuildFunction(torch.autograd.Function):
     def backward(ctx, *grads):
         job = ctx.job
         saved = ctx.saved_tensors
-        edge_index = saved[-1] if job.top_k is not None else None
+        edge_index = saved[-1] if job.pruned else None
         if ctx.normalized:
             node_raw, reid_raw, reid_n, edge_attr = saved[:4]
             g_x, g_ea, g_reid = grads[0], grads[1], grads[2]
@@ -306,7 +320,7 @@ class _GraphBuildFunction(torch.autograd.Function):
 
 
 def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds, only_appearance=False,
-                      only_dist=False, normalize=True, top_k=None, rank_by="ground", symmetric=None):
+                      only_dist=False, normalize=True, top_k=None, rank_by="ground", symmetric=None, radius=None, radius_unit="ground"):
     """One call per batch of frames.  Host inputs (numpy, one entry per detection, frames concatenated): xw, yw, ids,
     id_cam; graph_sizes / max_dist per frame.  Device inputs: node_embeds [N, D], reid_embeds [N, R].
     Returns a GraphBatch (x, edge_index, edge_attr) with .edge_labels and .y, laid out exactly like the reference's
@@ -339,8 +353,24 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
     symmetric without top_k, or an unknown value, is a ValueError raised before the GPU is touched.
     E now depends on the data, so a symmetric build SYNCHRONISES ONCE: one small pinned device-to-host copy carries the G + 1 per-frame
     edge offsets (the last one is E), queued behind the count launches and waited on through an event; there is no other host wait.
-    Under stream capture it raises RuntimeError before anything is launched.  The directed build (symmetric=None) still never waits."""
+    Under stream capture it raises RuntimeError before anything is launched.  The directed build (symmetric=None) still never waits.
+
+    radius=None (the default) is the code above, down to the native call.  radius=r keeps the dense edge (i, j) of frame g iff the two
+    detections are within r on the ground plane (no counterpart in the reference's graph build).  The definition (include/gnncca_mpn.h):
+    s = dx*dx + dy*dy with dx = xw[i] - xw[j], dy = yw[i] - yw[j] -- two products and one sum, each rounded once in float64, no FMA;
+    t_g = r for radius_unit='ground' (the units of xw / yw, before the division by max_dist), t_g = r * max_dist[g] (one rounded product)
+    for radius_unit='max_dist' (mixed-data-set batches; a gate in the units of edge_attr[:, 0]); t2_g = t_g * t_g; kept iff s <= t2_g.
+    The test is on the squared distance: s(i, j) == s(j, i) bit for bit, so the list is CLOSED UNDER REVERSAL by construction, and the
+    host plan (gnncca_plan_frames_radius) evaluates the identical IEEE sequence, so E is known before any launch: no wait, no closure
+    pass, capturable.  A NaN compares false (a pair with a NaN position is dropped); radius=inf keeps every pair without a NaN and is, on
+    NaN-free positions, the dense build bit for bit (edge_index, edge_attr, edge_labels, x, y, edge_ptr, node_ptr and the device copies).
+    The result is a subsequence of the dense list in dense order, a kept edge carries the dense build's bits, the reid rows are read for
+    the kept candidates only, and a source, a frame or the whole batch may end with no edge (E = 0 is legal).  Differentiable like the
+    capped build.  radius must be a finite number >= 0 or inf; a bool, NaN, negative or non-number, an unknown radius_unit, and radius
+    together with top_k or symmetric (a gated k-nearest list is not defined here yet) are ValueErrors raised before the GPU is touched.
+    The host plan evaluates every unordered pair of a frame once: O(sum n_g^2 / 2) host work per batch."""
     top_k, rank, sym = check_cap(top_k, rank_by, symmetric)
+    radius, unit = check_radius(radius, radius_unit, top_k, symmetric)
     if not (node_embeds.is_cuda and reid_embeds.is_cuda):
         raise RuntimeError("gnn_cca_amd.graph_build runs on MI355X only (no CPU fallback)")
     dev = reid_embeds.device
@@ -349,12 +379,12 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
         raise RuntimeError("embeddings and detections disagree on the number of nodes")
     if symmetric is not None and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("build_graph_batch(symmetric=...) waits for its edge count and cannot be captured into a graph")
-    frames.plan(dev, top_k)
+    frames.plan(dev, top_k, radius, unit)
     mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
     with _on(dev):
         staged = torch.empty(frames.layout.nbytes, dtype=torch.uint8, device=dev)
         frames.upload(staged)
-        job = _EdgeJob(staged, frames.layout, frames.e, mode, top_k, rank, frames.max_deg, sym, frames.arrays[4])
+        job = _EdgeJob(staged, frames.layout, frames.e, mode, top_k, rank, frames.max_deg, sym, frames.arrays[4], radius, unit)
         if _wants_grad(node_embeds, reid_embeds):
             # the differentiable build: x, edge_attr and reid_embeds are outputs of ONE autograd node (see _GraphBuildFunction)
             reid_embeds = _f32c(reid_embeds)

@@ -39,6 +39,15 @@ dense graph with every dropped edge predicted 0.  top_k=None (the default) is th
 no counterpart in the reference either): every kept edge then has its reverse.  E depends on the data, so such a pipeline takes the
 step-by-step path below and waits once per batch for its edge count; the one-call entry is not extended.
 
+`FramePipeline(model, radius=r, radius_unit='ground' | 'max_dist')` runs the chain on a RADIUS-GATED graph: a cross-camera pair is an edge iff
+the two detections are within r on the ground plane (build_graph_batch(radius=r) has the definition; no counterpart in the reference's graph
+build).  The gate is exactly symmetric, so the list is closed under reversal and the pruning sees every kept edge's reverse; E is counted by
+the host plan (`gnncca_plan_frames_radius`), so the pipeline takes the one-call path (`gnncca_frames_forward_radius`) under the conditions the
+capped one does, never waits and can be captured -- bit for bit what build_graph_batch(radius=r) -> model -> threshold -> prune_and_cluster
+give (tests/test_gpu_pipeline_radius.py).  A batch the gate leaves without any edge returns empty per-edge outputs and singleton clusters
+through the step-by-step path.  `evaluate()` scores the kept edges, `evaluate(against='dense')` the dense graph with every dropped edge
+predicted 0.  radius together with top_k / symmetric is a ValueError.
+
 `FramePipeline(model, threshold=th)` decides at sigmoid(logit) >= th instead of the reference's 0.5; `r.sweep(thresholds)` scores every
 candidate th of a batch in one pass (gnn_cca_amd.calibration).  Any th other than 0.5 takes the step-by-step path too.
 
@@ -50,7 +59,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .frames import StagedFrames, _on, _raw_stream, attach, check_cap
+from .frames import StagedFrames, _on, _raw_stream, attach, check_cap, check_radius
 from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, build_graph_batch
 from .postprocess import MAX_FRAME_NODES as EXCLUSIVE_MAX_FRAME_NODES
 from .postprocess import check_cameras, check_threshold, exclusive_clusters, finalize, prune_and_cluster, threshold
@@ -242,7 +251,7 @@ class _Finished:
 
 class FramePipeline:
     def __init__(self, model, only_appearance=False, only_dist=False, normalize=True, rounding=True, pruning=True, splitting=True, top_k=None,
-                 rank_by="ground", symmetric=None, threshold=0.5):
+                 rank_by="ground", symmetric=None, threshold=0.5, radius=None, radius_unit="ground"):
         self.model = model
         # the decision threshold on the edge probabilities: 0.5 is the reference's (inference.py:286-291) and every path below as it
         # always was; any other value in (0, 1) -- one chosen with r.sweep(...) -- takes the step-by-step path
@@ -252,6 +261,9 @@ class FramePipeline:
         # the cap: build_graph_batch's arguments and its refusals, here before any batch (or the GPU) is touched
         top_k = check_cap(top_k, rank_by, symmetric)[0]
         self.top_k, self.rank_by, self.symmetric = top_k, rank_by, symmetric
+        # the radius gate: build_graph_batch's arguments and its refusals (radius with top_k / symmetric among them), here as well
+        self.radius, self._unit = check_radius(radius, radius_unit, top_k, symmetric)
+        self.radius_unit = radius_unit
         self.switches = (bool(rounding), bool(pruning), bool(splitting))
         self.mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
         self.normalize = bool(normalize)
@@ -326,7 +338,7 @@ class FramePipeline:
     def _slow(self, xw, yw, ids, id_cam, sizes, max_dist, node, reid):
         b = build_graph_batch(xw, yw, ids, id_cam, sizes, max_dist, node, reid, only_appearance=self.mode == MODE_ONLY_APPEARANCE,
                               only_dist=self.mode == MODE_ONLY_DIST, normalize=self.normalize, top_k=self.top_k, rank_by=self.rank_by,
-                              symmetric=self.symmetric)
+                              symmetric=self.symmetric, radius=self.radius, radius_unit=self.radius_unit)
         with torch.no_grad():
             out = self.model(b)
         r = FrameResult()
@@ -358,7 +370,7 @@ class FramePipeline:
                                f"{tuple(reid_embeds.shape)} {reid_embeds.dtype}")
         node_embeds = node_embeds if node_embeds.is_contiguous() else node_embeds.contiguous()
         reid_embeds = reid_embeds if reid_embeds.is_contiguous() else reid_embeds.contiguous()
-        frames.plan(dev, top_k)
+        frames.plan(dev, top_k, self.radius, self._unit)
         e = frames.e
         if e == 0:   # no cross-camera pair in the whole batch: nothing to launch on the path (the step-by-step functions return the empty containers)
             return self._slow(*frames.arrays, node_embeds, reid_embeds)
@@ -418,14 +430,20 @@ class FramePipeline:
             io.logits, io.probs = fp + 4 * o_log, fp + 4 * o_prob
             io.edge_index, io.predictions, io.pruned = ip + 8 * o_ei, preds.data_ptr(), ip + 8 * o_prun
             io.counters, io.labels, io.counters_len = cp, cp + 4 * o_labels, o_labels
-            if top_k is None:
+            if self.radius is not None:
+                entry = "gnncca_frames_forward_radius"
+                st = lib.gnncca_frames_forward_radius(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(),
+                                                      post_ws.numel(), m._options(), self.radius, self._unit, _raw_stream(dev))
+            elif top_k is None:
+                entry = "gnncca_frames_forward"
                 st = lib.gnncca_frames_forward(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(), post_ws.numel(),
                                                m._options(), _raw_stream(dev))
             else:
+                entry = "gnncca_frames_forward_topk"
                 st = lib.gnncca_frames_forward_topk(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(),
                                                     post_ws.numel(), m._options(), top_k, nat.RANK_BY[self.rank_by], frames.max_deg, _raw_stream(dev))
         if st:
-            nat.check(st, "gnncca_frames_forward" if top_k is None else "gnncca_frames_forward_topk")
+            nat.check(st, entry)
         # views (the reference's containers): x, edge_index, edge_attr, logits as [E, 1] per classified step
         x = f32[o_node:o_node + n * d_in].view(n, d_in) if self.normalize else node_embeds
         reid_n = f32[o_reid:o_reid + n * r_dim].view(n, r_dim) if self.normalize else reid_embeds

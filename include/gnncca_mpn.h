@@ -296,6 +296,42 @@ GNNCCA_API int gnncca_build_edges_topk(const gnncca_frames* frames, const float*
                                        int64_t n_edges, int32_t mode, int32_t top_k, int32_t rank_by, int32_t max_deg,
                                        int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, gnncca_stream_t stream);
 
+/* ---- row N1 with a ground-plane gate: cross-camera candidates within a radius -----------------------------------------------------
+ * What is kept identical to the reference (inference.py:207-266): the enumeration and the attributes / label of every kept edge -- the
+ * bits gnncca_build_edges writes for that edge.  THE GATE HAS NO COUNTERPART IN THE REFERENCE'S GRAPH BUILD, which only builds the
+ * complete cross-camera graph.
+ *
+ * Definition.  For source i and a cross-camera candidate j of its own frame g:
+ *   s = dx*dx + dy*dy with dx = xw[i] - xw[j], dy = yw[i] - yw[j]: two products and one sum, each rounded once in fp64, no FMA
+ *     contraction.
+ *   t_g = radius for GNNCCA_RADIUS_UNIT_GROUND (the units of xw / yw, before the division by max_dist).
+ *   t_g = radius * max_dist[g] (one rounded product) for GNNCCA_RADIUS_UNIT_MAX_DIST (mixed-data-set batches; a gate stated in the units
+ *     of edge_attr[:, 0]).
+ *   t2_g = t_g * t_g (one rounded product).  The edge is kept iff s <= t2_g.
+ * The test is on the squared distance on purpose: it needs no square root on the host, s(i, j) == s(j, i) bit for bit, and the host
+ * and the device evaluate the identical IEEE sequence.  A NaN anywhere compares false, so a pair involving a NaN position is dropped;
+ * radius = inf keeps every pair without a NaN.  radius is a finite number >= 0 or inf; anything else (NaN, negative, an unknown unit) is
+ * GNNCCA_ERR_INVALID_ARG before anything is written or launched.  The kept edges stay in the dense order: the result is a subsequence of
+ * gnncca_build_edges' edge list, a kept edge carries the dense build's bits (index, attributes, label), it is closed under reversal by
+ * construction, and for radius = inf on NaN-free positions it is the dense build bit for bit.  A source, a frame or a whole batch may end
+ * with no edge: E == 0 is legal.
+ *
+ * gnncca_plan_frames_radius: gnncca_plan_frames with the gate -- the same staging image (same fields, same byte count), edge_ptr /
+ * edge_ptr_g counting the kept candidates per source; returns E (radius = inf, NaN-free positions: gnncca_plan_frames' image byte for
+ * byte).  Every unordered pair of a frame is evaluated once: O(sum_g n_g^2 / 2) host work.  A batch whose DENSE edge count reaches 2^31
+ * is refused (UNSUPPORTED) whatever the radius would keep.
+ *
+ * gnncca_build_edges_radius: `frames` is the uploaded image of gnncca_plan_frames_radius for the same radius / unit, n_edges its return
+ * value.  One launch, no workspace, no LDS, no atomics, no synchronisation, capturable.  The reid rows are read for the kept candidates
+ * only.  A source whose kept count on the device disagrees with the plan's run is left unwritten (never written beyond its run). */
+enum { GNNCCA_RADIUS_UNIT_GROUND = 0, GNNCCA_RADIUS_UNIT_MAX_DIST = 1 };
+GNNCCA_API int64_t gnncca_plan_frames_radius(const double* xw, const double* yw, const int64_t* ids, const int64_t* id_cam, int64_t n_nodes,
+                                             const int64_t* graph_sizes, const double* max_dist, int64_t n_frames, double radius,
+                                             int32_t unit, void* staging, size_t staging_bytes);
+GNNCCA_API int gnncca_build_edges_radius(const gnncca_frames* frames, const float* reid, int32_t reid_dim, int64_t n_nodes,
+                                         int64_t n_edges, int32_t mode, double radius, int32_t unit, int64_t* edge_index_out,
+                                         float* edge_attr_out, float* edge_labels_out, gnncca_stream_t stream);
+
 /* ---- the capped neighbourhood, closed under reversal ('union' / 'mutual') ------------------------------------------------------
  * With D the directed edge set of gnncca_build_edges_topk for the same top_k / rank_by (same keys, ties to the smaller destination id):
  *   GNNCCA_SYMMETRIC_UNION   keeps the dense edge (i, j) iff (i, j) in D or  (j, i) in D
@@ -569,6 +605,15 @@ GNNCCA_API int gnncca_frames_forward_topk(const gnncca_mpn_dims* dims, const voi
                                           void* mpn_workspace, size_t mpn_workspace_bytes, void* post_workspace,
                                           size_t post_workspace_bytes, uint32_t options, int32_t top_k, int32_t rank_by, int32_t max_deg,
                                           gnncca_stream_t stream);
+/* gnncca_frames_forward on a radius-gated graph (no counterpart in the reference): the same chain and the same gnncca_frames_io, with
+ * `staged_dev` the uploaded image of gnncca_plan_frames_radius(radius, unit), `n_edges` its return value and the build
+ * gnncca_build_edges_radius' kernel (which also zeroes the counters).  The gated list is closed under reversal, so the pruning sees every
+ * kept edge's reverse.  Refused before any launch: a radius that is not a number >= 0 or inf, an unknown unit (GNNCCA_ERR_INVALID_ARG);
+ * whatever gnncca_frames_forward refuses. */
+GNNCCA_API int gnncca_frames_forward_radius(const gnncca_mpn_dims* dims, const void* packed_dev, const gnncca_frames_io* io,
+                                            void* mpn_workspace, size_t mpn_workspace_bytes, void* post_workspace,
+                                            size_t post_workspace_bytes, uint32_t options, double radius, int32_t unit,
+                                            gnncca_stream_t stream);
 
 /* ---- backward pass (training through the HIP kernels, train.py:454-494) -----------------
  * Supported (GNNCCA_OK from gnncca_backward_supported): the MFMA family (both reattach flags, all three
