@@ -14,6 +14,11 @@
 // it), a ballot prefix, so every store of edge_index / edge_attr / labels is a contiguous wave store in the
 // reference's edge order.  Traffic: the reid table (N x R x 4 B) is re-read once per source from L2 -- it is 256 KB
 // for a 256-detection frame -- and 8+8+16+4 B are written per edge; the kernel is L2/latency bound, not HBM bound.
+//
+// The selections that keep a part of these edges -- graph_topk.cuh, graph_topk_sym.cuh, graph_radius.cuh, included below -- decide WHICH
+// candidates a source keeps in kernels of their own; what is computed and stored for a kept candidate is written once, here: EdgeSource /
+// load_edge_source (the per-source context), emit_edges (label, attributes, slot, stores) and zero_counters.  On the host one function,
+// build_edges_zeroing, checks the arguments and launches the kernel of an EdgeSelect (internal.h) for all three public entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,7 +42,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// The per-edge statements gnncca_build_edges and gnncca_build_edges_topk share (the same statements give the same bits).
+// The arithmetic of an edge's attributes, used by emit_edges below and by the capped selections' keys (graph_topk.cuh).
 // Ground-plane L2 and L1 distance of two detections in float64, no FMA contraction (sklearn paired_distances, inference.py:229-237):
 __device__ __forceinline__ void ground_dists(double xi, double yi, double xj, double yj, double& l2, double& l1) {
     const double dx = __dsub_rn(xi, xj), dy = __dsub_rn(yi, yj);
@@ -122,70 +127,102 @@ __device__ __forceinline__ void reid_sums_wave(const float* __restrict__ reid, c
     }
 }
 
+// ---- what the four selections (dense here, graph_topk.cuh, graph_topk_sym.cuh, graph_radius.cuh) share on the device ----
+// A kept edge carries the dense build's bits in every selection because all four kernels run emit_edges below: the statements exist once.
+
+// What a wave knows of its source, the detection at position p of src_order: its frame [gs, ge) of graph g, camera, person, ground
+// position, the frame's max_dist and its reid row.
+struct EdgeSource {
+    int i, g, gs, ge, ci, pi;
+    double xi, yi, md;
+    const float* __restrict__ ri;
+    bool vec4;
+};
+__device__ __forceinline__ EdgeSource load_edge_source(const gnncca_frames& fr, const float* __restrict__ reid, int R, int p) {
+    EdgeSource s;
+    s.i = fr.src_order[p];
+    s.g = fr.graph_of[s.i];
+    s.gs = fr.graph_ptr[s.g], s.ge = fr.graph_ptr[s.g + 1];
+    s.ci = fr.cam[s.i], s.pi = fr.person_id[s.i];
+    s.xi = fr.xw[s.i], s.yi = fr.yw[s.i], s.md = fr.max_dist[s.g];
+    s.ri = reid + (size_t)s.i * R;
+    s.vec4 = (R & 3) == 0;
+    return s;
+}
+
+// gnncca_frames_forward*: the post-processing counters of the same batch are zeroed by the build's launch, launches ahead of their first
+// use, instead of by a memset node of their own -- ahead of the kernel's early returns (a wave without a source, or a source without a
+// kept candidate, still does its share), by the workgroups with `mine`, `width` threads each.
+__device__ __forceinline__ void zero_counters(int* __restrict__ zero_ptr, int zero_n, bool mine, int width) {
+    if (zero_ptr && mine)
+        for (int t = blockIdx.x * width + threadIdx.x; t < zero_n; t += gridDim.x * width) zero_ptr[t] = 0;
+}
+
+// The edges of one 64-candidate round of source `s`: this lane holds candidate j, kept iff `keep`; `mask` is the wave's ballot of keep
+// (not zero) and row_of(t) the reid row of lane t's candidate (reid_sums_wave).  Label, ground attributes, reid terms, then the stores at
+// slot k = base + (kept lanes below this one), so a round's stores are contiguous and in candidate order; a kept lane stores iff slot_ok(k).
+template <int MODE, class RowOf, class SlotOk>
+__device__ __forceinline__ void emit_edges(const gnncca_frames& fr, const float* __restrict__ reid, int R, const EdgeSource& s, int j, bool keep,
+                                           unsigned long long mask, int lane, RowOf row_of, long long base, SlotOk slot_ok, long long E,
+                                           long long* __restrict__ ei_out, float* __restrict__ attr_out, float* __restrict__ lab_out) {
+    constexpr int NA = MODE == GNNCCA_EDGE_ATTR_FULL ? 4 : 2;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, lab = 0.f;
+    if (keep) {
+        lab = fr.person_id[j] == s.pi ? 1.f : 0.f;
+        if (MODE != GNNCCA_EDGE_ATTR_ONLY_APPEARANCE) {
+            // sklearn paired_distances on float64 rows, / max_dist, .type(float32); no FMA contraction
+            double l2, l1;
+            ground_dists(s.xi, s.yi, fr.xw[j], fr.yw[j], l2, l1);
+            a0 = (float)__ddiv_rn(l2, s.md);
+            a1 = (float)__ddiv_rn(l1, s.md);
+        }
+    }
+    if (MODE != GNNCCA_EDGE_ATTR_ONLY_DIST) {
+        float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;  // this lane's candidate: raw sums over the reid row
+        reid_sums_wave(reid, s.ri, R, s.vec4, mask, lane, row_of, sd, sab, saa, sbb);
+        const float emb = reid_emb(sd), cosv = reid_cos(sab, saa, sbb);
+        if (MODE == GNNCCA_EDGE_ATTR_FULL) {
+            a2 = emb;
+            a3 = cosv;
+        } else {
+            a0 = emb;
+            a1 = cosv;
+        }
+    }
+    if (keep) {
+        const long long k = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (slot_ok(k)) {
+            ei_out[k] = s.i;
+            ei_out[E + k] = j;
+            if (NA == 4) {
+                *reinterpret_cast<float4*>(attr_out + k * 4) = make_float4(a0, a1, a2, a3);
+            } else {
+                *reinterpret_cast<float2*>(attr_out + k * 2) = make_float2(a0, a1);
+            }
+            lab_out[k] = lab;
+        }
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void build_edges_kernel(const gnncca_frames fr, const float* __restrict__ reid, int R, int N,
                                                           long long E, long long* __restrict__ ei_out,
                                                           float* __restrict__ attr_out, float* __restrict__ lab_out,
                                                           int* __restrict__ zero_ptr, int zero_n) {
-    constexpr int NA = MODE == GNNCCA_EDGE_ATTR_FULL ? 4 : 2;
-    // (gnncca_frames_forward: the post-processing counters of the same batch are zeroed here, launches ahead of their first use, instead of
-    // by a memset node of their own)
-    if (zero_ptr && blockIdx.y == 0)
-        for (int t = blockIdx.x * 256 + threadIdx.x; t < zero_n; t += gridDim.x * 256) zero_ptr[t] = 0;
+    zero_counters(zero_ptr, zero_n, blockIdx.y == 0, 256);
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= N) return;
-    const int i = fr.src_order[p];
-    const int g = fr.graph_of[i];
-    const int gs = fr.graph_ptr[g], ge = fr.graph_ptr[g + 1];
-    const int ci = fr.cam[i], pi = fr.person_id[i];
-    const double xi = fr.xw[i], yi = fr.yw[i], md = fr.max_dist[g];
-    const float* __restrict__ ri = reid + (size_t)i * R;
-    const bool vec4 = (R & 3) == 0;
+    const EdgeSource s = load_edge_source(fr, reid, R, p);
     long long pos = fr.edge_ptr[p];
-    for (int c = 0, j0 = gs; j0 < ge; ++c, j0 += 64) {
+    for (int c = 0, j0 = s.gs; j0 < s.ge; ++c, j0 += 64) {
         const int j = j0 + lane;
-        const bool inb = j < ge;
-        const bool valid = inb && fr.cam[j] != ci;  // same camera: no edge (inference.py:210-211)
+        const bool valid = j < s.ge && fr.cam[j] != s.ci;  // same camera: no edge (inference.py:210-211)
         const unsigned long long mask = __ballot(valid);
-        const int n_valid = __popcll(mask);
-        if (c % (int)gridDim.y == (int)blockIdx.y && mask != 0ull) {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, lab = 0.f;
-            if (valid) {
-                lab = fr.person_id[j] == pi ? 1.f : 0.f;
-                if (MODE != GNNCCA_EDGE_ATTR_ONLY_APPEARANCE) {
-                    // sklearn paired_distances on float64 rows, / max_dist, .type(float32); no FMA contraction
-                    double l2, l1;
-                    ground_dists(xi, yi, fr.xw[j], fr.yw[j], l2, l1);
-                    a0 = (float)__ddiv_rn(l2, md);
-                    a1 = (float)__ddiv_rn(l1, md);
-                }
-            }
-            if (MODE != GNNCCA_EDGE_ATTR_ONLY_DIST) {
-                float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;  // this lane's candidate: raw sums over the reid row
-                reid_sums_wave(reid, ri, R, vec4, mask, lane, [&](int t) { return j0 + t; }, sd, sab, saa, sbb);
-                const float emb = reid_emb(sd), cosv = reid_cos(sab, saa, sbb);
-                if (MODE == GNNCCA_EDGE_ATTR_FULL) {
-                    a2 = emb;
-                    a3 = cosv;
-                } else {
-                    a0 = emb;
-                    a1 = cosv;
-                }
-            }
-            if (valid) {
-                const long long k = pos + __popcll(mask & ((1ull << lane) - 1ull));
-                ei_out[k] = i;
-                ei_out[E + k] = j;
-                if (NA == 4) {
-                    *reinterpret_cast<float4*>(attr_out + k * 4) = make_float4(a0, a1, a2, a3);
-                } else {
-                    *reinterpret_cast<float2*>(attr_out + k * 2) = make_float2(a0, a1);
-                }
-                lab_out[k] = lab;
-            }
-        }
-        pos += n_valid;
+        if (c % (int)gridDim.y == (int)blockIdx.y && mask != 0ull)
+            emit_edges<MODE>(fr, reid, R, s, j, valid, mask, lane, [&](int t) { return j0 + t; }, pos, [](long long) { return true; }, E,
+                             ei_out, attr_out, lab_out);
+        pos += __popcll(mask);
     }
 }
 
@@ -451,9 +488,10 @@ static TopkGeometry topk_geometry(int32_t max_deg, int64_t n_nodes) {
     return TopkGeometry{cap, per_wave * waves, dim3((unsigned)((n_nodes + waves - 1) / waves)), dim3(64 * waves)};
 }
 
-// Two refusals (GNNCCA_ERR_INVALID_ARG) that the dense, capped, symmetric-emit and backward entry points state alike.  What lies between them
-// keeps each entry point's own order, which the tests pin: the capped entry refuses max_deg before its early return for an empty batch, the
-// symmetric emit checks the 2^31 limits and its workspace before that return; the symmetric count has no n_edges and stays apart.
+// Two refusals (GNNCCA_ERR_INVALID_ARG) that the build (every selection), the symmetric emit and the backward entry points state alike.  What
+// lies between them keeps each entry point's own order, which the tests pin: the build refuses its selection's arguments (max_deg, the radius)
+// before its early return for an empty batch, the symmetric emit checks the 2^31 limits and its workspace before that return; the symmetric
+// count has no n_edges and stays apart.
 static bool edge_sizes_invalid(const gnncca_frames* fr, int64_t n_nodes, int64_t n_edges, int32_t reid_dim, int32_t mode) {
     return !fr || n_nodes < 0 || n_edges < 0 || reid_dim < 0 || mode < GNNCCA_EDGE_ATTR_FULL || mode > GNNCCA_EDGE_ATTR_ONLY_DIST;
 }
@@ -465,6 +503,17 @@ static bool edge_pointers_null(const gnncca_frames* fr, const void* edge_index_o
 // radius: a number >= 0 or +inf (a NaN fails the comparison); unit: one of GNNCCA_RADIUS_UNIT_*
 static bool radius_invalid(double radius, int32_t unit) {
     return !(radius >= 0.0) || (unit != GNNCCA_RADIUS_UNIT_GROUND && unit != GNNCCA_RADIUS_UNIT_MAX_DIST);
+}
+
+// What a selection refuses of its own arguments (internal.h): stated by every entry point that takes one before it looks at the sizes --
+// the build before its early return for an empty batch, gnncca_frames_forward_* before the normalisation's launch.
+int gnncca::edge_select_refusal(const EdgeSelect& sel) {
+    if (sel.kind == EdgeSelect::kCapped) {
+        if (sel.top_k < 1 || sel.max_deg < 0 || (sel.rank_by != GNNCCA_RANK_BY_GROUND && sel.rank_by != GNNCCA_RANK_BY_REID)) return GNNCCA_ERR_INVALID_ARG;
+        if (sel.max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
+    }
+    if (sel.kind == EdgeSelect::kGated && radius_invalid(sel.radius, sel.unit)) return GNNCCA_ERR_INVALID_ARG;
+    return GNNCCA_OK;
 }
 
 extern "C" {
@@ -584,16 +633,16 @@ int gnncca_build_edges_topk_backward(const gnncca_frames* fr, const float* reid,
 int gnncca_build_edges_topk(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
                             int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
                             float* edge_labels_out, gnncca_stream_t stream) {
-    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, true, top_k, rank_by, max_deg, edge_index_out, edge_attr_out,
-                                       edge_labels_out, nullptr, 0, stream);
+    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, EdgeSelect::capped(top_k, rank_by, max_deg), edge_index_out,
+                                       edge_attr_out, edge_labels_out, nullptr, 0, stream);
 }
 
 // ---- row N1 with a ground-plane gate (graph_radius.cuh) ----
 int gnncca_build_edges_radius(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
                               double radius, int32_t unit, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                               gnncca_stream_t stream) {
-    return gnncca::build_edges_radius_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, radius, unit, edge_index_out, edge_attr_out,
-                                              edge_labels_out, nullptr, 0, stream);
+    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, EdgeSelect::gated(radius, unit), edge_index_out, edge_attr_out,
+                                       edge_labels_out, nullptr, 0, stream);
 }
 
 // ---- the capped neighbourhood closed under reversal (graph_topk_sym.cuh) ----
@@ -729,66 +778,48 @@ int gnncca_normalize_columns_backward2(const float* x0, const float* grad_out0, 
 int gnncca_build_edges(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges,
                        int32_t mode, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                        gnncca_stream_t stream) {
-    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, false, 0, 0, 0, edge_index_out, edge_attr_out, edge_labels_out,
-                                       nullptr, 0, stream);
+    return gnncca::build_edges_zeroing(fr, reid, reid_dim, n_nodes, n_edges, mode, EdgeSelect::dense(), edge_index_out, edge_attr_out,
+                                       edge_labels_out, nullptr, 0, stream);
 }
 
 }  // extern "C"
 
-// gnncca_build_edges (capped == false: top_k, rank_by and max_deg are not looked at) and gnncca_build_edges_topk.  The capped entry's own
-// refusals stand where it stated them: its degree limit before the early return for an empty batch.
+// gnncca_build_edges, gnncca_build_edges_topk and gnncca_build_edges_radius, and the build of gnncca_frames_forward_* (zero_ptr: the post
+// stage's counters).  The selection's own refusals stand where the capped and the gated entry stated them: before the early return for an
+// empty batch.
 int gnncca::build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
-                                bool capped, int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out,
-                                float* edge_labels_out, int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream) {
-    if (edge_sizes_invalid(fr, n_nodes, n_edges, reid_dim, mode) || (capped && (top_k < 1 || max_deg < 0))) return GNNCCA_ERR_INVALID_ARG;
-    if (capped && rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID) return GNNCCA_ERR_INVALID_ARG;
-    if (capped && max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
+                                const EdgeSelect& sel, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, int32_t* zero_ptr,
+                                int64_t zero_n, gnncca_stream_t stream) {
+    if (edge_sizes_invalid(fr, n_nodes, n_edges, reid_dim, mode)) return GNNCCA_ERR_INVALID_ARG;
+    if (const int bad = edge_select_refusal(sel)) return bad;
     if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
     if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
     if (edge_pointers_null(fr, edge_index_out, edge_attr_out, edge_labels_out)) return GNNCCA_ERR_INVALID_ARG;
-    const bool reads_reid = mode != GNNCCA_EDGE_ATTR_ONLY_DIST || (capped && rank_by == GNNCCA_RANK_BY_REID);
+    const bool capped = sel.kind == EdgeSelect::kCapped;
+    const bool reads_reid = mode != GNNCCA_EDGE_ATTR_ONLY_DIST || (capped && sel.rank_by == GNNCCA_RANK_BY_REID);
     if (reads_reid && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     long long* ei = reinterpret_cast<long long*>(edge_index_out);
-    if (!capped) {
+    if (capped) {
+        const TopkGeometry geo = topk_geometry(sel.max_deg, n_nodes);
+        with_mode(mode, [&](auto M) { with_flag(sel.rank_by == GNNCCA_RANK_BY_GROUND, [&](auto ground) {
+            hipLaunchKernelGGL((build_edges_topk_kernel<M(), rank_of(ground)>), geo.grid, geo.block, geo.lds_bytes, st, *fr, reid, (int)reid_dim,
+                               (int)n_nodes, (long long)n_edges, geo.cap, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
+        }); });
+    } else {
         // few sources: split each source's candidate chunks over up to 16 waves so that the launch still fills the chip
         unsigned slices = 1;
         while (slices < 16 && (long long)n_nodes * slices < 4096) slices *= 2;
         const dim3 grid((unsigned)((n_nodes + 3) / 4), slices), block(256);
         with_mode(mode, [&](auto M) {
-            hipLaunchKernelGGL((build_edges_kernel<M()>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, ei,
-                               edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
+            if (sel.kind == EdgeSelect::kGated)
+                hipLaunchKernelGGL((build_edges_radius_kernel<M()>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges,
+                                   sel.radius, (int)sel.unit, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
+            else
+                hipLaunchKernelGGL((build_edges_kernel<M()>), grid, block, 0, st, *fr, reid, (int)reid_dim, (int)n_nodes, (long long)n_edges, ei,
+                                   edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
         });
-    } else {
-        const TopkGeometry geo = topk_geometry(max_deg, n_nodes);
-        with_mode(mode, [&](auto M) { with_flag(rank_by == GNNCCA_RANK_BY_GROUND, [&](auto ground) {
-            hipLaunchKernelGGL((build_edges_topk_kernel<M(), rank_of(ground)>), geo.grid, geo.block, geo.lds_bytes, st, *fr, reid, (int)reid_dim,
-                               (int)n_nodes, (long long)n_edges, geo.cap, ei, edge_attr_out, edge_labels_out, zero_ptr, (int)zero_n);
-        }); });
     }
-    HIP_TRY(hipGetLastError());
-    return GNNCCA_OK;
-}
-
-// gnncca_build_edges_radius, and the build of gnncca_frames_forward_radius (zero_ptr: the post stage's counters).  The gate's own refusals
-// come first, as the capped entry's do: before the early return for an empty batch.
-int gnncca::build_edges_radius_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
-                                       double radius, int32_t unit, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
-                                       int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream) {
-    if (edge_sizes_invalid(fr, n_nodes, n_edges, reid_dim, mode) || radius_invalid(radius, unit)) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes == 0 || n_edges == 0) return GNNCCA_OK;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    if (edge_pointers_null(fr, edge_index_out, edge_attr_out, edge_labels_out)) return GNNCCA_ERR_INVALID_ARG;
-    if (mode != GNNCCA_EDGE_ATTR_ONLY_DIST && (!reid || reid_dim == 0)) return GNNCCA_ERR_INVALID_ARG;
-    // few sources: the dense launch's split of a source's candidate chunks over up to 16 waves
-    unsigned slices = 1;
-    while (slices < 16 && (long long)n_nodes * slices < 4096) slices *= 2;
-    const dim3 grid((unsigned)((n_nodes + 3) / 4), slices), block(256);
-    with_mode(mode, [&](auto M) {
-        hipLaunchKernelGGL((build_edges_radius_kernel<M()>), grid, block, 0, static_cast<hipStream_t>(stream), *fr, reid, (int)reid_dim, (int)n_nodes,
-                           (long long)n_edges, radius, (int)unit, reinterpret_cast<long long*>(edge_index_out), edge_attr_out, edge_labels_out,
-                           zero_ptr, (int)zero_n);
-    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

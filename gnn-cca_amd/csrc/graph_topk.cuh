@@ -1,8 +1,9 @@
 #pragma once
 // Graph build with a capped neighbourhood: every detection keeps the k cross-camera candidates of its own frame with the smallest key
 // (ground-plane L2 distance in float64, or the fp32 reid distance), ties to the smaller destination id.  The enumeration, the four
-// (or two) attributes and the label of a kept edge are gnncca_build_edges' (inference.py:207-266) -- the same device statements, so a
-// kept edge carries the dense build's bits -- but the PRUNING HAS NO COUNTERPART IN THE REFERENCE, which only builds complete graphs.
+// (or two) attributes and the label of a kept edge are gnncca_build_edges' (inference.py:207-266): pass 3 calls graph_build.hip's
+// emit_edges, as the dense kernel does, so a kept edge carries the dense build's bits -- but the PRUNING HAS NO COUNTERPART IN THE
+// REFERENCE, which only builds complete graphs.
 //
 // Shape: ONE WAVE PER SOURCE POSITION (sources in src_order), three passes, no workgroup barrier (waves of a workgroup never meet):
 //   1. keys.  The frame is walked in 64-detection chunks, one candidate per lane, as in build_edges_kernel.  The key of a cross-camera
@@ -37,29 +38,28 @@ __device__ __forceinline__ void wave_lds_fence() {
 }
 
 // ---- passes 1 and 2, shared with the symmetric build (graph_topk_sym.cuh): one wave, the same statements, the same bits ----
-// 1. keys of source i (camera ci, at xi / yi, reid row ri) against its frame [gs, ge): key and node id of every cross-camera candidate at
-// its rank among the candidates -> s_key / s_node (slots below `cap` only).  Returns deg, the number of candidates found.
+// 1. keys of source s against its frame: key and node id of every cross-camera candidate at its rank among the candidates -> s_key /
+// s_node (slots below `cap` only).  Returns deg, the number of candidates found.
 template <int RANK>
-__device__ __forceinline__ int topk_keys(const gnncca_frames& fr, const float* __restrict__ reid, const float* __restrict__ ri, int R, bool vec4,
-                                         int gs, int ge, int ci, double xi, double yi, int cap, int lane,
+__device__ __forceinline__ int topk_keys(const gnncca_frames& fr, const float* __restrict__ reid, int R, const EdgeSource& s, int cap, int lane,
                                          unsigned long long* __restrict__ s_key, int* __restrict__ s_node) {
     const unsigned long long below = (1ull << lane) - 1ull;
     int deg = 0;
-    for (int j0 = gs; j0 < ge; j0 += 64) {
+    for (int j0 = s.gs; j0 < s.ge; j0 += 64) {
         const int j = j0 + lane;
-        const bool valid = j < ge && fr.cam[j] != ci;   // same camera: no edge (inference.py:210-211)
+        const bool valid = j < s.ge && fr.cam[j] != s.ci;   // same camera: no edge (inference.py:210-211)
         const unsigned long long mask = __ballot(valid);
         if (mask == 0ull) continue;
         unsigned long long key = 0ull;
         if (RANK == GNNCCA_RANK_BY_GROUND) {
             if (valid) {
                 double l2, l1;
-                ground_dists(xi, yi, fr.xw[j], fr.yw[j], l2, l1);
+                ground_dists(s.xi, s.yi, fr.xw[j], fr.yw[j], l2, l1);
                 key = (unsigned long long)__double_as_longlong(l2);
             }
         } else {
             float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;
-            reid_sums_wave(reid, ri, R, vec4, mask, lane, [&](int t) { return j0 + t; }, sd, sab, saa, sbb);
+            reid_sums_wave(reid, s.ri, R, s.vec4, mask, lane, [&](int t) { return j0 + t; }, sd, sab, saa, sbb);
             key = (unsigned long long)__float_as_uint(reid_emb(sd));
         }
         const int idx = deg + __popcll(mask & below);
@@ -94,13 +94,8 @@ __global__ __launch_bounds__(256) void build_edges_topk_kernel(const gnncca_fram
                                                                long long E, int cap, long long* __restrict__ ei_out,
                                                                float* __restrict__ attr_out, float* __restrict__ lab_out,
                                                                int* __restrict__ zero_ptr, int zero_n) {
-    constexpr int NA = MODE == GNNCCA_EDGE_ATTR_FULL ? 4 : 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_topk[];
-    // (gnncca_frames_forward_topk: the post-processing counters of the same batch are zeroed here, as build_edges_kernel does for the dense
-    // chain -- by every thread of the launch, ahead of the early returns: a wave without a source, or a source without a candidate, still
-    // does its share)
-    if (zero_ptr)
-        for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < zero_n; t += gridDim.x * blockDim.x) zero_ptr[t] = 0;
+    zero_counters(zero_ptr, zero_n, true, blockDim.x);   // (every thread of the launch: the grid has one row)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int p = blockIdx.x * (blockDim.x >> 6) + wave;
     if (p >= N) return;
@@ -109,17 +104,11 @@ __global__ __launch_bounds__(256) void build_edges_topk_kernel(const gnncca_fram
     const long long out0 = fr.edge_ptr[p];
     const int n_keep = fr.edge_ptr[p + 1] - fr.edge_ptr[p];   // min(k, deg) by the plan (gnncca_plan_frames_ex)
     if (n_keep <= 0) return;
-    const int i = fr.src_order[p];
-    const int g = fr.graph_of[i];
-    const int gs = fr.graph_ptr[g], ge = fr.graph_ptr[g + 1];
-    const int ci = fr.cam[i], pi = fr.person_id[i];
-    const double xi = fr.xw[i], yi = fr.yw[i], md = fr.max_dist[g];
-    const float* __restrict__ ri = reid + (size_t)i * R;
-    const bool vec4 = (R & 3) == 0;
+    const EdgeSource s = load_edge_source(fr, reid, R, p);
     const unsigned long long below = (1ull << lane) - 1ull;
 
     // ---- 1. keys ----
-    const int deg = topk_keys<RANK>(fr, reid, ri, R, vec4, gs, ge, ci, xi, yi, cap, lane, s_key, s_node);
+    const int deg = topk_keys<RANK>(fr, reid, R, s, cap, lane, s_key, s_node);
     if (deg > cap || n_keep > deg) return;   // more candidates than the caller declared, or a plan of another batch: nothing is written
     wave_lds_fence();
 
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(256) void build_edges_topk_kernel(const gnncca_fram
     for (int base = 0; base < deg && emitted < n_keep; base += 64) {
         const int idx = base + lane;
         const bool inb = idx < deg;
-        const int j = inb ? s_node[idx] : gs;
+        const int j = inb ? s_node[idx] : s.gs;
         bool keep = inb;
         if (!all) {
             const unsigned long long key = inb ? s_key[idx] : ~0ull;
@@ -145,39 +134,8 @@ __global__ __launch_bounds__(256) void build_edges_topk_kernel(const gnncca_fram
         }
         const unsigned long long mask = __ballot(keep);
         if (mask == 0ull) continue;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, lab = 0.f;
-        if (keep) {
-            lab = fr.person_id[j] == pi ? 1.f : 0.f;
-            if (MODE != GNNCCA_EDGE_ATTR_ONLY_APPEARANCE) {
-                double l2, l1;
-                ground_dists(xi, yi, fr.xw[j], fr.yw[j], l2, l1);
-                a0 = (float)__ddiv_rn(l2, md);
-                a1 = (float)__ddiv_rn(l1, md);
-            }
-        }
-        if (MODE != GNNCCA_EDGE_ATTR_ONLY_DIST) {
-            float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;
-            reid_sums_wave(reid, ri, R, vec4, mask, lane, [&](int t) { return __shfl(j, t); }, sd, sab, saa, sbb);
-            const float emb = reid_emb(sd), cosv = reid_cos(sab, saa, sbb);
-            if (MODE == GNNCCA_EDGE_ATTR_FULL) {
-                a2 = emb;
-                a3 = cosv;
-            } else {
-                a0 = emb;
-                a1 = cosv;
-            }
-        }
-        const long long k = out0 + emitted + __popcll(mask & below);
-        if (keep && k < E) {
-            ei_out[k] = i;
-            ei_out[E + k] = j;
-            if (NA == 4) {
-                *reinterpret_cast<float4*>(attr_out + k * 4) = make_float4(a0, a1, a2, a3);
-            } else {
-                *reinterpret_cast<float2*>(attr_out + k * 2) = make_float2(a0, a1);
-            }
-            lab_out[k] = lab;
-        }
+        emit_edges<MODE>(fr, reid, R, s, j, keep, mask, lane, [&](int t) { return __shfl(j, t); }, out0 + emitted,
+                         [&](long long k) { return k < E; }, E, ei_out, attr_out, lab_out);
         emitted += __popcll(mask);
     }
 }

@@ -7,8 +7,8 @@
 // in j's list is decided by j's OWN selection -- the key bits j's wave ranked with ('reid' keys are not symmetric: F.pairwise_distance adds
 // its eps to a - b) -- and NO KEY IS EVALUATED TWICE FROM TWO SIDES: the selection is made once per source and published as bits, the
 // closure is pure bit arithmetic on them, so a last-ulp difference between two evaluations cannot break it.  A kept edge carries the dense
-// build's bits (build_edges_kernel's statements).  LIKE THE CAP ITSELF THIS HAS NO COUNTERPART IN THE REFERENCE, which only builds complete
-// graphs (every pair in both directions).
+// build's bits (the emit kernel calls graph_build.hip's emit_edges, as build_edges_kernel does).  LIKE THE CAP ITSELF THIS HAS NO
+// COUNTERPART IN THE REFERENCE, which only builds complete graphs (every pair in both directions).
 //
 // Four launches, one wave per source position in the first, second and last, no atomics:
 //   1. select   passes 1-2 of the directed kernel (topk_keys / topk_threshold, the same code); its keep decision is written as a BIT ROW
@@ -45,21 +45,17 @@ __device__ __forceinline__ long long frame_row_base(const int* __restrict__ grap
 }
 
 struct SymRow {
-    int i, g, gs, ge, words;
-    long long row;   // first word of source i's row; -1: outside the declared matrix
+    int words;       // of a row of the source's frame
+    long long row;   // first word of the source's row; -1: outside the declared matrix
 };
 
-__device__ __forceinline__ SymRow sym_row(const gnncca_frames& fr, int p, int lane, long long total_words) {
+__device__ __forceinline__ SymRow sym_row(const gnncca_frames& fr, const EdgeSource& s, int lane, long long total_words) {
     SymRow r;
-    r.i = fr.src_order[p];
-    r.g = fr.graph_of[r.i];
-    r.gs = fr.graph_ptr[r.g];
-    r.ge = fr.graph_ptr[r.g + 1];
-    const int n_g = r.ge - r.gs;
+    const int n_g = s.ge - s.gs;
     r.words = (n_g + 63) >> 6;
-    const long long base = frame_row_base(fr.graph_ptr, r.g, lane);
-    const bool ok = n_g > 0 && r.i >= r.gs && r.i < r.ge && base >= 0 && base + (long long)n_g * r.words <= total_words;
-    r.row = ok ? base + (long long)(r.i - r.gs) * r.words : -1;
+    const long long base = frame_row_base(fr.graph_ptr, s.g, lane);
+    const bool ok = n_g > 0 && s.i >= s.gs && s.i < s.ge && base >= 0 && base + (long long)n_g * r.words <= total_words;
+    r.row = ok ? base + (long long)(s.i - s.gs) * r.words : -1;
     return r;
 }
 
@@ -73,15 +69,13 @@ __global__ __launch_bounds__(256) void topk_sym_select_kernel(const gnncca_frame
     if (p >= N) return;
     unsigned long long* __restrict__ s_key = reinterpret_cast<unsigned long long*>(s_topk + (size_t)wave * cap * kTopkSlotBytes);
     int* __restrict__ s_node = reinterpret_cast<int*>(s_key + cap);
-    const SymRow r = sym_row(fr, p, lane, total_words);
+    const EdgeSource s = load_edge_source(fr, reid, R, p);
+    const SymRow r = sym_row(fr, s, lane, total_words);
     if (r.row < 0) return;
-    const int i = r.i, gs = r.gs, ge = r.ge;
-    const int ci = fr.cam[i];
-    const float* __restrict__ ri = reid + (size_t)i * R;
     const unsigned long long below = (1ull << lane) - 1ull;
     unsigned long long* __restrict__ row = bits + r.row;
 
-    const int deg = topk_keys<RANK>(fr, reid, ri, R, (R & 3) == 0, gs, ge, ci, fr.xw[i], fr.yw[i], cap, lane, s_key, s_node);
+    const int deg = topk_keys<RANK>(fr, reid, R, s, cap, lane, s_key, s_node);
     const bool over = deg > cap;   // more candidates than the caller declared: the source selects nothing
     const int n_keep = over ? 0 : min(top_k, deg);
     wave_lds_fence();
@@ -92,9 +86,9 @@ __global__ __launch_bounds__(256) void topk_sym_select_kernel(const gnncca_frame
 
     // the keep decision of pass 3, by the frame's 64-detection chunks: a candidate's slot is its rank among the candidates so far
     int seen = 0, ties = 0;
-    for (int c = 0, j0 = gs; j0 < ge; ++c, j0 += 64) {
+    for (int c = 0, j0 = s.gs; j0 < s.ge; ++c, j0 += 64) {
         const int j = j0 + lane;
-        const bool valid = j < ge && fr.cam[j] != ci;
+        const bool valid = j < s.ge && fr.cam[j] != s.ci;
         const unsigned long long mask = __ballot(valid);
         const int idx = seen + __popcll(mask & below);
         bool keep = valid && n_keep > 0;
@@ -119,16 +113,17 @@ __global__ __launch_bounds__(256) void topk_sym_close_kernel(const gnncca_frames
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (p >= N) return;
-    const SymRow r = sym_row(fr, p, lane, total_words);
+    const EdgeSource s = load_edge_source(fr, nullptr, 0, p);   // (no reid table here: the frame and the node id are what it needs)
+    const SymRow r = sym_row(fr, s, lane, total_words);
     int cnt = 0;
     if (r.row >= 0) {
-        const int li = r.i - r.gs;
+        const int li = s.i - s.gs;
         const long long frame0 = r.row - (long long)li * r.words;   // the frame's first row
         const int my_word = li >> 6, my_bit = li & 63;
-        for (int c = 0, j0 = r.gs; j0 < r.ge; ++c, j0 += 64) {
-            const int lj = (j0 - r.gs) + lane;   // this lane's detection, as an offset in the frame
+        for (int c = 0, j0 = s.gs; j0 < s.ge; ++c, j0 += 64) {
+            const int lj = (j0 - s.gs) + lane;   // this lane's detection, as an offset in the frame
             const unsigned long long own = bits_a[r.row + c];
-            const bool back = j0 + lane < r.ge && ((bits_a[frame0 + (long long)lj * r.words + my_word] >> my_bit) & 1ull) != 0ull;
+            const bool back = j0 + lane < s.ge && ((bits_a[frame0 + (long long)lj * r.words + my_word] >> my_bit) & 1ull) != 0ull;
             const unsigned long long rev = __ballot(back);
             const unsigned long long closed = UNION ? (own | rev) : (own & rev);
             if (lane == 0) bits_b[r.row + c] = closed;
@@ -182,56 +177,20 @@ __global__ __launch_bounds__(256) void topk_sym_emit_kernel(const gnncca_frames 
                                                             const unsigned long long* __restrict__ bits, long long total_words,
                                                             long long* __restrict__ ei_out, float* __restrict__ attr_out,
                                                             float* __restrict__ lab_out) {
-    constexpr int NA = MODE == GNNCCA_EDGE_ATTR_FULL ? 4 : 2;
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (p >= N) return;
-    const SymRow r = sym_row(fr, p, lane, total_words);
+    const EdgeSource s = load_edge_source(fr, reid, R, p);
+    const SymRow r = sym_row(fr, s, lane, total_words);
     if (r.row < 0) return;
-    const int i = r.i, gs = r.gs, ge = r.ge;
-    const int ci = fr.cam[i], pi = fr.person_id[i];
-    const double xi = fr.xw[i], yi = fr.yw[i], md = fr.max_dist[r.g];
-    const float* __restrict__ ri = reid + (size_t)i * R;
-    const bool vec4 = (R & 3) == 0;
     long long pos = fr.edge_ptr[p];
-    for (int c = 0, j0 = gs; j0 < ge; ++c, j0 += 64) {
+    for (int c = 0, j0 = s.gs; j0 < s.ge; ++c, j0 += 64) {
         const int j = j0 + lane;
-        const bool keep = ((bits[r.row + c] >> lane) & 1ull) != 0ull && j < ge && fr.cam[j] != ci;
+        const bool keep = ((bits[r.row + c] >> lane) & 1ull) != 0ull && j < s.ge && fr.cam[j] != s.ci;
         const unsigned long long mask = __ballot(keep);
         if (mask == 0ull) continue;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, lab = 0.f;
-        if (keep) {   // build_edges_kernel's statements
-            lab = fr.person_id[j] == pi ? 1.f : 0.f;
-            if (MODE != GNNCCA_EDGE_ATTR_ONLY_APPEARANCE) {
-                double l2, l1;
-                ground_dists(xi, yi, fr.xw[j], fr.yw[j], l2, l1);
-                a0 = (float)__ddiv_rn(l2, md);
-                a1 = (float)__ddiv_rn(l1, md);
-            }
-        }
-        if (MODE != GNNCCA_EDGE_ATTR_ONLY_DIST) {
-            float sd = 0.f, sab = 0.f, saa = 1.f, sbb = 1.f;
-            reid_sums_wave(reid, ri, R, vec4, mask, lane, [&](int t) { return j0 + t; }, sd, sab, saa, sbb);
-            const float emb = reid_emb(sd), cosv = reid_cos(sab, saa, sbb);
-            if (MODE == GNNCCA_EDGE_ATTR_FULL) {
-                a2 = emb;
-                a3 = cosv;
-            } else {
-                a0 = emb;
-                a1 = cosv;
-            }
-        }
-        const long long k = pos + __popcll(mask & ((1ull << lane) - 1ull));
-        if (keep && k >= 0 && k < E) {
-            ei_out[k] = i;
-            ei_out[E + k] = j;
-            if (NA == 4) {
-                *reinterpret_cast<float4*>(attr_out + k * 4) = make_float4(a0, a1, a2, a3);
-            } else {
-                *reinterpret_cast<float2*>(attr_out + k * 2) = make_float2(a0, a1);
-            }
-            lab_out[k] = lab;
-        }
+        emit_edges<MODE>(fr, reid, R, s, j, keep, mask, lane, [&](int t) { return j0 + t; }, pos,
+                         [&](long long k) { return k >= 0 && k < E; }, E, ei_out, attr_out, lab_out);
         pos += __popcll(mask);
     }
 }

@@ -155,16 +155,25 @@ inline StagingImage staging_image(const void* base, int64_t n, int64_t g) {
 }
 inline size_t staging_image_bytes(int64_t n, int64_t g) { return n < 0 || g < 0 ? 0 : staging_image(nullptr, n, g).bytes; }
 
-// gnncca_build_edges (capped == false) / gnncca_build_edges_topk that also zero `zero_n` int32 words at `zero_ptr` (graph_build.hip;
-// gnncca_frames_forward hands them the post stage's counters); zero_ptr == nullptr: the public entry points, bit for bit
-int build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode, bool capped,
-                        int32_t top_k, int32_t rank_by, int32_t max_deg, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
-                        int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream);
+// Which of a source's cross-camera candidates a graph build keeps: all of them, the top_k with the smallest key (graph_topk.cuh), or those
+// within a ground-plane radius (graph_radius.cuh).  The fields of the other kinds are not looked at.
+struct EdgeSelect {
+    enum Kind { kDense, kCapped, kGated } kind;
+    int32_t top_k, rank_by, max_deg;   // kCapped: gnncca_build_edges_topk's arguments
+    double radius;                     // kGated: gnncca_build_edges_radius' arguments
+    int32_t unit;
+    static EdgeSelect dense() { return EdgeSelect{kDense, 0, 0, 0, 0.0, 0}; }
+    static EdgeSelect capped(int32_t top_k, int32_t rank_by, int32_t max_deg) { return EdgeSelect{kCapped, top_k, rank_by, max_deg, 0.0, 0}; }
+    static EdgeSelect gated(double radius, int32_t unit) { return EdgeSelect{kGated, 0, 0, 0, radius, unit}; }
+};
+// what the public entry points refuse of a selection's own arguments: GNNCCA_OK, GNNCCA_ERR_INVALID_ARG or GNNCCA_ERR_UNSUPPORTED (graph_build.hip)
+int edge_select_refusal(const EdgeSelect& sel);
 
-// gnncca_build_edges_radius with the same zeroing (graph_build.hip, graph_radius.cuh; gnncca_frames_forward_radius hands it the counters)
-int build_edges_radius_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
-                               double radius, int32_t unit, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
-                               int32_t* zero_ptr, int64_t zero_n, gnncca_stream_t stream);
+// gnncca_build_edges / _topk / _radius, by `sel`, that also zero `zero_n` int32 words at `zero_ptr` (graph_build.hip; gnncca_frames_forward*
+// hand them the post stage's counters); zero_ptr == nullptr: the public entry points, bit for bit
+int build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid_dim, int64_t n_nodes, int64_t n_edges, int32_t mode,
+                        const EdgeSelect& sel, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, int32_t* zero_ptr,
+                        int64_t zero_n, gnncca_stream_t stream);
 
 Family classify(const gnncca_mpn_dims* d);
 bool blob_header(const gnncca_mpn_dims* d, BlobHeader* out);  // false if unsupported

@@ -276,13 +276,13 @@ int gnncca_post_exclusive_frames(const int64_t* edge_index, const float* scores,
     return GNNCCA_OK;
 }
 
-// The one-call chain of gnncca_frames_forward (top_k == 0: the complete graph) and gnncca_frames_forward_topk (top_k >= 1: the staging image
-// and n_edges are gnncca_plan_frames_ex(top_k)'s, the build is the capped kernel) and gnncca_frames_forward_radius (gate != nullptr: the image
-// and n_edges are gnncca_plan_frames_radius', the build is the gated kernel).  Everything after the build sees an ordinary edge list.
-struct RadiusGate { double radius; int32_t unit; };
+// The one-call chain of gnncca_frames_forward (the complete graph), gnncca_frames_forward_topk (the staging image and n_edges are
+// gnncca_plan_frames_ex(top_k)'s, the build is the capped kernel) and gnncca_frames_forward_radius (the image and n_edges are
+// gnncca_plan_frames_radius', the build is the gated kernel), by `sel`.  Everything after the build sees an ordinary edge list.
 static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
                                size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
-                               int32_t top_k, int32_t rank_by, int32_t max_deg, const RadiusGate* gate, gnncca_stream_t stream) {
+                               const EdgeSelect& sel, gnncca_stream_t stream) {
+    if (const int bad = edge_select_refusal(sel)) return bad;
     if (!d || !io || !io->staged_dev) return GNNCCA_ERR_INVALID_ARG;
     const int64_t n = io->n_nodes, g = io->n_frames, e = io->n_edges;
     if (n < 1 || g < 1 || e < 0) return GNNCCA_ERR_INVALID_ARG;
@@ -291,9 +291,10 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
         !io->predictions || !io->pruned || !io->counters || !io->labels || (io->normalize && (!io->node_norm || !io->reid_norm)))
         return GNNCCA_ERR_INVALID_ARG;
     if (io->counters_len < 3 * n + 1 + g) return GNNCCA_ERR_INVALID_ARG;   // flow_out | flow_in | n_clusters | sizes | triggers (ABI 2: stated, not assumed)
-    // (what gnncca_build_edges_topk would refuse, refused here: before the normalisation's launch)
-    if ((top_k > 0 || gate) && (io->mode < GNNCCA_EDGE_ATTR_FULL || io->mode > GNNCCA_EDGE_ATTR_ONLY_DIST)) return GNNCCA_ERR_INVALID_ARG;
-    if (top_k > 0 && rank_by == GNNCCA_RANK_BY_REID && io->reid_dim <= 0) return GNNCCA_ERR_INVALID_ARG;   // the ranking reads the table in every mode
+    // (what gnncca_build_edges_topk / _radius would refuse, refused here: before the normalisation's launch)
+    if (sel.kind != EdgeSelect::kDense && (io->mode < GNNCCA_EDGE_ATTR_FULL || io->mode > GNNCCA_EDGE_ATTR_ONLY_DIST)) return GNNCCA_ERR_INVALID_ARG;
+    if (sel.kind == EdgeSelect::kCapped && sel.rank_by == GNNCCA_RANK_BY_REID && io->reid_dim <= 0)
+        return GNNCCA_ERR_INVALID_ARG;   // the ranking reads the table in every mode
     const StagingImage img = staging_image(io->staged_dev, n, g);
     const gnncca_frames fr = img.frames();
     const float* x = io->node_embeds;
@@ -308,12 +309,7 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
     const bool zero_here = e > 0 && mpn_workspace != nullptr;
     int32_t* zero_ptr = zero_here ? io->counters : nullptr;
     const int64_t zero_n = zero_here ? 3 * n + 1 + g : 0;
-    if (gate)
-        st = build_edges_radius_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, gate->radius, gate->unit, io->edge_index, io->edge_attr,
-                                        io->edge_labels, zero_ptr, zero_n, stream);
-    else
-        st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, top_k > 0, top_k, rank_by, max_deg, io->edge_index, io->edge_attr,
-                                 io->edge_labels, zero_ptr, zero_n, stream);
+    st = build_edges_zeroing(&fr, reid, io->reid_dim, n, e, io->mode, sel, io->edge_index, io->edge_attr, io->edge_labels, zero_ptr, zero_n, stream);
     if (st != GNNCCA_OK) return st;
     const int n_out = gnncca_num_outputs(d);
     if (n_out < 1) return GNNCCA_ERR_UNSUPPORTED;
@@ -353,25 +349,22 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
 int gnncca_frames_forward(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
                           size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
                           gnncca_stream_t stream) {
-    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, 0, 0, 0, nullptr, stream);
+    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, EdgeSelect::dense(),
+                               stream);
 }
 
 int gnncca_frames_forward_topk(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
                                size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
                                int32_t top_k, int32_t rank_by, int32_t max_deg, gnncca_stream_t stream) {
-    if (top_k < 1 || max_deg < 0 || (rank_by != GNNCCA_RANK_BY_GROUND && rank_by != GNNCCA_RANK_BY_REID)) return GNNCCA_ERR_INVALID_ARG;
-    if (max_deg > GNNCCA_TOPK_MAX_DEG) return GNNCCA_ERR_UNSUPPORTED;   // one wave's LDS holds the keys of at most that many candidates
-    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, top_k,
-                               rank_by, max_deg, nullptr, stream);
+    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options,
+                               EdgeSelect::capped(top_k, rank_by, max_deg), stream);
 }
 
 int gnncca_frames_forward_radius(const gnncca_mpn_dims* d, const void* packed_dev, const gnncca_frames_io* io, void* mpn_workspace,
                                  size_t mpn_workspace_bytes, void* post_workspace, size_t post_workspace_bytes, uint32_t options,
                                  double radius, int32_t unit, gnncca_stream_t stream) {
-    if (!(radius >= 0.0) || (unit != GNNCCA_RADIUS_UNIT_GROUND && unit != GNNCCA_RADIUS_UNIT_MAX_DIST)) return GNNCCA_ERR_INVALID_ARG;
-    const RadiusGate gate{radius, unit};
-    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options, 0, 0, 0,
-                               &gate, stream);
+    return frames_forward_impl(d, packed_dev, io, mpn_workspace, mpn_workspace_bytes, post_workspace, post_workspace_bytes, options,
+                               EdgeSelect::gated(radius, unit), stream);
 }
 
 }  // extern "C"

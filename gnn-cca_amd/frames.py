@@ -151,6 +151,49 @@ def check_radius(radius, radius_unit, top_k=None, symmetric=None):
     return radius, nat.RADIUS_UNIT[radius_unit]
 
 
+class Selection:
+    """Which of a detection's cross-camera candidates a graph keeps: all (dense), the top_k with the smallest key (capped; sym != 0 closes
+    the list under reversal), or those within a radius (gated).  The codes are check_cap's and check_radius'.  The native library has one
+    entry point per kind and stage -- gnncca_plan_frames / _ex / _radius, gnncca_build_edges / _topk / _radius, gnncca_frames_forward /
+    _topk / _radius -- and this class is the one place that chooses among them."""
+    __slots__ = ("top_k", "rank", "sym", "radius", "unit")
+
+    def __init__(self, top_k, rank, sym, radius, unit):
+        self.top_k, self.rank, self.sym, self.radius, self.unit = top_k, rank, sym, radius, unit
+
+    @property
+    def pruned(self):
+        """The edge list is a proper subsequence of the dense one."""
+        return self.top_k is not None or self.radius is not None
+
+    def plan(self, lib, arrays, image_ptr, nbytes, max_deg):
+        """The host plan of this selection into the image; `max_deg` (a c_int32) receives the largest uncapped degree of a capped plan."""
+        if self.radius is not None:
+            return lib.gnncca_plan_frames_radius(*arrays, self.radius, self.unit, image_ptr, nbytes)
+        if self.top_k is None:
+            return lib.gnncca_plan_frames(*arrays, image_ptr, nbytes)
+        return lib.gnncca_plan_frames_ex(*arrays, self.top_k, image_ptr, nbytes, C.byref(max_deg))
+
+    def launch(self, lib, base, head, max_deg, tail):
+        """base(*head, <this selection's own arguments>, *tail) at the entry point of this kind: `base` itself for the dense graph, base +
+        '_topk' / '_radius' otherwise, whose signatures differ from the dense one's by those arguments.  Raises on a refusal."""
+        if self.radius is not None:
+            base, own = base + "_radius", (self.radius, self.unit)
+        elif self.top_k is not None:
+            base, own = base + "_topk", (self.top_k, self.rank, max_deg)
+        else:
+            own = ()
+        st = getattr(lib, base)(*head, *own, *tail)
+        if st:
+            nat.check(st, base)
+
+
+def select(top_k, rank_by, symmetric, radius, radius_unit):
+    """The Selection of build_graph_batch's / FramePipeline's arguments, or their ValueError: check_cap, then check_radius."""
+    top_k, rank, sym = check_cap(top_k, rank_by, symmetric)
+    return Selection(top_k, rank, sym, *check_radius(radius, radius_unit, top_k, symmetric))
+
+
 class StagedFrames:
     """The host side of one batch of frames.  The constructor converts the six host arrays (`arrays`: xw, yw, ids, id_cam, graph_sizes,
     max_dist as contiguous float64 / int64) and checks their lengths; nothing else is touched, so the caller can still refuse the batch.
@@ -166,9 +209,8 @@ class StagedFrames:
             raise ValueError(self.LENGTHS_DISAGREE)
         self.arrays, self.n, self.g, self.layout = (xw, yw, ids64, cam64, sizes, md), n, g, FrameLayout(n, g)
 
-    def plan(self, dev, top_k=None, radius=None, unit=0):
-        """gnncca_plan_frames (top_k=None, radius=None), gnncca_plan_frames_ex or gnncca_plan_frames_radius into the ring's next slot; waits only
-        if that slot's upload is still queued."""
+    def plan(self, dev, sel):
+        """The host plan of Selection `sel` into the ring's next slot; waits only if that slot's upload is still queued."""
         lib = nat.lib()
         nbytes = lib.gnncca_plan_frames_bytes(self.n, self.g)
         assert nbytes == self.layout.nbytes   # the library's StagingImage and FrameLayout agree
@@ -177,12 +219,7 @@ class StagedFrames:
         xw, yw, ids64, cam64, sizes, md = self.arrays
         args = (xw.ctypes.data, yw.ctypes.data, ids64.ctypes.data, cam64.ctypes.data, self.n, sizes.ctypes.data, md.ctypes.data, self.g)
         max_deg = C.c_int32(0)
-        if radius is not None:
-            e = lib.gnncca_plan_frames_radius(*args, radius, unit, pinned.data_ptr(), nbytes)
-        elif top_k is None:
-            e = lib.gnncca_plan_frames(*args, pinned.data_ptr(), nbytes)
-        else:
-            e = lib.gnncca_plan_frames_ex(*args, top_k, pinned.data_ptr(), nbytes, C.byref(max_deg))
+        e = sel.plan(lib, args, pinned.data_ptr(), nbytes, max_deg)
         if e < 0:
             if -e == nat.ERR_INVALID_ARG:
                 raise ValueError("id_cam length does not match graph_sizes")

@@ -14,7 +14,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native as nat
-from .frames import StagedFrames, _current_stream, _f32c, _on, _raw_stream, attach, check_cap, check_radius  # noqa: F401  (the lean device helpers live there)
+from .frames import StagedFrames, _current_stream, _f32c, _on, _raw_stream, attach, check_cap, check_radius, select  # noqa: F401  (the lean device helpers live there)
 from .sharding import GraphBatch
 
 MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST = 0, 1, 2
@@ -151,22 +151,14 @@ def normalize_columns(x, other=None):
 
 
 class _EdgeJob:
-    """What the edge kernels of one batch need besides the reid table: the staged frame image and its layout; for a capped build
-    (top_k is not None) also the cap, the ranking key and the batch's largest uncapped degree; for a symmetric one (sym != 0) the host
-    array of frame sizes too -- and `e` / `edge_ptr_g` are what its count read back, set by _edges_launch; for a radius-gated build
-    (radius is not None) the radius and its unit code.  `pruned`: the edge list is a proper subsequence of the dense one, which the
-    backward then looks its edges up in."""
-    __slots__ = ("staged", "layout", "n", "g", "e", "mode", "top_k", "rank", "max_deg", "sym", "sizes", "edge_ptr_g", "radius", "unit")
+    """What the edge kernels of one batch need besides the reid table: the staged frame image and its layout, the Selection (frames.py) and,
+    for a capped one, the batch's largest uncapped degree; for a symmetric one the host array of frame sizes too -- and `e` /
+    `edge_ptr_g` are what its count read back, set by _edges_launch."""
+    __slots__ = ("staged", "layout", "n", "g", "e", "mode", "sel", "max_deg", "sizes", "edge_ptr_g")
 
-    def __init__(self, staged, layout, e, mode, top_k=None, rank=0, max_deg=0, sym=0, sizes=None, radius=None, unit=0):
+    def __init__(self, staged, layout, e, mode, sel, max_deg=0, sizes=None):
         self.staged, self.layout, self.n, self.g, self.e, self.mode = staged, layout, layout.n, layout.g, e, mode
-        self.top_k, self.rank, self.max_deg = top_k, rank, max_deg
-        self.sym, self.sizes, self.edge_ptr_g = sym, sizes, None
-        self.radius, self.unit = radius, unit
-
-    @property
-    def pruned(self):
-        return self.top_k is not None or self.radius is not None
+        self.sel, self.max_deg, self.sizes, self.edge_ptr_g = sel, max_deg, sizes, None
 
 
 _readback = {}   # device index -> (pinned int32 buffer, event) of the symmetric build's one read-back
@@ -183,8 +175,8 @@ def _sym_edges_launch(job, reid_embeds):
     nbytes = lib.gnncca_build_edges_topk_sym_bytes(sizes.ctypes.data, g)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     eptr_g = job.layout.view(job.staged, "edge_ptr_g")
-    st = lib.gnncca_build_edges_topk_sym_count(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, sizes.ctypes.data, g, job.top_k,
-                                               job.rank, job.max_deg, job.sym, ws.data_ptr(), nbytes, eptr_g.data_ptr(), _raw_stream(dev))
+    st = lib.gnncca_build_edges_topk_sym_count(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, sizes.ctypes.data, g, job.sel.top_k,
+                                               job.sel.rank, job.max_deg, job.sel.sym, ws.data_ptr(), nbytes, eptr_g.data_ptr(), _raw_stream(dev))
     if st:
         nat.check(st, "gnncca_build_edges_topk_sym_count")
     hit = _readback.get(dev.index)
@@ -211,9 +203,10 @@ def _sym_edges_launch(job, reid_embeds):
 
 
 def _edges_launch(job, reid_embeds):
-    """gnncca_build_edges (gnncca_build_edges_topk for a capped job, the two ..._topk_sym_* calls for a symmetric one,
-    gnncca_build_edges_radius for a gated one) on the current stream: (edge_index, edge_attr, edge_labels), new tensors."""
-    if job.sym:
+    """The build of job.sel on the current stream -- gnncca_build_edges, _topk or _radius (Selection.launch), or the two ..._topk_sym_*
+    calls for a symmetric one: (edge_index, edge_attr, edge_labels), new tensors."""
+    sel = job.sel
+    if sel.sym:
         return _sym_edges_launch(job, reid_embeds)
     dev, n, e = reid_embeds.device, job.n, job.e
     n_attr = 4 if job.mode == MODE_FULL else 2
@@ -221,23 +214,11 @@ def _edges_launch(job, reid_embeds):
     edge_index = torch.empty((2, e), dtype=torch.int64, device=dev)
     edge_attr = torch.empty((e, n_attr), dtype=torch.float32, device=dev)
     edge_labels = torch.empty(e, dtype=torch.float32, device=dev)
-    if job.radius is not None:
-        # (called with E == 0 too, as the capped entry is: it checks its arguments before it looks at the sizes, and launches nothing then)
-        st = nat.lib().gnncca_build_edges_radius(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode, job.radius, job.unit,
-                                                 edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
-        if st:
-            nat.check(st, "gnncca_build_edges_radius")
-    elif job.top_k is not None:
-        # (called with E == 0 too: the entry point checks its arguments, the degree limit among them, before it looks at the sizes)
-        st = nat.lib().gnncca_build_edges_topk(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode, job.top_k, job.rank,
-                                               job.max_deg, edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
-        if st:
-            nat.check(st, "gnncca_build_edges_topk")
-    elif e > 0:
-        st = nat.lib().gnncca_build_edges(C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode,
-                                          edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev))
-        if st:
-            nat.check(st, "gnncca_build_edges")
+    # (a capped or gated build is called with E == 0 too: its entry point checks its arguments, the degree limit among them, before it looks
+    # at the sizes, and launches nothing then)
+    if e > 0 or sel.pruned:
+        sel.launch(nat.lib(), "gnncca_build_edges", (C.byref(fr), reid_embeds.data_ptr(), reid_embeds.shape[1], n, e, job.mode), job.max_deg,
+                   (edge_index.data_ptr(), edge_attr.data_ptr(), edge_labels.data_ptr(), _raw_stream(dev)))
     return edge_index, edge_attr, edge_labels
 
 
@@ -263,7 +244,7 @@ class _GraphBuildFunction(torch.autograd.Function):
             reid_n, x = reid, None
         edge_index, edge_attr, edge_labels = _edges_launch(job, reid_n)
         ctx.mark_non_differentiable(edge_index, edge_labels)
-        pruned = (edge_index,) if job.pruned else ()   # the capped / gated backward looks its edges up in the forward's edge list
+        pruned = (edge_index,) if job.sel.pruned else ()   # the capped / gated backward looks its edges up in the forward's edge list
         if ctx.normalized:
             ctx.save_for_backward(node_raw, reid, reid_n, edge_attr, *pruned)
             return x, edge_attr, reid_n, edge_index, edge_labels
@@ -275,7 +256,7 @@ class _GraphBuildFunction(torch.autograd.Function):
     def backward(ctx, *grads):
         job = ctx.job
         saved = ctx.saved_tensors
-        edge_index = saved[-1] if job.pruned else None
+        edge_index = saved[-1] if job.sel.pruned else None
         if ctx.normalized:
             node_raw, reid_raw, reid_n, edge_attr = saved[:4]
             g_x, g_ea, g_reid = grads[0], grads[1], grads[2]
@@ -369,8 +350,7 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
     capped build.  radius must be a finite number >= 0 or inf; a bool, NaN, negative or non-number, an unknown radius_unit, and radius
     together with top_k or symmetric (a gated k-nearest list is not defined here yet) are ValueErrors raised before the GPU is touched.
     The host plan evaluates every unordered pair of a frame once: O(sum n_g^2 / 2) host work per batch."""
-    top_k, rank, sym = check_cap(top_k, rank_by, symmetric)
-    radius, unit = check_radius(radius, radius_unit, top_k, symmetric)
+    sel = select(top_k, rank_by, symmetric, radius, radius_unit)
     if not (node_embeds.is_cuda and reid_embeds.is_cuda):
         raise RuntimeError("gnn_cca_amd.graph_build runs on MI355X only (no CPU fallback)")
     dev = reid_embeds.device
@@ -379,12 +359,12 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
         raise RuntimeError("embeddings and detections disagree on the number of nodes")
     if symmetric is not None and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("build_graph_batch(symmetric=...) waits for its edge count and cannot be captured into a graph")
-    frames.plan(dev, top_k, radius, unit)
+    frames.plan(dev, sel)
     mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
     with _on(dev):
         staged = torch.empty(frames.layout.nbytes, dtype=torch.uint8, device=dev)
         frames.upload(staged)
-        job = _EdgeJob(staged, frames.layout, frames.e, mode, top_k, rank, frames.max_deg, sym, frames.arrays[4], radius, unit)
+        job = _EdgeJob(staged, frames.layout, frames.e, mode, sel, frames.max_deg, frames.arrays[4])
         if _wants_grad(node_embeds, reid_embeds):
             # the differentiable build: x, edge_attr and reid_embeds are outputs of ONE autograd node (see _GraphBuildFunction)
             reid_embeds = _f32c(reid_embeds)
@@ -400,7 +380,7 @@ def build_graph_batch(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, r
             edge_index, edge_attr, edge_labels = _edges_launch(job, reid_embeds)
     node_ptr, edge_ptr = frames.layout.host_ptrs(frames.pinned)
     # (a symmetric build: the offsets its count read back; the device image holds the same, the pinned one still the plan's)
-    batch = GraphBatch(node_embeds, edge_index, edge_attr, job.edge_ptr_g if sym else edge_ptr, node_ptr)
+    batch = GraphBatch(node_embeds, edge_index, edge_attr, job.edge_ptr_g if sel.sym else edge_ptr, node_ptr)
     attach(batch, staged, frames.layout, frames.arrays[3])
     batch.edge_labels = edge_labels
     batch.reid_embeds = reid_embeds

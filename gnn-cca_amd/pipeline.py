@@ -59,7 +59,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .frames import StagedFrames, _on, _raw_stream, attach, check_cap, check_radius
+from .frames import StagedFrames, _on, _raw_stream, attach, select
 from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, build_graph_batch
 from .postprocess import MAX_FRAME_NODES as EXCLUSIVE_MAX_FRAME_NODES
 from .postprocess import check_cameras, check_threshold, exclusive_clusters, finalize, prune_and_cluster, threshold
@@ -258,12 +258,10 @@ class FramePipeline:
         self.threshold = check_threshold(threshold)
         if not pruning:
             raise ValueError("FramePipeline prunes on the device (PRUNING = True, as config_inference.yaml:7 ships it)")
-        # the cap: build_graph_batch's arguments and its refusals, here before any batch (or the GPU) is touched
-        top_k = check_cap(top_k, rank_by, symmetric)[0]
-        self.top_k, self.rank_by, self.symmetric = top_k, rank_by, symmetric
-        # the radius gate: build_graph_batch's arguments and its refusals (radius with top_k / symmetric among them), here as well
-        self.radius, self._unit = check_radius(radius, radius_unit, top_k, symmetric)
-        self.radius_unit = radius_unit
+        # the cap and the radius gate: build_graph_batch's arguments and its refusals (radius with top_k / symmetric among them), here
+        # before any batch (or the GPU) is touched
+        self._sel = sel = select(top_k, rank_by, symmetric, radius, radius_unit)
+        self.top_k, self.rank_by, self.symmetric, self.radius, self.radius_unit = sel.top_k, rank_by, symmetric, sel.radius, radius_unit
         self.switches = (bool(rounding), bool(pruning), bool(splitting))
         self.mode = MODE_ONLY_APPEARANCE if only_appearance else (MODE_ONLY_DIST if only_dist else MODE_FULL)
         self.normalize = bool(normalize)
@@ -361,7 +359,7 @@ class FramePipeline:
         dev = reid_embeds.device
         lib = nat.lib()
         frames = StagedFrames(xw, yw, ids, id_cam, graph_sizes, max_dist)
-        g, layout, top_k = frames.g, frames.layout, self.top_k
+        g, layout = frames.g, frames.layout
         if frames.n != n or reid_embeds.shape[0] != n:
             raise ValueError(frames.LENGTHS_DISAGREE)
         d = m.native_dims()
@@ -370,7 +368,7 @@ class FramePipeline:
                                f"{tuple(reid_embeds.shape)} {reid_embeds.dtype}")
         node_embeds = node_embeds if node_embeds.is_contiguous() else node_embeds.contiguous()
         reid_embeds = reid_embeds if reid_embeds.is_contiguous() else reid_embeds.contiguous()
-        frames.plan(dev, top_k, self.radius, self._unit)
+        frames.plan(dev, self._sel)
         e = frames.e
         if e == 0:   # no cross-camera pair in the whole batch: nothing to launch on the path (the step-by-step functions return the empty containers)
             return self._slow(*frames.arrays, node_embeds, reid_embeds)
@@ -430,20 +428,8 @@ class FramePipeline:
             io.logits, io.probs = fp + 4 * o_log, fp + 4 * o_prob
             io.edge_index, io.predictions, io.pruned = ip + 8 * o_ei, preds.data_ptr(), ip + 8 * o_prun
             io.counters, io.labels, io.counters_len = cp, cp + 4 * o_labels, o_labels
-            if self.radius is not None:
-                entry = "gnncca_frames_forward_radius"
-                st = lib.gnncca_frames_forward_radius(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(),
-                                                      post_ws.numel(), m._options(), self.radius, self._unit, _raw_stream(dev))
-            elif top_k is None:
-                entry = "gnncca_frames_forward"
-                st = lib.gnncca_frames_forward(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(), post_ws.numel(),
-                                               m._options(), _raw_stream(dev))
-            else:
-                entry = "gnncca_frames_forward_topk"
-                st = lib.gnncca_frames_forward_topk(C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(),
-                                                    post_ws.numel(), m._options(), top_k, nat.RANK_BY[self.rank_by], frames.max_deg, _raw_stream(dev))
-        if st:
-            nat.check(st, entry)
+            self._sel.launch(lib, "gnncca_frames_forward", (C.byref(d), blob.data_ptr(), C.byref(io), ws.data_ptr(), ws.numel(), post_ws.data_ptr(),
+                                                            post_ws.numel(), m._options()), frames.max_deg, (_raw_stream(dev),))
         # views (the reference's containers): x, edge_index, edge_attr, logits as [E, 1] per classified step
         x = f32[o_node:o_node + n * d_in].view(n, d_in) if self.normalize else node_embeds
         reid_n = f32[o_reid:o_reid + n * r_dim].view(n, r_dim) if self.normalize else reid_embeds
