@@ -106,6 +106,10 @@ def main():
     r = pipe(xw, yw, ids, id_cam, [n_g] * frames, max_dist, node_embeds, reid_embeds)
     same = torch.equal(r.pruned, post["pruned"]) and torch.equal(r.labels, post["labels"])
     print(f"FramePipeline, {'one call' if r._d2h is not None else 'step by step'}: identity clusters {int(r.n_clusters.item())}, equal to the step-by-step result: {same}")
+    # PRUNING: False (config_inference.yaml:7): nothing is pruned, the clusters are the strongly connected components of the active edges
+    u = FramePipeline(model, pruning=False, splitting=False, **cap)(xw, yw, ids, id_cam, [n_g] * frames, max_dist, node_embeds, reid_embeds)
+    print(f"FramePipeline(pruning=False, splitting=False): active edges {int(u.pruned.sum())}, identity clusters {int(u.n_clusters.item())} "
+          f"(strongly connected components), {int(u.final()['n_clusters'].item())} after ROUNDING")
     # per-frame metrics against the ground truth the graph build wrote (batch.edge_labels: same person id), then main.py's aggregates
     acc = EvalAccumulator().add(evaluate_frames(batch, post["pruned"], post["labels"]))
     print("aggregates over the frames:", ", ".join(f"{k} {v:.4g}" if isinstance(v, float) else f"{k} {v}" for k, v in acc.result().items()))

@@ -29,6 +29,7 @@ CMP = {"ge": 0, "gt": 1, "le": 2, "lt": 3}   # GNNCCA_CMP_*
 RANK_MAX_SCORES, RANK_MAX_FRAME_EDGES, RANK_POOL_MAX_THRESHOLDS = 4, 16384, 65536   # gnncca_rank_metrics, gnncca_rank_pool_add
 EXCLUSIVE_MAX_FRAME_NODES, EXCLUSIVE_MAX_CAMERAS = 4096, 64   # gnncca_post_exclusive_frames: 12-bit local ids, one 64-bit camera mask
 EXCLUSIVE_BAD_CAMERA, EXCLUSIVE_BAD_RANGE = 1, 2              # its flags_out[g]
+STRONG_MAX_FRAME_NODES, STRONG_BAD_RANGE = 1024, 2             # gnncca_post_strong_frames: a frame's reachability bit matrix lives in LDS
 RERANK_MAX_FRAME_NODES, RERANK_MAX_K1 = 128, 64  # gnncca_rerank_frames, gnncca_rank_predictions: a frame's tables and masks live in LDS
 
 
@@ -160,6 +161,8 @@ _SIGNATURES = {
     "gnncca_post_exclusive_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_size_t, C.c_void_p]),
+    "gnncca_post_strong_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnncca_post_finalize_frame_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnncca_post_finalize_frames_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,

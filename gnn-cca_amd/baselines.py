@@ -8,9 +8,11 @@ one pass (csrc/eval_sweep_joint.cuh):
     rows = sweep_grid(batch, [batch.edge_attr[:, 0], batch.edge_attr[:, 2]], [geom_axis, reid_axis], ['lt', 'lt'],
                       frame_div=np.stack([max_dist, np.ones_like(max_dist)]))   # the tables GEOM_TH / OPT_TH, both axes at once
 
-Not reproduced (include/gnncca_mpn.h has it in full): the reference clusters with the strongly connected components of the digraph of
-active edges and does not prune, so with a score that is not symmetric (F.pairwise_distance adds eps to a - b) a directed cycle
-without a mutual pair joins nodes there; here only mutual pairs join.  And inference.py:892,896 use the last graph's labels and
+Not reproduced by these calls (include/gnncca_mpn.h has it in full): the reference clusters with the strongly connected components of
+the digraph of active edges and does not prune, so with a score that is not symmetric (F.pairwise_distance adds eps to a - b) a
+directed cycle without a mutual pair joins nodes there; sweep_joint and geometry_baseline score mutual pairs only.  The reference's
+partition of one prediction vector is postprocess.strong_clusters(batch.edge_index, predictions, ...) -> evaluate_frames(batch,
+predictions, labels); a sweep over that partition does not exist.  And inference.py:892,896 use the last graph's labels and
 max_dist[0] for a whole batch; here every frame has its own labels and its own max_dist.
 
 What these baselines score on real features is unmeasured here, like the others: no data set and no trained ReID model exist in this

@@ -1,11 +1,12 @@
 // mpn_post.hip -- post-processing on the device (threshold, pruning, flow counters, connected components; kernels in
-// postprocess.cuh), the camera-exclusive clusters (exclusive.cuh) and the one-call frame pipeline gnncca_frames_forward, which chains graph
-// build, forward and post stage on one stream.
+// postprocess.cuh), the camera-exclusive clusters (exclusive.cuh), the strongly connected components of the unpruned edges (strong.cuh) and
+// the one-call frame pipeline gnncca_frames_forward, which chains graph build, forward and post stage on one stream.
 // The graph-plan kernels it needs are compiled in mpn_forward.hip and reached through their launchers (internal.h).
 #include "common.cuh"
 #include "plan.cuh"
 #include "postprocess.cuh"
 #include "exclusive.cuh"
+#include "strong.cuh"
 
 using namespace gnncca;
 
@@ -272,6 +273,53 @@ int gnncca_post_exclusive_frames(const int64_t* edge_index, const float* scores,
                        flags_out)
     if (P <= 64) GNNCCA_EXCL(64); else GNNCCA_EXCL(256);   // (eval_frames' choice: a Terrace frame has ~20 detections, one wave per frame)
 #undef GNNCCA_EXCL
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- identity clusters without pruning: strongly connected components (strong.cuh) ---------------------------------------------------------
+int gnncca_post_strong_frames(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                              const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes,
+                              int32_t* flow_out, int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out, int32_t* triggers_out,
+                              uint32_t* flags_out, gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > kStrongMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if ((node_ptr_dev == nullptr) != (edge_ptr_dev == nullptr) || (node_ptr_dev == nullptr) != (n_frames == 0)) return GNNCCA_ERR_INVALID_ARG;
+    if (!n_clusters_out || !triggers_out || !flags_out) return GNNCCA_ERR_INVALID_ARG;   // (one trigger / flag word at least: the whole graph)
+    if (n_nodes > 0 && (!flow_out || !flow_in || !labels_out)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !predictions)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t N = (size_t)n_nodes;
+    // zero the counters: one memset when the caller laid flow_out | flow_in | n_clusters out back to back (gnn_cca_amd.postprocess does)
+    if (N == 0 || (flow_in == flow_out + N && n_clusters_out == flow_in + N)) {
+        HIP_TRY(hipMemsetAsync(N ? flow_out : n_clusters_out, 0, (2 * N + 1) * 4, st));
+    } else {
+        HIP_TRY(hipMemsetAsync(flow_out, 0, N * 4, st));
+        HIP_TRY(hipMemsetAsync(flow_in, 0, N * 4, st));
+        HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), st));
+    }
+    const int P = (max_frame_nodes + 31) / 32 * 32;            // the LDS capacity in nodes: rows of P / 32 words
+    const size_t lds = (size_t)P * (size_t)(P / 32) * 4;       // 128 B at 32, 2 KiB at 128, 128 KiB at 1024
+    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (exclusive frames above)
+        static thread_local int attr_dev = -1;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if (attr_dev != dev) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(strong_cluster_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        kStrongMaxNodes * (kStrongMaxNodes / 32) * 4));
+            attr_dev = dev;
+        }
+    }
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    const long long* pred = reinterpret_cast<const long long*>(predictions);
+#define GNNCCA_STRONG(B)                                                                                                                     \
+    hipLaunchKernelGGL((strong_cluster_kernel<B>), dim3(node_ptr_dev ? (unsigned)n_frames : 1u), dim3(B), lds, st, ei, pred, (long long)n_edges, \
+                       (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, flow_out, flow_in, labels_out, n_clusters_out, triggers_out, flags_out)
+    // the block covers the largest frame with one node per thread: one wave for Terrace-sized frames (~20 detections), 1024 threads only
+    // where a frame needs them
+    if (P <= 64) GNNCCA_STRONG(64); else if (P <= 256) GNNCCA_STRONG(256); else GNNCCA_STRONG(1024);
+#undef GNNCCA_STRONG
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

@@ -48,6 +48,14 @@ give (tests/test_gpu_pipeline_radius.py).  A batch the gate leaves without any e
 through the step-by-step path.  `evaluate()` scores the kept edges, `evaluate(against='dense')` the dense graph with every dropped edge
 predicted 0.  radius together with top_k / symmetric is a ValueError.
 
+`FramePipeline(model, pruning=False, splitting=False)` is PRUNING: False of config_inference.yaml:7: nothing is pruned, `r.pruned` is the
+thresholded predictions and `r.labels` are the STRONGLY CONNECTED COMPONENTS of the active edges (postprocess.strong_clusters: one memset and
+one launch where prune_and_cluster stands; inference.py:302-304) -- a directed cycle without a mutual pair is one identity.  Such a pipeline
+takes the step-by-step path; `final()` / `final_async()` go through `finalize(pruning=False)` (only ROUNDING can change a frame), and
+`evaluate()`, `identities()` and FrameLinker work unchanged, since they take predictions and labels.  With `top_k=` the directed capped list is
+clustered by its strongly connected components, the reference's own rule, with no closure and no wait.  `sweep()` and `exclusive()` keep
+their own rules (mutual pairs).  `splitting=True` without pruning is a ValueError: the reference has no behaviour there.
+
 `FramePipeline(model, threshold=th)` decides at sigmoid(logit) >= th instead of the reference's 0.5; `r.sweep(thresholds)` scores every
 candidate th of a batch in one pass (gnn_cca_amd.calibration).  Any th other than 0.5 takes the step-by-step path too.
 
@@ -62,7 +70,8 @@ from . import _native as nat
 from .frames import StagedFrames, _on, _raw_stream, attach, select
 from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, build_graph_batch
 from .postprocess import MAX_FRAME_NODES as EXCLUSIVE_MAX_FRAME_NODES
-from .postprocess import check_cameras, check_threshold, exclusive_clusters, finalize, prune_and_cluster, threshold
+from .postprocess import (NO_SPLITTING_WITHOUT_PRUNING, STRONG_MAX_FRAME_NODES, check_cameras, check_threshold, exclusive_clusters, finalize,
+                          prune_and_cluster, strong_clusters, threshold)
 from .sharding import GraphBatch
 
 MAX_NODES = 4096
@@ -159,7 +168,8 @@ class FrameResult:
     def evaluate(self, final=True, against="kept"):
         """The per-frame metrics of inference.py:349-371 for this batch (gnn_cca_amd.evaluation.evaluate_frames): float64 [G, 16] on the
         device, columns evaluation.METRICS.  final=True scores final()'s predictions / partition (which waits for this batch's host
-        heuristics), final=False the device chain's pruned predictions / labels.  against='kept' (the default) scores the batch's own
+        heuristics), final=False the device chain's pruned predictions / labels (with pruning=False: the thresholded predictions and
+        their strongly connected components).  against='kept' (the default) scores the batch's own
         edges; against='dense' scores a capped batch as the dense graph with every dropped edge predicted 0 (evaluate_frames has the
         definition).  Computed once per mode."""
         from .evaluation import AGAINST, evaluate_frames
@@ -181,7 +191,9 @@ class FrameResult:
         """Every operating point of this batch in one pass: calibration.sweep_thresholds(self.batch, self.probs, thresholds, 'ge') ->
         float64 [T, G, 16] on the device; rows[t] is what evaluate(final=False) returns for a pipeline run at threshold thresholds[t].
         partition='exclusive': the operating points of exclusive() instead -- rows[t] is evaluate_frames(batch, ex['predictions'],
-        ex['labels']) of a pipeline run at thresholds[t]; like exclusive() it judges the batch's host camera ids before any launch."""
+        ex['labels']) of a pipeline run at thresholds[t]; like exclusive() it judges the batch's host camera ids before any launch.
+        Both partitions are built from MUTUAL pairs (the pruning rule), also in a pipeline with pruning=False: the sweep does not score the
+        strongly connected components."""
         from .calibration import sweep_thresholds
         if partition == "exclusive":
             b = self.batch
@@ -215,7 +227,8 @@ class FrameResult:
         """Camera-exclusive identity clusters of this batch (postprocess.exclusive_clusters on self.probs, the batch's device camera ids
         and the pipeline's threshold): dict(predictions, labels, n_clusters, cut, flags) on the device, no cluster holding two detections of
         one camera whatever the number of cameras, WITHOUT the wait final() needs.  Computed once; nothing else of this result changes.
-        On a capped batch the candidates are the mutual pairs, as pruning has it.  Compose: evaluate_frames(r.batch, ex['predictions'],
+        On a capped batch the candidates are the mutual pairs, as pruning has it -- also in a pipeline with pruning=False, whose own
+        labels are strongly connected components: this rule is not changed by that switch.  Compose: evaluate_frames(r.batch, ex['predictions'],
         ex['labels']), cluster_summaries(r.batch, ex['labels']) -> FrameLinker.  ValueError before any launch if the batch's camera ids
         leave [0, 64)."""
         ex = getattr(self, "_excl", None)
@@ -256,8 +269,10 @@ class FramePipeline:
         # the decision threshold on the edge probabilities: 0.5 is the reference's (inference.py:286-291) and every path below as it
         # always was; any other value in (0, 1) -- one chosen with r.sweep(...) -- takes the step-by-step path
         self.threshold = check_threshold(threshold)
-        if not pruning:
-            raise ValueError("FramePipeline prunes on the device (PRUNING = True, as config_inference.yaml:7 ships it)")
+        # PRUNING = False (config_inference.yaml:7): the clusters are the strongly connected components of the unpruned predictions
+        # (postprocess.strong_clusters) on the step-by-step path; the reference has no SPLITTING there
+        if not pruning and splitting:
+            raise ValueError(NO_SPLITTING_WITHOUT_PRUNING)
         # the cap and the radius gate: build_graph_batch's arguments and its refusals (radius with top_k / symmetric among them), here
         # before any batch (or the GPU) is touched
         self._sel = sel = select(top_k, rank_by, symmetric, radius, radius_unit)
@@ -342,7 +357,15 @@ class FramePipeline:
         r = FrameResult()
         r.batch, r.outputs = b, out
         r.probs, r.preds = threshold(out["classified_edges"][-1], at=self.threshold)
-        post = prune_and_cluster(b.edge_index, r.preds, b.x.shape[0], b.node_ptr_dev, b.edge_ptr_dev)
+        if self.switches[1]:
+            post = prune_and_cluster(b.edge_index, r.preds, b.x.shape[0], b.node_ptr_dev, b.edge_ptr_dev)
+        else:   # PRUNING = False: nothing is pruned, the clusters are the strongly connected components of the thresholded predictions
+            sizes_h = np.diff(np.asarray(b.node_ptr, dtype=np.int64))
+            widest = int(sizes_h.max()) if sizes_h.size else 0
+            if widest > STRONG_MAX_FRAME_NODES:
+                raise ValueError(f"a frame has {widest} detections; a pipeline with pruning=False takes frames of at most {STRONG_MAX_FRAME_NODES}")
+            post = strong_clusters(b.edge_index, r.preds, b.x.shape[0], b.node_ptr_dev, b.edge_ptr_dev, max_frame_nodes=widest)
+            post["pruned"] = post["predictions"]
         r.pruned, r.flow_out, r.flow_in, r.labels, r.n_clusters = post["pruned"], post["flow_out"], post["flow_in"], post["labels"], post["n_clusters"]
         r.triggers, r._switches, r._final = post["triggers"], self.switches, None
         r._keep = post
@@ -354,7 +377,7 @@ class FramePipeline:
         if not (node_embeds.is_cuda and reid_embeds.is_cuda):
             raise RuntimeError("gnn_cca_amd.pipeline runs on MI355X only (no CPU fallback)")
         n = int(node_embeds.shape[0])
-        if m.training or n > MAX_NODES or n == 0 or self.symmetric is not None or self.threshold != 0.5 or m._containers_hooked():
+        if m.training or n > MAX_NODES or n == 0 or self.symmetric is not None or self.threshold != 0.5 or not self.switches[1] or m._containers_hooked():
             return self._slow(xw, yw, ids, id_cam, graph_sizes, max_dist, node_embeds, reid_embeds)
         dev = reid_embeds.device
         lib = nat.lib()

@@ -10,6 +10,10 @@ configuration (config_inference.yaml:6-8 ROUNDING / PRUNING / SPLITTING = True; 
 raised a bit: native host code (csrc/post_host.cpp; SURVEY.md 8f keeps the bridge searches on the CPU), one frame at a time
 as the reference does.  A frame with no bit set already has its final partition.
 
+`strong_clusters` is PRUNING = False (config_inference.yaml:7): nothing is pruned and the clusters are the strongly connected components
+of the active edges (inference.py:302-304), one memset and one launch (csrc/strong.cuh); `finalize(..., pruning=False)` runs the host
+heuristics on that result without the pruning switch.
+
 `exclusive_clusters` has no counterpart in the reference: a partition in which no cluster holds two detections of one camera, for any
 number of cameras, computed on the device without a wait (csrc/exclusive.cuh).
 """
@@ -218,6 +222,98 @@ def exclusive_clusters(edge_index, probs, cam, n_nodes, node_ptr, edge_ptr, at=0
             "cut": ints[n_nodes + 1:n_nodes + 1 + g], "flags": ints[n_nodes + 1 + g:]}
 
 
+STRONG_MAX_FRAME_NODES = nat.STRONG_MAX_FRAME_NODES
+
+NO_SPLITTING_WITHOUT_PRUNING = ("SPLITTING = True needs PRUNING = True: the reference itself has no behaviour there -- disjoint_big_clusters "
+                                "(libs/utils.py:319-386) looks up the reverse of every edge it removes, and on unpruned predictions that "
+                                "reverse need not be active (inference.py:339-345 then ends in 'ValueError: ... is not in list')")
+
+
+def strong_clusters(edge_index, predictions, n_nodes, node_ptr=None, edge_ptr=None, max_frame_nodes=None):
+    """Identity clusters WITHOUT pruning: the strongly connected components of every frame's active edges, which is what
+    utils.compute_SCC_and_Clusters (libs/utils.py:295-317) returns under PRUNING = False (inference.py:302-304, 733-738, 904-908) -- a
+    directed cycle without a mutual pair is one identity -- on the device and without a synchronisation (csrc/strong.cuh; include/gnncca_mpn.h
+    has the rule in full).  One memset and one launch: no graph plan, no workspace.  On a directed capped list (top_k=) these are the
+    reference's own clusters, with no closure and no wait.  On symmetric predictions the result is prune_and_cluster's exactly.
+
+    edge_index int64 [2, E], predictions [E] or [E, 1] (1 = active): device tensors.  node_ptr / edge_ptr (both or neither): the frame
+    ranges as prune_and_cluster takes them (sequences of G + 1 ints, or int32 device tensors); without them the whole graph is one frame.
+    With device tensors the largest frame is not known on the host: pass max_frame_nodes (default: min(n_nodes, 1024), which sizes the
+    kernel's LDS for the worst case, 128 KiB).
+
+    -> dict(predictions int64 [E]: the input, contiguous -- nothing is pruned; flow_out / flow_in int32 [N]: active edges leaving / entering
+    each node; labels int32 [N]: the smallest node id of the node's component; n_clusters int32 [1]; triggers int32 [G]: bit 0 = a node with
+    a flow above 3, bit 1 = a component of more than four members (prune_and_cluster's bits); flags uint32-valued int32 [G]: 0, or 2 = the
+    frame's ranges do not fit -- every node of such a frame is its own cluster with flows and triggers 0), all on the device.  ValueError
+    before any launch: mismatched lengths, offsets that do not ascend from 0 to N / E, a frame of more than 1024 detections (where the host
+    knows the sizes)."""
+    if (node_ptr is None) != (edge_ptr is None):
+        raise ValueError("node_ptr and edge_ptr go together")
+    n_nodes = int(n_nodes)
+    if n_nodes < 0:
+        raise ValueError(f"n_nodes must not be negative, not {n_nodes}")
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError(f"edge_index must be [2, E], not {tuple(edge_index.shape)}")
+    e = int(edge_index.shape[1])
+    if predictions.numel() != e:
+        raise ValueError(f"predictions [{predictions.numel()}] does not match edge_index (E={e})")
+    g = 0
+    if node_ptr is not None:
+        np_h, ep_h = _host_ptr(node_ptr, "node_ptr"), _host_ptr(edge_ptr, "edge_ptr")
+        g = (np_h.size if np_h is not None else node_ptr.numel()) - 1
+        if (ep_h.size if ep_h is not None else edge_ptr.numel()) != g + 1 or g < 1:
+            raise ValueError("node_ptr / edge_ptr must both have G + 1 entries")
+        if np_h is not None:
+            if int(np_h[0]) != 0 or int(np_h[-1]) != n_nodes or (np.diff(np_h) < 0).any():
+                raise ValueError("node_ptr must ascend from 0 to n_nodes")
+            widest = int(np.diff(np_h).max())
+            if widest > STRONG_MAX_FRAME_NODES:
+                raise ValueError(f"a frame has {widest} detections; strong_clusters takes frames of at most {STRONG_MAX_FRAME_NODES}")
+            max_frame_nodes = widest if max_frame_nodes is None else max_frame_nodes
+        if ep_h is not None and (int(ep_h[0]) != 0 or int(ep_h[-1]) != e or (np.diff(ep_h) < 0).any()):
+            raise ValueError("edge_ptr must ascend from 0 to E")
+    elif n_nodes > STRONG_MAX_FRAME_NODES:
+        raise ValueError(f"the graph has {n_nodes} detections; strong_clusters takes frames of at most {STRONG_MAX_FRAME_NODES} "
+                         "(pass node_ptr / edge_ptr for a batch of frames)")
+    if max_frame_nodes is None:
+        max_frame_nodes = min(n_nodes, STRONG_MAX_FRAME_NODES)
+    max_frame_nodes = int(max_frame_nodes)
+    if not 0 <= max_frame_nodes <= STRONG_MAX_FRAME_NODES:
+        raise ValueError(f"max_frame_nodes must lie in [0, {STRONG_MAX_FRAME_NODES}], not {max_frame_nodes}")
+    max_frame_nodes = min(max_frame_nodes, n_nodes)
+    if not (edge_index.is_cuda and predictions.is_cuda):
+        raise RuntimeError("gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)")
+    dev = edge_index.device
+    lib = nat.lib()
+    with _on(dev):
+        ei = edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.long().contiguous()
+        pred = predictions.reshape(-1)
+        if pred.dtype != torch.int64 or not pred.is_contiguous():
+            pred = pred.long().contiguous()
+
+        def as_dev(v):
+            if torch.is_tensor(v):
+                if v.dtype == torch.int32 and v.device == dev and v.is_contiguous():
+                    return v
+                return v.to(device=dev, dtype=torch.int32).contiguous()
+            return torch.tensor([int(q) for q in v], dtype=torch.int32).to(dev)
+        np_dev, ep_dev = (as_dev(node_ptr), as_dev(edge_ptr)) if g else (None, None)
+        n_trig = max(g, 1)
+        # flow_out | flow_in | n_clusters (zeroed by ONE memset) | labels | triggers | flags
+        ints = torch.empty(3 * n_nodes + 1 + 2 * n_trig, dtype=torch.int32, device=dev)
+        ip = ints.data_ptr()
+        o_lab, o_trig = 2 * n_nodes + 1, 3 * n_nodes + 1
+        st = lib.gnncca_post_strong_frames(ei.data_ptr() if e else None, pred.data_ptr() if e else None, n_nodes, e,
+                                           np_dev.data_ptr() if g else None, ep_dev.data_ptr() if g else None, g, max_frame_nodes,
+                                           ip, ip + 4 * n_nodes, ip + 4 * o_lab, ip + 8 * n_nodes, ip + 4 * o_trig, ip + 4 * (o_trig + n_trig),
+                                           _stream(dev))
+    if st:
+        nat.check(st, "gnncca_post_strong_frames")
+    return {"predictions": pred, "flow_out": ints[:n_nodes], "flow_in": ints[n_nodes:2 * n_nodes], "labels": ints[o_lab:o_lab + n_nodes],
+            "n_clusters": ints[2 * n_nodes:2 * n_nodes + 1], "triggers": ints[o_trig:o_trig + n_trig], "flags": ints[o_trig + n_trig:],
+            "_keep": (ei, np_dev, ep_dev)}
+
+
 def finalize(edge_index, probs, pruned, labels, n_clusters, triggers, node_ptr=None, edge_ptr=None, rounding=True, pruning=True,
              splitting=True):
     """The reference's FINAL predictions and identity clusters under the three switches of config_inference.yaml:6-8 (inference.py:306-345:
@@ -230,9 +326,14 @@ def finalize(edge_index, probs, pruned, labels, n_clusters, triggers, node_ptr=N
     `node_ptr` / `edge_ptr`: HOST sequences of G + 1 ints (GraphBatch.node_ptr / .edge_ptr); None = the whole graph is one frame.
 
     -> dict(predictions int64 [E], labels int32 [N], n_clusters int32 [1] on the device, frames_finalized: list of frame ids,
-            triggers: host int32 [G]).  `pruning=False` is refused: the device chain has already pruned."""
-    if not pruning:
-        raise ValueError("finalize works on the pruned predictions of prune_and_cluster (PRUNING = True, as shipped)")
+            triggers: host int32 [G]).
+
+    `pruning=False` (PRUNING: False): `pruned` is then the THRESHOLDED predictions and labels / n_clusters / triggers are those of
+    `strong_clusters` on them (the strongly connected components of the unpruned edges, inference.py:302-304); the host pass gets the
+    switches without the pruning, so only ROUNDING can change a frame (inference.py:316-329 on unpruned predictions).  `pruning=False` with
+    `splitting=True` is a ValueError: the reference has no behaviour there (NO_SPLITTING_WITHOUT_PRUNING)."""
+    if not pruning and splitting:
+        raise ValueError(NO_SPLITTING_WITHOUT_PRUNING)
     trig = triggers.cpu().numpy()          # the one synchronisation of this stage
     want = (nat.POST_TRIGGER_ROUNDING if rounding else 0) | (nat.POST_TRIGGER_SPLITTING if splitting else 0)
     todo = np.nonzero(trig & want)[0].tolist()
@@ -248,7 +349,7 @@ def finalize(edge_index, probs, pruned, labels, n_clusters, triggers, node_ptr=N
     lab = labels.cpu().numpy().copy()
     src, dst = np.ascontiguousarray(ei[0]), np.ascontiguousarray(ei[1])
     total = int(n_clusters.cpu().numpy()[0])
-    switches = (nat.POST_ROUNDING if rounding else 0) | nat.POST_PRUNING | (nat.POST_SPLITTING if splitting else 0)
+    switches = (nat.POST_ROUNDING if rounding else 0) | (nat.POST_PRUNING if pruning else 0) | (nat.POST_SPLITTING if splitting else 0)
     lib = nat.lib()
     np_h, ep_h = np.asarray(node_ptr, dtype=np.int32), np.asarray(edge_ptr, dtype=np.int32)
     listed, k_new = np.asarray(todo, dtype=np.int32), np.zeros(len(todo), dtype=np.int32)

@@ -497,6 +497,46 @@ GNNCCA_API int gnncca_post_exclusive_frames(const int64_t* edge_index, const flo
                                             int32_t* n_clusters_out, int32_t* cut_out, uint32_t* flags_out, void* workspace,
                                             size_t workspace_bytes, gnncca_stream_t stream);
 
+/* ---- Identity clusters WITHOUT pruning (csrc/strong.cuh): strongly connected components on the device ---------------------------------
+ * With PRUNING = False (config_inference.yaml:7; inference.py:302-304, 733-738, 904-908) the reference's utils.compute_SCC_and_Clusters
+ * (libs/utils.py:295-317) clusters the digraph of ALL active edges: a directed cycle without a single mutual pair is one identity.
+ * gnncca_post_prune_cluster* computes components of the pruned, symmetric edge set; this entry computes the strongly connected
+ * components of the unpruned one -- also the reference's own rule for a directed capped list (gnncca_build_edges_topk), with no closure
+ * and no host wait.  Frame ranges node_ptr_dev / edge_ptr_dev (int32 [n_frames + 1], DEVICE memory) as gnncca_post_prune_cluster_frames
+ * takes them; both NULL with n_frames == 0: the whole graph is one frame, as gnncca_post_prune_cluster has it.  `max_frame_nodes`: the
+ * largest frame as the caller's host copy of node_ptr knows it (at most GNNCCA_STRONG_MAX_FRAME_NODES).  The rule for frame g:
+ *   active       edge k is active iff predictions[k] == 1 and both of its ends lie in [node_ptr[g], node_ptr[g + 1]); everything else is
+ *                ignored (gnncca_post_prune_cluster_frames' rule).  The edge list may be in any order; self loops and duplicates are harmless.
+ *   reachability a bit matrix in LDS, n_pad rows of n_pad / 32 words (n_pad = the frame's node count rounded up to 32), diagonal set,
+ *                active edges set; closed transitively by repeated squaring in place (the owner of a word ORs in that word of every row
+ *                whose bit is set in its own row; every set bit is a true fact at all times, so a row read before or after its update
+ *                of the same round is sound).
+ *   rounds       a COUNTED loop of ceil(log2(n_pad)) + 1 rounds at most (11 at 1024 nodes): r rounds cover every path of 2^r edges, a
+ *                simple path has fewer than n_pad, and the last round only detects that nothing changes.  A round that changes nothing
+ *                ends the loop early; nothing else about the run time depends on the data.
+ *   outputs      labels_out[v] (int32 [N]) = the smallest batch-global node id u with v -> u and u -> v reachable (gnncca_post_prune_cluster's
+ *                convention); flow_out / flow_in (int32 [N]) = active, UNPRUNED edges leaving / entering each node; *n_clusters_out
+ *                (int32) = the batch total; triggers_out[g] (int32 [max(n_frames, 1)]) bit 0 (GNNCCA_POST_TRIGGER_ROUNDING) = a node of
+ *                the frame has flow_out or flow_in > 3, bit 1 (GNNCCA_POST_TRIGGER_SPLITTING) = a component has more than four members;
+ *                flags_out[g] (uint32 [max(n_frames, 1)]) = 0, or the refusal below.
+ * ORs, integer adds and a scan in id order only: two runs give the same bits, and a frame's result does not depend on the rest of the
+ * batch.  On symmetric predictions labels, counts, flows and triggers are gnncca_post_prune_cluster_frames_ex's exactly.
+ * flags_out[g] = GNNCCA_STRONG_BAD_RANGE: the frame's ranges do not fit (gnncca_post_exclusive_frames' test; a frame larger than
+ * max_frame_nodes rounded up to 32 included).  Every node of such a frame is its own cluster, its flows and its trigger word are 0 (as far
+ * as the ranges allow writing at all); other frames are unaffected.
+ * Launches: one memset of the counters when they lie back to back (flow_out | flow_in | n_clusters, as gnn_cca_amd.postprocess lays them
+ * out; three memsets otherwise) and one kernel, one workgroup per frame of 64, 256 or 1024 threads by max_frame_nodes.  Dynamic LDS:
+ * P * P / 8 bytes for P = max_frame_nodes rounded up to 32 (128 B at 32, 2 KiB at 128, 128 KiB at 1024).  No workspace, no allocation, no
+ * host synchronisation: capturable.  GNNCCA_ERR_INVALID_ARG before any launch: max_frame_nodes outside [0, GNNCCA_STRONG_MAX_FRAME_NODES]
+ * or above n_nodes, a negative size, frame ranges given half or with n_frames == 0 (or n_frames > 0 without them), a null pointer where
+ * the count is positive (n_clusters_out, triggers_out and flags_out always hold one word at least).  n_edges == 0 and n_nodes == 0 are legal. */
+#define GNNCCA_STRONG_MAX_FRAME_NODES 1024
+#define GNNCCA_STRONG_BAD_RANGE 2u
+GNNCCA_API int gnncca_post_strong_frames(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                                         const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                         int32_t max_frame_nodes, int32_t* flow_out, int32_t* flow_in, int32_t* labels_out,
+                                         int32_t* n_clusters_out, int32_t* triggers_out, uint32_t* flags_out, gnncca_stream_t stream);
+
 /* Row N2, second half, for ONE frame on the HOST ("bridges-based heuristics stay on CPU"): the reference's call sequence
  * inference.py:306-345 after the threshold -- by the three switches of config_inference.yaml:6-8 (all True as shipped):
  * utils.remove_edges_single_direction (libs/utils.py:387-404) -> utils.compute_rounding (25-173) -> remove_edges_single_direction ->
@@ -854,9 +894,10 @@ GNNCCA_API int gnncca_eval_sweep_exclusive(const int64_t* edge_index, const floa
  *              batch-global id of its component; rows_out[t][g] (fp64 [n_points][n_frames][16]) = the 16 columns of
  *              gnncca_eval_frames.  The workgroup body is gnncca_eval_sweep's own code with another predicate: with one score, no
  *              divisor and GNNCCA_CMP_GE / GNNCCA_CMP_LE the rows and labels are that entry's bit for bit.
- * NOT reproduced: the reference clusters with the strongly connected components of the digraph of active edges and does not prune; with
- * a score that is not symmetric (F.pairwise_distance adds eps to a - b) a directed cycle without a mutual pair joins nodes there, here
- * only mutual pairs join.  inference.py:892,896 use the last graph's labels and max_dist[0] for a whole batch; here every frame has its
+ * NOT reproduced BY THIS SWEEP: the reference clusters with the strongly connected components of the digraph of active edges and does not
+ * prune; with a score that is not symmetric (F.pairwise_distance adds eps to a - b) a directed cycle without a mutual pair joins nodes
+ * there, here only mutual pairs join.  The reference's partition of ONE prediction vector is gnncca_post_strong_frames' (above); the
+ * sweep over that partition does not exist.  inference.py:892,896 use the last graph's labels and max_dist[0] for a whole batch; here every frame has its
  * own.  A frame whose ranges do not fit gets a NaN row; edge lists with duplicate ordered pairs are unspecified (as above).
  * Four launches whatever n_points and n_scores are (graph plan, plan finish, gnncca_eval_sweep's prepare kernel unchanged, one launch of
  * n_frames x n_points workgroups); the workspace (gnncca_eval_sweep_joint_workspace_bytes) is gnncca_eval_sweep's, O(E + N); no host
