@@ -9,6 +9,7 @@ launches and one int64 [E] prediction vector per threshold; `sweep_thresholds` i
     rows = sweep_thresholds(batch, scores, thresholds)             # float64 [T, G, 16] on the device, columns evaluation.METRICS
     rows = r.sweep(thresholds)                                     # r: a pipeline.FrameResult, its probabilities, keep='ge'
     rows = r.sweep(thresholds, partition='exclusive')              # the operating points of r.exclusive(), not of the components
+    rows = r.sweep(thresholds, partition='strong')                 # ... of a pipeline with pruning=False: strongly connected clusters
     acc = SweepAccumulator(thresholds); acc.add(rows) ...          # no synchronisation
     res = acc.result()                                             # one synchronisation
     th = acc.thresholds[acc.best('F_micro')]                       # every threshold of maximal F (main.py:190)
@@ -18,10 +19,12 @@ The rule for threshold t (include/gnncca_mpn.h has it in full): an edge is activ
 distances); it is kept iff its reverse edge is active too; the partition is the connected components of the kept edges; the row is
 evaluate_frames' for those predictions and that partition.  With partition='exclusive' the partition is the camera-exclusive one of
 postprocess.exclusive_clusters at thresholds[t] and the predictions are its predictions (one pass as well: a pair's place in the rule's
-order does not depend on the threshold).
+order does not depend on the threshold).  With partition='strong' nothing is pruned and the partition is the strongly connected
+components of the active edges (postprocess.strong_clusters at thresholds[t]; two launches, csrc/eval_sweep_strong.cuh).
 
 Several scores at once (csrc/eval_sweep_joint.cuh): the reference's position baselines keep an edge iff its ground distance AND its ReID
-distance pass (inference.py:722-724, :896), and their tables were swept one axis at a time.
+distance pass (inference.py:722-724, :896), and their tables were swept one axis at a time.  partition='strong' in either call is the
+reference's own clustering for them: no pruning, strongly connected components.
 
     rows = sweep_joint(batch, [attr[:, 0], attr[:, 2]], points, ['lt', 'lt'], frame_div=div)   # points host [T, 2]; float64 [T, G, 16]
     rows = sweep_grid(batch, [attr[:, 0], attr[:, 2]], [axis0, axis1], ['lt', 'lt'])           # ... viewed [T0, T1, G, 16]
@@ -45,7 +48,9 @@ from .postprocess import check_cameras, check_threshold
 
 MAX_THRESHOLDS = nat.SWEEP_MAX_THRESHOLDS
 KEEP = ("ge", "le")
-PARTITIONS = ("components", "exclusive")
+PARTITIONS = ("components", "exclusive")            # the partitions built from mutual pairs (the pruning rule)
+SWEEP_PARTITIONS = PARTITIONS + ("strong",)         # every partition sweep_thresholds takes: 'strong' prunes nothing
+JOINT_PARTITIONS = ("components", "strong")   # the camera-exclusive partition is not swept jointly
 MICRO = ("P_micro", "R_micro", "F_micro")
 
 
@@ -76,11 +81,23 @@ def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False, 
     ex['labels'] -- the threshold of FrameResult.exclusive() is calibrated on this partition, not on the components.  `cam`: int32 [N]
     camera ids on the device (default: batch.cam_dev).  Its domain is exclusive_clusters': every threshold strictly inside (0, 1),
     keep='ge' only (the rule needs positive weights), camera ids in [0, 64) (judged on the host where batch.cam_host or a host `cam`
-    exists; an id that reaches the device makes its frame "every node its own cluster"), frames of at most 4096 detections."""
+    exists; an id that reaches the device makes its frame "every node its own cluster"), frames of at most 4096 detections.
+
+    partition='strong' sweeps the STRONGLY CONNECTED clusters of the unpruned edges (csrc/eval_sweep_strong.cuh), the reference's rule
+    with PRUNING off: rows[t] bit for bit evaluate_frames(batch, pred_t, strong_clusters(batch.edge_index, pred_t, ...)['labels']) with
+    pred_t the active edges at thresholds[t], nothing pruned -- the threshold of a FramePipeline(pruning=False, splitting=False) is
+    calibrated on this partition.  Both `keep` values and any finite thresholds are allowed; `cam` is ignored; frames of at most 1024
+    detections (a frame's reachability matrix lives in LDS).  Two launches whatever the number of thresholds."""
     if keep not in KEEP:
         raise ValueError(f"keep must be 'ge' or 'le', not {keep!r}")
-    if not isinstance(partition, str) or partition not in PARTITIONS:
-        raise ValueError(f"partition must be 'components' or 'exclusive', not {partition!r}")
+    if not isinstance(partition, str) or partition not in SWEEP_PARTITIONS:
+        raise ValueError(f"partition must be one of {SWEEP_PARTITIONS}, not {partition!r}")
+    if partition == "strong":   # the K = 1 case of the joint form (csrc/eval_sweep_strong.cuh): the same entry, the same host checks
+        th = _thresholds(thresholds)
+        if not torch.is_tensor(scores) or scores.numel() != int(batch.edge_index.shape[1]):
+            size = scores.numel() if torch.is_tensor(scores) else type(scores).__name__
+            raise ValueError(f"scores [{size}] do not match the batch (E={int(batch.edge_index.shape[1])})")
+        return sweep_joint(batch, [scores.reshape(-1)], th.reshape(-1, 1), [keep], return_labels=return_labels, partition="strong")
     exclusive = partition == "exclusive"
     if exclusive and keep != "ge":
         raise ValueError("partition='exclusive' takes keep='ge' only: the camera-exclusive rule orders pairs by a positive weight")
@@ -249,7 +266,7 @@ def _score_list(scores, e):
     return out
 
 
-def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False):
+def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False, partition="components"):
     """Scores every frame of `batch` at every point of a CONJUNCTION of K conditions (csrc/eval_sweep_joint.cuh): the rule of the
     reference's position baselines (inference.py:722-724, :896).  `scores`: a sequence of K (1 to 4) device tensors [E] or [E, 1] --
     float32 views with a stride, such as batch.edge_attr[:, 0], are read in place, not copied -- or one [K, E] tensor; `points`: host
@@ -264,7 +281,17 @@ def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False
 
     Every argument is checked on the host (ValueError) before the GPU is touched; points and divisors go up through pinned memory
     without a wait; four launches whatever T and K are.  Returns float64 [T, G, 16] on the device, and with return_labels=True also
-    int32 [T, N]."""
+    int32 [T, N].
+
+    partition='strong': the reference's own rule for these baselines (inference.py:733-738, 904-908) -- nothing is pruned, no reverse
+    edge is consulted, and the partition is the strongly connected components of the active edges (csrc/eval_sweep_strong.cuh): rows[t]
+    bit for bit evaluate_frames(batch, pred_t, strong_clusters(batch.edge_index, pred_t, ...)['labels']) for the int64 vector pred_t of
+    active edges.  Two launches; frames of at most 1024 detections.  partition='exclusive' is a ValueError: the camera-exclusive
+    partition is swept for a single score only (sweep_thresholds)."""
+    if not isinstance(partition, str) or partition not in JOINT_PARTITIONS:
+        raise ValueError(f"partition must be one of {JOINT_PARTITIONS} in a joint sweep (the camera-exclusive partition is swept by "
+                         f"sweep_thresholds only), not {partition!r}")
+    strong = partition == "strong"
     node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
     g = len(node_ptr) - 1
     n = int(node_ptr[-1]) if g > 0 else 0
@@ -294,8 +321,9 @@ def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False
             raise ValueError("frame_div must be finite and > 0")
         div = np.ascontiguousarray(div)
     max_n = int(np.diff(node_ptr).max()) if g > 0 else 0
-    if max_n > MAX_FRAME_NODES:
-        raise ValueError(f"a frame has {max_n} detections; sweep_joint scores frames of at most {MAX_FRAME_NODES}")
+    limit = nat.STRONG_MAX_FRAME_NODES if strong else MAX_FRAME_NODES
+    if max_n > limit:
+        raise ValueError(f"a frame has {max_n} detections; sweep_joint(partition={partition!r}) scores frames of at most {limit}")
     if batch.edge_labels.numel() != e:
         raise ValueError(f"edge_labels [{batch.edge_labels.numel()}] do not match the batch (E={e})")
     if not all(s.is_cuda for s in sl):
@@ -328,13 +356,14 @@ def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False
             ptrs = (nat.C.c_void_p * k)(*[s.data_ptr() if e else None for s in flat])
             strides = (nat.C.c_int64 * k)(*[max(int(s.stride(0)), 1) if e else 1 for s in flat])
             cmps = (nat.C.c_int32 * k)(*[nat.CMP[c] for c in keep])
-            ws_bytes = lib.gnncca_eval_sweep_joint_workspace_bytes(n, e, g)
+            name = "gnncca_eval_sweep_strong" if strong else "gnncca_eval_sweep_joint"   # (one argument list)
+            ws_bytes = getattr(lib, name + "_workspace_bytes")(n, e, g)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            st = lib.gnncca_eval_sweep_joint(ei.data_ptr() if e else None, el.data_ptr() if e else None, ptrs, strides, cmps, k, n, e,
-                                             nptr.data_ptr(), eptr.data_ptr(), g, max_n, up.data_ptr(), t, div_ptr, rows.data_ptr(),
-                                             labels.data_ptr() if return_labels and n else None, ws.data_ptr(), ws_bytes, _raw_stream(dev))
+            st = getattr(lib, name)(ei.data_ptr() if e else None, el.data_ptr() if e else None, ptrs, strides, cmps, k, n, e,
+                                    nptr.data_ptr(), eptr.data_ptr(), g, max_n, up.data_ptr(), t, div_ptr, rows.data_ptr(),
+                                    labels.data_ptr() if return_labels and n else None, ws.data_ptr(), ws_bytes, _raw_stream(dev))
             if st:
-                nat.check(st, "gnncca_eval_sweep_joint")
+                nat.check(st, name)
     return (rows, labels) if return_labels else rows
 
 
@@ -354,12 +383,12 @@ def grid_points(axes):
     return np.stack([m.reshape(-1) for m in np.meshgrid(*axes, indexing="ij")], axis=1), shape
 
 
-def sweep_grid(batch, scores, axes, keep, frame_div=None, return_labels=False):
+def sweep_grid(batch, scores, axes, keep, frame_div=None, return_labels=False, partition="components"):
     """sweep_joint over the Cartesian product of K host sequences `axes` (C order: the last axis varies fastest) -- main.py's own 0.01
     step on two axes is 100 x 100 points in one call.  Rows come back viewed as [T1, ..., TK, G, 16] (labels as [T1, ..., TK, N]); a
-    product above 16384 points is a ValueError."""
+    product above 16384 points is a ValueError.  `partition`: sweep_joint's ('components' or 'strong')."""
     pts, shape = grid_points(axes)
-    out = sweep_joint(batch, scores, pts, keep, frame_div=frame_div, return_labels=return_labels)
+    out = sweep_joint(batch, scores, pts, keep, frame_div=frame_div, return_labels=return_labels, partition=partition)
     if return_labels:
         rows, labels = out
         return rows.view(*shape, *rows.shape[1:]), labels.view(*shape, labels.shape[1])

@@ -13,10 +13,10 @@
 //              the widened fp32 score; a NaN score is never active under any comparator.
 //   pruning, partition, scores   gnncca_eval_sweep's: kept iff the reverse edge of the same frame is active too, the connected
 //              components of the kept edges, the 16 columns of gnncca_eval_frames.
-// Not reproduced: the reference clusters with the strongly connected components of the digraph of active edges and does not prune, so a
-// directed cycle without a mutual pair joins nodes there (possible when a score is not symmetric: F.pairwise_distance adds eps to
-// a - b); here only mutual pairs join.  And inference.py:892,896 use the LAST graph's labels and max_dist[0] for a whole batch; here every
-// frame has its own labels and its own divisor.
+// Not reproduced by THIS kernel: the reference clusters with the strongly connected components of the digraph of active edges and does not
+// prune, so a directed cycle without a mutual pair joins nodes there (possible when a score is not symmetric: F.pairwise_distance adds
+// eps to a - b); here only mutual pairs join.  eval_sweep_strong.cuh is that rule, on the same arguments.  And inference.py:892,896 use
+// the LAST graph's labels and max_dist[0] for a whole batch; here every frame has its own labels and its own divisor.
 //
 // Launches (their number depends on neither T nor K): the graph plan, the plan finish, eval_sweep_prepare_kernel, eval_sweep_joint_kernel
 // with grid (G, T).  Workspace: gnncca_eval_sweep's layout, O(E + N).
@@ -36,12 +36,11 @@ __device__ __forceinline__ bool joint_compare(double s, int cmp, double th) {   
     return cmp == GNNCCA_CMP_GE ? s >= th : cmp == GNNCCA_CMP_GT ? s > th : cmp == GNNCCA_CMP_LE ? s <= th : s < th;
 }
 
-// "is edge k predicted" of the joint sweep: every condition holds on it and on the reverse edge of the same frame
-struct SweepJointPred {
+// "is edge k active" at one operating point: every condition holds on it.  The test every joint predicate is made of (the sweep over
+// the strongly connected components, eval_sweep_strong.cuh, uses it alone).
+struct JointActive {
     JointScores sc;
     double th[kJointMaxScores];
-    const int* __restrict__ rev;
-    long long k0, k1;   // the frame's edges
     __device__ __forceinline__ bool active(long long k) const {
         bool on = true;
 #pragma unroll
@@ -49,6 +48,26 @@ struct SweepJointPred {
             if (q < sc.K) on = on && joint_compare((double)sc.p[q][k * sc.stride[q]], sc.cmp[q], th[q]);
         return on;
     }
+    // th[q] of workgroup (g, t): points[t][q], divided by frame_div[q][g] where given (the same operands in every thread: one value)
+    __device__ __forceinline__ void set_point(const JointScores& s, const double* __restrict__ points, const double* __restrict__ frame_div,
+                                              int t, int g, int n_frames) {
+        sc = s;
+#pragma unroll
+        for (int q = 0; q < kJointMaxScores; ++q) {
+            double v = 0.0;
+            if (q < s.K) {
+                v = points[(size_t)t * s.K + q];
+                if (frame_div) v = v / frame_div[(size_t)q * n_frames + g];
+            }
+            th[q] = v;
+        }
+    }
+};
+
+// "is edge k predicted" of the joint sweep: every condition holds on it and on the reverse edge of the same frame
+struct SweepJointPred : JointActive {
+    const int* __restrict__ rev;
+    long long k0, k1;   // the frame's edges
     __device__ __forceinline__ long long operator()(long long k) const {
         if (!active(k)) return 0;
         const long long r = rev[k];
@@ -71,16 +90,8 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_joint_kernel(const long long
     SweepFrame f;
     if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, P_lds, row, lab_t, f)) return;
     SweepJointPred pred;
-    pred.sc = sc, pred.rev = rev, pred.k0 = f.k0, pred.k1 = f.k1;
-#pragma unroll
-    for (int q = 0; q < kJointMaxScores; ++q) {
-        double th = 0.0;
-        if (q < sc.K) {   // (the same operands in every thread of the workgroup: one value)
-            th = points[(size_t)t * sc.K + q];
-            if (frame_div) th = th / frame_div[(size_t)q * n_frames + g];
-        }
-        pred.th[q] = th;
-    }
+    pred.set_point(sc, points, frame_div, t, g, n_frames);
+    pred.rev = rev, pred.k0 = f.k0, pred.k1 = f.k1;
     eval_sweep_body<BLOCK>(g, f, pred, ei, E, elab, N_all, node_ptr, edge_ptr, P_lds, row, lab_t, lf_ws);
 }
 

@@ -392,6 +392,7 @@ __global__ __launch_bounds__(BLOCK) void eval_frames_kernel(const long long* __r
 #include "eval_sweep.cuh"            // the threshold sweep: its kernels call eval_frame_body
 #include "eval_sweep_exclusive.cuh"  // the same sweep over the camera-exclusive partition
 #include "eval_sweep_joint.cuh"      // the sweep of a conjunction of conditions: eval_sweep.cuh's workgroup body, another predicate
+#include "eval_sweep_strong.cuh"     // the joint sweep over the strongly connected components of the unpruned edges: no plan, no rev
 #include "rank_metrics.cuh"          // threshold-free ranking scores per frame (AUROC, AP, best F) and the pooled curve's histograms
 
 using namespace gnncca;
@@ -662,6 +663,66 @@ int gnncca_eval_sweep_joint(const int64_t* edge_index, const float* edge_labels,
                        frame_div_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
     if (P <= 64) GNNCCA_SWEEP_JOINT(64); else GNNCCA_SWEEP_JOINT(256);   // (eval_frames' choice)
 #undef GNNCCA_SWEEP_JOINT
+    HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+// ---- the sweep over the strongly connected clusters (eval_sweep_strong.cuh) -------------------------------------------------------------
+// workspace: the lgamma tables fp64 [N + G], nothing else (no plan, no reverse edges)
+size_t gnncca_eval_sweep_strong_workspace_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_frames) {
+    return gnncca_eval_workspace_bytes(n_nodes, n_edges, n_frames);
+}
+
+int gnncca_eval_sweep_strong(const int64_t* edge_index, const float* edge_labels, const float* const* scores, const int64_t* score_strides,
+                             const int32_t* comparators, int32_t n_scores, int64_t n_nodes, int64_t n_edges, const int32_t* node_ptr_dev,
+                             const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes, const double* points_dev,
+                             int32_t n_points, const double* frame_div_dev, double* rows_out, int32_t* labels_out, void* workspace,
+                             size_t workspace_bytes, gnncca_stream_t stream) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0 || n_points < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_scores < 1 || n_scores > GNNCCA_EVAL_JOINT_MAX_SCORES) return GNNCCA_ERR_INVALID_ARG;
+    if (n_points > GNNCCA_EVAL_JOINT_MAX_POINTS) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > kSweepStrongMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if (!scores || !score_strides || !comparators) return GNNCCA_ERR_INVALID_ARG;
+    JointScores sc;
+    std::memset(&sc, 0, sizeof(sc));
+    sc.K = n_scores;
+    for (int k = 0; k < n_scores; ++k) {
+        if (comparators[k] < GNNCCA_CMP_GE || comparators[k] > GNNCCA_CMP_LT || score_strides[k] < 1) return GNNCCA_ERR_INVALID_ARG;
+        if (n_edges > 0 && !scores[k]) return GNNCCA_ERR_INVALID_ARG;
+        sc.p[k] = scores[k], sc.stride[k] = score_strides[k], sc.cmp[k] = comparators[k];
+    }
+    if (n_frames == 0 || n_points == 0) return GNNCCA_OK;
+    if (!points_dev || !node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!edge_index || !edge_labels)) return GNNCCA_ERR_INVALID_ARG;
+    if (workspace_bytes < gnncca_eval_sweep_strong_workspace_bytes(n_nodes, n_edges, n_frames)) return GNNCCA_ERR_WORKSPACE;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    int P = 1;
+    while (P < max_frame_nodes) P <<= 1;
+    const size_t lds = sweep_strong_shared_bytes(P) + (size_t)P * sizeof(unsigned short);
+    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (gnncca_eval_sweep_exclusive's way)
+        static thread_local int attr_dev = -1;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if (attr_dev != dev) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_sweep_strong_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)(sweep_strong_shared_bytes(kSweepStrongMaxNodes) + kSweepStrongMaxNodes * sizeof(unsigned short))));
+            attr_dev = dev;
+        }
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int N = (int)n_nodes, E = (int)n_edges;
+    const long long* ei = reinterpret_cast<const long long*>(edge_index);
+    double* lf = static_cast<double*>(workspace);
+    // the lgamma tables: eval_sweep_prepare_kernel's frame blocks alone (no edge blocks: nothing about edges is read)
+    hipLaunchKernelGGL(eval_sweep_prepare_kernel, dim3((unsigned)n_frames), dim3(256), 0, st, ei, (long long)E, (const int*)nullptr,
+                       (const int*)nullptr, (const int*)nullptr, (const unsigned*)nullptr, (int*)nullptr, 0, node_ptr_dev, N, lf);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid((unsigned)n_frames, (unsigned)n_points);
+#define GNNCCA_SWEEP_STRONG(B)                                                                                                            \
+    hipLaunchKernelGGL((eval_sweep_strong_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, sc, points_dev, frame_div_dev, \
+                       N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
+    if (P <= 64) GNNCCA_SWEEP_STRONG(64); else GNNCCA_SWEEP_STRONG(256);   // (eval_frames' choice)
+#undef GNNCCA_SWEEP_STRONG
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }

@@ -29,14 +29,11 @@
 // flags_out[g] = GNNCCA_STRONG_BAD_RANGE: the frame's ranges do not fit (excl_frame_ok, the LDS capacity P included); every node of such a
 // frame is its own cluster, its flows and its trigger word are 0 -- as far as the ranges allow writing at all.
 #include "excl_common.cuh"   // excl_frame_ok: one test of a frame's ranges for every one-workgroup-per-frame kernel of this unit
+#include "strong_closure.cuh"   // the matrix's diagonal, its closure and a node's label: shared with the sweep over this partition
 
 namespace gnncca {
 
 constexpr int kStrongMaxNodes = GNNCCA_STRONG_MAX_FRAME_NODES;
-constexpr int kStrongMaxRounds = 12;   // ceil(log2(1024)) + 1 = 11 (one flag word per round: no reset, one barrier per round)
-
-__device__ __forceinline__ unsigned strong_ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void strong_st(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // Workgroup g: frame g (node_ptr / edge_ptr null: the whole graph is the one frame).  Dynamic LDS: R, P * (P / 32) words, P = the largest
 // frame rounded up to 32 (128 B at 32 nodes, 2 KiB at 128, 128 KiB at 1024).  The launcher picks BLOCK >= P, so a thread owns at most one
@@ -63,14 +60,10 @@ __global__ __launch_bounds__(BLOCK) void strong_cluster_kernel(const long long* 
         if (tid == 0) triggers[g] = 0, flags_out[g] = GNNCCA_STRONG_BAD_RANGE;
         return;
     }
-    const int W = (n + 31) >> 5, n_pad = W << 5;   // (n <= P: W * n_pad words fit the launch's LDS)
-    const int words = n_pad * W, items = n * W;
+    const int W = (n + 31) >> 5;   // n_pad = 32 W (n <= P: W * n_pad words fit the launch's LDS)
     if (tid < kStrongMaxRounds) s_round[tid] = 0;
     if (tid < 2) s_misc[tid] = 0;
-    for (int t = tid; t < words; t += BLOCK) {
-        const int i = t / W, w = t - i * W;
-        R[t] = (i < n && w == (i >> 5)) ? 1u << (i & 31) : 0u;
-    }
+    strong_diagonal<BLOCK>(R, n, W);
     __syncthreads();
     int trig = 0;
     for (long long k = k0 + tid; k < k1; k += BLOCK) {
@@ -84,53 +77,12 @@ __global__ __launch_bounds__(BLOCK) void strong_cluster_kernel(const long long* 
         if (atomicAdd(&flow_in[b], 1) >= 3) trig = GNNCCA_POST_TRIGGER_ROUNDING;
     }
     __syncthreads();
-    int lg = 0;
-    while ((1 << lg) < n_pad) ++lg;
-    const int max_rounds = lg + 1;   // <= kStrongMaxRounds - 1: the bound, whatever the data
-    for (int round = 0; round < max_rounds; ++round) {
-        int changed = 0;
-        for (int t = tid; t < items; t += BLOCK) {
-            const int i = t / W, w = t - i * W;
-            const unsigned* row = R + i * W;
-            const unsigned old = strong_ld(&row[w]);
-            unsigned acc = old;
-            for (int w2 = 0; w2 < W; ++w2) {
-                unsigned bits = strong_ld(&row[w2]);
-                while (bits) {
-                    const int j = (w2 << 5) + __builtin_ctz(bits);   // j < n: only real nodes' bits are ever set
-                    bits &= bits - 1;
-                    acc |= strong_ld(&R[j * W + w]);
-                }
-            }
-            if (acc != old) {
-                strong_st(&R[t], acc);   // the word's only writer
-                changed = 1;
-            }
-        }
-        if (changed) s_round[round] = 1;
-        __syncthreads();
-        if (!s_round[round]) break;   // (uniform: nobody writes this round's word after the barrier)
-    }
+    strong_close<BLOCK>(R, n, W, s_round);
     // labels: one node per thread (n <= BLOCK)
     const int v = tid;
     int lab = v;
     if (v < n) {
-        const unsigned* row = R + v * W;
-        const int wv = v >> 5;
-        const unsigned bv = 1u << (v & 31);
-        bool found = false;
-        for (int w2 = 0; w2 <= wv && !found; ++w2) {
-            unsigned bits = row[w2];
-            while (bits) {
-                const int u = (w2 << 5) + __builtin_ctz(bits);
-                bits &= bits - 1;
-                if (u >= v || (R[u * W + wv] & bv)) {   // v's own bit ends the scan at the latest
-                    lab = u >= v ? v : u;
-                    found = true;
-                    break;
-                }
-            }
-        }
+        lab = strong_root(R, W, v);
         labels[v0 + v] = v0 + lab;
     }
     __syncthreads();   // R is no longer read as a matrix: its first n words (words >= n_pad >= n) count the members of every root

@@ -54,7 +54,7 @@ one launch where prune_and_cluster stands; inference.py:302-304) -- a directed c
 takes the step-by-step path; `final()` / `final_async()` go through `finalize(pruning=False)` (only ROUNDING can change a frame), and
 `evaluate()`, `identities()` and FrameLinker work unchanged, since they take predictions and labels.  With `top_k=` the directed capped list is
 clustered by its strongly connected components, the reference's own rule, with no closure and no wait.  `sweep()` and `exclusive()` keep
-their own rules (mutual pairs).  `splitting=True` without pruning is a ValueError: the reference has no behaviour there.
+their own rules (mutual pairs) by default; `sweep(thresholds, partition='strong')` scores this pipeline's own operating points.  `splitting=True` without pruning is a ValueError: the reference has no behaviour there.
 
 `FramePipeline(model, threshold=th)` decides at sigmoid(logit) >= th instead of the reference's 0.5; `r.sweep(thresholds)` scores every
 candidate th of a batch in one pass (gnn_cca_amd.calibration).  Any th other than 0.5 takes the step-by-step path too.
@@ -192,8 +192,10 @@ class FrameResult:
         float64 [T, G, 16] on the device; rows[t] is what evaluate(final=False) returns for a pipeline run at threshold thresholds[t].
         partition='exclusive': the operating points of exclusive() instead -- rows[t] is evaluate_frames(batch, ex['predictions'],
         ex['labels']) of a pipeline run at thresholds[t]; like exclusive() it judges the batch's host camera ids before any launch.
-        Both partitions are built from MUTUAL pairs (the pruning rule), also in a pipeline with pruning=False: the sweep does not score the
-        strongly connected components."""
+        Both of these partitions are built from MUTUAL pairs (the pruning rule), also in a pipeline with pruning=False.
+        partition='strong': the strongly connected components of the unpruned active edges -- in a FramePipeline(model, pruning=False,
+        splitting=False) rows[t] is what evaluate(final=False) returns for that pipeline run at thresholds[t] (frames of at most 1024
+        detections)."""
         from .calibration import sweep_thresholds
         if partition == "exclusive":
             b = self.batch

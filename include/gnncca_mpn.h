@@ -896,8 +896,8 @@ GNNCCA_API int gnncca_eval_sweep_exclusive(const int64_t* edge_index, const floa
  *              divisor and GNNCCA_CMP_GE / GNNCCA_CMP_LE the rows and labels are that entry's bit for bit.
  * NOT reproduced BY THIS SWEEP: the reference clusters with the strongly connected components of the digraph of active edges and does not
  * prune; with a score that is not symmetric (F.pairwise_distance adds eps to a - b) a directed cycle without a mutual pair joins nodes
- * there, here only mutual pairs join.  The reference's partition of ONE prediction vector is gnncca_post_strong_frames' (above); the
- * sweep over that partition does not exist.  inference.py:892,896 use the last graph's labels and max_dist[0] for a whole batch; here every frame has its
+ * there, here only mutual pairs join.  The reference's own rule is gnncca_eval_sweep_strong's (below), with this entry's arguments.
+ * inference.py:892,896 use the last graph's labels and max_dist[0] for a whole batch; here every frame has its
  * own.  A frame whose ranges do not fit gets a NaN row; edge lists with duplicate ordered pairs are unspecified (as above).
  * Four launches whatever n_points and n_scores are (graph plan, plan finish, gnncca_eval_sweep's prepare kernel unchanged, one launch of
  * n_frames x n_points workgroups); the workspace (gnncca_eval_sweep_joint_workspace_bytes) is gnncca_eval_sweep's, O(E + N); no host
@@ -924,6 +924,45 @@ GNNCCA_API int gnncca_eval_sweep_joint(const int64_t* edge_index, const float* e
                                        gnncca_stream_t stream);
 GNNCCA_API int gnncca_eval_rows_accumulate(const double* rows, int32_t n_points, int32_t n_frames, double* sums, int64_t* frames,
                                            gnncca_stream_t stream);
+
+/* ---- Sweep over the STRONGLY CONNECTED clusters: every operating point without pruning (csrc/eval_sweep_strong.cuh) --------------------
+ * With PRUNING = False, and always in geometrical_association / geometrical_appearance_association (inference.py:733-738, 904-908), the
+ * reference prunes nothing and clusters a frame by the strongly connected components of the digraph of its active edges
+ * (gnncca_post_strong_frames for ONE prediction vector).  This entry scores every operating point of that rule in one pass: what
+ * threshold -> gnncca_post_strong_frames -> gnncca_eval_frames compute one point at a time.  The arguments are gnncca_eval_sweep_joint's
+ * (K = n_scores conditions; the sweep of a single score is K = 1 with GNNCCA_CMP_GE or GNNCCA_CMP_LE).  The rule for frame g at point t:
+ *   threshold    th[q] = points_dev[t][q] for condition q; with frame_div_dev, th[q] = points_dev[t][q] / frame_div_dev[q][g], one IEEE
+ *                fp64 division.
+ *   active edges edge k of the frame is active iff EVERY one of the K conditions holds; condition q is
+ *                (double)scores[q][k * score_strides[q]] cmp_q th[q]: the fp32 score is widened and the comparison is made in fp64.  A NaN
+ *                score is never active.  No reverse edge is consulted.
+ *   predictions  predictions_t[k] = active ? 1 : 0 -- the UNPRUNED predictions.
+ *   labels       labels_out[t][v] (int32 [n_points][N], nullable) = the smallest batch-global id u of the frame with v -> u and u -> v
+ *                reachable over active edges whose two ends both lie in the frame: gnncca_post_strong_frames' rule and label
+ *                convention.  An active edge that leaves its frame sets no bit; self loops and duplicates are harmless; the edge list
+ *                may be in any order.
+ *   row          rows_out[t][g] (fp64 [n_points][n_frames][16]) = the 16 columns of gnncca_eval_frames for predictions_t and labels_t.
+ * Contract, bit for bit: with pred_t the int64 vector of `predictions` computed on the host in float64, rows_out[t] is
+ * gnncca_eval_frames(pred_t, labels) and labels_out[t] is labels, for labels = gnncca_post_strong_frames(pred_t)'s.  On scores whose
+ * activity is symmetric the rows and labels are gnncca_eval_sweep_joint's.
+ * The closure is gnncca_post_strong_frames' own code (csrc/strong_closure.cuh): a counted loop of ceil(log2(n_pad)) + 1 rounds at most,
+ * early exit after a round that changes nothing.  One workgroup per (frame, point) of 64 threads (largest frame <= 64) or 256; dynamic
+ * LDS max(12 P, max(P, 32)^2 / 8) + 2 P bytes for P = the power of two >= max_frame_nodes (130 KiB at 1024 detections).
+ * TWO launches whatever n_points and n_scores are: gnncca_eval_sweep's prepare kernel with no edge blocks (the lgamma tables) and the
+ * sweep.  No graph plan, no CSR, no reverse-edge table, no memset, no host synchronisation, no allocation: capturable.  The workspace
+ * (gnncca_eval_sweep_strong_workspace_bytes) holds the lgamma tables only, (n_nodes + n_frames) doubles.
+ * A frame whose ranges do not fit (more nodes than P included) gets a NaN row and identity labels; other frames are unaffected.
+ * GNNCCA_ERR_INVALID_ARG before any launch: a negative size, n_scores outside [1, GNNCCA_EVAL_JOINT_MAX_SCORES], n_points above
+ * GNNCCA_EVAL_JOINT_MAX_POINTS, an unknown comparator code, a stride < 1, max_frame_nodes outside [0, GNNCCA_STRONG_MAX_FRAME_NODES] or
+ * above n_nodes, a null array, a null pointer where its count is positive; GNNCCA_ERR_WORKSPACE: a short workspace (as the joint entry
+ * answers it).  n_frames == 0 or n_points == 0 returns GNNCCA_OK and launches nothing. */
+GNNCCA_API size_t gnncca_eval_sweep_strong_workspace_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_frames);
+GNNCCA_API int gnncca_eval_sweep_strong(const int64_t* edge_index, const float* edge_labels, const float* const* scores,
+                                        const int64_t* score_strides, const int32_t* comparators, int32_t n_scores, int64_t n_nodes,
+                                        int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
+                                        int32_t max_frame_nodes, const double* points_dev, int32_t n_points, const double* frame_div_dev,
+                                        double* rows_out, int32_t* labels_out, void* workspace, size_t workspace_bytes,
+                                        gnncca_stream_t stream);
 
 /* ---- Ranking scores without a threshold: AUROC, average precision, best F per frame; the pooled curve (csrc/rank_metrics.cuh) --------
  * Every entry above judges a score AT a threshold.  gnncca_rank_metrics says how well a score ORDERS a frame's edges: one launch of

@@ -26,6 +26,13 @@ loop is TA * TB points: --loop-reps 1 is plenty.  It also times folding `--acc-b
 (`accumulate`: one add per batch) against keeping a copy of each and reducing them once with torch (`keep_rows`: clone, cat, sum),
 both on the device alone; prints the bytes each way holds there; and times one result() (`result_ms`: the synchronisation, the copy
 and the host's T dicts).
+
+`--partition strong` times the sweep over the STRONGLY CONNECTED clusters (sweep_thresholds(partition='strong'), nothing pruned) on two
+batches, tools/time_strong_clusters.py's shapes: 64 frames x 32 detections and 16 frames x 128 detections.  Its loop is per threshold
+`postprocess.threshold(logits, at=t)`, `postprocess.strong_clusters`, `evaluate_frames` -- all older than the sweep and untouched by it
+-- and the 'components' sweep of the same scores is timed next to it (another partition: mutual pairs; not the same rows).  With
+`--joint TAxTB` the same for sweep_grid(partition='strong') against per point two float64 comparisons, `strong_clusters`,
+`evaluate_frames`, and sweep_grid over the components.
 """
 import argparse
 import json
@@ -160,6 +167,71 @@ def time_joint(torch, args, b):
     print(json.dumps(res))
 
 
+def time_strong(torch, args):
+    from gnn_cca_amd.calibration import grid_points, sweep_grid, sweep_thresholds
+    from gnn_cca_amd.evaluation import evaluate_frames
+    from gnn_cca_amd.postprocess import strong_clusters, threshold
+    out = {"metric": "sweep over the strongly connected clusters, ms per sweep", "rounds": args.rounds, "batches": {}}
+    for frames, per_cam in ((64, 8), (16, 32)):
+        b, logits = make_batch(torch, frames, 4, per_cam)
+        n, g, widest = int(b.node_ptr[-1]), frames, int(np.diff(b.node_ptr).max())
+        probs, _ = threshold(logits)
+
+        def clusters_rows(preds):
+            post = strong_clusters(b.edge_index, preds, n, b.node_ptr_dev, b.edge_ptr_dev, max_frame_nodes=widest)
+            return evaluate_frames(b, preds, post["labels"])
+
+        if args.joint:
+            try:
+                ta, tb = (int(v) for v in args.joint.lower().split("x"))
+            except ValueError:
+                raise SystemExit("--joint takes TAxTB, such as 100x100") from None
+            s0, s1 = b.edge_attr[:, 0], probs          # a symmetric ground distance AND an asymmetric score: directed cycles exist
+            axes = [np.linspace(float(s.min()), float(s.max()), t + 1)[1:] for s, t in ((s0, ta), (s1, tb))]
+            pts, _ = grid_points(axes)
+            d0, d1 = s0.double(), s1.double()
+            points = len(pts)
+
+            def loop():
+                return [clusters_rows(((d0 < float(a)) & (d1 >= float(c))).to(torch.int64)) for a, c in pts]
+
+            def sweep():
+                return sweep_grid(b, [s0, s1], axes, ["lt", "ge"], partition="strong")
+
+            def components():
+                return sweep_grid(b, [s0, s1], axes, ["lt", "ge"])
+        else:
+            ths = np.arange(0.01, 1.00, 0.01)   # (99: `threshold(at=t)` takes thresholds strictly inside (0, 1))
+            points = len(ths)
+
+            def loop():
+                return [clusters_rows(threshold(logits, at=float(t))[1]) for t in ths]
+
+            def sweep():
+                return sweep_thresholds(b, probs, ths, partition="strong")
+
+            def components():
+                return sweep_thresholds(b, probs, ths)
+
+        rows = sweep().reshape(points, g, 16)
+        if not torch.equal(rows, torch.stack(loop())):   # (no NaN rows in these batches)
+            raise SystemExit("the strong sweep and its loop disagree: nothing to time")
+        differ = int((rows != components().reshape(points, g, 16)).any(dim=2).sum())
+        sides = {"sweep_strong": (sweep, args.reps), "loop_strong": (loop, args.loop_reps), "sweep_components": (components, args.reps)}
+        for fn, _ in sides.values():   # warm-up: every shape and kernel of the timed windows (each side also ran once above)
+            fn()
+        got = {k: [] for k in sides}
+        for _ in range(args.rounds):
+            for k, (fn, reps) in sides.items():   # the sides alternate inside a round
+                got[k].append(timed(torch, fn, reps))
+        res = {"frames": g, "nodes": n, "edges": int(b.edge_index.shape[1]), "points": points,
+               "cells_where_strong_rows_differ_from_components": differ, "cells": points * g}
+        res.update({k: summary(v) for k, v in got.items()})
+        res["loop_over_sweep"] = round(float(np.median(got["loop_strong"]) / np.median(got["sweep_strong"])), 1)
+        out["batches"][f"{frames}x{4 * per_cam}"] = res
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -168,7 +240,7 @@ def main():
     ap.add_argument("--root", default=os.path.dirname(HERE), help="the tree whose gnn_cca_amd is timed")
     ap.add_argument("--loop-only", action="store_true", help="time loop_torch alone (what a child run in the parent's tree does)")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: its loop_torch is timed in a child process")
-    ap.add_argument("--partition", choices=("components", "exclusive"), default="components", help="which partition's sweep is timed")
+    ap.add_argument("--partition", choices=("components", "exclusive", "strong"), default="components", help="which partition's sweep is timed")
     ap.add_argument("--joint", default=None, metavar="TAxTB", help="time sweep_grid over a TA x TB grid against its per-point loop")
     ap.add_argument("--acc-reps", type=int, default=200, help="--joint: accumulate / keep_rows calls per timed window (a call is well under 1 ms)")
     ap.add_argument("--acc-batches", type=int, default=8, help="--joint: row sets folded into the accumulator / kept, per timed call")
@@ -180,6 +252,8 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_sweep.py measures on the GPU; no device found")
+    if args.partition == "strong":
+        return time_strong(torch, args)
     ths = np.arange(0.01, 1.01, 0.01)
     b, logits = make_batch(torch, 64, 4, 8)
     n = int(b.node_ptr[-1])
