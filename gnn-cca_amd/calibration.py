@@ -68,6 +68,45 @@ def _thresholds(thresholds):
     return th
 
 
+def _batch_dims(batch):
+    """-> (g, n, e, max_n): the frames, nodes and edges of a GraphBatch and the detections of its widest frame."""
+    node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
+    g = len(node_ptr) - 1
+    return g, int(node_ptr[-1]) if g > 0 else 0, int(batch.edge_index.shape[1]), int(np.diff(node_ptr).max()) if g > 0 else 0
+
+
+def _stage(host, dev):
+    """A flat host float64 array -> (the pinned staging tensor, its copy on the device), without a wait.  The caller holds the pinned
+    tensor until its launches are enqueued: freeing it makes the host allocator record an event on the stream, and that marker belongs
+    behind the sweep's kernels, not between the copy and the first of them."""
+    staged = torch.empty(host.size, dtype=torch.float64, pin_memory=True)
+    staged.copy_(torch.from_numpy(host))
+    return staged, staged.to(dev, non_blocking=True)
+
+
+def _outputs(t, g, n, return_labels, dev):
+    """-> (rows float64 [T, G, 16], labels int32 [T, N] or None, the labels' pointer as the entries take it); nothing is initialised."""
+    rows = torch.empty((t, g, 16), dtype=torch.float64, device=dev)
+    labels = torch.empty((t, n), dtype=torch.int32, device=dev) if return_labels else None
+    return rows, labels, labels.data_ptr() if return_labels and n else None
+
+
+_ENTRIES = {}   # name -> (`name`_workspace_bytes, `name`) of the loaded library: looked up once, not per sweep
+
+
+def _run(name, size_args, dev, *args):
+    """Calls the sweep entry `name` on the current stream: `args`, then a workspace of `name`_workspace_bytes(*size_args) bytes (allocated
+    on this stream, so freed in stream order: nothing to keep) and the stream; raises on a bad status."""
+    fns = _ENTRIES.get(name)
+    if fns is None:
+        fns = _ENTRIES[name] = (getattr(nat.lib(), name + "_workspace_bytes"), getattr(nat.lib(), name))
+    ws_bytes = fns[0](*size_args)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    st = fns[1](*args, ws.data_ptr(), ws_bytes, _raw_stream(dev))
+    if st:
+        nat.check(st, name)
+
+
 def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False, partition="components", cam=None):
     """Scores every frame of `batch` (a GraphBatch as evaluate_frames takes it) at every threshold: `scores` float32 [E] or [E, 1] on the
     device, any per-edge score; `thresholds` a host sequence of finite reals (at most 1024; any order, duplicates allowed); keep='ge'
@@ -105,11 +144,7 @@ def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False, 
     if exclusive:
         for v in th.tolist():
             check_threshold(v)
-    node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
-    g = len(node_ptr) - 1
-    n = int(node_ptr[-1]) if g > 0 else 0
-    e = int(batch.edge_index.shape[1])
-    max_n = int(np.diff(node_ptr).max()) if g > 0 else 0
+    g, n, e, max_n = _batch_dims(batch)
     if max_n > MAX_FRAME_NODES:
         raise ValueError(f"a frame has {max_n} detections; sweep_thresholds scores frames of at most {MAX_FRAME_NODES}")
     if scores.numel() != e or batch.edge_labels.numel() != e:
@@ -129,40 +164,51 @@ def sweep_thresholds(batch, scores, thresholds, keep="ge", return_labels=False, 
         raise RuntimeError("gnn_cca_amd.calibration runs on MI355X only (no CPU fallback)")
     dev = scores.device
     t = int(th.size)
-    lib = nat.lib()
     with _on(dev):
         sc = scores.reshape(-1)
         if sc.dtype != torch.float32 or not sc.is_contiguous():
             sc = sc.float().contiguous()
         ei = batch.edge_index.contiguous()
         el = batch.edge_labels.contiguous()
-        rows = torch.empty((t, g, 16), dtype=torch.float64, device=dev)
-        labels = torch.empty((t, n), dtype=torch.int32, device=dev) if return_labels else None
+        rows, labels, lab_ptr = _outputs(t, g, n, return_labels, dev)
         if g > 0:
             nptr, eptr = _dev_i32(batch.node_ptr_dev, sc), _dev_i32(batch.edge_ptr_dev, sc)
-            staged = torch.empty(t, dtype=torch.float64, pin_memory=True)
-            staged.copy_(torch.from_numpy(th))
-            th_dev = staged.to(dev, non_blocking=True)
-            lab_ptr = labels.data_ptr() if return_labels and n else None
+            pinned, th_dev = _stage(th, dev)
+            ei_ptr, el_ptr, sc_ptr = (ei.data_ptr(), el.data_ptr(), sc.data_ptr()) if e else (None, None, None)
             if exclusive:
                 cm = _dev_i32(cam.reshape(-1), sc)
-                ws_bytes = lib.gnncca_eval_sweep_exclusive_workspace_bytes(n, e, g, t)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                st = lib.gnncca_eval_sweep_exclusive(ei.data_ptr() if e else None, el.data_ptr() if e else None, sc.data_ptr() if e else None,
-                                                     cm.data_ptr() if n else None, n, e, nptr.data_ptr(), eptr.data_ptr(), g, max_n,
-                                                     th_dev.data_ptr(), t, rows.data_ptr(), lab_ptr, ws.data_ptr(), ws_bytes, _raw_stream(dev))
-                if st:
-                    nat.check(st, "gnncca_eval_sweep_exclusive")
+                _run("gnncca_eval_sweep_exclusive", (n, e, g, t), dev, ei_ptr, el_ptr, sc_ptr, cm.data_ptr() if n else None, n, e, nptr.data_ptr(),
+                     eptr.data_ptr(), g, max_n, th_dev.data_ptr(), t, rows.data_ptr(), lab_ptr)
             else:
-                ws_bytes = lib.gnncca_eval_sweep_workspace_bytes(n, e, g, t)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                st = lib.gnncca_eval_sweep(ei.data_ptr() if e else None, el.data_ptr() if e else None, sc.data_ptr() if e else None, n, e,
-                                           nptr.data_ptr(), eptr.data_ptr(), g, max_n, th_dev.data_ptr(), t, int(keep == "le"), rows.data_ptr(),
-                                           lab_ptr, ws.data_ptr(), ws_bytes, _raw_stream(dev))
-                if st:
-                    nat.check(st, "gnncca_eval_sweep")
-            # workspace and thresholds are freed by the caching allocator in stream order (allocated on this stream): nothing to keep
+                _run("gnncca_eval_sweep", (n, e, g, t), dev, ei_ptr, el_ptr, sc_ptr, n, e, nptr.data_ptr(), eptr.data_ptr(), g, max_n,
+                     th_dev.data_ptr(), t, int(keep == "le"), rows.data_ptr(), lab_ptr)
     return (rows, labels) if return_labels else rows
+
+
+def _micro_prf(out):
+    """Completes an accumulator's result `out` (it holds 'aggregates', one dict per operating point) with the summed TP / FP / FN / TN as
+    int64 arrays and P_micro / R_micro / F_micro, `compute_P_R_F`'s expressions (inference.py:53-66) on those sums."""
+    for name in ("TP", "FP", "FN", "TN"):
+        out[name] = np.array([a[name] for a in out["aggregates"]], dtype=np.int64)
+    p, r, f = [], [], []
+    for TP, FP, FN in zip(out["TP"], out["FP"], out["FN"]):   # compute_P_R_F, expression for expression (numpy int64 counts)
+        P = TP / (TP + FP) if (TP + FP) != 0 else 0
+        R = TP / (TP + FN) if (TP + FN) != 0 else 0
+        F = 2 * (P * R) / (P + R) if (P + R) != 0 else 0
+        p.append(P), r.append(R), f.append(F)
+    out["P_micro"], out["R_micro"], out["F_micro"] = (np.array(v, dtype=np.float64) for v in (p, r, f))
+    return out
+
+
+def _best(res, metric):
+    """Indices of ALL operating points of an accumulator's result at which `metric` equals its maximum."""
+    if metric in MICRO:
+        vals = res[metric]
+    elif metric in res["aggregates"][0]:
+        vals = np.array([a[metric] for a in res["aggregates"]], dtype=np.float64)
+    else:
+        raise ValueError(f"unknown metric {metric!r}")
+    return np.where(vals == np.max(vals))[0]
 
 
 class SweepAccumulator:
@@ -200,30 +246,13 @@ class SweepAccumulator:
             red.append(_reduce_rows(allr))
         host = torch.stack(red).cpu().numpy()    # the one synchronisation
         agg = [_aggregates(h) for h in host]
-        out = {"thresholds": self.thresholds.copy(), "aggregates": agg}
-        for name in ("TP", "FP", "FN", "TN"):
-            out[name] = np.array([a[name] for a in agg], dtype=np.int64)
-        p, r, f = [], [], []
-        for TP, FP, FN in zip(out["TP"], out["FP"], out["FN"]):   # compute_P_R_F, expression for expression (numpy int64 counts)
-            P = TP / (TP + FP) if (TP + FP) != 0 else 0
-            R = TP / (TP + FN) if (TP + FN) != 0 else 0
-            F = 2 * (P * R) / (P + R) if (P + R) != 0 else 0
-            p.append(P), r.append(R), f.append(F)
-        out["P_micro"], out["R_micro"], out["F_micro"] = (np.array(v, dtype=np.float64) for v in (p, r, f))
-        self._res = out
-        return out
+        self._res = _micro_prf({"thresholds": self.thresholds.copy(), "aggregates": agg})
+        return self._res
 
     def best(self, metric="F_micro"):
         """Indices of ALL thresholds at which `metric` equals its maximum -- main.py:190's np.where(F_list == np.max(F_list)).  `metric`:
         P_micro / R_micro / F_micro, or one of the aggregates' names (P, R, F, TP, ..., prec1)."""
-        res = self.result()
-        if metric in MICRO:
-            vals = res[metric]
-        elif metric in res["aggregates"][0]:
-            vals = np.array([a[metric] for a in res["aggregates"]], dtype=np.float64)
-        else:
-            raise ValueError(f"unknown metric {metric!r}")
-        return np.where(vals == np.max(vals))[0]
+        return _best(self.result(), metric)
 
 
 MAX_POINTS = nat.JOINT_MAX_POINTS
@@ -292,10 +321,7 @@ def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False
         raise ValueError(f"partition must be one of {JOINT_PARTITIONS} in a joint sweep (the camera-exclusive partition is swept by "
                          f"sweep_thresholds only), not {partition!r}")
     strong = partition == "strong"
-    node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
-    g = len(node_ptr) - 1
-    n = int(node_ptr[-1]) if g > 0 else 0
-    e = int(batch.edge_index.shape[1])
+    g, n, e, max_n = _batch_dims(batch)
     sl = _score_list(scores, e)
     k = len(sl)
     if isinstance(keep, str) or keep is None:
@@ -320,7 +346,6 @@ def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False
         if not (np.isfinite(div).all() and (div > 0).all()):
             raise ValueError("frame_div must be finite and > 0")
         div = np.ascontiguousarray(div)
-    max_n = int(np.diff(node_ptr).max()) if g > 0 else 0
     limit = nat.STRONG_MAX_FRAME_NODES if strong else MAX_FRAME_NODES
     if max_n > limit:
         raise ValueError(f"a frame has {max_n} detections; sweep_joint(partition={partition!r}) scores frames of at most {limit}")
@@ -332,7 +357,6 @@ def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False
     if any(s.device != dev for s in sl):
         raise ValueError("the scores of a joint sweep must be on one device")
     t = int(pts.shape[0])
-    lib = nat.lib()
     with _on(dev):
         flat = []
         for s in sl:
@@ -344,26 +368,17 @@ def sweep_joint(batch, scores, points, keep, frame_div=None, return_labels=False
             flat.append(s)
         ei = batch.edge_index.contiguous()
         el = batch.edge_labels.contiguous()
-        rows = torch.empty((t, g, 16), dtype=torch.float64, device=dev)
-        labels = torch.empty((t, n), dtype=torch.int32, device=dev) if return_labels else None
+        rows, labels, lab_ptr = _outputs(t, g, n, return_labels, dev)
         if g > 0:
             nptr, eptr = _dev_i32(batch.node_ptr_dev, flat[0]), _dev_i32(batch.edge_ptr_dev, flat[0])
-            host = np.concatenate([pts.reshape(-1)] + ([div.reshape(-1)] if div is not None else []))
-            staged = torch.empty(host.size, dtype=torch.float64, pin_memory=True)
-            staged.copy_(torch.from_numpy(host))
-            up = staged.to(dev, non_blocking=True)
+            pinned, up = _stage(np.concatenate([pts.reshape(-1)] + ([div.reshape(-1)] if div is not None else [])), dev)   # (one copy for both)
             div_ptr = up.data_ptr() + 8 * t * k if div is not None else None
             ptrs = (nat.C.c_void_p * k)(*[s.data_ptr() if e else None for s in flat])
             strides = (nat.C.c_int64 * k)(*[max(int(s.stride(0)), 1) if e else 1 for s in flat])
             cmps = (nat.C.c_int32 * k)(*[nat.CMP[c] for c in keep])
-            name = "gnncca_eval_sweep_strong" if strong else "gnncca_eval_sweep_joint"   # (one argument list)
-            ws_bytes = getattr(lib, name + "_workspace_bytes")(n, e, g)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            st = getattr(lib, name)(ei.data_ptr() if e else None, el.data_ptr() if e else None, ptrs, strides, cmps, k, n, e,
-                                    nptr.data_ptr(), eptr.data_ptr(), g, max_n, up.data_ptr(), t, div_ptr, rows.data_ptr(),
-                                    labels.data_ptr() if return_labels and n else None, ws.data_ptr(), ws_bytes, _raw_stream(dev))
-            if st:
-                nat.check(st, name)
+            _run("gnncca_eval_sweep_strong" if strong else "gnncca_eval_sweep_joint", (n, e, g), dev,   # (one argument list)
+                 ei.data_ptr() if e else None, el.data_ptr() if e else None, ptrs, strides, cmps, k, n, e, nptr.data_ptr(), eptr.data_ptr(), g,
+                 max_n, up.data_ptr(), t, div_ptr, rows.data_ptr(), lab_ptr)
     return (rows, labels) if return_labels else rows
 
 
@@ -456,29 +471,12 @@ class JointSweepAccumulator:
         red = sums / np.float64(frames)
         red[:, _COUNT_COLUMNS] = sums[:, _COUNT_COLUMNS]
         agg = [_aggregates(h) for h in red]
-        out = {"points": self.points.copy(), "frames": frames, "sums": sums, "aggregates": agg}
-        for name in ("TP", "FP", "FN", "TN"):
-            out[name] = np.array([a[name] for a in agg], dtype=np.int64)
-        p, r, f = [], [], []
-        for TP, FP, FN in zip(out["TP"], out["FP"], out["FN"]):   # compute_P_R_F, expression for expression (numpy int64 counts)
-            P = TP / (TP + FP) if (TP + FP) != 0 else 0
-            R = TP / (TP + FN) if (TP + FN) != 0 else 0
-            F = 2 * (P * R) / (P + R) if (P + R) != 0 else 0
-            p.append(P), r.append(R), f.append(F)
-        out["P_micro"], out["R_micro"], out["F_micro"] = (np.array(v, dtype=np.float64) for v in (p, r, f))
-        self._res = out
-        return out
+        self._res = _micro_prf({"points": self.points.copy(), "frames": frames, "sums": sums, "aggregates": agg})
+        return self._res
 
     def best(self, metric="F_micro"):
         """Indices of ALL points at which `metric` equals its maximum (SweepAccumulator.best's rule and names)."""
-        res = self.result()
-        if metric in MICRO:
-            vals = res[metric]
-        elif metric in res["aggregates"][0]:
-            vals = np.array([a[metric] for a in res["aggregates"]], dtype=np.float64)
-        else:
-            raise ValueError(f"unknown metric {metric!r}")
-        return np.where(vals == np.max(vals))[0]
+        return _best(self.result(), metric)
 
 
 __all__ = ["MAX_THRESHOLDS", "MAX_POINTS", "sweep_thresholds", "SweepAccumulator", "sweep_joint", "sweep_grid", "grid_points", "JointSweepAccumulator"]

@@ -22,8 +22,8 @@ namespace gnncca {
 
 // rev[k] = the edge (dst k, src k), or -1.  Blocks [0, edge_blocks): one edge per thread, searched in the CSR segment of dst k as
 // post_prune_kernel does (a plan with GNNCCA_GRAPH_BAD_INDEX prunes everything there: no edge has a reverse here).
-// Blocks [edge_blocks, edge_blocks + G): frame g's lgamma table, lf[k] = lgamma(k + 1) for k <= n_g at lf_ws + node_ptr[g] + g -- the
-// expression of eval_frame_body<.., FILL_LF = true>, so the table has the same bits whoever wrote it.
+// Blocks [edge_blocks, edge_blocks + G): frame g's lgamma table, lf[k] = lgamma(k + 1) for k <= n_g at lf_ws + node_ptr[g] + g, written
+// by fill_lgamma_table like eval_frame_body<.., FILL_LF = true>'s.
 __global__ __launch_bounds__(256) void eval_sweep_prepare_kernel(const long long* __restrict__ ei, long long E, const int* __restrict__ seg_ptr,
                                                                  const int* __restrict__ col32, const int* __restrict__ perm,
                                                                  const unsigned* __restrict__ flags, int* __restrict__ rev, int edge_blocks,
@@ -39,8 +39,7 @@ __global__ __launch_bounds__(256) void eval_sweep_prepare_kernel(const long long
     const int v0 = node_ptr[g], v1 = node_ptr[g + 1];
     const int n = v1 - v0;
     if (v0 < 0 || n < 0 || n > kEvalMaxNodes || v1 > N_all) return;   // a NaN row: nobody reads its table
-    double* lf = lf_ws + v0 + g;
-    for (int k = tid; k <= n; k += 256) lf[k] = lgamma((double)k + 1.0);
+    fill_lgamma_table(lf_ws + v0 + g, n, tid, 256);
 }
 
 // "is edge k predicted" of the sweep: active, and the reverse edge of the same frame is active too
@@ -65,6 +64,15 @@ struct SweepLabel {
     const unsigned short* lab16;
     __device__ __forceinline__ int operator()(int v0, int v) const { return v0 + (int)lab16[v]; }
 };
+
+// Where workgroup (g, t) of a sweep writes: its row of rows_out [T][G][16] and point t's labels in labels_out [T][N_all] (null: none).
+struct SweepOut {
+    double* row;
+    int* lab_t;
+};
+__device__ __forceinline__ SweepOut sweep_out(double* rows_out, int* labels_out, int g, int t, int n_frames, int N_all) {
+    return SweepOut{rows_out + ((size_t)t * n_frames + g) * 16, labels_out ? labels_out + (size_t)t * N_all : nullptr};
+}
 
 // The part of a sweep workgroup that comes before the predicate exists: the frame's ranges.  A frame whose ranges do not fit
 // (eval_frame_body's test) gets a NaN row and identity labels, and the workgroup is done (false).
@@ -142,13 +150,11 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_kernel(const long long* __re
                                                            double* __restrict__ rows_out, int* __restrict__ labels_out,
                                                            double* __restrict__ lf_ws) {
     const int g = blockIdx.x, t = blockIdx.y;
-    const int n_frames = gridDim.x;
-    double* row = rows_out + ((size_t)t * n_frames + g) * 16;
-    int* lab_t = labels_out ? labels_out + (size_t)t * N_all : nullptr;
+    const SweepOut out = sweep_out(rows_out, labels_out, g, t, gridDim.x, N_all);
     SweepFrame f;
-    if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, P_lds, row, lab_t, f)) return;
+    if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, P_lds, out.row, out.lab_t, f)) return;
     const SweepPred pred{scores, rev, thresholds[t], f.k0, f.k1, keep_le != 0};
-    eval_sweep_body<BLOCK>(g, f, pred, ei, E, elab, N_all, node_ptr, edge_ptr, P_lds, row, lab_t, lf_ws);
+    eval_sweep_body<BLOCK>(g, f, pred, ei, E, elab, N_all, node_ptr, edge_ptr, P_lds, out.row, out.lab_t, lf_ws);
 }
 
 }  // namespace gnncca

@@ -24,7 +24,7 @@ namespace gnncca {
 // otherwise.  EVERY slot is written.  The frame of edge k is the last g with edge_ptr[g] <= k, checked (edge_ptr[g] <= k < edge_ptr[g + 1]
 // and ranges that pass excl_frame_ok with the sweep kernel's P): with ranges that do not ascend a slot can only become 0 or the key of a
 // pair of the frame found, and the sweep kernel checks the ids of every key against its own frame.
-// Blocks [edge_blocks, edge_blocks + G): frame g's lgamma table, as eval_sweep_prepare_kernel fills it (the same expression, the same bits).
+// Blocks [edge_blocks, edge_blocks + G): frame g's lgamma table, as eval_sweep_prepare_kernel fills it (fill_lgamma_table).
 __global__ __launch_bounds__(256) void eval_sweep_excl_prepare_kernel(const long long* __restrict__ ei, long long E, const int* __restrict__ seg_ptr,
                                                                       const int* __restrict__ col32, const int* __restrict__ perm,
                                                                       const unsigned* __restrict__ flags, const float* __restrict__ scores,
@@ -62,8 +62,7 @@ __global__ __launch_bounds__(256) void eval_sweep_excl_prepare_kernel(const long
     const int v0 = node_ptr[g], v1 = node_ptr[g + 1];
     const int n = v1 - v0;
     if (v0 < 0 || n < 0 || n > kEvalMaxNodes || v1 > N_all) return;   // a NaN row: nobody reads its table
-    double* lf = lf_ws + v0 + g;
-    for (int k = tid; k <= n; k += 256) lf[k] = lgamma((double)k + 1.0);
+    fill_lgamma_table(lf_ws + v0 + g, n, tid, 256);
 }
 
 // "is edge k predicted" of the exclusive sweep -- the epilogue of excl_cluster_kernel: the reverse edge is the frame's own, both are
@@ -112,16 +111,14 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_excl_kernel(const long long*
     int* parent = reinterpret_cast<int*>(mask + P);
     unsigned short* lab16 = reinterpret_cast<unsigned short*>(s_sweep_excl + (size_t)12 * P);
     const int g = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
-    const int n_frames = gridDim.x;
-    double* row = rows_out + ((size_t)t * n_frames + g) * 16;
-    int* lab_t = labels_out ? labels_out + (size_t)t * N_all : nullptr;
+    const SweepOut out = sweep_out(rows_out, labels_out, g, t, gridDim.x, N_all);
     const int v0 = node_ptr[g], v1 = node_ptr[g + 1];
     const long long k0 = edge_ptr[g], k1 = edge_ptr[g + 1];
     const int n = v1 - v0;
-    if (!excl_frame_ok(v0, v1, k0, k1, N_all, E, P)) {   // eval_frame_body's test: a NaN row
-        if (tid < 16) row[tid] = __builtin_nan("");
-        if (lab_t && v0 >= 0 && v1 <= N_all)
-            for (int v = v0 + tid; v < v1; v += BLOCK) lab_t[v] = v;
+    if (!excl_frame_ok(v0, v1, k0, k1, N_all, E, P)) {   // eval_sweep_frame's test and answer: a NaN row, identity labels
+        if (tid < 16) out.row[tid] = __builtin_nan("");
+        if (out.lab_t && v0 >= 0 && v1 <= N_all)
+            for (int v = v0 + tid; v < v1; v += BLOCK) out.lab_t[v] = v;
         return;
     }
     const double th = thresholds[t];
@@ -160,11 +157,11 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_excl_kernel(const long long*
     for (int v = tid; v < n; v += BLOCK) {   // (`mask` is dead: its last read lies before the barrier above)
         const int r = parent[v];
         lab16[v] = (unsigned short)r;
-        if (lab_t) lab_t[v0 + v] = v0 + r;
+        if (out.lab_t) out.lab_t[v0 + v] = v0 + r;
     }
     __syncthreads();
     const SweepExclPred pred{ei, E, scores, rev, lab16, th, k0, k1, v0, n, dead};
-    eval_frame_body<BLOCK, false, false>(g, row, ei, E, elab, pred, SweepLabel{lab16}, N_all, node_ptr, edge_ptr, P, nullptr, lf_ws, nullptr,
+    eval_frame_body<BLOCK, false, false>(g, out.row, ei, E, elab, pred, SweepLabel{lab16}, N_all, node_ptr, edge_ptr, P, nullptr, lf_ws, nullptr,
                                          nullptr);
 }
 

@@ -85,14 +85,13 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_joint_kernel(const long long
                                                                  double* __restrict__ lf_ws) {
     const int g = blockIdx.x, t = blockIdx.y;
     const int n_frames = gridDim.x;
-    double* row = rows_out + ((size_t)t * n_frames + g) * 16;
-    int* lab_t = labels_out ? labels_out + (size_t)t * N_all : nullptr;
+    const SweepOut out = sweep_out(rows_out, labels_out, g, t, n_frames, N_all);
     SweepFrame f;
-    if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, P_lds, row, lab_t, f)) return;
+    if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, P_lds, out.row, out.lab_t, f)) return;
     SweepJointPred pred;
     pred.set_point(sc, points, frame_div, t, g, n_frames);
     pred.rev = rev, pred.k0 = f.k0, pred.k1 = f.k1;
-    eval_sweep_body<BLOCK>(g, f, pred, ei, E, elab, N_all, node_ptr, edge_ptr, P_lds, row, lab_t, lf_ws);
+    eval_sweep_body<BLOCK>(g, f, pred, ei, E, elab, N_all, node_ptr, edge_ptr, P_lds, out.row, out.lab_t, lf_ws);
 }
 
 // sums[t][c] = ((sums[t][c] + rows[t][0][c]) + rows[t][1][c]) + ... : one thread per (t, c), the frames in ascending g, plain fp64 adds

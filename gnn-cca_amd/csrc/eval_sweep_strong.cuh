@@ -51,10 +51,9 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_strong_kernel(const long lon
     __shared__ int s_round[kStrongMaxRounds];   // [r]: round r changed a word
     const int g = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
     const int n_frames = gridDim.x;
-    double* row = rows_out + ((size_t)t * n_frames + g) * 16;
-    int* lab_t = labels_out ? labels_out + (size_t)t * N_all : nullptr;
+    const SweepOut out = sweep_out(rows_out, labels_out, g, t, n_frames, N_all);
     SweepFrame f;
-    if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, min(P_lds, kSweepStrongMaxNodes), row, lab_t, f)) return;
+    if (!eval_sweep_frame<BLOCK>(g, N_all, E, node_ptr, edge_ptr, min(P_lds, kSweepStrongMaxNodes), out.row, out.lab_t, f)) return;
     SweepStrongPred pred;
     pred.set_point(sc, points, frame_div, t, g, n_frames);
     unsigned* R = reinterpret_cast<unsigned*>(s_dyn);
@@ -75,10 +74,10 @@ __global__ __launch_bounds__(BLOCK) void eval_sweep_strong_kernel(const long lon
     for (int v = tid; v < n; v += BLOCK) {   // (the block is narrower than the frame)
         const int r = strong_root(R, W, v);
         lab16[v] = (unsigned short)r;
-        if (lab_t) lab_t[v0 + v] = v0 + r;
+        if (out.lab_t) out.lab_t[v0 + v] = v0 + r;
     }
     __syncthreads();   // R is dead: the body takes its bytes
-    eval_frame_body<BLOCK, false, false>(g, row, ei, E, elab, pred, SweepLabel{lab16}, N_all, node_ptr, edge_ptr, P_lds, nullptr, lf_ws,
+    eval_frame_body<BLOCK, false, false>(g, out.row, ei, E, elab, pred, SweepLabel{lab16}, N_all, node_ptr, edge_ptr, P_lds, nullptr, lf_ws,
                                          nullptr, nullptr);
 }
 

@@ -56,6 +56,12 @@ __device__ __forceinline__ double block_sum(double v, double* scratch) {
 
 __device__ __forceinline__ int lds_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
+// A frame's lgamma table, lf[k] = lgamma(k + 1) for k <= n: the one loop of every writer (eval_frame_body<.., FILL_LF = true> and the
+// sweeps' prepare kernels), so the table has the same bits whoever wrote it.  `stride`: the workgroup's threads.
+__device__ __forceinline__ void fill_lgamma_table(double* lf, int n, int tid, int stride) {
+    for (int k = tid; k <= n; k += stride) lf[k] = lgamma((double)k + 1.0);
+}
+
 // out[g][16] = P, R, F, TP, FP, FN, TN, ARI, AMI, homogeneity, completeness, V, precision0, precision1, n_clusters_gt, n_clusters_pred.
 // P_lds: ints per LDS region (a power of two >= every frame's node count, <= kEvalMaxNodes).  lf_ws: the lgamma tables, frame g's at
 // lf_ws + node_ptr[g] + g.  A frame whose ranges do not fit (node count above P_lds, ranges outside the arrays) gets a NaN row.
@@ -107,8 +113,7 @@ __device__ __forceinline__ void eval_frame_body(const int g, double* __restrict_
         cnt[v] = DENSE ? (unsigned)cam[v0 + v] : 0u;
         if (DENSE) keys[v] = (unsigned)person[v0 + v];
     }
-    if (FILL_LF)
-        for (int k = tid; k <= n; k += BLOCK) lf[k] = lgamma((double)k + 1.0);   // read only after the barriers below
+    if (FILL_LF) fill_lgamma_table(lf, n, tid, BLOCK);   // read only after the barriers below
     if (tid < I_COUNT) s_int[tid] = 0;
     __syncthreads();
     if (DENSE) {
@@ -418,8 +423,7 @@ static int eval_frames(const int64_t* edge_index, const float* edge_labels, cons
     if (n_edges > 0 && (!edge_index || !edge_labels || !predictions)) return GNNCCA_ERR_INVALID_ARG;
     if (workspace_bytes < gnncca_eval_workspace_bytes(n_nodes, n_edges, n_frames)) return GNNCCA_ERR_WORKSPACE;
     if (n_nodes >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    int P = 1;
-    while (P < max_frame_nodes) P <<= 1;
+    const int P = frame_capacity(max_frame_nodes);
     const size_t lds = (size_t)3 * P * sizeof(int);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
@@ -428,11 +432,10 @@ static int eval_frames(const int64_t* edge_index, const float* edge_labels, cons
 #define GNNCCA_EVAL(B, D)                                                                                                            \
     hipLaunchKernelGGL((eval_frames_kernel<B, D>), dim3((unsigned)n_frames), dim3(B), lds, st, ei, (long long)n_edges, edge_labels, pr, \
                        labels, (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, gt_labels_out, out, lf, person_id, cam)
-    if (P <= 64) {   // small frames (a Terrace frame has ~20 detections): one wave per frame
-        if (dense) GNNCCA_EVAL(64, true); else GNNCCA_EVAL(64, false);
-    } else {
-        if (dense) GNNCCA_EVAL(256, true); else GNNCCA_EVAL(256, false);
-    }
+    launch_frame_block(P, [&](auto block) {
+        constexpr int B = decltype(block)::value;
+        if (dense) GNNCCA_EVAL(B, true); else GNNCCA_EVAL(B, false);
+    });
 #undef GNNCCA_EVAL
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
@@ -455,50 +458,118 @@ int gnncca_eval_frames_dense(const int64_t* edge_index, const float* edge_labels
 }
 
 // ---- the threshold sweep (eval_sweep.cuh) ---------------------------------------------------------------------------------------------
-// workspace: [the graph plan, as gnncca_post_workspace_bytes lays it out | rev int32 [E] | lgamma tables fp64 [N + G]] -- O(E + N); the
-// only thing of size T x N is the caller's labels_out
-struct SweepWorkspace { PostWorkspace plan; size_t rev, lf, total; };
-static SweepWorkspace carve_sweep(int64_t n, int64_t e, int64_t g) {
+// The four sweeps -- gnncca_eval_sweep, _exclusive (eval_sweep_exclusive.cuh), _joint (eval_sweep_joint.cuh) and _strong
+// (eval_sweep_strong.cuh) -- share one host path: sweep_check, joint_scores, carve_sweep + sweep_prepare, and launch_frame_block for the
+// grid (G, T) launch.  What differs between them is an argument of those, never a copy.
+//
+// workspace of the sweeps that prune: [the graph plan, as gnncca_post_workspace_bytes lays it out | rev int32 [E] | pair keys u64 [E], the
+// exclusive sweep only | lgamma tables fp64 [N + G]] -- O(E + N) whatever T is; the only thing of size T x N is the caller's labels_out.
+// The strong sweep has neither plan nor reverse edges: its workspace is the lgamma tables alone (gnncca_eval_workspace_bytes).
+struct SweepWorkspace { PostWorkspace plan; size_t rev, keys, lf, total; };
+static SweepWorkspace carve_sweep(int64_t n, int64_t e, int64_t g, bool with_keys) {
     SweepWorkspace w;
     w.plan = carve_post(n, e);
     size_t off = w.plan.total;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    w.rev = take((size_t)e * 4), w.lf = take(((size_t)n + (size_t)g) * sizeof(double)), w.total = off;
+    const size_t N = (size_t)(n > 0 ? n : 0), E = (size_t)(e > 0 ? e : 0), G = (size_t)(g > 0 ? g : 0);   // (carve_post's clamp: an entry carves first and checks then)
+    w.rev = take(E * 4), w.keys = take(with_keys ? E * 8 : 0), w.lf = take((N + G) * sizeof(double)), w.total = off;
     return w;
 }
 
 size_t gnncca_eval_sweep_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames, int64_t n_thresholds) {
     if (n_nodes < 0 || n_edges < 0 || n_frames < 0 || n_thresholds < 0) return 0;
-    return carve_sweep(n_nodes, n_edges, n_frames).total;
+    return carve_sweep(n_nodes, n_edges, n_frames, false).total;
+}
+size_t gnncca_eval_sweep_exclusive_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames, int64_t n_thresholds) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0 || n_thresholds < 0) return 0;
+    return carve_sweep(n_nodes, n_edges, n_frames, true).total;
+}
+size_t gnncca_eval_sweep_joint_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames) {   // (whatever the numbers of points and scores)
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return 0;
+    return carve_sweep(n_nodes, n_edges, n_frames, false).total;
+}
+size_t gnncca_eval_sweep_strong_workspace_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_frames) {
+    return gnncca_eval_workspace_bytes(n_nodes, n_edges, n_frames);
 }
 
-// The three launches every sweep over the connected components starts with: the plan of gnncca_post_prune_cluster (no padded layout to
-// validate), its finish, and eval_sweep_prepare_kernel (rev and the lgamma tables, handed back as pointers into the workspace).
-static int sweep_prepare(const SweepWorkspace& ws, void* workspace, const long long* ei, int E, int N, const int32_t* node_ptr_dev,
-                         int32_t n_frames, hipStream_t st, int** rev_out, double** lf_out) {
-    char* base = static_cast<char*>(workspace);
-    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
-    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
-    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
-    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
-    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
-    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
-    int* rev = reinterpret_cast<int*>(base + ws.rev);
-    double* lf = reinterpret_cast<double*>(base + ws.lf);
-    if (E > 0) {
-        EncPlanParams ep;
-        std::memset(&ep, 0, sizeof(ep));
-        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
-        launch_plan_only(ep, plan_num_blocks(E), st);
-        HIP_TRY(hipGetLastError());
-        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
-        HIP_TRY(hipGetLastError());
+// The argument check of the four sweeps, in one order: the sizes, the points, "nothing to do" (OK with *work = false: the caller returns
+// without a launch), the pointers the work reads (INVALID_ARG), the 32-bit index range (UNSUPPORTED), the workspace (WORKSPACE).
+struct SweepLimits {
+    int max_nodes;         // the widest frame: kEvalMaxNodes, kExclMaxNodes or kSweepStrongMaxNodes
+    int max_points;        // GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS or GNNCCA_EVAL_JOINT_MAX_POINTS
+    bool zero_points_ok;   // the strong sweep: no points is nothing to do, as no frames is, and `points` is looked at only when there is work
+    bool need_cam;         // the exclusive sweep
+};
+//                                            max_nodes             max_points                        zero_points_ok  need_cam
+constexpr SweepLimits kLimitsComponents{kEvalMaxNodes,        GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS, false,          false};
+constexpr SweepLimits kLimitsExclusive {kExclMaxNodes,        GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS, false,          true};
+constexpr SweepLimits kLimitsJoint     {kEvalMaxNodes,        GNNCCA_EVAL_JOINT_MAX_POINTS,     false,          false};
+constexpr SweepLimits kLimitsStrong    {kSweepStrongMaxNodes, GNNCCA_EVAL_JOINT_MAX_POINTS,     true,           false};
+struct SweepPtrs {   // the arrays of a sweep as its entry got them (null: missing), set by name at the call sites
+    const double* points;
+    const int64_t* edge_index;   // these three are needed when there are edges; `scores` is the array, or the joint form's array of arrays
+    const float* edge_labels;
+    const void* scores;
+    const int32_t* cam;          // (need_cam, when there are nodes)
+    const int32_t* node_ptr;
+    const int32_t* edge_ptr;
+    const double* rows_out;
+    const void* workspace;
+};
+static int sweep_check(const SweepLimits& lim, int64_t n_nodes, int64_t n_edges, int32_t n_frames, int32_t max_frame_nodes, int32_t n_points,
+                       const SweepPtrs& p, size_t workspace_bytes, size_t workspace_need, bool* work) {
+    *work = false;
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (n_points < (lim.zero_points_ok ? 0 : 1) || n_points > lim.max_points) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > lim.max_nodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    const bool nothing = n_frames == 0 || n_points == 0;
+    if (!p.points && !(lim.zero_points_ok && nothing)) return GNNCCA_ERR_INVALID_ARG;
+    if (nothing) return GNNCCA_OK;
+    if (!p.node_ptr || !p.edge_ptr || !p.rows_out || !p.workspace) return GNNCCA_ERR_INVALID_ARG;
+    if (lim.need_cam && n_nodes > 0 && !p.cam) return GNNCCA_ERR_INVALID_ARG;
+    if (n_edges > 0 && (!p.edge_index || !p.edge_labels || !p.scores)) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (workspace_bytes < workspace_need) return GNNCCA_ERR_WORKSPACE;
+    *work = true;
+    return GNNCCA_OK;
+}
+
+// The K score arrays of the joint and the strong sweep, checked and packed into the kernels' by-value argument.
+static int joint_scores(const float* const* scores, const int64_t* score_strides, const int32_t* comparators, int32_t n_scores, int64_t n_edges,
+                        JointScores* sc) {
+    if (n_scores < 1 || n_scores > GNNCCA_EVAL_JOINT_MAX_SCORES) return GNNCCA_ERR_INVALID_ARG;
+    if (!scores || !score_strides || !comparators) return GNNCCA_ERR_INVALID_ARG;
+    std::memset(sc, 0, sizeof(*sc));
+    sc->K = n_scores;
+    for (int k = 0; k < n_scores; ++k) {
+        if (comparators[k] < GNNCCA_CMP_GE || comparators[k] > GNNCCA_CMP_LT || score_strides[k] < 1) return GNNCCA_ERR_INVALID_ARG;
+        if (n_edges > 0 && !scores[k]) return GNNCCA_ERR_INVALID_ARG;
+        sc->p[k] = scores[k], sc->stride[k] = score_strides[k], sc->cmp[k] = comparators[k];
     }
+    return GNNCCA_OK;
+}
+
+// The three launches every sweep that prunes starts with: the graph plan (launch_post_plan: plan_only + plan finish, nothing without
+// edges) and one prepare kernel -- rev and the lgamma tables; with `keys` (the exclusive sweep) its own kernel, which writes the pair keys
+// too.  The tables come back as pointers into the workspace.
+struct SweepTables { int* rev; excl_u64* keys; double* lf; };
+struct SweepExclKeys { const float* scores; const int32_t* edge_ptr_dev; int P; };   // what the pair keys are made of, besides the plan
+static int sweep_prepare(const SweepWorkspace& ws, void* workspace, const long long* ei, int E, int N, const int32_t* node_ptr_dev,
+                         int32_t n_frames, const SweepExclKeys* keys, hipStream_t st, SweepTables* out) {
+    char* base = static_cast<char*>(workspace);
+    const PostPlanPtrs plan = post_plan_ptrs(workspace, ws.plan);
+    *out = SweepTables{reinterpret_cast<int*>(base + ws.rev), reinterpret_cast<excl_u64*>(base + ws.keys), reinterpret_cast<double*>(base + ws.lf)};
+    if (const int rc = launch_post_plan(ei, E, N, plan, EmptyPlan::kSkip, st)) return rc;
     const int edge_blocks = (E + 255) / 256;
-    hipLaunchKernelGGL(eval_sweep_prepare_kernel, dim3((unsigned)edge_blocks + (unsigned)n_frames), dim3(256), 0, st, ei, (long long)E,
-                       (const int*)seg_ptr, (const int*)col32, (const int*)perm, (const unsigned*)flags, rev, edge_blocks, node_ptr_dev, N, lf);
+    const dim3 grid((unsigned)edge_blocks + (unsigned)n_frames);
+    if (keys)
+        hipLaunchKernelGGL(eval_sweep_excl_prepare_kernel, grid, dim3(256), 0, st, ei, (long long)E, (const int*)plan.seg_ptr, (const int*)plan.col32,
+                           (const int*)plan.perm, (const unsigned*)plan.flags, keys->scores, out->rev, out->keys, edge_blocks, node_ptr_dev,
+                           keys->edge_ptr_dev, (int)n_frames, N, keys->P, out->lf);
+    else
+        hipLaunchKernelGGL(eval_sweep_prepare_kernel, grid, dim3(256), 0, st, ei, (long long)E, (const int*)plan.seg_ptr, (const int*)plan.col32,
+                           (const int*)plan.perm, (const unsigned*)plan.flags, out->rev, edge_blocks, node_ptr_dev, N, out->lf);
     HIP_TRY(hipGetLastError());
-    *rev_out = rev, *lf_out = lf;
     return GNNCCA_OK;
 }
 
@@ -506,122 +577,56 @@ int gnncca_eval_sweep(const int64_t* edge_index, const float* edge_labels, const
                       const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes,
                       const double* thresholds_dev, int32_t n_thresholds, int32_t keep_le, double* rows_out, int32_t* labels_out,
                       void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (n_thresholds < 1 || n_thresholds > GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS) return GNNCCA_ERR_INVALID_ARG;
-    if (max_frame_nodes < 0 || max_frame_nodes > kEvalMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
-    if (!thresholds_dev) return GNNCCA_ERR_INVALID_ARG;
-    if (n_frames == 0) return GNNCCA_OK;
-    if (!node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
-    if (n_edges > 0 && (!edge_index || !edge_labels || !scores)) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    const SweepWorkspace ws = carve_sweep(n_nodes, n_edges, n_frames);
-    if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    const SweepWorkspace ws = carve_sweep(n_nodes, n_edges, n_frames, false);
+    SweepPtrs p{};
+    p.points = thresholds_dev, p.edge_index = edge_index, p.edge_labels = edge_labels, p.scores = scores, p.cam = nullptr;
+    p.node_ptr = node_ptr_dev, p.edge_ptr = edge_ptr_dev, p.rows_out = rows_out, p.workspace = workspace;
+    bool work;
+    if (const int rc = sweep_check(kLimitsComponents, n_nodes, n_edges, n_frames, max_frame_nodes, n_thresholds, p, workspace_bytes, ws.total, &work); rc || !work) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = (int)n_nodes, E = (int)n_edges;
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
-    int* rev = nullptr;
-    double* lf = nullptr;
-    if (const int rc = sweep_prepare(ws, workspace, ei, E, N, node_ptr_dev, n_frames, st, &rev, &lf)) return rc;
-    int P = 1;
-    while (P < max_frame_nodes) P <<= 1;
+    SweepTables tb;
+    if (const int rc = sweep_prepare(ws, workspace, ei, E, N, node_ptr_dev, n_frames, nullptr, st, &tb)) return rc;
+    const int P = frame_capacity(max_frame_nodes);
     const size_t lds = (size_t)3 * P * sizeof(int) + (size_t)P * sizeof(unsigned short);
     const dim3 grid((unsigned)n_frames, (unsigned)n_thresholds);
-#define GNNCCA_SWEEP(B)                                                                                                                  \
-    hipLaunchKernelGGL((eval_sweep_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, scores, (const int*)rev, thresholds_dev, \
-                       (int)keep_le, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
-    if (P <= 64) GNNCCA_SWEEP(64); else GNNCCA_SWEEP(256);   // (eval_frames' choice)
-#undef GNNCCA_SWEEP
+    launch_frame_block(P, [&](auto block) {
+        constexpr int B = decltype(block)::value;
+        hipLaunchKernelGGL((eval_sweep_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, scores, (const int*)tb.rev, thresholds_dev,
+                           (int)keep_le, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, tb.lf);
+    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
-}
-
-// ---- the threshold sweep over the camera-exclusive partition (eval_sweep_exclusive.cuh) ------------------------------------------------
-// workspace: [the graph plan | rev int32 [E] | pair keys u64 [E] | lgamma tables fp64 [N + G]] -- O(E + N) whatever T is
-struct SweepExclWorkspace { PostWorkspace plan; size_t rev, keys, lf, total; };
-static SweepExclWorkspace carve_sweep_excl(int64_t n, int64_t e, int64_t g) {
-    SweepExclWorkspace w;
-    w.plan = carve_post(n, e);
-    size_t off = w.plan.total;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    w.rev = take((size_t)e * 4), w.keys = take((size_t)e * 8), w.lf = take(((size_t)n + (size_t)g) * sizeof(double)), w.total = off;
-    return w;
-}
-
-size_t gnncca_eval_sweep_exclusive_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames, int64_t n_thresholds) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0 || n_thresholds < 0) return 0;
-    return carve_sweep_excl(n_nodes, n_edges, n_frames).total;
 }
 
 int gnncca_eval_sweep_exclusive(const int64_t* edge_index, const float* edge_labels, const float* scores, const int32_t* cam, int64_t n_nodes,
                                 int64_t n_edges, const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
                                 int32_t max_frame_nodes, const double* thresholds_dev, int32_t n_thresholds, double* rows_out,
                                 int32_t* labels_out, void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (n_thresholds < 1 || n_thresholds > GNNCCA_EVAL_SWEEP_MAX_THRESHOLDS) return GNNCCA_ERR_INVALID_ARG;
-    if (max_frame_nodes < 0 || max_frame_nodes > kExclMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
-    if (!thresholds_dev) return GNNCCA_ERR_INVALID_ARG;
-    if (n_frames == 0) return GNNCCA_OK;
-    if (!node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes > 0 && !cam) return GNNCCA_ERR_INVALID_ARG;
-    if (n_edges > 0 && (!edge_index || !edge_labels || !scores)) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    const SweepExclWorkspace ws = carve_sweep_excl(n_nodes, n_edges, n_frames);
-    if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    const SweepWorkspace ws = carve_sweep(n_nodes, n_edges, n_frames, true);
+    SweepPtrs p{};
+    p.points = thresholds_dev, p.edge_index = edge_index, p.edge_labels = edge_labels, p.scores = scores, p.cam = cam;
+    p.node_ptr = node_ptr_dev, p.edge_ptr = edge_ptr_dev, p.rows_out = rows_out, p.workspace = workspace;
+    bool work;
+    if (const int rc = sweep_check(kLimitsExclusive, n_nodes, n_edges, n_frames, max_frame_nodes, n_thresholds, p, workspace_bytes, ws.total, &work); rc || !work) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = (int)n_nodes, E = (int)n_edges;
-    int P = 1;
-    while (P < max_frame_nodes) P <<= 1;
-    const size_t lds = (size_t)20 * P;   // best u64 | mask u64 | parent int; the scoring's 14 P lie inside (eval_sweep_exclusive.cuh)
-    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (exclusive.cuh's entry, rerank.hip)
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (attr_dev != dev) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_sweep_excl_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)20 * kExclMaxNodes)));
-            attr_dev = dev;
-        }
-    }
-    char* base = static_cast<char*>(workspace);
-    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
-    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
-    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
-    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
-    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
-    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
-    int* rev = reinterpret_cast<int*>(base + ws.rev);
-    excl_u64* keys = reinterpret_cast<excl_u64*>(base + ws.keys);
-    double* lf = reinterpret_cast<double*>(base + ws.lf);
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
-    if (E > 0) {   // the plan of gnncca_post_prune_cluster (no padded layout to validate)
-        EncPlanParams ep;
-        std::memset(&ep, 0, sizeof(ep));
-        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
-        launch_plan_only(ep, plan_num_blocks(E), st);
-        HIP_TRY(hipGetLastError());
-        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
-        HIP_TRY(hipGetLastError());
-    }
-    const int edge_blocks = (E + 255) / 256;
-    hipLaunchKernelGGL(eval_sweep_excl_prepare_kernel, dim3((unsigned)edge_blocks + (unsigned)n_frames), dim3(256), 0, st, ei, (long long)E,
-                       (const int*)seg_ptr, (const int*)col32, (const int*)perm, (const unsigned*)flags, scores, rev, keys, edge_blocks,
-                       node_ptr_dev, edge_ptr_dev, (int)n_frames, N, P, lf);
-    HIP_TRY(hipGetLastError());
+    const int P = frame_capacity(max_frame_nodes);
+    const size_t lds = (size_t)20 * P;   // best u64 | mask u64 | parent int; the scoring's 14 P lie inside (eval_sweep_exclusive.cuh)
+    if (lds > 64 * 1024) HIP_TRY(lds_opt_in<eval_sweep_excl_kernel<256>>((size_t)20 * kExclMaxNodes));
+    const SweepExclKeys keys{scores, edge_ptr_dev, P};
+    SweepTables tb;
+    if (const int rc = sweep_prepare(ws, workspace, ei, E, N, node_ptr_dev, n_frames, &keys, st, &tb)) return rc;
     const dim3 grid((unsigned)n_frames, (unsigned)n_thresholds);
-#define GNNCCA_SWEEP_EXCL(B)                                                                                                                \
-    hipLaunchKernelGGL((eval_sweep_excl_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, scores, cam, (const int*)rev,    \
-                       (const excl_u64*)keys, thresholds_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
-    if (P <= 64) GNNCCA_SWEEP_EXCL(64); else GNNCCA_SWEEP_EXCL(256);   // (gnncca_eval_sweep's choice, which is eval_frames')
-#undef GNNCCA_SWEEP_EXCL
+    launch_frame_block(P, [&](auto block) {
+        constexpr int B = decltype(block)::value;
+        hipLaunchKernelGGL((eval_sweep_excl_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, scores, cam, (const int*)tb.rev,
+                           (const excl_u64*)tb.keys, thresholds_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, tb.lf);
+    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
-}
-
-// ---- the sweep of a conjunction of conditions (eval_sweep_joint.cuh) ------------------------------------------------------------------
-// workspace: gnncca_eval_sweep's, whatever the numbers of points and scores are
-size_t gnncca_eval_sweep_joint_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_frames) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return 0;
-    return carve_sweep(n_nodes, n_edges, n_frames).total;
 }
 
 int gnncca_eval_sweep_joint(const int64_t* edge_index, const float* edge_labels, const float* const* scores, const int64_t* score_strides,
@@ -629,48 +634,29 @@ int gnncca_eval_sweep_joint(const int64_t* edge_index, const float* edge_labels,
                             const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes, const double* points_dev,
                             int32_t n_points, const double* frame_div_dev, double* rows_out, int32_t* labels_out, void* workspace,
                             size_t workspace_bytes, gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (n_scores < 1 || n_scores > GNNCCA_EVAL_JOINT_MAX_SCORES) return GNNCCA_ERR_INVALID_ARG;
-    if (n_points < 1 || n_points > GNNCCA_EVAL_JOINT_MAX_POINTS) return GNNCCA_ERR_INVALID_ARG;
-    if (max_frame_nodes < 0 || max_frame_nodes > kEvalMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
-    if (!points_dev || !scores || !score_strides || !comparators) return GNNCCA_ERR_INVALID_ARG;
     JointScores sc;
-    std::memset(&sc, 0, sizeof(sc));
-    sc.K = n_scores;
-    for (int k = 0; k < n_scores; ++k) {
-        if (comparators[k] < GNNCCA_CMP_GE || comparators[k] > GNNCCA_CMP_LT || score_strides[k] < 1) return GNNCCA_ERR_INVALID_ARG;
-        if (n_edges > 0 && !scores[k]) return GNNCCA_ERR_INVALID_ARG;
-        sc.p[k] = scores[k], sc.stride[k] = score_strides[k], sc.cmp[k] = comparators[k];
-    }
-    if (n_frames == 0) return GNNCCA_OK;
-    if (!node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
-    if (n_edges > 0 && (!edge_index || !edge_labels)) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    const SweepWorkspace ws = carve_sweep(n_nodes, n_edges, n_frames);
-    if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
+    if (const int rc = joint_scores(scores, score_strides, comparators, n_scores, n_edges, &sc)) return rc;
+    const SweepWorkspace ws = carve_sweep(n_nodes, n_edges, n_frames, false);
+    SweepPtrs p{};
+    p.points = points_dev, p.edge_index = edge_index, p.edge_labels = edge_labels, p.scores = scores, p.cam = nullptr;
+    p.node_ptr = node_ptr_dev, p.edge_ptr = edge_ptr_dev, p.rows_out = rows_out, p.workspace = workspace;
+    bool work;
+    if (const int rc = sweep_check(kLimitsJoint, n_nodes, n_edges, n_frames, max_frame_nodes, n_points, p, workspace_bytes, ws.total, &work); rc || !work) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = (int)n_nodes, E = (int)n_edges;
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
-    int* rev = nullptr;
-    double* lf = nullptr;
-    if (const int rc = sweep_prepare(ws, workspace, ei, E, N, node_ptr_dev, n_frames, st, &rev, &lf)) return rc;
-    int P = 1;
-    while (P < max_frame_nodes) P <<= 1;
-    const size_t lds = (size_t)3 * P * sizeof(int) + (size_t)P * sizeof(unsigned short);   // (gnncca_eval_sweep's: the body is the same)
+    SweepTables tb;
+    if (const int rc = sweep_prepare(ws, workspace, ei, E, N, node_ptr_dev, n_frames, nullptr, st, &tb)) return rc;
+    const int P = frame_capacity(max_frame_nodes);
+    const size_t lds = (size_t)3 * P * sizeof(int) + (size_t)P * sizeof(unsigned short);   // (eval_sweep_body's, as in gnncca_eval_sweep)
     const dim3 grid((unsigned)n_frames, (unsigned)n_points);
-#define GNNCCA_SWEEP_JOINT(B)                                                                                                               \
-    hipLaunchKernelGGL((eval_sweep_joint_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, sc, (const int*)rev, points_dev, \
-                       frame_div_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
-    if (P <= 64) GNNCCA_SWEEP_JOINT(64); else GNNCCA_SWEEP_JOINT(256);   // (eval_frames' choice)
-#undef GNNCCA_SWEEP_JOINT
+    launch_frame_block(P, [&](auto block) {
+        constexpr int B = decltype(block)::value;
+        hipLaunchKernelGGL((eval_sweep_joint_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, sc, (const int*)tb.rev, points_dev,
+                           frame_div_dev, N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, tb.lf);
+    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
-}
-
-// ---- the sweep over the strongly connected clusters (eval_sweep_strong.cuh) -------------------------------------------------------------
-// workspace: the lgamma tables fp64 [N + G], nothing else (no plan, no reverse edges)
-size_t gnncca_eval_sweep_strong_workspace_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_frames) {
-    return gnncca_eval_workspace_bytes(n_nodes, n_edges, n_frames);
 }
 
 int gnncca_eval_sweep_strong(const int64_t* edge_index, const float* edge_labels, const float* const* scores, const int64_t* score_strides,
@@ -678,37 +664,17 @@ int gnncca_eval_sweep_strong(const int64_t* edge_index, const float* edge_labels
                              const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes, const double* points_dev,
                              int32_t n_points, const double* frame_div_dev, double* rows_out, int32_t* labels_out, void* workspace,
                              size_t workspace_bytes, gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0 || n_points < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (n_scores < 1 || n_scores > GNNCCA_EVAL_JOINT_MAX_SCORES) return GNNCCA_ERR_INVALID_ARG;
-    if (n_points > GNNCCA_EVAL_JOINT_MAX_POINTS) return GNNCCA_ERR_INVALID_ARG;
-    if (max_frame_nodes < 0 || max_frame_nodes > kSweepStrongMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
-    if (!scores || !score_strides || !comparators) return GNNCCA_ERR_INVALID_ARG;
     JointScores sc;
-    std::memset(&sc, 0, sizeof(sc));
-    sc.K = n_scores;
-    for (int k = 0; k < n_scores; ++k) {
-        if (comparators[k] < GNNCCA_CMP_GE || comparators[k] > GNNCCA_CMP_LT || score_strides[k] < 1) return GNNCCA_ERR_INVALID_ARG;
-        if (n_edges > 0 && !scores[k]) return GNNCCA_ERR_INVALID_ARG;
-        sc.p[k] = scores[k], sc.stride[k] = score_strides[k], sc.cmp[k] = comparators[k];
-    }
-    if (n_frames == 0 || n_points == 0) return GNNCCA_OK;
-    if (!points_dev || !node_ptr_dev || !edge_ptr_dev || !rows_out || !workspace) return GNNCCA_ERR_INVALID_ARG;
-    if (n_edges > 0 && (!edge_index || !edge_labels)) return GNNCCA_ERR_INVALID_ARG;
-    if (workspace_bytes < gnncca_eval_sweep_strong_workspace_bytes(n_nodes, n_edges, n_frames)) return GNNCCA_ERR_WORKSPACE;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
-    int P = 1;
-    while (P < max_frame_nodes) P <<= 1;
-    const size_t lds = sweep_strong_shared_bytes(P) + (size_t)P * sizeof(unsigned short);
-    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (gnncca_eval_sweep_exclusive's way)
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (attr_dev != dev) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_sweep_strong_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(sweep_strong_shared_bytes(kSweepStrongMaxNodes) + kSweepStrongMaxNodes * sizeof(unsigned short))));
-            attr_dev = dev;
-        }
-    }
+    if (const int rc = joint_scores(scores, score_strides, comparators, n_scores, n_edges, &sc)) return rc;
+    SweepPtrs p{};
+    p.points = points_dev, p.edge_index = edge_index, p.edge_labels = edge_labels, p.scores = scores, p.cam = nullptr;
+    p.node_ptr = node_ptr_dev, p.edge_ptr = edge_ptr_dev, p.rows_out = rows_out, p.workspace = workspace;
+    bool work;
+    if (const int rc = sweep_check(kLimitsStrong, n_nodes, n_edges, n_frames, max_frame_nodes, n_points, p, workspace_bytes, gnncca_eval_sweep_strong_workspace_bytes(n_nodes, n_edges, n_frames), &work); rc || !work) return rc;
+    const int P = frame_capacity(max_frame_nodes);
+    const auto lds_at = [](int nodes) { return sweep_strong_shared_bytes(nodes) + (size_t)nodes * sizeof(unsigned short); };
+    const size_t lds = lds_at(P);
+    if (lds > 64 * 1024) HIP_TRY(lds_opt_in<eval_sweep_strong_kernel<256>>(lds_at(kSweepStrongMaxNodes)));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = (int)n_nodes, E = (int)n_edges;
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
@@ -718,11 +684,11 @@ int gnncca_eval_sweep_strong(const int64_t* edge_index, const float* edge_labels
                        (const int*)nullptr, (const int*)nullptr, (const unsigned*)nullptr, (int*)nullptr, 0, node_ptr_dev, N, lf);
     HIP_TRY(hipGetLastError());
     const dim3 grid((unsigned)n_frames, (unsigned)n_points);
-#define GNNCCA_SWEEP_STRONG(B)                                                                                                            \
-    hipLaunchKernelGGL((eval_sweep_strong_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, sc, points_dev, frame_div_dev, \
-                       N, node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf)
-    if (P <= 64) GNNCCA_SWEEP_STRONG(64); else GNNCCA_SWEEP_STRONG(256);   // (eval_frames' choice)
-#undef GNNCCA_SWEEP_STRONG
+    launch_frame_block(P, [&](auto block) {
+        constexpr int B = decltype(block)::value;
+        hipLaunchKernelGGL((eval_sweep_strong_kernel<B>), grid, dim3(B), lds, st, ei, (long long)E, edge_labels, sc, points_dev, frame_div_dev, N,
+                           node_ptr_dev, edge_ptr_dev, P, rows_out, labels_out, lf);
+    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -766,16 +732,7 @@ int gnncca_rank_metrics(const float* edge_labels, const float* const* scores, co
     const int cap = (int)(lds / sizeof(rank_u64));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)n_frames, (unsigned)n_scores);
-    if (cap > 4096) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (gnncca_eval_sweep_exclusive's way)
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (attr_dev != dev) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_metrics_kernel<1024>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kRankMaxEdges * sizeof(rank_u64))));
-            attr_dev = dev;
-        }
-    }
+    if (cap > 4096) HIP_TRY(lds_opt_in<rank_metrics_kernel<1024>>(kRankMaxEdges * sizeof(rank_u64)));   // (above 64 KiB of dynamic LDS)
 #define GNNCCA_RANK(B)                                                                                                             \
     hipLaunchKernelGGL((rank_metrics_kernel<B>), grid, dim3(B), lds, st, edge_labels, (long long)n_edges, sc, edge_ptr_dev, cap, rows_out)
     if (cap <= 1024) GNNCCA_RANK(256);   // threads by capacity: at most 16 words of the image per thread

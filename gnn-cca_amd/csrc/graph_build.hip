@@ -538,14 +538,7 @@ int gnncca_normalize_columns2(const float* x0, int64_t n_cols0, float* out0, con
     static const bool no_lds = diag_env("GNNCCA_COLNORM_NOLDS") != nullptr;   // diagnostics: A/B against the two-pass form
     if (!no_lds && n_rows <= kLdsRowsMax && vec_ok(x0, out0, n_cols0) && vec_ok(x1, out1, n_cols1)) {
         const int lds = (int)((n_rows + kColChunk - 1) / kColChunk) * kLdsChunkBytes;
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (attr_dev != dev) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(colnorm_fused_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (kLdsRowsMax / kColChunk) * kLdsChunkBytes));
-            attr_dev = dev;
-        }
+        HIP_TRY(lds_opt_in<colnorm_fused_lds_kernel>((kLdsRowsMax / kColChunk) * kLdsChunkBytes));
         hipLaunchKernelGGL(colnorm_fused_lds_kernel, dim3((unsigned)(b0 + b1)), dim3(256), (size_t)lds, static_cast<hipStream_t>(stream), j0, j1,
                            (long long)n_rows);
     } else {

@@ -193,14 +193,7 @@ static int assign_level_launch(hipStream_t st, int n_frames, int P, const int* n
                                const GapFrames& in, int* succ_ws, int* matched_prev, int* matched_gap, int* new_rank_ws, int* n_new_ws,
                                double miss_cost, const double* frame_time, double max_dt) {
     if (P > kTrackMaxOptimalNodes) return GNNCCA_ERR_INVALID_ARG;   // (the entry refused such a frame already)
-    static thread_local int attr_dev = -1;   // above 64 KiB of dynamic LDS the function needs the attribute, once per device
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (attr_dev != dev) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gap_level_assign_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)assign_lds_bytes(kTrackMaxOptimalNodes)));
-        attr_dev = dev;
-    }
+    HIP_TRY(lds_opt_in<gap_level_assign_kernel<256>>(assign_lds_bytes(kTrackMaxOptimalNodes)));
     hipLaunchKernelGGL((gap_level_assign_kernel<256>), dim3((unsigned)n_frames), dim3(256), assign_lds_bytes(P), st, node_ptr_dev, n_nodes, count,
                        pos, emb, R, level_rule, miss_cost, level, last_level, sin, in, P, succ_ws, matched_prev, matched_gap, new_rank_ws,
                        n_new_ws, frame_time, max_dt);

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gnncca_mpn.h"
 
 namespace gnncca {
@@ -395,6 +397,40 @@ inline PostWorkspace carve_post(int64_t n, int64_t e) {
     w.flags = take(256), w.blockflags = take((E / 256 + 2) * 4), w.seg_ptr = take((N + 1) * 4), w.col32 = take(E * 4);
     w.perm = take(E * 4), w.cursor = take((N + 1) * 4), w.total = off;
     return w;
+}
+// The plan's six arrays inside a workspace that starts with a PostWorkspace (the post stage's, the sweeps', the exclusive clusters').
+struct PostPlanPtrs {
+    unsigned* flags;
+    unsigned* blockflags;
+    int* seg_ptr;
+    int* col32;
+    int* perm;
+    int* cursor;
+};
+inline PostPlanPtrs post_plan_ptrs(void* workspace, const PostWorkspace& w) {
+    char* base = static_cast<char*>(workspace);
+    return PostPlanPtrs{reinterpret_cast<unsigned*>(base + w.flags), reinterpret_cast<unsigned*>(base + w.blockflags),
+                        reinterpret_cast<int*>(base + w.seg_ptr),    reinterpret_cast<int*>(base + w.col32),
+                        reinterpret_cast<int*>(base + w.perm),       reinterpret_cast<int*>(base + w.cursor)};
+}
+// Builds the plan of edge_index into those arrays: plan_only + plan finish, no padded layout to validate (mpn_post.hip defines it; the
+// status is HIP_TRY's).  A graph without edges launches nothing (kSkip: the sweeps, the exclusive clusters), or the finish alone, which
+// leaves a finished plan -- flag word and segment offsets -- in the workspace all the same (kFinish: gnncca_post_prune_cluster*).
+enum class EmptyPlan { kSkip, kFinish };
+int launch_post_plan(const long long* ei, int E, int N, const PostPlanPtrs& p, EmptyPlan when_empty, gnncca_stream_t stream);
+
+// The frame-local kernels (one workgroup per frame, the frame in LDS): their LDS capacity in nodes is the batch's largest frame rounded
+// up to a power of two, and their block is one wave while that capacity fits one (a Terrace frame has ~20 detections), 256 threads
+// otherwise.  launch(std::integral_constant<int, BLOCK>) makes the launch.
+inline int frame_capacity(int32_t max_frame_nodes) {
+    int P = 1;
+    while (P < max_frame_nodes) P <<= 1;
+    return P;
+}
+template <class Launch>
+inline void launch_frame_block(int P, Launch&& launch) {
+    if (P <= 64) launch(std::integral_constant<int, 64>{});
+    else launch(std::integral_constant<int, 256>{});
 }
 
 // ---- kernels of mpn_forward.hip that mpn_post.hip and mpn_train.hip launch too ---------------------------------------------------

@@ -8,6 +8,25 @@
 #include "exclusive.cuh"
 #include "strong.cuh"
 
+namespace gnncca {
+
+int launch_post_plan(const long long* ei, int E, int N, const PostPlanPtrs& p, EmptyPlan when_empty, gnncca_stream_t stream) {
+    if (E > 0) {
+        EncPlanParams ep;
+        std::memset(&ep, 0, sizeof(ep));
+        ep.ei = ei, ep.seg_ptr = p.seg_ptr, ep.col32 = p.col32, ep.blockflags = p.blockflags, ep.E = E, ep.N = N;
+        launch_plan_only(ep, plan_num_blocks(E), stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (E > 0 || when_empty == EmptyPlan::kFinish) {
+        launch_gen_plan_finish(ei, E, N, p.seg_ptr, p.col32, p.perm, p.cursor, p.flags, p.blockflags, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return GNNCCA_OK;
+}
+
+}  // namespace gnncca
+
 using namespace gnncca;
 
 extern "C" {
@@ -123,17 +142,12 @@ static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* pre
     if (!plan && workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = (int)n_nodes, E = (int)n_edges;
-    char* base = static_cast<char*>(workspace);
-    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.flags);
-    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.blockflags);
-    int* seg_ptr = reinterpret_cast<int*>(base + ws.seg_ptr);
-    int* col32 = reinterpret_cast<int*>(base + ws.col32);
-    int* perm = reinterpret_cast<int*>(base + ws.perm);
-    int* cursor = reinterpret_cast<int*>(base + ws.cursor);
-    if (plan) {   // the MPN forward's plan of the same edge_index: nothing to build here
-        seg_ptr = const_cast<int*>(plan->seg_ptr), col32 = const_cast<int*>(plan->col32), perm = const_cast<int*>(plan->perm);
-        flags = const_cast<unsigned*>(plan->flags);
-    }
+    const PostPlanPtrs own = post_plan_ptrs(workspace, ws);
+    // (with `plan`: the MPN forward's plan of the same edge_index, nothing to build here)
+    const int* seg_ptr = plan ? plan->seg_ptr : own.seg_ptr;
+    const int* col32 = plan ? plan->col32 : own.col32;
+    const int* perm = plan ? plan->perm : own.perm;
+    const unsigned* flags = plan ? plan->flags : own.flags;
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
     const long long* pred = reinterpret_cast<const long long*>(predictions);
     long long* pruned = reinterpret_cast<long long*>(pruned_out);
@@ -155,31 +169,15 @@ static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* pre
         HIP_TRY(hipMemsetAsync(sizes_scratch, 0, (size_t)N * 4, st));
         HIP_TRY(hipMemsetAsync(triggers_out, 0, n_trig * 4, st));
     }
-    if (E > 0 && !plan) {
-        EncPlanParams ep;
-        std::memset(&ep, 0, sizeof(ep));
-        ep.ei = ei;
-        ep.seg_ptr = seg_ptr;
-        ep.col32 = col32;
-        ep.blockflags = blockflags;
-        ep.E = E;
-        ep.N = N;
-        launch_plan_only(ep, plan_num_blocks(E), st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!plan) {
-        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
-        HIP_TRY(hipGetLastError());
-    }
+    if (!plan)   // (kFinish: this entry's finish runs without edges too, so the workspace always holds a finished plan afterwards)
+        if (const int rc = launch_post_plan(ei, E, N, own, EmptyPlan::kFinish, st)) return rc;
     if (E > 0) {
         if (plan && plan->logits)
-            hipLaunchKernelGGL(post_prune_kernel<true>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, (const int*)seg_ptr,
-                               (const int*)col32, (const int*)perm, (const unsigned*)flags, pruned, flow_out, flow_in, plan->logits,
-                               plan->probs_out, reinterpret_cast<long long*>(plan->preds_out));
+            hipLaunchKernelGGL(post_prune_kernel<true>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, seg_ptr, col32, perm, flags,
+                               pruned, flow_out, flow_in, plan->logits, plan->probs_out, reinterpret_cast<long long*>(plan->preds_out));
         else
-            hipLaunchKernelGGL(post_prune_kernel<false>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, (const int*)seg_ptr,
-                               (const int*)col32, (const int*)perm, (const unsigned*)flags, pruned, flow_out, flow_in, (const float*)nullptr,
-                               (float*)nullptr, (long long*)nullptr);
+            hipLaunchKernelGGL(post_prune_kernel<false>, grid1((size_t)E, 256), dim3(256), 0, st, ei, pred, (long long)E, seg_ptr, col32, perm, flags,
+                               pruned, flow_out, flow_in, (const float*)nullptr, (float*)nullptr, (long long*)nullptr);
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(post_cc_kernel, dim3(node_ptr_dev ? (unsigned)n_frames : 1u), dim3(1024), 0, st, ei,
@@ -231,48 +229,25 @@ int gnncca_post_exclusive_frames(const int64_t* edge_index, const float* scores,
     if (workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
     const int N = (int)n_nodes, E = (int)n_edges;
     char* base = static_cast<char*>(workspace);
-    unsigned* flags = reinterpret_cast<unsigned*>(base + ws.plan.flags);
-    unsigned* blockflags = reinterpret_cast<unsigned*>(base + ws.plan.blockflags);
-    int* seg_ptr = reinterpret_cast<int*>(base + ws.plan.seg_ptr);
-    int* col32 = reinterpret_cast<int*>(base + ws.plan.col32);
-    int* perm = reinterpret_cast<int*>(base + ws.plan.perm);
-    int* cursor = reinterpret_cast<int*>(base + ws.plan.cursor);
+    const PostPlanPtrs plan = post_plan_ptrs(workspace, ws.plan);
     int* rev = reinterpret_cast<int*>(base + ws.rev);
     excl_u64* cand = reinterpret_cast<excl_u64*>(base + ws.cand);
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
-    int P = 1;
-    while (P < max_frame_nodes) P <<= 1;
-    const size_t lds = (size_t)P * (2 * sizeof(excl_u64) + sizeof(int)) + 8 * sizeof(int);
-    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (rerank.hip)
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (attr_dev != dev) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(excl_cluster_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)kExclMaxNodes * (2 * sizeof(excl_u64) + sizeof(int)) + 8 * sizeof(int))));
-            attr_dev = dev;
-        }
-    }
-    if (E > 0) {   // the plan of gnncca_post_prune_cluster (no padded layout to validate)
-        EncPlanParams ep;
-        std::memset(&ep, 0, sizeof(ep));
-        ep.ei = ei, ep.seg_ptr = seg_ptr, ep.col32 = col32, ep.blockflags = blockflags, ep.E = E, ep.N = N;
-        launch_plan_only(ep, plan_num_blocks(E), st);
-        HIP_TRY(hipGetLastError());
-        launch_gen_plan_finish(ei, E, N, seg_ptr, col32, perm, cursor, flags, blockflags, st);
-        HIP_TRY(hipGetLastError());
-    }
+    const int P = frame_capacity(max_frame_nodes);
+    const auto lds_at = [](size_t nodes) { return nodes * (2 * sizeof(excl_u64) + sizeof(int)) + 8 * sizeof(int); };
+    const size_t lds = lds_at(P);
+    if (lds > 64 * 1024) HIP_TRY(lds_opt_in<excl_cluster_kernel<256>>(lds_at(kExclMaxNodes)));
+    if (const int rc = launch_post_plan(ei, E, N, plan, EmptyPlan::kSkip, st)) return rc;
     // the reverse edges, and *n_clusters_out = 0 (kernels only on the stream: no memset)
-    hipLaunchKernelGGL(excl_prepare_kernel, grid1((size_t)std::max(E, 1), 256), dim3(256), 0, st, ei, (long long)E, (const int*)seg_ptr,
-                       (const int*)col32, (const int*)perm, (const unsigned*)flags, rev, n_clusters_out);
+    hipLaunchKernelGGL(excl_prepare_kernel, grid1((size_t)std::max(E, 1), 256), dim3(256), 0, st, ei, (long long)E, (const int*)plan.seg_ptr,
+                       (const int*)plan.col32, (const int*)plan.perm, (const unsigned*)plan.flags, rev, n_clusters_out);
     HIP_TRY(hipGetLastError());
     long long* preds = reinterpret_cast<long long*>(predictions_out);
-#define GNNCCA_EXCL(B)                                                                                                                      \
-    hipLaunchKernelGGL((excl_cluster_kernel<B>), dim3((unsigned)n_frames), dim3(B), lds, st, ei, (long long)E, scores, threshold, cam,         \
-                       (const int*)rev, cand, N, node_ptr_dev, edge_ptr_dev, P, preds, labels_out, n_clusters_out, cut_out, \
-                       flags_out)
-    if (P <= 64) GNNCCA_EXCL(64); else GNNCCA_EXCL(256);   // (eval_frames' choice: a Terrace frame has ~20 detections, one wave per frame)
-#undef GNNCCA_EXCL
+    launch_frame_block(P, [&](auto block) {
+        constexpr int B = decltype(block)::value;
+        hipLaunchKernelGGL((excl_cluster_kernel<B>), dim3((unsigned)n_frames), dim3(B), lds, st, ei, (long long)E, scores, threshold, cam,
+                           (const int*)rev, cand, N, node_ptr_dev, edge_ptr_dev, P, preds, labels_out, n_clusters_out, cut_out, flags_out);
+    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -301,16 +276,7 @@ int gnncca_post_strong_frames(const int64_t* edge_index, const int64_t* predicti
     }
     const int P = (max_frame_nodes + 31) / 32 * 32;            // the LDS capacity in nodes: rows of P / 32 words
     const size_t lds = (size_t)P * (size_t)(P / 32) * 4;       // 128 B at 32, 2 KiB at 128, 128 KiB at 1024
-    if (lds > 64 * 1024) {   // above 64 KiB of dynamic LDS the function needs the attribute, once per device (exclusive frames above)
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (attr_dev != dev) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(strong_cluster_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        kStrongMaxNodes * (kStrongMaxNodes / 32) * 4));
-            attr_dev = dev;
-        }
-    }
+    if (lds > 64 * 1024) HIP_TRY(lds_opt_in<strong_cluster_kernel<1024>>((size_t)kStrongMaxNodes * (kStrongMaxNodes / 32) * 4));
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
     const long long* pred = reinterpret_cast<const long long*>(predictions);
 #define GNNCCA_STRONG(B)                                                                                                                     \

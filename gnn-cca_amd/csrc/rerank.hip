@@ -52,17 +52,10 @@ int gnncca_rerank_frames(const float* dist, int64_t total, int64_t n_nodes, cons
     const int P = max_frame_nodes;
     const size_t lds = rerank_lds(P, k1, k2).total;
     const bool big = P > 64;   // 16 waves share the one workgroup a CU holds at that size; small frames take 4 and several fit
-    if (lds > 64 * 1024) {     // above 64 KiB of dynamic LDS the function needs the attribute, once per device
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (attr_dev != dev) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rerank_frames_kernel<1024, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)rerank_lds(kRerankMaxNodes, kRerankMaxK1, kRerankMaxK1).total));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(rerank_frames_kernel<1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)rerank_lds(kRerankMaxNodes, kRerankMaxK1, kRerankMaxK1).total));
-            attr_dev = dev;
-        }
+    if (lds > 64 * 1024) {     // (both forms: either may be the one launched below)
+        const size_t most = rerank_lds(kRerankMaxNodes, kRerankMaxK1, kRerankMaxK1).total;
+        HIP_TRY((lds_opt_in<rerank_frames_kernel<1024, false>>(most)));
+        HIP_TRY((lds_opt_in<rerank_frames_kernel<1024, true>>(most)));
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float lam32 = (float)lam, one_minus = (float)(1.0 - lam);   // the reference's python floats, rounded once as numpy rounds them

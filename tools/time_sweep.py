@@ -274,8 +274,8 @@ def main():
     if not args.loop_only:
         from gnn_cca_amd.calibration import sweep_thresholds
 
-        def loop_at():
-            return [one(threshold(logits, at=float(t))[1]) for t in ths]
+        def loop_at():   # (`threshold(at=t)` takes t strictly inside (0, 1): the sweep's last point, 1.0, is compared in torch)
+            return [one(threshold(logits, at=float(t))[1] if t < 1.0 else (probs.double() >= float(t)).to(torch.int64)) for t in ths]
 
         sides = {"sweep": (lambda: sweep_thresholds(b, probs, ths), args.reps), "loop_at": (loop_at, args.loop_reps), **sides}
         rows = sweep_thresholds(b, probs, ths)
