@@ -44,7 +44,7 @@ import torch
 from . import _native as nat
 from .evaluation import AGGREGATES, MAX_FRAME_NODES, METRICS, _aggregates, _dev_i32, _reduce_rows
 from .frames import _on, _raw_stream
-from .postprocess import check_cameras, check_threshold
+from .postprocess import check_cameras, check_threshold, widest_frame
 
 MAX_THRESHOLDS = nat.SWEEP_MAX_THRESHOLDS
 KEEP = ("ge", "le")
@@ -72,7 +72,7 @@ def _batch_dims(batch):
     """-> (g, n, e, max_n): the frames, nodes and edges of a GraphBatch and the detections of its widest frame."""
     node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
     g = len(node_ptr) - 1
-    return g, int(node_ptr[-1]) if g > 0 else 0, int(batch.edge_index.shape[1]), int(np.diff(node_ptr).max()) if g > 0 else 0
+    return g, int(node_ptr[-1]) if g > 0 else 0, int(batch.edge_index.shape[1]), widest_frame(node_ptr)
 
 
 def _stage(host, dev):

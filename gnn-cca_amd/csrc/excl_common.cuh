@@ -25,6 +25,27 @@ __device__ __forceinline__ bool excl_frame_ok(int v0, int v1, long long k0, long
     return !(v0 < 0 || n < 0 || n > P || v1 > N_all || k0 < 0 || k1 < k0 || k1 > E);
 }
 
+// Frame g's node and edge range; the whole graph where the offsets are null (post_cc_kernel, strong_cluster_kernel).
+struct FrameRange {
+    int v0, v1;
+    long long k0, k1;
+};
+__device__ __forceinline__ FrameRange frame_range(const int* __restrict__ node_ptr, const int* __restrict__ edge_ptr, int g, int N_all,
+                                                  long long E) {
+    return FrameRange{node_ptr ? node_ptr[g] : 0, node_ptr ? node_ptr[g + 1] : N_all, edge_ptr ? edge_ptr[g] : 0, edge_ptr ? edge_ptr[g + 1] : E};
+}
+
+// The answer for a frame that is refused (ranges that do not fit, a camera id out of range): every node its own cluster,
+// *n_clusters += n -- as far as the node range allows writing at all.
+template <int BLOCK>
+__device__ __forceinline__ void frame_singletons(int* __restrict__ labels, int* __restrict__ n_clusters, int v0, int v1, int N_all, int tid) {
+    const int n = v1 - v0;
+    if (v0 >= 0 && v1 <= N_all && n >= 0) {
+        for (int v = v0 + tid; v < v1; v += BLOCK) labels[v] = v;
+        if (tid == 0 && n > 0) atomicAdd(n_clusters, n);
+    }
+}
+
 // 64-bit key of the pair {lo, hi} (frame-local, lo < hi < 4096) of weight w > 0: (fp32 bits of w) << 24 | (4095 - lo) << 12 | (4095 - hi).
 // Positive floats order as their bits do, so the LARGEST key is the FIRST candidate of the rule's order; the key alone names the pair;
 // 0 is no key.  Nothing in it depends on a threshold: w >= th is read off the key (excl_key_weight).

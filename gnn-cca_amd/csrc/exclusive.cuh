@@ -67,10 +67,7 @@ __global__ __launch_bounds__(BLOCK) void excl_cluster_kernel(const long long* __
     const long long k0 = edge_ptr[g], k1 = edge_ptr[g + 1];
     const int n = v1 - v0;
     if (!excl_frame_ok(v0, v1, k0, k1, N_all, E, P)) {
-        if (v0 >= 0 && v1 <= N_all && n >= 0) {
-            for (int v = v0 + tid; v < v1; v += BLOCK) labels[v] = v;
-            if (tid == 0 && n > 0) atomicAdd(n_clusters, n);
-        }
+        frame_singletons<BLOCK>(labels, n_clusters, v0, v1, N_all, tid);
         if (k0 >= 0 && k1 >= k0 && k1 <= E)
             for (long long k = k0 + tid; k < k1; k += BLOCK) preds[k] = 0;
         if (tid == 0) cut[g] = 0, flags_out[g] = GNNCCA_EXCLUSIVE_BAD_RANGE;
@@ -87,12 +84,9 @@ __global__ __launch_bounds__(BLOCK) void excl_cluster_kernel(const long long* __
     }
     __syncthreads();
     if (s_misc[1]) {
-        for (int v = v0 + tid; v < v1; v += BLOCK) labels[v] = v;
+        frame_singletons<BLOCK>(labels, n_clusters, v0, v1, N_all, tid);   // (the ranges fit: its guard holds)
         for (long long k = k0 + tid; k < k1; k += BLOCK) preds[k] = 0;
-        if (tid == 0) {
-            if (n > 0) atomicAdd(n_clusters, n);
-            cut[g] = 0, flags_out[g] = GNNCCA_EXCLUSIVE_BAD_CAMERA;
-        }
+        if (tid == 0) cut[g] = 0, flags_out[g] = GNNCCA_EXCLUSIVE_BAD_CAMERA;
         return;
     }
     excl_u64* mine = cand + k0;

@@ -421,16 +421,21 @@ int launch_post_plan(const long long* ei, int E, int N, const PostPlanPtrs& p, E
 
 // The frame-local kernels (one workgroup per frame, the frame in LDS): their LDS capacity in nodes is the batch's largest frame rounded
 // up to a power of two, and their block is one wave while that capacity fits one (a Terrace frame has ~20 detections), 256 threads
-// otherwise.  launch(std::integral_constant<int, BLOCK>) makes the launch.
+// otherwise -- their threads stride over a frame's nodes.  launch(std::integral_constant<int, BLOCK>) makes the launch.
 inline int frame_capacity(int32_t max_frame_nodes) {
     int P = 1;
     while (P < max_frame_nodes) P <<= 1;
     return P;
 }
-template <class Launch>
+// strong_cluster_kernel's capacity is the largest frame rounded up to 32 instead: its LDS holds a bit matrix of P rows of P / 32 words,
+// which a power of two would up to quadruple, and its label phase gives every node a thread of its own, hence the third rung
+// (MAX_BLOCK = 1024) for frames of more than 256 nodes.
+inline int strong_capacity(int32_t max_frame_nodes) { return (max_frame_nodes + 31) / 32 * 32; }
+template <int MAX_BLOCK = 256, class Launch>
 inline void launch_frame_block(int P, Launch&& launch) {
     if (P <= 64) launch(std::integral_constant<int, 64>{});
-    else launch(std::integral_constant<int, 256>{});
+    else if (MAX_BLOCK <= 256 || P <= 256) launch(std::integral_constant<int, 256>{});
+    else launch(std::integral_constant<int, MAX_BLOCK>{});
 }
 
 // ---- kernels of mpn_forward.hip that mpn_post.hip and mpn_train.hip launch too ---------------------------------------------------

@@ -75,22 +75,6 @@ int gnncca_post_threshold_at(const float* logits, int64_t n_edges, double at, fl
     return GNNCCA_OK;
 }
 
-int gnncca_post_prune_cluster(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                              void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
-                              int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out, gnncca_stream_t stream) {
-    return gnncca_post_prune_cluster_frames(edge_index, predictions, n_nodes, n_edges, nullptr, nullptr, 0, workspace,
-                                            workspace_bytes, pruned_out, flow_out, flow_in, labels_out, n_clusters_out, stream);
-}
-
-int gnncca_post_prune_cluster_frames(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                                     const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames,
-                                     void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
-                                     int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out,
-                                     gnncca_stream_t stream) {
-    return gnncca_post_prune_cluster_frames_ex(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace,
-                                               workspace_bytes, pruned_out, flow_out, flow_in, labels_out, n_clusters_out, nullptr, nullptr, stream);
-}
-
 // `plan` (internal; null from the public entry points): the graph plan the MPN forward of the same batch left in ITS workspace (seg_ptr,
 // col32, perm, flags) -- gnncca_frames_forward hands it over, so the pruning needs no plan launches of its own
 struct PostPlan {
@@ -105,19 +89,44 @@ struct PostPlan {
     float* probs_out;
     int64_t* preds_out;
 };
-static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                                   const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
-                                   size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in, int32_t* labels_out,
-                                   int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out, const PostPlan* plan,
-                                   gnncca_stream_t stream);
+// The plan the forward of (d, n, e) left in `workspace`, whichever family's carve applies (both name the four offsets alike); the rest unset.
+static PostPlan forward_plan(const gnncca_mpn_dims* d, void* workspace, int64_t n, int64_t e) {
+    const auto at = [&](const auto& ws) {
+        const char* wb = static_cast<const char*>(workspace);
+        return PostPlan{reinterpret_cast<const int*>(wb + ws.seg_ptr), reinterpret_cast<const int*>(wb + ws.col32),
+                        reinterpret_cast<const int*>(wb + ws.perm), reinterpret_cast<const unsigned*>(wb + ws.flags), false, nullptr, nullptr, nullptr};
+    };
+    return classify(d) == kFamilyMfma32x6 ? at(carve(d, n, e)) : at(carve_generic(d, n, e));
+}
 
-int gnncca_post_prune_cluster_frames_ex(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
-                                        const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
-                                        size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in,
-                                        int32_t* labels_out, int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out,
-                                        gnncca_stream_t stream) {
-    return post_prune_cluster_impl(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace, workspace_bytes,
-                                   pruned_out, flow_out, flow_in, labels_out, n_clusters_out, sizes_scratch, triggers_out, nullptr, stream);
+// Zeroes the counters the cluster kernels add to: flow_out [N], flow_in [N], *n_clusters and -- where the caller has them (`triggers`
+// not null) -- the cluster sizes [N] and the n_trig trigger words.  ONE memset when the caller laid them out back to back in that order
+// (gnn_cca_amd.postprocess does), one per array otherwise, the flows and the count in one where only those three adjoin.  N == 0: there
+// are no flows and no sizes; the count (where there is one) and the trigger words.
+static int zero_post_counters(int32_t* flow_out, int32_t* flow_in, int32_t* n_clusters, size_t N, int32_t* sizes, int32_t* triggers,
+                              size_t n_trig, hipStream_t st) {
+    if (N == 0) {
+        if (n_clusters) HIP_TRY(hipMemsetAsync(n_clusters, 0, sizeof(int32_t), st));
+        if (triggers) HIP_TRY(hipMemsetAsync(triggers, 0, n_trig * 4, st));
+        return GNNCCA_OK;
+    }
+    const bool one_block = flow_in == flow_out + N && n_clusters == flow_in + N;
+    if (one_block && triggers && sizes == n_clusters + 1 && triggers == sizes + N) {
+        HIP_TRY(hipMemsetAsync(flow_out, 0, (3 * N + 1 + n_trig) * 4, st));
+        return GNNCCA_OK;
+    }
+    if (one_block) {
+        HIP_TRY(hipMemsetAsync(flow_out, 0, (2 * N + 1) * 4, st));
+    } else {
+        HIP_TRY(hipMemsetAsync(flow_out, 0, N * 4, st));
+        HIP_TRY(hipMemsetAsync(flow_in, 0, N * 4, st));
+        HIP_TRY(hipMemsetAsync(n_clusters, 0, sizeof(int32_t), st));
+    }
+    if (triggers) {
+        HIP_TRY(hipMemsetAsync(sizes, 0, N * 4, st));
+        HIP_TRY(hipMemsetAsync(triggers, 0, n_trig * 4, st));
+    }
+    return GNNCCA_OK;
 }
 
 static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
@@ -131,16 +140,12 @@ static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* pre
         return GNNCCA_ERR_INVALID_ARG;
     if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
     const size_t n_trig = (size_t)(node_ptr_dev ? n_frames : 1);
-    if (n_nodes == 0) {
-        if (n_clusters_out) HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
-        if (triggers_out) HIP_TRY(hipMemsetAsync(triggers_out, 0, n_trig * sizeof(int32_t), static_cast<hipStream_t>(stream)));
-        return GNNCCA_OK;
-    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_nodes == 0) return zero_post_counters(nullptr, nullptr, n_clusters_out, 0, nullptr, triggers_out, n_trig, st);
     if (!workspace || !flow_out || !flow_in || !labels_out || !n_clusters_out) return GNNCCA_ERR_INVALID_ARG;
     if (n_edges > 0 && (!edge_index || !predictions || !pruned_out)) return GNNCCA_ERR_INVALID_ARG;
     const PostWorkspace ws = carve_post(n_nodes, n_edges);
     if (!plan && workspace_bytes < ws.total) return GNNCCA_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = (int)n_nodes, E = (int)n_edges;
     const PostPlanPtrs own = post_plan_ptrs(workspace, ws);
     // (with `plan`: the MPN forward's plan of the same edge_index, nothing to build here)
@@ -151,24 +156,8 @@ static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* pre
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
     const long long* pred = reinterpret_cast<const long long*>(predictions);
     long long* pruned = reinterpret_cast<long long*>(pruned_out);
-    // zero the counters: one memset when the caller laid flow_out | flow_in | n_clusters out back to back (gnn_cca_amd.postprocess does)
-    const bool one_block = flow_in == flow_out + N && n_clusters_out == flow_in + N;
-    const bool trig_block = one_block && triggers_out && sizes_scratch == n_clusters_out + 1 && triggers_out == sizes_scratch + N;
-    if (plan && plan->counters_zeroed) {
-        // nothing: done launches ago
-    } else if (trig_block) {
-        HIP_TRY(hipMemsetAsync(flow_out, 0, ((size_t)3 * N + 1 + n_trig) * 4, st));
-    } else if (one_block) {
-        HIP_TRY(hipMemsetAsync(flow_out, 0, ((size_t)2 * N + 1) * 4, st));
-    } else {
-        HIP_TRY(hipMemsetAsync(flow_out, 0, (size_t)N * 4, st));
-        HIP_TRY(hipMemsetAsync(flow_in, 0, (size_t)N * 4, st));
-        HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), st));
-    }
-    if (triggers_out && !trig_block && !(plan && plan->counters_zeroed)) {
-        HIP_TRY(hipMemsetAsync(sizes_scratch, 0, (size_t)N * 4, st));
-        HIP_TRY(hipMemsetAsync(triggers_out, 0, n_trig * 4, st));
-    }
+    if (!(plan && plan->counters_zeroed))   // (else: done launches ago)
+        if (const int rc = zero_post_counters(flow_out, flow_in, n_clusters_out, (size_t)N, sizes_scratch, triggers_out, n_trig, st)) return rc;
     if (!plan)   // (kFinish: this entry's finish runs without edges too, so the workspace always holds a finished plan afterwards)
         if (const int rc = launch_post_plan(ei, E, N, own, EmptyPlan::kFinish, st)) return rc;
     if (E > 0) {
@@ -184,6 +173,40 @@ static int post_prune_cluster_impl(const int64_t* edge_index, const int64_t* pre
                        (const long long*)pruned, (long long)E, N, node_ptr_dev, edge_ptr_dev, labels_out, n_clusters_out,
                        (const int*)flow_out, (const int*)flow_in, sizes_scratch, triggers_out);
     HIP_TRY(hipGetLastError());
+    return GNNCCA_OK;
+}
+
+int gnncca_post_prune_cluster(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                              void* workspace, size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out,
+                              int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out, gnncca_stream_t stream) {
+    return post_prune_cluster_impl(edge_index, predictions, n_nodes, n_edges, nullptr, nullptr, 0, workspace, workspace_bytes, pruned_out, flow_out,
+                                   flow_in, labels_out, n_clusters_out, nullptr, nullptr, nullptr, stream);
+}
+
+int gnncca_post_prune_cluster_frames(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                                     const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
+                                     size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in, int32_t* labels_out,
+                                     int32_t* n_clusters_out, gnncca_stream_t stream) {
+    return post_prune_cluster_impl(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace, workspace_bytes,
+                                   pruned_out, flow_out, flow_in, labels_out, n_clusters_out, nullptr, nullptr, nullptr, stream);
+}
+
+int gnncca_post_prune_cluster_frames_ex(const int64_t* edge_index, const int64_t* predictions, int64_t n_nodes, int64_t n_edges,
+                                        const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, void* workspace,
+                                        size_t workspace_bytes, int64_t* pruned_out, int32_t* flow_out, int32_t* flow_in,
+                                        int32_t* labels_out, int32_t* n_clusters_out, int32_t* sizes_scratch, int32_t* triggers_out,
+                                        gnncca_stream_t stream) {
+    return post_prune_cluster_impl(edge_index, predictions, n_nodes, n_edges, node_ptr_dev, edge_ptr_dev, n_frames, workspace, workspace_bytes,
+                                   pruned_out, flow_out, flow_in, labels_out, n_clusters_out, sizes_scratch, triggers_out, nullptr, stream);
+}
+
+// The argument checks the exclusive and the strong entry share: GNNCCA_ERR_INVALID_ARG for a negative count or a max_frame_nodes outside
+// [0, min(limit, n_nodes)], else GNNCCA_ERR_UNSUPPORTED for 2^31 - 64 nodes or edges and more, else GNNCCA_OK.  Seen from outside the
+// second refusal comes after the entry's own null-pointer checks: an entry returns the first at once and the second after those.
+static int check_frames_args(int64_t n_nodes, int64_t n_edges, int32_t n_frames, int32_t max_frame_nodes, int limit) {
+    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    if (max_frame_nodes < 0 || max_frame_nodes > limit || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
     return GNNCCA_OK;
 }
 
@@ -209,12 +232,12 @@ int gnncca_post_exclusive_frames(const int64_t* edge_index, const float* scores,
                                  const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes,
                                  double threshold, int64_t* predictions_out, int32_t* labels_out, int32_t* n_clusters_out, int32_t* cut_out,
                                  uint32_t* flags_out, void* workspace, size_t workspace_bytes, gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
+    const int args = check_frames_args(n_nodes, n_edges, n_frames, max_frame_nodes, kExclMaxNodes);
+    if (args == GNNCCA_ERR_INVALID_ARG) return args;
     if (!(threshold > 0.0 && threshold < 1.0)) return GNNCCA_ERR_INVALID_ARG;   // (a NaN included)
-    if (max_frame_nodes < 0 || max_frame_nodes > kExclMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
     if (!n_clusters_out) return GNNCCA_ERR_INVALID_ARG;
     if (n_frames == 0 && n_nodes > 0) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (args) return args;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_frames == 0) {   // nothing to cluster: the zero alone
         hipLaunchKernelGGL(excl_prepare_kernel, dim3(1), dim3(256), 0, st, (const long long*)nullptr, 0ll, (const int*)nullptr, (const int*)nullptr,
@@ -257,35 +280,28 @@ int gnncca_post_strong_frames(const int64_t* edge_index, const int64_t* predicti
                               const int32_t* node_ptr_dev, const int32_t* edge_ptr_dev, int32_t n_frames, int32_t max_frame_nodes,
                               int32_t* flow_out, int32_t* flow_in, int32_t* labels_out, int32_t* n_clusters_out, int32_t* triggers_out,
                               uint32_t* flags_out, gnncca_stream_t stream) {
-    if (n_nodes < 0 || n_edges < 0 || n_frames < 0) return GNNCCA_ERR_INVALID_ARG;
-    if (max_frame_nodes < 0 || max_frame_nodes > kStrongMaxNodes || max_frame_nodes > n_nodes) return GNNCCA_ERR_INVALID_ARG;
+    const int args = check_frames_args(n_nodes, n_edges, n_frames, max_frame_nodes, kStrongMaxNodes);
+    if (args == GNNCCA_ERR_INVALID_ARG) return args;
     if ((node_ptr_dev == nullptr) != (edge_ptr_dev == nullptr) || (node_ptr_dev == nullptr) != (n_frames == 0)) return GNNCCA_ERR_INVALID_ARG;
     if (!n_clusters_out || !triggers_out || !flags_out) return GNNCCA_ERR_INVALID_ARG;   // (one trigger / flag word at least: the whole graph)
     if (n_nodes > 0 && (!flow_out || !flow_in || !labels_out)) return GNNCCA_ERR_INVALID_ARG;
     if (n_edges > 0 && (!edge_index || !predictions)) return GNNCCA_ERR_INVALID_ARG;
-    if (n_nodes >= (1ll << 31) - 64 || n_edges >= (1ll << 31) - 64) return GNNCCA_ERR_UNSUPPORTED;
+    if (args) return args;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t N = (size_t)n_nodes;
-    // zero the counters: one memset when the caller laid flow_out | flow_in | n_clusters out back to back (gnn_cca_amd.postprocess does)
-    if (N == 0 || (flow_in == flow_out + N && n_clusters_out == flow_in + N)) {
-        HIP_TRY(hipMemsetAsync(N ? flow_out : n_clusters_out, 0, (2 * N + 1) * 4, st));
-    } else {
-        HIP_TRY(hipMemsetAsync(flow_out, 0, N * 4, st));
-        HIP_TRY(hipMemsetAsync(flow_in, 0, N * 4, st));
-        HIP_TRY(hipMemsetAsync(n_clusters_out, 0, sizeof(int32_t), st));
-    }
-    const int P = (max_frame_nodes + 31) / 32 * 32;            // the LDS capacity in nodes: rows of P / 32 words
+    // (the kernel writes every trigger word itself and keeps its sizes in LDS: the flows and the count alone)
+    if (const int rc = zero_post_counters(flow_out, flow_in, n_clusters_out, (size_t)n_nodes, nullptr, nullptr, 0, st)) return rc;
+    const int P = strong_capacity(max_frame_nodes);            // the LDS capacity in nodes: rows of P / 32 words
     const size_t lds = (size_t)P * (size_t)(P / 32) * 4;       // 128 B at 32, 2 KiB at 128, 128 KiB at 1024
     if (lds > 64 * 1024) HIP_TRY(lds_opt_in<strong_cluster_kernel<1024>>((size_t)kStrongMaxNodes * (kStrongMaxNodes / 32) * 4));
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
     const long long* pred = reinterpret_cast<const long long*>(predictions);
-#define GNNCCA_STRONG(B)                                                                                                                     \
-    hipLaunchKernelGGL((strong_cluster_kernel<B>), dim3(node_ptr_dev ? (unsigned)n_frames : 1u), dim3(B), lds, st, ei, pred, (long long)n_edges, \
-                       (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, flow_out, flow_in, labels_out, n_clusters_out, triggers_out, flags_out)
     // the block covers the largest frame with one node per thread: one wave for Terrace-sized frames (~20 detections), 1024 threads only
     // where a frame needs them
-    if (P <= 64) GNNCCA_STRONG(64); else if (P <= 256) GNNCCA_STRONG(256); else GNNCCA_STRONG(1024);
-#undef GNNCCA_STRONG
+    launch_frame_block<1024>(P, [&](auto block) {
+        constexpr int B = decltype(block)::value;
+        hipLaunchKernelGGL((strong_cluster_kernel<B>), dim3(node_ptr_dev ? (unsigned)n_frames : 1u), dim3(B), lds, st, ei, pred, (long long)n_edges,
+                           (int)n_nodes, node_ptr_dev, edge_ptr_dev, P, flow_out, flow_in, labels_out, n_clusters_out, triggers_out, flags_out);
+    });
     HIP_TRY(hipGetLastError());
     return GNNCCA_OK;
 }
@@ -341,16 +357,7 @@ static int frames_forward_impl(const gnncca_mpn_dims* d, const void* packed_dev,
     PostPlan plan;
     const PostPlan* have_plan = nullptr;
     if (e > 0 && mpn_workspace) {
-        char* wb = static_cast<char*>(mpn_workspace);
-        if (classify(d) == kFamilyMfma32x6) {
-            const Workspace ws = carve(d, n, e);
-            plan = PostPlan{reinterpret_cast<const int*>(wb + ws.seg_ptr), reinterpret_cast<const int*>(wb + ws.col32),
-                            reinterpret_cast<const int*>(wb + ws.perm), reinterpret_cast<const unsigned*>(wb + ws.flags), false, nullptr, nullptr, nullptr};
-        } else {
-            const GenWorkspace ws = carve_generic(d, n, e);
-            plan = PostPlan{reinterpret_cast<const int*>(wb + ws.seg_ptr), reinterpret_cast<const int*>(wb + ws.col32),
-                            reinterpret_cast<const int*>(wb + ws.perm), reinterpret_cast<const unsigned*>(wb + ws.flags), false, nullptr, nullptr, nullptr};
-        }
+        plan = forward_plan(d, mpn_workspace, n, e);
         plan.counters_zeroed = zero_here;
         plan.logits = io->logits + (size_t)(n_out - 1) * e, plan.probs_out = io->probs, plan.preds_out = io->predictions;
         have_plan = &plan;

@@ -5,6 +5,8 @@
 // components of a symmetric digraph == connected components).  The bridge-based rounding / splitting heuristics
 // (libs/utils.py:25-173, 319-386) stay on the host, as SURVEY.md 8f prescribes.
 // Part of the translation unit mpn_post.hip.
+#include "excl_common.cuh"   // frame_range: a frame's node and edge range, shared with the other one-workgroup-per-frame kernels of this unit
+
 namespace gnncca {
 
 __global__ __launch_bounds__(256) void post_threshold_kernel(const float* __restrict__ logits, long long E,
@@ -96,9 +98,9 @@ __global__ __launch_bounds__(1024) void post_cc_kernel(const long long* __restri
                                                        int* triggers) {
     __shared__ int s_changed;
     const int tid = threadIdx.x;
-    const int v0 = node_ptr ? node_ptr[blockIdx.x] : 0, v1 = node_ptr ? node_ptr[blockIdx.x + 1] : N_all;
-    const long long k0 = edge_ptr ? edge_ptr[blockIdx.x] : 0, k1 = edge_ptr ? edge_ptr[blockIdx.x + 1] : E_all;
-    const long long E = E_all;
+    const FrameRange fr = frame_range(node_ptr, edge_ptr, blockIdx.x, N_all, E_all);
+    const int v0 = fr.v0, v1 = fr.v1;
+    const long long k0 = fr.k0, k1 = fr.k1, E = E_all;
     const int N = v1 - v0;  // bound on the number of sweeps
     auto ld = [&](int v) { return __hip_atomic_load(&labels[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
     for (int v = v0 + tid; v < v1; v += 1024) __hip_atomic_store(&labels[v], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

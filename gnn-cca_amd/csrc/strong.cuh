@@ -28,7 +28,7 @@
 // a frame's result does not depend on the rest of the batch.  flow_out / flow_in / *n_clusters must be zero on entry.
 // flags_out[g] = GNNCCA_STRONG_BAD_RANGE: the frame's ranges do not fit (excl_frame_ok, the LDS capacity P included); every node of such a
 // frame is its own cluster, its flows and its trigger word are 0 -- as far as the ranges allow writing at all.
-#include "excl_common.cuh"   // excl_frame_ok: one test of a frame's ranges for every one-workgroup-per-frame kernel of this unit
+#include "excl_common.cuh"   // frame_range, excl_frame_ok, frame_singletons: one reading, one test and one refusal of a frame's ranges in this unit
 #include "strong_closure.cuh"   // the matrix's diagonal, its closure and a node's label: shared with the sweep over this partition
 
 namespace gnncca {
@@ -49,14 +49,11 @@ __global__ __launch_bounds__(BLOCK) void strong_cluster_kernel(const long long* 
     __shared__ int s_misc[2];                   // [0] roots, [1] trigger bits
     unsigned* R = reinterpret_cast<unsigned*>(s_strong);
     const int g = blockIdx.x, tid = threadIdx.x;
-    const int v0 = node_ptr ? node_ptr[g] : 0, v1 = node_ptr ? node_ptr[g + 1] : N_all;
-    const long long k0 = edge_ptr ? edge_ptr[g] : 0, k1 = edge_ptr ? edge_ptr[g + 1] : E;
-    const int n = v1 - v0;
+    const FrameRange fr = frame_range(node_ptr, edge_ptr, g, N_all, E);
+    const int v0 = fr.v0, v1 = fr.v1, n = v1 - v0;
+    const long long k0 = fr.k0, k1 = fr.k1;
     if (!excl_frame_ok(v0, v1, k0, k1, N_all, E, min(P, BLOCK))) {
-        if (v0 >= 0 && v1 <= N_all && n >= 0) {
-            for (int v = v0 + tid; v < v1; v += BLOCK) labels[v] = v;
-            if (tid == 0 && n > 0) atomicAdd(n_clusters, n);
-        }
+        frame_singletons<BLOCK>(labels, n_clusters, v0, v1, N_all, tid);
         if (tid == 0) triggers[g] = 0, flags_out[g] = GNNCCA_STRONG_BAD_RANGE;
         return;
     }

@@ -71,7 +71,7 @@ from .frames import StagedFrames, _on, _raw_stream, attach, select
 from .graph_build import MODE_FULL, MODE_ONLY_APPEARANCE, MODE_ONLY_DIST, build_graph_batch
 from .postprocess import MAX_FRAME_NODES as EXCLUSIVE_MAX_FRAME_NODES
 from .postprocess import (NO_SPLITTING_WITHOUT_PRUNING, STRONG_MAX_FRAME_NODES, check_cameras, check_threshold, exclusive_clusters, finalize,
-                          prune_and_cluster, strong_clusters, threshold)
+                          prune_and_cluster, strong_clusters, threshold, widest_frame)
 from .sharding import GraphBatch
 
 MAX_NODES = 4096
@@ -240,8 +240,7 @@ class FrameResult:
                 raise ValueError("exclusive() needs a batch of build_graph_batch / FramePipeline (its host camera ids are judged before any launch)")
             check_cameras(b.cam_host)
             n = int(b.x.shape[0])
-            sizes = np.diff(np.asarray(b.node_ptr, dtype=np.int64))
-            widest = int(sizes.max()) if sizes.size else 0
+            widest = widest_frame(b.node_ptr)
             if widest > EXCLUSIVE_MAX_FRAME_NODES:
                 raise ValueError(f"a frame has {widest} detections; exclusive() takes frames of at most {EXCLUSIVE_MAX_FRAME_NODES}")
             ex = self._excl = exclusive_clusters(b.edge_index, self.probs, b.cam_dev, n, b.node_ptr_dev, b.edge_ptr_dev, at=self._pipe.threshold,
@@ -362,8 +361,7 @@ class FramePipeline:
         if self.switches[1]:
             post = prune_and_cluster(b.edge_index, r.preds, b.x.shape[0], b.node_ptr_dev, b.edge_ptr_dev)
         else:   # PRUNING = False: nothing is pruned, the clusters are the strongly connected components of the thresholded predictions
-            sizes_h = np.diff(np.asarray(b.node_ptr, dtype=np.int64))
-            widest = int(sizes_h.max()) if sizes_h.size else 0
+            widest = widest_frame(b.node_ptr)
             if widest > STRONG_MAX_FRAME_NODES:
                 raise ValueError(f"a frame has {widest} detections; a pipeline with pruning=False takes frames of at most {STRONG_MAX_FRAME_NODES}")
             post = strong_clusters(b.edge_index, r.preds, b.x.shape[0], b.node_ptr_dev, b.edge_ptr_dev, max_frame_nodes=widest)

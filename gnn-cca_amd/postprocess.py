@@ -39,16 +39,38 @@ def check_threshold(at):
     return th
 
 
+NO_CPU = "gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)"
+
+
+def _edge_index_i64(edge_index):
+    """edge_index as a contiguous int64 tensor: itself where it already is one."""
+    return edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.long().contiguous()
+
+
+def _flat(t, dtype):
+    """t flattened to a contiguous tensor of `dtype`: a view of itself where it already is one."""
+    t = t.reshape(-1)
+    return t if t.dtype == dtype and t.is_contiguous() else t.to(dtype).contiguous()
+
+
+def _int32_on(v, dev):
+    """A tensor or a host sequence of integers (numpy's included) as a contiguous int32 tensor on `dev`: itself where it already is one.
+    (evaluation._dev_i32 is the batch-level cousin: tensors only, and it trusts the device of a tensor that is already int32.)"""
+    if torch.is_tensor(v):
+        if v.dtype == torch.int32 and v.device == dev and v.is_contiguous():
+            return v
+        return v.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.tensor([int(q) for q in v], dtype=torch.int32).to(dev)
+
+
 def threshold(logits, at=0.5):
     """logits: Tensor[E] or [E,1] on the GPU -> (probs float32 [E], predictions int64 [E]): probs = sigmoid(logits), predictions =
     (probs >= at).  at=0.5 is the reference's threshold (inference.py:286-291) and the launch this function has always made; any other
     value in (0, 1) -- one chosen with calibration.sweep_thresholds -- is compared in float64 against the widened float32 probability."""
     at = check_threshold(at)
     if not logits.is_cuda:
-        raise RuntimeError("gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)")
-    x = logits.reshape(-1)
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        x = x.float().contiguous()
+        raise RuntimeError(NO_CPU)
+    x = _flat(logits, torch.float32)
     probs = torch.empty_like(x)
     preds = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
     with _on(x.device):
@@ -69,12 +91,9 @@ def prune_and_cluster(edge_index, predictions, n_nodes, node_ptr=None, edge_ptr=
     Batch.from_data_list -- sequences of G + 1 ints or int32 device tensors (GraphBatch.node_ptr / .edge_ptr, or the
     device copies build_graph_batch keeps).  With them every frame is clustered by its own workgroup."""
     if not (edge_index.is_cuda and predictions.is_cuda):
-        raise RuntimeError("gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)")
+        raise RuntimeError(NO_CPU)
     dev = edge_index.device
-    ei = edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.long().contiguous()
-    pred = predictions.reshape(-1)
-    if pred.dtype != torch.int64 or not pred.is_contiguous():
-        pred = pred.long().contiguous()
+    ei, pred = _edge_index_i64(edge_index), _flat(predictions, torch.int64)
     e = ei.shape[1]
     lib = nat.lib()
     ws = torch.empty(lib.gnncca_post_workspace_bytes(n_nodes, e) + 256, dtype=torch.uint8, device=dev)
@@ -89,14 +108,8 @@ def prune_and_cluster(edge_index, predictions, n_nodes, node_ptr=None, edge_ptr=
            "n_clusters": counters[2 * n_nodes:2 * n_nodes + 1],
            "triggers": counters[3 * n_nodes + 1:3 * n_nodes + 1 + max(n_trig, 1)]}
     n_frames, np_dev, ep_dev = 0, None, None
-    if node_ptr is not None:
-        def as_dev(v):
-            if torch.is_tensor(v):
-                if v.dtype == torch.int32 and v.device == dev and v.is_contiguous():
-                    return v
-                return v.to(device=dev, dtype=torch.int32).contiguous()
-            return torch.tensor(list(v), dtype=torch.int32).to(dev)
-        np_dev, ep_dev = as_dev(node_ptr), as_dev(edge_ptr)
+    if node_ptr is not None:   # (the offsets' VALUES are not judged here, unlike in _frame_ranges: deliberate -- the benchmark's host-bound leg)
+        np_dev, ep_dev = _int32_on(node_ptr, dev), _int32_on(edge_ptr, dev)
         n_frames = np_dev.numel() - 1
         if ep_dev.numel() != n_frames + 1 or n_frames < 1:
             raise ValueError("node_ptr / edge_ptr must both have G + 1 entries")
@@ -139,6 +152,45 @@ def _host_ptr(v, name):
     return a.astype(np.int64)
 
 
+def widest_frame(node_ptr):
+    """The detections of the widest frame of HOST offsets (G + 1 ints; 0 without a frame)."""
+    sizes = np.diff(np.asarray(node_ptr, dtype=np.int64))
+    return int(sizes.max()) if sizes.size else 0
+
+
+def _frame_ranges(node_ptr, edge_ptr, n_nodes, e, limit, who, max_frame_nodes):
+    """The frame ranges of exclusive_clusters / strong_clusters (`who`, for the messages) -> (g, max_frame_nodes), or a ValueError: both
+    must have G + 1 entries, G >= 1; HOST offsets must ascend from 0 to n_nodes / E and no frame may be wider than `limit` (the values of a
+    device tensor are not read: no synchronisation -- the kernel flags such a frame).  max_frame_nodes: the caller's, else the widest
+    frame where the host knows it, else min(n_nodes, limit); in [0, limit], clamped to n_nodes.  node_ptr None (strong_clusters): the
+    whole graph is the one frame, g = 0, and n_nodes itself must fit.  prune_and_cluster, on the benchmark's host-bound step-by-step leg,
+    makes none of these checks and never has."""
+    g = 0
+    if node_ptr is not None:
+        np_h, ep_h = _host_ptr(node_ptr, "node_ptr"), _host_ptr(edge_ptr, "edge_ptr")
+        g = (np_h.size if np_h is not None else node_ptr.numel()) - 1
+        if (ep_h.size if ep_h is not None else edge_ptr.numel()) != g + 1 or g < 1:
+            raise ValueError("node_ptr / edge_ptr must both have G + 1 entries")
+        if np_h is not None:
+            if int(np_h[0]) != 0 or int(np_h[-1]) != n_nodes or (np.diff(np_h) < 0).any():
+                raise ValueError("node_ptr must ascend from 0 to n_nodes")
+            widest = widest_frame(np_h)
+            if widest > limit:
+                raise ValueError(f"a frame has {widest} detections; {who} takes frames of at most {limit}")
+            max_frame_nodes = widest if max_frame_nodes is None else max_frame_nodes
+        if ep_h is not None and (int(ep_h[0]) != 0 or int(ep_h[-1]) != e or (np.diff(ep_h) < 0).any()):
+            raise ValueError("edge_ptr must ascend from 0 to E")
+    elif n_nodes > limit:
+        raise ValueError(f"the graph has {n_nodes} detections; {who} takes frames of at most {limit} "
+                         "(pass node_ptr / edge_ptr for a batch of frames)")
+    if max_frame_nodes is None:
+        max_frame_nodes = min(n_nodes, limit)
+    max_frame_nodes = int(max_frame_nodes)
+    if not 0 <= max_frame_nodes <= limit:
+        raise ValueError(f"max_frame_nodes must lie in [0, {limit}], not {max_frame_nodes}")
+    return g, min(max_frame_nodes, n_nodes)
+
+
 def exclusive_clusters(edge_index, probs, cam, n_nodes, node_ptr, edge_ptr, at=0.5, max_frame_nodes=None):
     """Camera-exclusive identity clusters: a partition of every frame in which no cluster holds two detections of one camera, for any
     number of cameras, on the device and without a synchronisation (csrc/exclusive.cuh; no counterpart in the reference).  The rule
@@ -170,42 +222,14 @@ def exclusive_clusters(edge_index, probs, cam, n_nodes, node_ptr, edge_ptr, at=0
         raise ValueError(f"cam [{cam.numel()}] does not match n_nodes ({n_nodes})")
     if not cam.is_cuda:   # a host array can be judged here (the batch-level entry points do; a device tensor is judged by the kernel)
         check_cameras(cam.numpy())
-    np_h, ep_h = _host_ptr(node_ptr, "node_ptr"), _host_ptr(edge_ptr, "edge_ptr")
-    g = (np_h.size if np_h is not None else node_ptr.numel()) - 1
-    if (ep_h.size if ep_h is not None else edge_ptr.numel()) != g + 1 or g < 1:
-        raise ValueError("node_ptr / edge_ptr must both have G + 1 entries")
-    if np_h is not None:
-        if int(np_h[0]) != 0 or int(np_h[-1]) != n_nodes or (np.diff(np_h) < 0).any():
-            raise ValueError("node_ptr must ascend from 0 to n_nodes")
-        widest = int(np.diff(np_h).max())
-        if widest > MAX_FRAME_NODES:
-            raise ValueError(f"a frame has {widest} detections; exclusive_clusters takes frames of at most {MAX_FRAME_NODES}")
-        max_frame_nodes = widest if max_frame_nodes is None else max_frame_nodes
-    if ep_h is not None and (int(ep_h[0]) != 0 or int(ep_h[-1]) != e or (np.diff(ep_h) < 0).any()):
-        raise ValueError("edge_ptr must ascend from 0 to E")
-    if max_frame_nodes is None:
-        max_frame_nodes = min(n_nodes, MAX_FRAME_NODES)
-    max_frame_nodes = int(max_frame_nodes)
-    if not 0 <= max_frame_nodes <= MAX_FRAME_NODES:
-        raise ValueError(f"max_frame_nodes must lie in [0, {MAX_FRAME_NODES}], not {max_frame_nodes}")
-    max_frame_nodes = min(max_frame_nodes, n_nodes)
+    g, max_frame_nodes = _frame_ranges(node_ptr, edge_ptr, n_nodes, e, MAX_FRAME_NODES, "exclusive_clusters", max_frame_nodes)
     if not (edge_index.is_cuda and probs.is_cuda and cam.is_cuda):
-        raise RuntimeError("gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)")
+        raise RuntimeError(NO_CPU)
     dev = edge_index.device
     lib = nat.lib()
     with _on(dev):
-        ei = edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.long().contiguous()
-        pr = probs.reshape(-1)
-        if pr.dtype != torch.float32 or not pr.is_contiguous():
-            pr = pr.float().contiguous()
-
-        def as_dev(v):
-            if torch.is_tensor(v):
-                if v.dtype == torch.int32 and v.device == dev and v.is_contiguous():
-                    return v
-                return v.to(device=dev, dtype=torch.int32).contiguous()
-            return torch.tensor([int(q) for q in v], dtype=torch.int32).to(dev)
-        cm, np_dev, ep_dev = as_dev(cam), as_dev(node_ptr), as_dev(edge_ptr)
+        ei, pr = _edge_index_i64(edge_index), _flat(probs, torch.float32)
+        cm, np_dev, ep_dev = _int32_on(cam, dev), _int32_on(node_ptr, dev), _int32_on(edge_ptr, dev)
         ws_bytes = lib.gnncca_post_exclusive_workspace_bytes(n_nodes, e, g)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         preds = torch.empty(e, dtype=torch.int64, device=dev)
@@ -257,47 +281,14 @@ def strong_clusters(edge_index, predictions, n_nodes, node_ptr=None, edge_ptr=No
     e = int(edge_index.shape[1])
     if predictions.numel() != e:
         raise ValueError(f"predictions [{predictions.numel()}] does not match edge_index (E={e})")
-    g = 0
-    if node_ptr is not None:
-        np_h, ep_h = _host_ptr(node_ptr, "node_ptr"), _host_ptr(edge_ptr, "edge_ptr")
-        g = (np_h.size if np_h is not None else node_ptr.numel()) - 1
-        if (ep_h.size if ep_h is not None else edge_ptr.numel()) != g + 1 or g < 1:
-            raise ValueError("node_ptr / edge_ptr must both have G + 1 entries")
-        if np_h is not None:
-            if int(np_h[0]) != 0 or int(np_h[-1]) != n_nodes or (np.diff(np_h) < 0).any():
-                raise ValueError("node_ptr must ascend from 0 to n_nodes")
-            widest = int(np.diff(np_h).max())
-            if widest > STRONG_MAX_FRAME_NODES:
-                raise ValueError(f"a frame has {widest} detections; strong_clusters takes frames of at most {STRONG_MAX_FRAME_NODES}")
-            max_frame_nodes = widest if max_frame_nodes is None else max_frame_nodes
-        if ep_h is not None and (int(ep_h[0]) != 0 or int(ep_h[-1]) != e or (np.diff(ep_h) < 0).any()):
-            raise ValueError("edge_ptr must ascend from 0 to E")
-    elif n_nodes > STRONG_MAX_FRAME_NODES:
-        raise ValueError(f"the graph has {n_nodes} detections; strong_clusters takes frames of at most {STRONG_MAX_FRAME_NODES} "
-                         "(pass node_ptr / edge_ptr for a batch of frames)")
-    if max_frame_nodes is None:
-        max_frame_nodes = min(n_nodes, STRONG_MAX_FRAME_NODES)
-    max_frame_nodes = int(max_frame_nodes)
-    if not 0 <= max_frame_nodes <= STRONG_MAX_FRAME_NODES:
-        raise ValueError(f"max_frame_nodes must lie in [0, {STRONG_MAX_FRAME_NODES}], not {max_frame_nodes}")
-    max_frame_nodes = min(max_frame_nodes, n_nodes)
+    g, max_frame_nodes = _frame_ranges(node_ptr, edge_ptr, n_nodes, e, STRONG_MAX_FRAME_NODES, "strong_clusters", max_frame_nodes)
     if not (edge_index.is_cuda and predictions.is_cuda):
-        raise RuntimeError("gnn_cca_amd.postprocess runs on MI355X only (no CPU fallback)")
+        raise RuntimeError(NO_CPU)
     dev = edge_index.device
     lib = nat.lib()
     with _on(dev):
-        ei = edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.long().contiguous()
-        pred = predictions.reshape(-1)
-        if pred.dtype != torch.int64 or not pred.is_contiguous():
-            pred = pred.long().contiguous()
-
-        def as_dev(v):
-            if torch.is_tensor(v):
-                if v.dtype == torch.int32 and v.device == dev and v.is_contiguous():
-                    return v
-                return v.to(device=dev, dtype=torch.int32).contiguous()
-            return torch.tensor([int(q) for q in v], dtype=torch.int32).to(dev)
-        np_dev, ep_dev = (as_dev(node_ptr), as_dev(edge_ptr)) if g else (None, None)
+        ei, pred = _edge_index_i64(edge_index), _flat(predictions, torch.int64)
+        np_dev, ep_dev = (_int32_on(node_ptr, dev), _int32_on(edge_ptr, dev)) if g else (None, None)
         n_trig = max(g, 1)
         # flow_out | flow_in | n_clusters (zeroed by ONE memset) | labels | triggers | flags
         ints = torch.empty(3 * n_nodes + 1 + 2 * n_trig, dtype=torch.int32, device=dev)

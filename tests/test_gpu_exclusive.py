@@ -119,6 +119,18 @@ def test_wave_and_block_boundaries_inside_frames_and_degenerate_frames():
     assert got["n_clusters"] == 14 and got["labels"].tolist() == list(range(14))
 
 
+@pytest.mark.parametrize("n", [64, 65])
+def test_block_rungs_a_ring_of_mutual_pairs_as_the_only_frame(n):
+    """The size at which the launch changes its block (one wave up to a capacity of 64, 256 threads above): a single frame, so the frame
+    itself sizes the launch.  Cameras v % 4: a cluster can hold four neighbours of the ring at most, and at 65 the closing pair (64, 0)
+    joins two detections of camera 0."""
+    pairs = [(v, (v + 1) % n) if v + 1 < n else (0, v) for v in range(n)]
+    weights = [0.55 + ((7 * v) % 16) / 64.0 for v in range(n)]                     # exact in fp32, ties among them
+    got = _check(_hand_batch([_pairs_frame(n, pairs, weights, np.arange(n) % 4)]), 0.5, f"ring of {n}")
+    assert got["flags"].tolist() == [0] and got["cut"][0] > 0 and n // 4 <= got["n_clusters"] < n
+    assert np.bincount(got["labels"]).max() <= 4
+
+
 def test_edge_cases_of_the_rule():
     # camera ids 0 and 63 in one cluster (mask bit 63), next to a pair that shares camera 63
     f0 = _pairs_frame(4, [(0, 1), (1, 2), (2, 3)], [0.9, 0.8, 0.7], [0, 63, 63, 5])

@@ -134,3 +134,60 @@ def test_separate_counter_buffers_and_empty_inputs():
     # nodes without edges: every node its own cluster, zero flows
     out = prune_and_cluster(torch.zeros((2, 0), dtype=torch.int64, device="cuda"), torch.zeros(0, dtype=torch.int64, device="cuda"), 7)
     assert int(out["n_clusters"].item()) == 7 and int(out["flow_out"].abs().sum()) == 0 and int(out["flow_in"].abs().sum()) == 0
+
+
+def _frames_batch(rng, sizes):
+    """Frames of `sizes` nodes, the first an active symmetric clique, the others random pairs in both directions with a prediction per
+    direction (so some are pruned); edges of a frame contiguous, sorted by (src, dst).  -> edge_index [2, E], predictions [E], node_ptr,
+    edge_ptr (host)."""
+    node_ptr, edge_ptr, ei, pred = [0], [0], [], []
+    for q, n in enumerate(sizes):
+        half = [(i, j) for i in range(n) for j in range(i + 1, n) if q == 0 or rng.random() < 2.5 / n]
+        pairs = sorted(half + [(j, i) for i, j in half])
+        ei.append(np.array(pairs, dtype=np.int64).reshape(-1, 2).T + node_ptr[-1])
+        pred.append(np.ones(len(pairs), np.int64) if q == 0 else (rng.random(len(pairs)) < 0.8).astype(np.int64))
+        node_ptr.append(node_ptr[-1] + n), edge_ptr.append(edge_ptr[-1] + len(pairs))
+    return np.ascontiguousarray(np.concatenate(ei, axis=1)), np.concatenate(pred), node_ptr, edge_ptr   # (row-major: the C entry reads raw memory)
+
+
+def test_counter_reset_on_five_separate_dirty_buffers_equals_the_one_block_layout():
+    """gnncca_post_prune_cluster_frames_ex zeroes flow_out, flow_in, n_clusters, the cluster sizes and the trigger words itself, one array
+    at a time where they do not adjoin: on five separate buffers that held garbage it gives exactly what prune_and_cluster's back-to-back
+    layout (one memset) gives -- with frame ranges, without them (one trigger word), and for a batch without nodes."""
+    from gnn_cca_amd import _native as nat
+    from gnn_cca_amd.postprocess import prune_and_cluster
+    lib, stream = nat.lib(), torch.cuda.current_stream().cuda_stream
+    ei, pred, node_ptr, edge_ptr = _frames_batch(np.random.default_rng(11), [6, 33, 70])
+    n, e = node_ptr[-1], ei.shape[1]
+    d_ei, d_pred = torch.from_numpy(ei).cuda(), torch.from_numpy(pred).cuda()
+    nptr, eptr = torch.tensor(node_ptr, dtype=torch.int32).cuda(), torch.tensor(edge_ptr, dtype=torch.int32).cuda()
+
+    def dirty(m):
+        return torch.full((m,), 12345, dtype=torch.int32, device="cuda")
+
+    for ranges in (True, False):
+        g = 3 if ranges else 0
+        want = prune_and_cluster(d_ei, d_pred, n, nptr, eptr) if ranges else prune_and_cluster(d_ei, d_pred, n)
+        assert want["flow_in"].data_ptr() == want["flow_out"].data_ptr() + 4 * n                      # the one-block layout
+        assert want["n_clusters"].data_ptr() + 4 * (n + 1) == want["triggers"].data_ptr() and want["triggers"].numel() == max(g, 1)
+        ws = torch.empty(lib.gnncca_post_workspace_bytes(n, e) + 256, dtype=torch.uint8, device="cuda")
+        got = {"pruned": torch.full((e,), 12345, dtype=torch.int64, device="cuda"), "flow_out": dirty(n), "flow_in": dirty(n), "labels": dirty(n),
+               "n_clusters": dirty(1), "triggers": dirty(max(g, 1))}
+        sizes = dirty(n)
+        st = lib.gnncca_post_prune_cluster_frames_ex(d_ei.data_ptr(), d_pred.data_ptr(), n, e, nptr.data_ptr() if ranges else None,
+                                                     eptr.data_ptr() if ranges else None, g, ws.data_ptr(), ws.numel(), got["pruned"].data_ptr(),
+                                                     got["flow_out"].data_ptr(), got["flow_in"].data_ptr(), got["labels"].data_ptr(),
+                                                     got["n_clusters"].data_ptr(), sizes.data_ptr(), got["triggers"].data_ptr(), stream)
+        assert st == nat.OK
+        for k in got:
+            assert torch.equal(got[k], want[k]), (ranges, k)
+        trig = got["triggers"].cpu().numpy()
+        assert (trig & nat.POST_TRIGGER_ROUNDING).any() and (trig & nat.POST_TRIGGER_SPLITTING).any()   # the clique: flows of 5, six members
+        if ranges:
+            assert trig[0] == (nat.POST_TRIGGER_ROUNDING | nat.POST_TRIGGER_SPLITTING) and (got["labels"][:6] == 0).all()
+    # no nodes: the count and every trigger word come back zero
+    k, trig, sizes = dirty(1), dirty(3), dirty(1)
+    zeros = torch.zeros(4, dtype=torch.int32, device="cuda")
+    st = lib.gnncca_post_prune_cluster_frames_ex(None, None, 0, 0, zeros.data_ptr(), zeros.data_ptr(), 3, None, 0, None, None, None, None,
+                                                 k.data_ptr(), sizes.data_ptr(), trig.data_ptr(), stream)
+    assert st == nat.OK and k.tolist() == [0] and trig.tolist() == [0, 0, 0]

@@ -416,3 +416,13 @@ def test_a_pruning_pipeline_next_to_it_gives_what_it_gave_before(scene):
     want = np.concatenate([po.clusters(ei[:, k0:k1] - v0, po.prune(ei[:, k0:k1] - v0, pr[k0:k1]), v1 - v0)[0] + v0
                            for v0, v1, k0, k1 in _frames_of(r) if v1 > v0])
     assert np.array_equal(r.labels.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize("n", [64, 65, 256, 257])
+def test_block_rungs_a_directed_ring_with_a_chord_as_the_only_frame(n):
+    """The sizes at which the launch changes its block (64 / 256 / 1024 threads, one node per thread in the label phase): a single frame, so
+    the frame itself sizes the launch.  A ring is one component only after the full count of rounds; the chord gives node 0 a second edge."""
+    v = np.arange(n)
+    got = _check(_batch([(n, np.append(v, 0), np.append((v + 1) % n, n // 2))]), f"ring of {n}")
+    assert got["labels"].tolist() == [0] * n and got["n_clusters"] == 1 and got["triggers"].tolist() == [2] and got["flags"].tolist() == [0]
+    assert got["flow_out"][0] == 2 and got["flow_in"][n // 2] == 2 and got["flow_out"].sum() == n + 1
