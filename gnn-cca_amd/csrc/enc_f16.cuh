@@ -279,7 +279,7 @@ __device__ __forceinline__ void enc_gemm_f16_body(const EncF16Params p, const En
         for (int i = 0; i < 16; ++i) accA[c][i] = 0.f, accB[c][i] = 0.f;
     float amax = 0.f;
     // fragment addresses: A from the wave's fp32 ring (row l32, granules 4 s + 2 h and + 1, XOR (l32 >> 1) & 7); B from the W ring, whose
-    // image is fragment-major (pack.cpp: w2h_index): piece p, column tile c, k-step s = the 1 KB at (p * 8 + c * 2 + s) * 1024, lane * 16 inside
+    // image is fragment-major (pack_elem.h: w2h_index): piece p, column tile c, k-step s = the 1 KB at (p * 8 + c * 2 + s) * 1024, lane * 16 inside
     const int aswz = (l32 >> 1) & 7;
     const unsigned char* abase = xring + l32 * 128;
     // two waves share every SIMD; the later-dispatched half loses every arbitration at equal priority (stamps: its compute phase took

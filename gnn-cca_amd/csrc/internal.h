@@ -56,7 +56,7 @@ struct BlobHeader {
     int32_t enc_w3;                         // first encoder weight as 3 bf16 pieces, [in/32][3][out][32], or 0
     int32_t wne_bf16;                       // [9][64] dwords: W_ne as packed bf16 piece pairs, the B operands of msg_bf16.cuh
     int32_t enc_w2h;                        // first encoder weight as 2 fp16 pieces (w = w0 + w1 / 2048), the B-operand image of enc_f16.cuh:
-                                            // [in/32][2 pieces][4 column tiles][2 k-steps][64 lanes][8] halfs (pack.cpp: w2h_index); or 0
+                                            // [in/32][2 pieces][4 column tiles][2 k-steps][64 lanes][8] halfs (pack_elem.h: w2h_index); or 0
     int32_t enc_w2h_bad;                    // [kW2hBadWords] words: non-zero where a weight does not fit fp16 (|w| >= 65520): the fp16 GEMM then
                                             // hands every tile to its bf16 arm
     int32_t pad[3];
@@ -85,22 +85,25 @@ constexpr int kFcProjB = 104;  // [48]
 constexpr int kFastConsts = 152;
 bool fast_consts_ok(const gnncca_mpn_dims* d);
 
-// Device-side packing (gnncca_pack_weights_device): the blob as a list of strided copies out of the parameter
-// tensors, built once per GRAPH_NET_PARAMS by pack_program() and interpreted by pack_device_kernel -- the same
-// folding / splitting as gnncca_pack_weights, bit for bit, without the parameters ever visiting the host.
+// The fast family's blob as a program: a list of strided copies out of the parameter tensors, built per GRAPH_NET_PARAMS by
+// pack_program() (pack.cpp) and interpreted by gnncca_pack_weights on the host and by pack_device_kernel on the GPU
+// (gnncca_pack_weights_device: the parameters never visit the host).  Both go through pack_elem.h, which has the fold, the piece
+// splits and the layouts of the kinds; this is the one description of the kinds themselves.
 struct PackSeg {
-    int32_t kind;               // 0: weight element, 1: bias element, 2: weight element split into 3 bf16 planes,
-                                // 3: W_ne element (row = channel, column = k < 6) as bf16 pieces in the MsgB lane layout,
+    int32_t kind;               // 0: weight element, 1: bias element (both: blob[dst + r * drs + c * dcs]),
+                                // 2: weight element split into 3 bf16 planes, [in/32][3][out][32] (BlobHeader::enc_w3),
+                                // 3: W_ne element (row = channel, column = k < 6) as bf16 pieces in the MsgB lane layout (wne_bf16),
                                 // 4: weight element split into 2 fp16 pieces in the swizzled chunk image of BlobHeader::enc_w2h
-                                //    (dst = enc_w2h, unit0 unused, plane = float offset of the kW2hBadWords flag words)
+                                //    (dst = enc_w2h, plane = float offset of the kW2hBadWords flag words)
+                                // kinds 2 - 4 address by (r, c) alone: drs and dcs are unused and 0
     int32_t dst;                // float offset in the blob (kind 2: offset of plane 0)
-    int32_t param;              // index of the Linear's weight (kind 0, 2) or bias (kind 1) in the parameter list
+    int32_t param;              // index of the Linear's weight (kind 0, 2, 3, 4) or bias (kind 1) in the parameter list
     int32_t bn;                 // index of the BatchNorm weight (gamma; beta, mean, var follow), or -1
     int32_t src_off;            // element offset inside the parameter
     int32_t rows, cols;         // rows = output units (the BatchNorm channel of element (r, c) is unit0 + r)
     int32_t unit0;
     int32_t drs, dcs, srs, scs; // destination / source strides per row and per column
-    int32_t plane;              // kind 2: out * 32, the piece stride inside a 32-deep k-chunk of [in/32][3][out][32]
+    int32_t plane;              // kind 2: out * 32, the piece stride inside a 32-deep k-chunk of [in/32][3][out][32]; kind 4: see above
     int32_t pad[3];
 };
 constexpr int kMaxPackSegs = 96;
@@ -180,7 +183,18 @@ int build_edges_zeroing(const gnncca_frames* fr, const float* reid, int32_t reid
 Family classify(const gnncca_mpn_dims* d);
 bool blob_header(const gnncca_mpn_dims* d, BlobHeader* out);  // false if unsupported
 bool dims_valid(const gnncca_mpn_dims* d);
+// The canonical parameter order (what gnncca_pack_weights, the training entry points and MOTMPNet.native_param_tensors agree on): MLP by
+// MLP (mlp_by_index), layer by layer: weight, bias, then -- where has_bn -- BatchNorm weight, bias, running_mean, running_var.
+struct ParamSlots {
+    int w, b;   // the Linear's weight and bias
+    int bn;     // the BatchNorm's gamma (beta, running mean, running var follow), or -1
+};
+ParamSlots mlp_param_slots(const gnncca_mlp& m, int layer);                        // counted from the MLP's own first tensor
+ParamSlots param_slots(const gnncca_mpn_dims* d, int mlp_index, int layer);        // in the whole list
 int mlp_param_count(const gnncca_mlp& m);
+// Split-K factor of the f32 plan GEMM (enc_gemm_plan_kernel: 32-row tiles, slices at least 64 deep): enough workgroups to cover the
+// chip when there are few rows.  The forward's workspace, the generic family's first layer and the backward's a1 recompute use it.
+int plan_gemm_ksplit(int64_t n_rows, int K);
 
 // Workspace carve-up (byte offsets, all multiples of 256).
 struct Workspace {

@@ -120,19 +120,6 @@ static bool backward_ok(const gnncca_mpn_dims* d) {
     return true;  // BatchNorm is allowed only between the classifier's two layers (the shipped inference config)
 }
 
-// index of the first tensor of layer `l` of MLP `mi` in the canonical parameter order
-static int param_index(const gnncca_mpn_dims* d, int mi, int l) {
-    int idx = 0;
-    for (int m = 0; m < 5; ++m) {
-        const gnncca_mlp& mlp = mlp_by_index(d, m);
-        for (int k = 0; k < mlp.n_layers; ++k) {
-            if (m == mi && k == l) return idx;
-            idx += 2 + (mlp.layers[k].has_bn ? 4 : 0);
-        }
-    }
-    return idx;
-}
-
 // Train-mode classifier with BatchNorm1d between its two layers: batch statistics over the E edges for every
 // classified step (models/mpn.py:290-293 with models/mlp.py:15 in train mode); running buffers updated in place.
 int gnncca_classifier_train(const gnncca_mpn_dims* d, const float* const* params_dev, int n_params, const float* e_steps,
@@ -155,10 +142,10 @@ int gnncca_classifier_train_dropout(const gnncca_mpn_dims* d, const float* const
     if (!e_steps || !scratch || !bn_stat_out || !logits_out) return GNNCCA_ERR_INVALID_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int C1 = d->cls_edge.layers[0].out_dim, L = d->num_enc_steps, first_cls = L - d->num_class_steps + 1;
-    const int pc = param_index(d, 4, 0);
-    const float *W1 = params_dev[pc], *b1 = params_dev[pc + 1], *gamma = params_dev[pc + 2], *beta = params_dev[pc + 3];
-    float *rm = const_cast<float*>(params_dev[pc + 4]), *rv = const_cast<float*>(params_dev[pc + 5]);
-    const float *W2 = params_dev[pc + 6], *b2 = params_dev[pc + 7];
+    const ParamSlots c1s = param_slots(d, 4, 0), c2s = param_slots(d, 4, 1);
+    const float *W1 = params_dev[c1s.w], *b1 = params_dev[c1s.b], *gamma = params_dev[c1s.bn], *beta = params_dev[c1s.bn + 1];
+    float *rm = const_cast<float*>(params_dev[c1s.bn + 2]), *rv = const_cast<float*>(params_dev[c1s.bn + 3]);
+    const float *W2 = params_dev[c2s.w], *b2 = params_dev[c2s.b];
     const long long E = n_edges;
     double* sums = static_cast<double*>(scratch);
     int li = 0;
@@ -268,14 +255,14 @@ int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* d, const float* const* par
     const int c1 = d->cls_edge.n_layers == 2 ? d->cls_edge.layers[0].out_dim : 0;
     // zero every gradient
     if (!(options & GNNCCA_BWD_GRADS_ZEROED)) {
-        const gnncca_mlp* all[5] = {&d->enc_node, &d->enc_edge, &d->edge_mlp, &d->node_mlp, &d->cls_edge};
-        int pi = 0;
-        for (const gnncca_mlp* m : all)
-            for (int l = 0; l < m->n_layers; ++l) {
-                HIP_TRY(hipMemsetAsync(grads_dev[pi++], 0, (size_t)m->layers[l].in_dim * m->layers[l].out_dim * 4, st));
-                HIP_TRY(hipMemsetAsync(grads_dev[pi++], 0, (size_t)m->layers[l].out_dim * 4, st));
-                if (m->layers[l].has_bn)  // gamma, beta, and the two buffers (no gradient: left at zero)
-                    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemsetAsync(grads_dev[pi++], 0, (size_t)m->layers[l].out_dim * 4, st));
+        for (int mi = 0; mi < 5; ++mi)
+            for (int l = 0; l < mlp_by_index(d, mi).n_layers; ++l) {
+                const gnncca_layer& ly = mlp_by_index(d, mi).layers[l];
+                const ParamSlots ps = param_slots(d, mi, l);
+                HIP_TRY(hipMemsetAsync(grads_dev[ps.w], 0, (size_t)ly.in_dim * ly.out_dim * 4, st));
+                HIP_TRY(hipMemsetAsync(grads_dev[ps.b], 0, (size_t)ly.out_dim * 4, st));
+                if (ps.bn >= 0)  // gamma, beta, and the two buffers (no gradient: left at zero)
+                    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemsetAsync(grads_dev[ps.bn + k], 0, (size_t)ly.out_dim * 4, st));
             }
     }
     if (N == 0 || E == 0) {   // no edge, no logit: nothing reaches either input
@@ -300,16 +287,19 @@ int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* d, const float* const* par
     float* a1 = reinterpret_cast<float*>(base + ws.a1);
     float* gz1 = reinterpret_cast<float*>(base + ws.gz1);
     float* part = reinterpret_cast<float*>(base + ws.part);
-    const float *W1 = params_dev[0], *b1 = params_dev[1], *W2 = params_dev[2];
-    const float *We = params_dev[6], *Wn = params_dev[8], *bn = params_dev[9];
-    const bool cls_bn = d->cls_edge.layers[0].has_bn != 0;
+    // the tensors' places in the parameter list (backward_ok: a two-layer node encoder; the second classifier layer only where c1)
+    const ParamSlots sx1 = param_slots(d, 0, 0), sx2 = param_slots(d, 0, 1), se0 = param_slots(d, 1, 0), se = param_slots(d, 2, 0);
+    const ParamSlots sn = param_slots(d, 3, 0), sc1 = param_slots(d, 4, 0), sc2 = param_slots(d, 4, 1);
+    const float *W1 = params_dev[sx1.w], *b1 = params_dev[sx1.b], *W2 = params_dev[sx2.w];
+    const float *We = params_dev[se.w], *Wn = params_dev[sn.w], *bn = params_dev[sn.b];
+    const bool cls_bn = sc1.bn >= 0;
     if (cls_bn && !cls_bn_stat) return GNNCCA_ERR_INVALID_ARG;
-    const int pw2 = cls_bn ? 16 : 12;  // second classifier layer follows the four BatchNorm tensors
-    const float *Wc1 = params_dev[10], *bc1 = params_dev[11], *Wc2 = c1 ? params_dev[pw2] : nullptr;
-    float *gW1 = grads_dev[0], *gb1 = grads_dev[1], *gW2 = grads_dev[2], *gb2 = grads_dev[3];
-    float *gWe0 = grads_dev[4], *gbe0 = grads_dev[5], *gWe = grads_dev[6], *gbe = grads_dev[7];
-    float *gWn = grads_dev[8], *gbn = grads_dev[9], *gWc1 = grads_dev[10], *gbc1 = grads_dev[11];
-    float *gWc2 = c1 ? grads_dev[pw2] : nullptr, *gbc2 = c1 ? grads_dev[pw2 + 1] : nullptr;
+    const float *Wc1 = params_dev[sc1.w], *bc1 = params_dev[sc1.b], *Wc2 = c1 ? params_dev[sc2.w] : nullptr;
+    const float *cls_gamma = cls_bn ? params_dev[sc1.bn] : nullptr, *cls_beta = cls_bn ? params_dev[sc1.bn + 1] : nullptr;
+    float *gW1 = grads_dev[sx1.w], *gb1 = grads_dev[sx1.b], *gW2 = grads_dev[sx2.w], *gb2 = grads_dev[sx2.b];
+    float *gWe0 = grads_dev[se0.w], *gbe0 = grads_dev[se0.b], *gWe = grads_dev[se.w], *gbe = grads_dev[se.b];
+    float *gWn = grads_dev[sn.w], *gbn = grads_dev[sn.b], *gWc1 = grads_dev[sc1.w], *gbc1 = grads_dev[sc1.b];
+    float *gWc2 = c1 ? grads_dev[sc2.w] : nullptr, *gbc2 = c1 ? grads_dev[sc2.b] : nullptr;
     double* bn_sums = reinterpret_cast<double*>(base + ws.bn_sums);
     float* bn_red = reinterpret_cast<float*>(base + ws.bn_red);
     const long long* ei = reinterpret_cast<const long long*>(edge_index);
@@ -361,12 +351,12 @@ int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* d, const float* const* par
             const float* stat = cls_bn_stat + (size_t)out_idx * c1 * 2;
             HIP_TRY(hipMemsetAsync(bn_sums, 0, sizeof(double) * 2 * c1, st));
             hipLaunchKernelGGL(bwd_cls_bn_reduce_kernel, grid1((size_t)E, 256), dim3(256), 0, st, e_cur, bp.g_logit, (long long)E, Wc1,
-                               bc1, params_dev[12], params_dev[13], stat, Wc2, c1, bn_sums, gWc2, gbc2, drop, out_idx);
+                               bc1, cls_gamma, cls_beta, stat, Wc2, c1, bn_sums, gWc2, gbc2, drop, out_idx);
             hipLaunchKernelGGL(bwd_cls_bn_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)bn_sums, (long long)E, c1, bn_red,
-                               grads_dev[12], grads_dev[13]);
+                               grads_dev[sc1.bn], grads_dev[sc1.bn + 1]);
             HIP_TRY(hipGetLastError());
-            bp.bn_gamma = params_dev[12];
-            bp.bn_beta = params_dev[13];
+            bp.bn_gamma = cls_gamma;
+            bp.bn_beta = cls_beta;
             bp.bn_stat = stat;
             bp.bn_red = bn_red;
         }
@@ -430,8 +420,7 @@ int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* d, const float* const* par
                        gWe0, gbe0, 1.f / (1.f - drop.p_enc));
     HIP_TRY(hipGetLastError());
     {   // a1 = ReLU(x W1^T + b1) is recomputed instead of stored: the forward's split-K MFMA GEMM + its reduce kernel
-        int ks = 1;
-        while (ks < 32 && (size_t)((N + 31) / 32) * ks < 512 && D / (ks * 2) >= 64) ks *= 2;
+        const int ks = plan_gemm_ksplit(N, D);
         int kslice = (D + ks - 1) / ks;
         kslice = (kslice + 63) / 64 * 64;
         EncPlanParams ep;
@@ -467,7 +456,7 @@ int gnncca_mpn_backward_inputs(const gnncca_mpn_dims* d, const float* const* par
     HIP_TRY(hipGetLastError());
     // ---- inputs (only what the caller asked for) ----------------------------------------------------------------------
     if (dattr_out) {
-        hipLaunchKernelGGL(bwd_edge_attr_kernel, grid1((size_t)E * A, 256), dim3(256), 0, st, ge_in, saved->e_enc, params_dev[4],
+        hipLaunchKernelGGL(bwd_edge_attr_kernel, grid1((size_t)E * A, 256), dim3(256), 0, st, ge_in, saved->e_enc, params_dev[se0.w],
                            dattr_out, A, (long long)E, enc_scale);
         HIP_TRY(hipGetLastError());
     }

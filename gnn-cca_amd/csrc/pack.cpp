@@ -1,22 +1,17 @@
 // pack.cpp -- host side of libgnncca_mpn: dims validation, weight packing, workspace carve-up.
 // Pure C++ (no HIP calls): testable on a machine without a GPU.
 //
-// What the packing does, with the reference lines it derives from:
-//   * eval-mode BatchNorm1d (models/mlp.py:14-15) is folded into the preceding Linear:
-//       y = ((W x + b) - mean) / sqrt(var + 1e-5) * gamma + beta  ==  (s.W) x + ((b - mean) s + beta),
-//       s = gamma / sqrt(var + 1e-5)                       (computed in double, rounded once to fp32)
-//   * the edge MLP weight [EF][nf*2H + ef*EF] is split by the cat order of models/mpn.py:68
-//       [ x[row] | x[col] | edge_attr ]  ->  W_src, W_dst (per-node projections) and W_ee (per edge)
-//   * the node MLP weight [H][nf*H + EF] is split by the cat order of models/mpn.py:97
-//       [ x[row] | edge_attr ]           ->  W_nx (per-node projection Q) and W_ne (per edge, MFMA B operand)
+// What the packing does: the fast family's blob is stated ONCE, as the program of pack_program() below (which regions there are and how
+// the edge / node MLP weights split by cat order), and gnncca_pack_weights interprets that program; what happens to one element -- the
+// BatchNorm fold, the bf16 / fp16 piece splits, the operand layouts -- is in pack_elem.h, shared with the device packer.  The generic
+// family has no program: pack_generic walks its layers itself, through the same fold.
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <vector>
 
 #include "internal.h"
+#include "pack_elem.h"
 
 namespace gnncca {
 
@@ -24,10 +19,27 @@ thread_local int g_last_hip_error = 0;  // the one definition (internal.h); ever
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-int mlp_param_count(const gnncca_mlp& m) {
-    int n = 0;
-    for (int i = 0; i < m.n_layers; ++i) n += 2 + (m.layers[i].has_bn ? 4 : 0);
-    return n;
+// THE walk of the canonical parameter order: weight, bias, then gamma, beta, running mean, running var where has_bn, layer by layer
+ParamSlots mlp_param_slots(const gnncca_mlp& m, int layer) {
+    int i = 0;
+    for (int l = 0; l < layer; ++l) i += m.layers[l].has_bn ? 6 : 2;
+    return ParamSlots{i, i + 1, layer < m.n_layers && m.layers[layer].has_bn ? i + 2 : -1};
+}
+
+int mlp_param_count(const gnncca_mlp& m) { return mlp_param_slots(m, m.n_layers).w; }
+
+ParamSlots param_slots(const gnncca_mpn_dims* d, int mlp_index, int layer) {
+    int base = 0;
+    for (int m = 0; m < mlp_index; ++m) base += mlp_param_count(mlp_by_index(d, m));
+    const ParamSlots s = mlp_param_slots(mlp_by_index(d, mlp_index), layer);
+    return ParamSlots{base + s.w, base + s.b, s.bn < 0 ? -1 : base + s.bn};
+}
+
+int plan_gemm_ksplit(int64_t n_rows, int K) {
+    const size_t row_tiles = ((size_t)(n_rows > 0 ? n_rows : 0) + 31) / 32;
+    int ks = 1;
+    while (ks < 32 && row_tiles * (size_t)ks < 512 && K / (ks * 2) >= 64) ks *= 2;
+    return ks;
 }
 
 static bool mlp_chain_ok(const gnncca_mlp& m, int in_dim, int out_dim) {
@@ -143,11 +155,7 @@ static GenBlobPlan plan_gen_blob(const gnncca_mpn_dims* d) {
 
 int gen_enc0_ksplit(const gnncca_mpn_dims* d, int64_t n_nodes) {
     if (classify(d) != kFamilyGeneric || plan_gen_blob(d).h.enc0_rowmajor == 0) return 0;
-    const int k0 = d->enc_node.layers[0].in_dim;
-    const size_t row_tiles = ((size_t)(n_nodes > 0 ? n_nodes : 0) + 31) / 32;
-    int ks = 1;
-    while (ks < 32 && row_tiles * (size_t)ks < 512 && k0 / (ks * 2) >= 64) ks *= 2;
-    return ks;
+    return plan_gemm_ksplit(n_nodes, d->enc_node.layers[0].in_dim);
 }
 
 bool gen_blob_header(const gnncca_mpn_dims* d, GenBlobHeader* out) {
@@ -164,67 +172,6 @@ bool fast_consts_ok(const gnncca_mpn_dims* d) {
 bool enc_split_ok(const gnncca_mpn_dims* d) {
     return classify(d) == kFamilyMfma32x6 && d->enc_node.n_layers >= 2 && d->enc_node.layers[0].out_dim == 128 &&
            d->enc_node.layers[0].in_dim % 32 == 0;
-}
-
-// fp32 -> bf16, round to nearest even (finite inputs; weights are finite)
-static inline uint16_t bf16_rne(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float bf16_to_float(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-
-// fp32 -> fp16, round to nearest even, subnormals kept, |f| >= 65520 -> infinity: bit for bit v_cvt_f16_f32 in the default float mode
-// (what `(_Float16)v` compiles to in pack_device_kernel)
-static inline uint16_t f16_rne(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
-    const uint32_t a = u & 0x7FFFFFFFu;
-    if (a >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | ((a > 0x7F800000u) ? 0x0200u : 0u));   // inf / NaN
-    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);                                          // >= 65520: rounds to infinity
-    if (a >= 0x38800000u) {                                                                            // normal fp16 range: 2^-14 ...
-        const uint32_t m = a - 0x38000000u;                                                            // rebias 127 -> 15
-        return (uint16_t)(sign | (uint16_t)((m + 0xFFFu + ((m >> 13) & 1u)) >> 13));                  // (a carry into the exponent is the right answer)
-    }
-    if (a < 0x33000000u) return sign;                                                                  // < 2^-25: rounds to zero (2^-25 itself ties to even = 0)
-    // subnormal fp16: value = mant * 2^-24 with mant = round(|f| * 2^24)
-    const int e = (int)(a >> 23);                                                                      // 102 ... 112
-    const uint32_t mant = (a & 0x7FFFFFu) | 0x800000u;                                                // 24-bit significand, |f| = mant * 2^(e - 150)
-    const int sh = 126 - e;                                                                            // mant >> sh = |f| * 2^24
-    const uint32_t q = mant >> sh, rem = mant & ((1u << sh) - 1u), half = 1u << (sh - 1);
-    return (uint16_t)(sign | (uint16_t)(q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
-}
-static inline float f16_to_float(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
-    uint32_t u;
-    if (e == 0x1Fu) u = sign | 0x7F800000u | (m << 13);
-    else if (e != 0) u = sign | ((e + 112u) << 23) | (m << 13);
-    else if (m == 0) u = sign;
-    else {
-        int s = 0;
-        uint32_t mm = m;
-        while (!(mm & 0x400u)) mm <<= 1, ++s;
-        u = sign | ((uint32_t)(113 - s) << 23) | ((mm & 0x3FFu) << 13);
-    }
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-// position (in halfs) of piece 0 of weight element (output column o, input i) in the enc_w2h image; piece 1 sits 128 * 32 halfs further.
-// FRAGMENT-major inside a 32-deep chunk: [piece][column tile c = o / 32][k-step s = (i % 32) / 16][lane = o % 32 + 32 * ((i % 16) / 8)][i % 8] --
-// the 1 KB the 64 lanes of one B operand of v_mfma_f32_32x32x16_f16 hold is one contiguous run, so the same image serves the LDS ring of
-// the 256-row kernel (ds_read_b128 at consecutive addresses: conflict-free without a swizzle) and the straight-to-register loads of the
-// 32-row kernel (one fully coalesced 1 KB load per fragment)
-static inline size_t w2h_index(int o, int i) {
-    const int kk = i % 32, lane = (o % 32) + 32 * ((kk % 16) / 8);
-    return (size_t)(i / 32) * (2 * 128 * 32) + (size_t)((((o / 32) * 2 + kk / 16) * 64 + lane) * 8 + (kk % 8));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -286,43 +233,18 @@ bool blob_header(const gnncca_mpn_dims* d, BlobHeader* out) {
     return true;
 }
 
-// One Linear with its BatchNorm folded in: returns W' [out][in] and b' [out].
-struct Folded {
-    std::vector<float> w, b;
-    int in, out;
-};
-
-static Folded fold_layer(const gnncca_layer& l, const float* const*& cur) {
-    Folded f;
-    f.in = l.in_dim;
-    f.out = l.out_dim;
-    const float* w = *cur++;
-    const float* b = *cur++;
-    f.w.resize((size_t)l.in_dim * l.out_dim);
-    f.b.resize(l.out_dim);
-    if (!l.has_bn) {
-        std::memcpy(f.w.data(), w, f.w.size() * sizeof(float));
-        std::memcpy(f.b.data(), b, f.b.size() * sizeof(float));
-        return f;
-    }
-    const float* gamma = *cur++;
-    const float* beta = *cur++;
-    const float* mean = *cur++;
-    const float* var = *cur++;
-    for (int o = 0; o < l.out_dim; ++o) {
-        // BatchNorm1d eval, eps = 1e-5 (torch default; models/mlp.py:15)
-        const double s = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-        for (int i = 0; i < l.in_dim; ++i) f.w[(size_t)o * l.in_dim + i] = (float)((double)w[(size_t)o * l.in_dim + i] * s);
-        f.b[o] = (float)(((double)b[o] - (double)mean[o]) * s + (double)beta[o]);
-    }
-    return f;
-}
-
-
 // ---------------------------------------------------------------------------------------------
-// The blob of gnncca_pack_weights restated as data: every region is a strided copy out of one parameter tensor,
-// optionally through the BatchNorm fold.  Kept next to the host packer on purpose -- tests/test_boundary.py and
-// tests/test_gpu_parity.py check that interpreting this program reproduces the host blob byte for byte.
+// THE statement of the fast family's blob: every region is a strided copy out of one parameter tensor, optionally through the
+// BatchNorm fold and a piece split (internal.h: PackSeg; pack_elem.h has the element rules).  gnncca_pack_weights interprets it on
+// the host, pack_device_kernel on the GPU; tests/test_boundary.py holds an independent numpy interpreter and the readers' layouts
+// against it.  The splits by cat order:
+//   * the edge MLP weight [EF][nf*2H + ef*EF] is split by the cat order of models/mpn.py:68
+//       [ x[row] | x[col] | edge_attr ]  ->  W_src, W_dst (per-node projections) and W_ee (per edge)
+//   * the node MLP weight [H][nf*H + EF] is split by the cat order of models/mpn.py:97
+//       [ x[row] | edge_attr ]           ->  W_nx (per-node projection Q) and W_ne (per edge, MFMA B operand)
+// kMaxPackSegs cannot be reached by dims that classify() admits: at most 8 encoder layers x (weight + bias) + enc_w3 + enc_w2h +
+// enc_last_wT = 19, the edge encoder 2, the edge MLP 4, the node MLP 2 + the 6 columns of wne_b + wne_bf16 = 9, the classifier 4 and
+// fast_consts 9: 47 of 96.
 bool pack_program(const gnncca_mpn_dims* d, PackProgram* out) {
     if (!out || classify(d) != kFamilyMfma32x6) return false;
     const BlobPlan p = plan_blob(d);
@@ -333,16 +255,10 @@ bool pack_program(const gnncca_mpn_dims* d, PackProgram* out) {
     struct Lin {
         int w, b, bn, in, out;
     };
-    int cur = 0;
-    auto next = [&](const gnncca_layer& l) {
-        Lin r;
-        r.w = cur++;
-        r.b = cur++;
-        r.bn = l.has_bn ? cur : -1;
-        if (l.has_bn) cur += 4;
-        r.in = l.in_dim;
-        r.out = l.out_dim;
-        return r;
+    auto lin = [&](int mlp, int layer) {
+        const ParamSlots s = param_slots(d, mlp, layer);
+        const gnncca_layer& l = mlp_by_index(d, mlp).layers[layer];
+        return Lin{s.w, s.b, s.bn, l.in_dim, l.out_dim};
     };
     auto weight = [&](const Lin& L, int dst, int src_off, int rows, int cols, int unit0, int drs, int dcs, int srs, int scs) {
         if (n >= kMaxPackSegs) { overflow = true; return; }
@@ -359,14 +275,14 @@ bool pack_program(const gnncca_mpn_dims* d, PackProgram* out) {
     const int hin = nf * kH, ein = ef * kEF;
     // encoder.node_mlp
     for (int i = 0; i < d->enc_node.n_layers; ++i) {
-        const Lin L = next(d->enc_node.layers[i]);
+        const Lin L = lin(0, i);
         weight(L, p.h.enc_node_w[i], 0, L.out, L.in, 0, L.in, 1, L.in, 1);
         bias(L, p.h.enc_node_b[i], L.out);
         if (i == 0 && p.h.enc_w3) {
             if (n >= kMaxPackSegs) return false;
             PackSeg& g = out->segs[n++];
             g.kind = 2, g.dst = p.h.enc_w3, g.param = L.w, g.bn = L.bn, g.rows = L.out, g.cols = L.in, g.drs = 0, g.dcs = 0;
-            g.srs = L.in, g.scs = 1, g.plane = L.out * 32;  // [in/32][3 pieces][out][32]: see gnncca_pack_weights
+            g.srs = L.in, g.scs = 1, g.plane = L.out * 32;  // [in/32][3 pieces][out][32]: pack_elem.h, w3_index
         }
         if (i == 0 && p.h.enc_w2h) {
             if (n >= kMaxPackSegs) return false;
@@ -377,17 +293,17 @@ bool pack_program(const gnncca_mpn_dims* d, PackProgram* out) {
         if (i == d->enc_node.n_layers - 1) weight(L, p.h.enc_last_wT, 0, kH, L.in, 0, 1, kH, L.in, 1);
     }
     // encoder.edge_mlp
-    const Lin Le0 = next(d->enc_edge.layers[0]);
+    const Lin Le0 = lin(1, 0);
     weight(Le0, p.h.enc_edge_w, 0, kEF, d->edge_in, 0, d->edge_in, 1, d->edge_in, 1);
     bias(Le0, p.h.enc_edge_b, kEF);
     // MPNet.edge_model.edge_mlp : columns [src | dst | edge]   (mpn.py:68)
-    const Lin Le = next(d->edge_mlp.layers[0]);
+    const Lin Le = lin(2, 0);
     weight(Le, p.h.proj_wT + 8, 0, kEF, hin, 0, 1, kProjOut, Le.in, 1);        // P_src
     weight(Le, p.h.proj_wT + 0, hin, kEF, hin, 0, 1, kProjOut, Le.in, 1);      // P_dst
     weight(Le, p.h.wee, 2 * hin, kEF, ein, 0, ein, 1, Le.in, 1);
     bias(Le, p.h.proj_b + 8, kEF);
     // MPNet.node_model.node_mlp : columns [x[row] | edge]        (mpn.py:97)
-    const Lin Ln = next(d->node_mlp.layers[0]);
+    const Lin Ln = lin(3, 0);
     weight(Ln, p.h.proj_wT + 16, 0, kH, hin, 0, 1, kProjOut, Ln.in, 1);        // Q
     bias(Ln, p.h.proj_b + 16, kH);
     for (int s = 0; s < 3; ++s)
@@ -399,12 +315,12 @@ bool pack_program(const gnncca_mpn_dims* d, PackProgram* out) {
         g.drs = 0, g.dcs = 0, g.srs = Ln.in, g.scs = 1;
     }
     // classifier.edge_mlp
-    const Lin Lc1 = next(d->cls_edge.layers[0]);
+    const Lin Lc1 = lin(4, 0);
     weight(Lc1, p.h.cls_w1, 0, Lc1.out, kEF, 0, kEF, 1, kEF, 1);
     bias(Lc1, p.h.cls_b1, Lc1.out);
     Lin Lc2 = Lc1;
     if (d->cls_edge.n_layers == 2) {
-        Lc2 = next(d->cls_edge.layers[1]);
+        Lc2 = lin(4, 1);
         weight(Lc2, p.h.cls_w2, 0, 1, Lc2.in, 0, Lc2.in, 1, Lc2.in, 1);
         bias(Lc2, p.h.cls_b2, 1);
     }
@@ -421,7 +337,7 @@ bool pack_program(const gnncca_mpn_dims* d, PackProgram* out) {
         bias(Ln, fc + kFcProjB + 16, kH);
     }
     out->n_segs = n;
-    return !overflow && cur == gnncca_param_count(d);
+    return !overflow;
 }
 
 }  // namespace gnncca
@@ -473,6 +389,26 @@ size_t gnncca_packed_weights_bytes(const gnncca_mpn_dims* d) {
 
 static int pack_generic(const gnncca_mpn_dims* d, const float* const* params, void* packed_host, size_t packed_bytes);
 
+// The host interpreter of the pack program: the loop of pack_device_kernel (pack_device.cuh) in row order.  The fold scale is the
+// row's, computed once; a row that is neither folded nor strided on either side is copied as one run.
+static void run_pack_program(const PackProgram& prog, const float* const* params, float* blob) {
+    for (int i = 0; i < prog.n_segs; ++i) {
+        const PackSeg& g = prog.segs[i];
+        const PackSrc src = pack_src(g, params);
+        uint32_t* bad = reinterpret_cast<uint32_t*>(blob + g.plane);   // kind 4 only
+        const bool runs = !src.gamma && g.kind <= 1 && g.scs == 1 && g.dcs == 1;
+        for (int r = 0; r < g.rows; ++r) {
+            if (runs) {
+                std::memcpy(blob + g.dst + (size_t)r * g.drs, src.v + g.src_off + (size_t)r * g.srs, (size_t)g.cols * sizeof(float));
+                continue;
+            }
+            const double scale = pack_scale(src, g, r);
+            for (int c = 0; c < g.cols; ++c)
+                if (pack_store(blob, g, r, c, pack_value(src, g, r, c, scale))) bad[(((size_t)r * g.cols + c) / 256) % kW2hBadWords] = 1u;
+        }
+    }
+}
+
 int gnncca_pack_weights(const gnncca_mpn_dims* d, const float* const* params, int n_params, void* packed_host,
                         size_t packed_bytes) {
     if (!dims_valid(d) || !params || !packed_host) return GNNCCA_ERR_INVALID_ARG;
@@ -481,138 +417,13 @@ int gnncca_pack_weights(const gnncca_mpn_dims* d, const float* const* params, in
     for (int i = 0; i < n_params; ++i)
         if (!params[i]) return GNNCCA_ERR_INVALID_ARG;
     if (classify(d) == kFamilyGeneric) return pack_generic(d, params, packed_host, packed_bytes);
-    const BlobPlan p = plan_blob(d);
-    if (packed_bytes < p.total_floats * sizeof(float)) return GNNCCA_ERR_INVALID_ARG;
+    if (packed_bytes < gnncca_packed_weights_bytes(d)) return GNNCCA_ERR_INVALID_ARG;
+    PackProgram prog;
+    if (!pack_program(d, &prog)) return GNNCCA_ERR_UNSUPPORTED;
     float* blob = static_cast<float*>(packed_host);
-    std::memset(blob, 0, p.total_floats * sizeof(float));
-    std::memcpy(blob, &p.h, sizeof(BlobHeader));
-    const int nf = d->reattach_nodes ? 2 : 1, ef = d->reattach_edges ? 2 : 1;
-    const float* const* cur = params;
-
-    // encoder.node_mlp
-    for (int i = 0; i < d->enc_node.n_layers; ++i) {
-        Folded f = fold_layer(d->enc_node.layers[i], cur);
-        std::memcpy(blob + p.h.enc_node_w[i], f.w.data(), f.w.size() * sizeof(float));
-        std::memcpy(blob + p.h.enc_node_b[i], f.b.data(), f.b.size() * sizeof(float));
-        if (i == 0 && p.h.enc_w3) {
-            // w = w0 + w1 + w2 with bf16 pieces (24 mantissa bits in all): the split-bf16 GEMM multiplies the
-            // pieces on the bf16 MFMA pipe and recovers fp32-level accuracy
-            // Layout [in/32][3 pieces][out][32]: the 32-deep k-chunk a GEMM workgroup stages per iteration (all three
-            // pieces of all output columns, 24 KB for out = 128) is one contiguous run -- full-line coalesced loads.
-            uint16_t* w3 = reinterpret_cast<uint16_t*>(blob + p.h.enc_w3);
-            const size_t plane = (size_t)f.out * 32;
-            for (int o = 0; o < f.out; ++o)
-                for (int i = 0; i < f.in; ++i) {
-                    const float v = f.w[(size_t)o * f.in + i];
-                    const uint16_t h0 = bf16_rne(v);
-                    const float r1 = v - bf16_to_float(h0);
-                    const uint16_t h1 = bf16_rne(r1);
-                    const float r2 = r1 - bf16_to_float(h1);
-                    const size_t k = (size_t)(i / 32) * 3 * plane + (size_t)o * 32 + (size_t)(i % 32);
-                    w3[k] = h0;
-                    w3[plane + k] = h1;
-                    w3[2 * plane + k] = bf16_rne(r2);
-                }
-        }
-        if (i == 0 && p.h.enc_w2h) {
-            // w = w0 + w1 / 2048 with fp16 pieces (w1 = the residual scaled into w0's exponent range; 22 significant bits in all): the
-            // fp16-split GEMM of enc_f16.cuh needs THREE piece products where the bf16 form needs six.  A weight beyond fp16's range sets
-            // the flag word of the pack block that owns the element (device packer: element t belongs to block (t / 256) % 64).
-            uint16_t* w2 = reinterpret_cast<uint16_t*>(blob + p.h.enc_w2h);
-            uint32_t* bad = reinterpret_cast<uint32_t*>(blob + p.h.enc_w2h_bad);
-            for (int o = 0; o < f.out; ++o)
-                for (int i = 0; i < f.in; ++i) {
-                    const float v = f.w[(size_t)o * f.in + i];
-                    const uint16_t h0 = f16_rne(v);
-                    const float r = (v - f16_to_float(h0)) * 2048.0f;
-                    const size_t k = w2h_index(o, i);
-                    w2[k] = h0;
-                    w2[k + 128 * 32] = f16_rne(r);
-                    if (!(std::fabs(v) < kF16Limit)) bad[(((size_t)o * f.in + i) / 256) % kW2hBadWords] = 1u;
-                }
-        }
-        if (i == d->enc_node.n_layers - 1)
-            for (int o = 0; o < kH; ++o)
-                for (int k = 0; k < f.in; ++k) blob[p.h.enc_last_wT + (size_t)k * kH + o] = f.w[(size_t)o * f.in + k];
-    }
-    // encoder.edge_mlp
-    {
-        Folded f = fold_layer(d->enc_edge.layers[0], cur);
-        std::memcpy(blob + p.h.enc_edge_w, f.w.data(), f.w.size() * sizeof(float));
-        std::memcpy(blob + p.h.enc_edge_b, f.b.data(), f.b.size() * sizeof(float));
-    }
-    // MPNet.edge_model.edge_mlp : columns [src nf*H | dst nf*H | edge ef*EF]   (mpn.py:68)
-    const int hin = nf * kH, ein = ef * kEF;
-    float* projT = blob + p.h.proj_wT;
-    float* projb = blob + p.h.proj_b;
-    {
-        Folded f = fold_layer(d->edge_mlp.layers[0], cur);
-        const int in = f.in;  // 2*hin + ein
-        for (int o = 0; o < kEF; ++o) {
-            for (int c = 0; c < hin; ++c) {
-                projT[(size_t)c * kProjOut + 8 + o] = f.w[(size_t)o * in + c];        // P_src
-                projT[(size_t)c * kProjOut + 0 + o] = f.w[(size_t)o * in + hin + c];  // P_dst
-            }
-            for (int g = 0; g < ein; ++g) blob[p.h.wee + (size_t)o * ein + g] = f.w[(size_t)o * in + 2 * hin + g];
-            projb[8 + o] = f.b[o];
-        }
-    }
-    // MPNet.node_model.node_mlp : columns [x[row] nf*H | edge EF]                (mpn.py:97)
-    {
-        Folded f = fold_layer(d->node_mlp.layers[0], cur);
-        const int in = f.in;  // hin + EF
-        for (int o = 0; o < kH; ++o) {
-            for (int c = 0; c < hin; ++c) projT[(size_t)c * kProjOut + 16 + o] = f.w[(size_t)o * in + c];  // Q
-            projb[16 + o] = f.b[o];
-        }
-        // B operand of v_mfma_f32_32x32x2_f32, k-step s: lane l holds B[k = l>>5][j = l&31] = Wne[j][2s + k]
-        for (int s = 0; s < 3; ++s)
-            for (int l = 0; l < 64; ++l) blob[p.h.wne_b + s * 64 + l] = f.w[(size_t)(l & 31) * in + hin + 2 * s + (l >> 5)];
-        // B operands of the split-bf16 message (msg_bf16.cuh: MsgB): dword [plane * 3 + j][lane] = the pieces of
-        // (W_ne[ch][2j], W_ne[ch][2j + 1]), ch = lane & 31; plane 0 = first pieces in both halves, plane 1 = second pieces,
-        // plane 2 = third pieces in lanes < 32 and FIRST pieces in lanes >= 32
-        uint16_t* wb = reinterpret_cast<uint16_t*>(blob + p.h.wne_bf16);
-        for (int ch = 0; ch < kH; ++ch)
-            for (int k = 0; k < kEF; ++k) {
-                const float v = f.w[(size_t)ch * in + hin + k];
-                const uint16_t h0 = bf16_rne(v);
-                const float r1 = v - bf16_to_float(h0);
-                const uint16_t h1 = bf16_rne(r1);
-                const float r2 = r1 - bf16_to_float(h1);
-                const uint16_t h2 = bf16_rne(r2);
-                auto at = [&](int plane, int lane) { return ((size_t)(plane * 3 + k / 2) * 64 + lane) * 2 + (k & 1); };
-                wb[at(0, ch)] = wb[at(0, ch + 32)] = h0;
-                wb[at(1, ch)] = wb[at(1, ch + 32)] = h1;
-                wb[at(2, ch)] = h2;
-                wb[at(2, ch + 32)] = h0;
-            }
-    }
-    // classifier.edge_mlp
-    {
-        Folded f1 = fold_layer(d->cls_edge.layers[0], cur);
-        std::memcpy(blob + p.h.cls_w1, f1.w.data(), f1.w.size() * sizeof(float));
-        std::memcpy(blob + p.h.cls_b1, f1.b.data(), f1.b.size() * sizeof(float));
-        if (d->cls_edge.n_layers == 2) {
-            Folded f2 = fold_layer(d->cls_edge.layers[1], cur);
-            std::memcpy(blob + p.h.cls_w2, f2.w.data(), f2.w.size() * sizeof(float));
-            std::memcpy(blob + p.h.cls_b2, f2.b.data(), f2.b.size() * sizeof(float));
-        }
-    }
-    if (p.h.fast_consts) {  // contiguous copy of the per-step scalars for the specialised kernel
-        float* fc = blob + p.h.fast_consts;
-        auto transpose = [&](int dst, int src, int rows, int cols) {  // [rows][cols] -> [cols][rows]
-            for (int r = 0; r < rows; ++r)
-                for (int c = 0; c < cols; ++c) fc[dst + c * rows + r] = blob[src + r * cols + c];
-        };
-        transpose(kFcEncW, p.h.enc_edge_w, 6, 4);
-        std::memcpy(fc + kFcEncB, blob + p.h.enc_edge_b, 6 * sizeof(float));
-        transpose(kFcWee, p.h.wee, 6, 6);
-        transpose(kFcCw1, p.h.cls_w1, 4, 6);
-        std::memcpy(fc + kFcCb1, blob + p.h.cls_b1, 4 * sizeof(float));
-        std::memcpy(fc + kFcCw2, blob + p.h.cls_w2, 4 * sizeof(float));
-        std::memcpy(fc + kFcCb2, blob + p.h.cls_b2, 1 * sizeof(float));
-        std::memcpy(fc + kFcProjB, blob + p.h.proj_b, kProjOut * sizeof(float));
-    }
+    std::memset(blob, 0, (size_t)prog.header.total_floats * sizeof(float));
+    std::memcpy(blob, &prog.header, sizeof(BlobHeader));
+    run_pack_program(prog, params, blob);
     return GNNCCA_OK;
 }
 
@@ -622,17 +433,26 @@ static int pack_generic(const gnncca_mpn_dims* d, const float* const* params, vo
     float* blob = static_cast<float*>(packed_host);
     std::memset(blob, 0, p.total_floats * sizeof(float));
     std::memcpy(blob, &p.h, sizeof(GenBlobHeader));
-    const float* const* cur = params;
     for (int m = 0; m < 5; ++m) {
         const gnncca_mlp& mlp = mlp_by_index(d, m);
         for (int l = 0; l < mlp.n_layers; ++l) {
-            Folded f = fold_layer(mlp.layers[l], cur);
-            const size_t op = ((size_t)f.out + 7) / 8 * 8;  // padding stays zero
-            for (int o = 0; o < f.out; ++o)
-                for (int k = 0; k < f.in; ++k) blob[p.h.w[m][l] + (size_t)k * op + o] = f.w[(size_t)o * f.in + k];
-            std::memcpy(blob + p.h.b[m][l], f.b.data(), f.b.size() * sizeof(float));
-            if (m == 0 && l == 0 && p.h.enc0_rowmajor)
-                std::memcpy(blob + p.h.enc0_rowmajor, f.w.data(), f.w.size() * sizeof(float));
+            const int in = mlp.layers[l].in_dim, out = mlp.layers[l].out_dim;
+            const ParamSlots ps = param_slots(d, m, l);
+            PackSeg gw = {}, gb = {};   // the layer's weight [out][in] and bias as sources of the shared fold (pack_elem.h)
+            gw.kind = 0, gw.param = ps.w, gw.bn = ps.bn, gw.srs = in, gw.scs = 1;
+            gb.kind = 1, gb.param = ps.b, gb.bn = ps.bn, gb.srs = 1;
+            const PackSrc sw = pack_src(gw, params), sb = pack_src(gb, params);
+            const size_t op = ((size_t)out + 7) / 8 * 8;  // padding stays zero
+            float* rowmajor = (m == 0 && l == 0 && p.h.enc0_rowmajor) ? blob + p.h.enc0_rowmajor : nullptr;
+            for (int o = 0; o < out; ++o) {
+                const double s = pack_scale(sw, gw, o);
+                for (int k = 0; k < in; ++k) {
+                    const float v = pack_value(sw, gw, o, k, s);
+                    blob[p.h.w[m][l] + (size_t)k * op + o] = v;
+                    if (rowmajor) rowmajor[(size_t)o * in + k] = v;
+                }
+                blob[p.h.b[m][l] + o] = pack_value(sb, gb, o, 0, s);
+            }
         }
     }
     if (p.h.step_w) {   // the fused step's stage image: copies of the rows above
@@ -788,9 +608,7 @@ Workspace carve(const gnncca_mpn_dims* d, int64_t n, int64_t e) {
     if (w.ell_S > 0) w.e_stride = std::max<int64_t>(w.e_stride, (int64_t)align_up(N * (size_t)w.ell_S, 64));
     // split-K of the first (widest) encoder GEMM: enough workgroups to cover the chip when N is small
     const int k0 = d->enc_node.layers[0].in_dim;
-    const size_t row_tiles = (N + 31) / 32;
-    int ks = 1;
-    while (ks < 32 && row_tiles * (size_t)ks < 512 && k0 / (ks * 2) >= 64) ks *= 2;
+    int ks = plan_gemm_ksplit(n, k0);
     // from 1024 nodes on the split-bf16 GEMM runs with 128-row workgroups: room for its split-K factor too
     if (N >= 1024)
         while (ks < 8 && ((N + 127) / 128) * (size_t)ks < 512 && k0 / (ks * 2) >= 64) ks *= 2;

@@ -304,7 +304,6 @@ struct TrCall {          // one application of an MLP (models/mlp.py:26-28)
 struct TrPlan {
     size_t flags, blockflags, seg_ptr, col32, perm, cursor, row32, colo32;
     size_t wt[5][GNNCCA_MAX_LAYERS], bp[5][GNNCCA_MAX_LAYERS];
-    int p0[5];                       // index of each MLP's first entry in the parameter list
     TrCall enc_node, enc_edge;
     std::vector<TrCall> edge, node, cls;   // per step; per classified step
     std::vector<size_t> h, hin, ein, arg;  // per step: aggregated node latents [N][H]; cat(h0, h) / cat(e0, e) when reattaching; max arg
@@ -330,11 +329,9 @@ static bool tr_plan(const gnncca_mpn_dims* d, int64_t n, int64_t e, TrPlan* P) {
     P->cursor = take((N + 1) * 4);
     P->row32 = take(E * 4);
     P->colo32 = take(E * 4);
-    int pidx = 0, maxw = 1;
+    int maxw = 1;
     for (int m = 0; m < 5; ++m) {
         const gnncca_mlp& mlp = mlp_by_index(d, m);
-        P->p0[m] = pidx;
-        pidx += mlp_param_count(mlp);
         for (int l = 0; l < mlp.n_layers; ++l) {
             const int OP = (mlp.layers[l].out_dim + 7) / 8 * 8;
             P->wt[m][l] = take((size_t)mlp.layers[l].in_dim * OP * 4);
@@ -405,13 +402,7 @@ struct TrCtx {
     hipStream_t st;
     float* at(size_t off) const { return reinterpret_cast<float*>(base + off); }
     float p_of(int mlp) const { return mlp <= 1 ? drop.p_enc : (mlp == 2 ? drop.p_edge : (mlp == 3 ? drop.p_node : drop.p_cls)); }
-    // index of layer l's weight in the parameter list (weight, bias, [BatchNorm weight, bias, running_mean, running_var])
-    int pw(int mlp, int l) const {
-        const gnncca_mlp& m = mlp_by_index(d, mlp);
-        int i = P->p0[mlp];
-        for (int q = 0; q < l; ++q) i += 2 + (m.layers[q].has_bn ? 4 : 0);
-        return i;
-    }
+    ParamSlots slots(int mlp, int l) const { return param_slots(d, mlp, l); }   // layer l's tensors in the parameter list
 };
 
 // `second_pass` (mode 1 only): the squared deviations go to sums[O .. 2 O) next to the first pass's column sums, which stay (no memset) and
@@ -448,7 +439,7 @@ static int tr_mlp_forward(const TrCtx& c, const TrCall& call, const float* xin, 
     for (int l = 0; l < mlp.n_layers; ++l) {
         const gnncca_layer& L = mlp.layers[l];
         const int O = L.out_dim, K = L.in_dim, OP = (O + 7) / 8 * 8;
-        const int pi = c.pw(call.mlp, l);
+        const ParamSlots ps = c.slots(call.mlp, l);
         float* dst = L.has_bn ? c.at(call.lay[l].z) : c.at(call.lay[l].a);
         if (M * O > 0) {
             for (int o0 = 0; o0 < O; o0 += 2048) {
@@ -468,16 +459,16 @@ static int tr_mlp_forward(const TrCtx& c, const TrCall& call, const float* xin, 
                     s = tr_col_reduce(c, nullptr, dst, nullptr, M, O, 1, true);
                     if (s != GNNCCA_OK) return s;
                     hipLaunchKernelGGL(tr_bn_apply_fused_kernel, grid1((size_t)M * O, 256), dim3(256), 0, c.st, (const float*)dst, sums, stat,
-                                       (const float*)c.params[pi + 2], (const float*)c.params[pi + 3], c.params[pi + 4], c.params[pi + 5],
+                                       (const float*)c.params[ps.bn], (const float*)c.params[ps.bn + 1], c.params[ps.bn + 2], c.params[ps.bn + 3],
                                        c.at(call.lay[l].a), M, O, (int)L.relu);
                 } else {
                     hipLaunchKernelGGL(tr_bn_mean_kernel, dim3((O + 255) / 256), dim3(256), 0, c.st, sums, M, O, stat);
                     s = tr_col_reduce(c, nullptr, dst, stat, M, O, 1);
                     if (s != GNNCCA_OK) return s;
-                    hipLaunchKernelGGL(tr_bn_var_kernel, dim3((O + 255) / 256), dim3(256), 0, c.st, sums, M, O, stat, c.params[pi + 4],
-                                       c.params[pi + 5]);
+                    hipLaunchKernelGGL(tr_bn_var_kernel, dim3((O + 255) / 256), dim3(256), 0, c.st, sums, M, O, stat, c.params[ps.bn + 2],
+                                       c.params[ps.bn + 3]);
                     hipLaunchKernelGGL(tr_bn_apply_kernel, grid1((size_t)M * O, 256), dim3(256), 0, c.st, (const float*)dst,
-                                       (const float*)stat, (const float*)c.params[pi + 2], (const float*)c.params[pi + 3],
+                                       (const float*)stat, (const float*)c.params[ps.bn], (const float*)c.params[ps.bn + 1],
                                        c.at(call.lay[l].a), M, O, (int)L.relu);
                 }
                 HIP_TRY(hipGetLastError());
@@ -507,7 +498,7 @@ static int tr_mlp_backward(const TrCtx& c, const TrCall& call, const float* xin,
     for (int l = mlp.n_layers - 1; l >= 0; --l) {
         const gnncca_layer& L = mlp.layers[l];
         const int O = L.out_dim, K = L.in_dim;
-        const int pi = c.pw(call.mlp, l);
+        const ParamSlots ps = c.slots(call.mlp, l);
         if (M * O > 0) {
             if (L.relu) {
                 hipLaunchKernelGGL(bwd_relu_mask_kernel, grid1((size_t)M * O, 256), dim3(256), 0, c.st, cur,
@@ -520,22 +511,22 @@ static int tr_mlp_backward(const TrCtx& c, const TrCall& call, const float* xin,
                 int s = tr_col_reduce(c, cur, z, stat, M, O, 2);
                 if (s != GNNCCA_OK) return s;
                 hipLaunchKernelGGL(tr_bn_bwd_apply_kernel, grid1(std::max<size_t>((size_t)M * O, (size_t)O), 256), dim3(256), 0, c.st, cur, z,
-                                   stat, (const float*)c.params[pi + 2], reinterpret_cast<const double*>(c.base + c.P->dsum), M, O,
-                                   c.grads[pi + 2], c.grads[pi + 3]);
+                                   stat, (const float*)c.params[ps.bn], reinterpret_cast<const double*>(c.base + c.P->dsum), M, O,
+                                   c.grads[ps.bn], c.grads[ps.bn + 1]);
                 HIP_TRY(hipGetLastError());
             }
             const float* X = l == 0 ? xin : c.at(call.lay[l - 1].a);
-            if (c.grads[pi] != nullptr || c.grads[pi + 1] != nullptr) {
+            if (c.grads[ps.w] != nullptr || c.grads[ps.b] != nullptr) {
                 // d W[o][k] += sum_r g[r][o] X[r][k], d b[o] += sum_r g[r][o]
-                HIP_TRY(launch_outer(cur, O, X, K, c.grads[pi], K, c.grads[pi + 1], (int)M, O, K, c.st));
+                HIP_TRY(launch_outer(cur, O, X, K, c.grads[ps.w], K, c.grads[ps.b], (int)M, O, K, c.st));
             }
             if (l > 0 || want_dx) {
                 float* nxt = (l == 0 && dx_out) ? dx_out : (cur == gbuf0 ? gbuf1 : gbuf0);
                 if (l == 0 && call.mlp == 0) {   // d x of the node encoder ([N][node_in]): the matrix pipe (input_grads.cuh)
-                    HIP_TRY(launch_dx(cur, c.params[pi], nxt, M, O, K, c.st));
+                    HIP_TRY(launch_dx(cur, c.params[ps.w], nxt, M, O, K, c.st));
                 } else {
                     hipLaunchKernelGGL(tr_matmul_kernel, grid1((size_t)M * K, 256), dim3(256), 0, c.st, (const float*)cur,
-                                       (const float*)c.params[pi], nxt, M, O, K);
+                                       (const float*)c.params[ps.w], nxt, M, O, K);
                     HIP_TRY(hipGetLastError());
                 }
                 cur = nxt;
@@ -599,9 +590,10 @@ static int train_forward_impl(const gnncca_mpn_dims* d, float* const* params, in
     for (int m = 0; m < 5; ++m) {
         const gnncca_mlp& mlp = mlp_by_index(d, m);
         for (int l = 0; l < mlp.n_layers; ++l) {
-            const int O = mlp.layers[l].out_dim, K = mlp.layers[l].in_dim, OP = (O + 7) / 8 * 8, pi = c.pw(m, l);
-            hipLaunchKernelGGL(tr_transpose_pad_kernel, grid1((size_t)K * OP, 256), dim3(256), 0, st, (const float*)params[pi],
-                               (const float*)params[pi + 1], c.at(P.wt[m][l]), c.at(P.bp[m][l]), O, K, OP);
+            const int O = mlp.layers[l].out_dim, K = mlp.layers[l].in_dim, OP = (O + 7) / 8 * 8;
+            const ParamSlots ps = c.slots(m, l);
+            hipLaunchKernelGGL(tr_transpose_pad_kernel, grid1((size_t)K * OP, 256), dim3(256), 0, st, (const float*)params[ps.w],
+                               (const float*)params[ps.b], c.at(P.wt[m][l]), c.at(P.bp[m][l]), O, K, OP);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -884,13 +876,13 @@ static int mlp_eval_impl(const gnncca_mlp* m, const float* const* params, int n_
     if (m->n_layers == 0 || M == 0) return GNNCCA_OK;
     const GenSeg none = {nullptr, nullptr, 0, 0};
     const float* cur = in;
-    int pi = 0;
     for (int l = 0; l < m->n_layers; ++l) {
         const gnncca_layer& L = m->layers[l];
+        const ParamSlots ps = mlp_param_slots(*m, l);
         const int O = L.out_dim, K = L.in_dim, OP = (O + 7) / 8 * 8;
         float* Wt = reinterpret_cast<float*>(base + wt[l]);
         float* bpad = reinterpret_cast<float*>(base + bp[l]);
-        hipLaunchKernelGGL(tr_transpose_pad_kernel, grid1((size_t)K * OP, 256), dim3(256), 0, st, params[pi], params[pi + 1], Wt, bpad, O, K, OP);
+        hipLaunchKernelGGL(tr_transpose_pad_kernel, grid1((size_t)K * OP, 256), dim3(256), 0, st, params[ps.w], params[ps.b], Wt, bpad, O, K, OP);
         const bool last = l == m->n_layers - 1;
         float* dst = last ? out : reinterpret_cast<float*>(base + buf[l & 1]);
         for (int o0 = 0; o0 < O; o0 += 2048) {
@@ -900,13 +892,12 @@ static int mlp_eval_impl(const gnncca_mlp* m, const float* const* params, int n_
         }
         if (L.has_bn) {
             float* sp = reinterpret_cast<float*>(base + stat[l]);
-            hipLaunchKernelGGL(tr_bn_eval_stat_kernel, dim3((O + 255) / 256), dim3(256), 0, st, params[pi + 4], params[pi + 5], sp, O);
+            hipLaunchKernelGGL(tr_bn_eval_stat_kernel, dim3((O + 255) / 256), dim3(256), 0, st, params[ps.bn + 2], params[ps.bn + 3], sp, O);
             hipLaunchKernelGGL(tr_bn_apply_kernel, grid1((size_t)M * O, 256), dim3(256), 0, st, (const float*)dst, (const float*)sp,
-                               params[pi + 2], params[pi + 3], dst, M, O, (int)L.relu);
+                               params[ps.bn], params[ps.bn + 1], dst, M, O, (int)L.relu);
         }
         HIP_TRY(hipGetLastError());
         cur = dst;
-        pi += 2 + (L.has_bn ? 4 : 0);
     }
     return GNNCCA_OK;
 }

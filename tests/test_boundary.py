@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import pack_configs
 from conftest import GOLDEN_DIR, ROOT, golden_cases
 from oracle.mpn_oracle import load_case
 
@@ -196,6 +197,18 @@ class BlobHeader(C.Structure):  # mirror of csrc/internal.h: BlobHeader
                 ("pad", C.c_int32 * 3)]
 
 
+def _bf16_split3(w):
+    """w (float32) as three bf16 pieces (uint16 bit patterns) with h0 + h1 + h2 = w to 2^-24: each piece is the round-to-nearest-even
+    bf16 of what the pieces before it left over (the integer rule: add 0x7FFF plus the lowest kept bit, drop the low 16 bits)."""
+    pieces, rest = [], w.astype(np.float32)
+    for _ in range(3):
+        u = rest.view(np.uint32).astype(np.uint64)
+        hi = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+        pieces.append(hi)
+        rest = rest - (hi.astype(np.uint32) << 16).view(np.float32)
+    return pieces
+
+
 def blob_forward(blob_u8, params, arch, x, edge_index, edge_attr):
     raw = blob_u8.numpy().tobytes()
     h = BlobHeader.from_buffer_copy(raw[:C.sizeof(BlobHeader)])
@@ -204,7 +217,7 @@ def blob_forward(blob_u8, params, arch, x, edge_index, edge_attr):
     enc = params["encoder_feats_dict"]["nodes"][arch]
     dims = [enc["node_in_dim"]] + list(enc["node_fc_dims"]) + [enc["node_out_dim"]]
     if h.enc_w2h:   # the fp16 piece image of the first encoder weight (csrc/enc_f16.cuh): w0 = fp16(w), w1 = fp16((w - w0) * 2048), bit for bit
-        # numpy's round-to-nearest-even conversions, fragment-major inside every 32-deep chunk (csrc/pack.cpp: w2h_index)
+        # numpy's round-to-nearest-even conversions, fragment-major inside every 32-deep chunk (csrc/pack_elem.h: w2h_index)
         K, O = dims[0], dims[1]
         assert O == 128 and K % 32 == 0
         W = f[h.enc_node_w[0]:h.enc_node_w[0] + K * O].reshape(O, K)
@@ -218,6 +231,14 @@ def blob_forward(blob_u8, params, arch, x, edge_index, edge_attr):
         assert np.array_equal(w0.view(np.uint16), want0.view(np.uint16)) and np.array_equal(w1.view(np.uint16), want1.view(np.uint16))
         bad = np.frombuffer(raw, dtype=np.uint32)[h.enc_w2h_bad:h.enc_w2h_bad + 64]
         assert bad.any() == bool((np.abs(W) >= 65520).any())
+    if h.enc_w3:    # the bf16 piece planes of the same weight as csrc/encoder.cuh reads them: [in/32][3 pieces][out][32], the pieces
+        # being w -> h0, (w - h0) -> h1, ((w - h0) - h1) -> h2 by round-to-nearest-even
+        K, O = dims[0], dims[1]
+        assert K % 32 == 0
+        W = f[h.enc_node_w[0]:h.enc_node_w[0] + K * O].reshape(O, K)
+        img = np.frombuffer(raw, dtype=np.uint16)[2 * h.enc_w3:2 * h.enc_w3 + 3 * K * O].reshape(K // 32, 3, O, 32)
+        for got, want in zip(img.transpose(1, 2, 0, 3).reshape(3, O, K), _bf16_split3(W)):   # [piece][column][chunk][32] -> (column, k)
+            assert np.array_equal(got, want)
     nf = 2 if params["reattach_initial_nodes"] else 1
     ef = 2 if params["reattach_initial_edges"] else 1
     edge_in = params["encoder_feats_dict"]["edges"]["edge_in_dim"]
@@ -240,6 +261,13 @@ def blob_forward(blob_u8, params, arch, x, edge_index, edge_attr):
     for s in range(3):
         for l in range(64):
             wne[l & 31, 2 * s + (l >> 5)] = wneb[s, l]
+    # the MsgB image of the same W_ne (csrc/msg_bf16.cuh: msg_b_weights): dword [plane * 3 + j][lane] = the bf16 pieces of
+    # (W_ne[ch][2j], W_ne[ch][2j + 1]), ch = lane & 31, the even column in the low half; plane 0 = first pieces in both lane halves,
+    # plane 1 = second pieces, plane 2 = third pieces in lanes < 32 and FIRST pieces in lanes >= 32
+    msgb = np.frombuffer(raw, dtype=np.uint16)[2 * h.wne_bf16:2 * h.wne_bf16 + 2 * 9 * 64].reshape(3, 3, 64, 2)
+    p0, p1, p2 = (p.reshape(32, 3, 2).transpose(1, 0, 2) for p in _bf16_split3(wne))   # [j][ch][column parity]
+    for plane, (lo, hi) in enumerate([(p0, p0), (p1, p1), (p2, p0)]):
+        assert np.array_equal(msgb[plane, :, :32], lo) and np.array_equal(msgb[plane, :, 32:], hi), plane
     row, col = edge_index
     n = x.shape[0]
     L, first = params["num_enc_steps"], params["num_enc_steps"] - params["num_class_steps"] + 1
@@ -282,6 +310,10 @@ def blob_forward(blob_u8, params, arch, x, edge_index, edge_attr):
         assert np.array_equal(fc[0:24].reshape(4, 6).T.ravel(), f[h.enc_edge_w:h.enc_edge_w + 24]) and fc[100] == f[h.cls_b2]
         if h.cls_w1:
             assert np.array_equal(fc[68:92].reshape(6, 4).T.ravel(), f[h.cls_w1:h.cls_w1 + 24])
+        # the vectors (csrc/internal.h: kFcEncB, kFcCb1, kFcCw2); the block exists only for the classifier Linear(6,4)+ReLU+Linear(4,1)
+        assert h.cls_layers == 2 and h.cls_hidden == 4
+        assert np.array_equal(fc[24:30], f[h.enc_edge_b:h.enc_edge_b + 6])
+        assert np.array_equal(fc[92:96], f[h.cls_b1:h.cls_b1 + 4]) and np.array_equal(fc[96:100], f[h.cls_w2:h.cls_w2 + 4])
     return out
 
 
@@ -372,6 +404,24 @@ def test_pack_program_reproduces_host_blob(name):
     tensors = [t.detach().numpy() for t in m.native_param_tensors()]
     emulated = run_pack_program(prog, tensors, host.size)
     assert np.array_equal(emulated.view(np.uint8), host), name
+
+
+@pytest.mark.parametrize("name", pack_configs.NAMES)
+def test_pack_program_reproduces_host_blob_synthetic(name):
+    """The branches of the program no golden case takes (tests/pack_configs.py), held against the numpy interpreter above and against
+    the readers' layouts that blob_forward asserts."""
+    from gnn_cca_amd import _native as nat
+    m = pack_configs.build(name)
+    d, prog = m.native_dims(), PackProgram()
+    nat.check(nat.lib().gnncca_pack_program(C.byref(d), C.byref(prog), C.sizeof(prog)), "gnncca_pack_program")
+    host = m.pack_weights_host()
+    with np.errstate(over="ignore"):   # the planted weights beyond fp16's range become infinities, as on the device
+        emulated = run_pack_program(prog, [t.detach().numpy() for t in m.native_param_tensors()], host.numel())
+        rng = np.random.default_rng(0)
+        x = rng.normal(size=(3, d.node_in)).astype(np.float32)
+        edge_index = np.array([[0, 0, 1, 2], [1, 2, 0, 1]])
+        blob_forward(host, pack_configs.model_params(name), pack_configs.ARCH, x, edge_index, rng.normal(size=(4, d.edge_in)).astype(np.float32))
+    assert np.array_equal(emulated.view(np.uint8), host.numpy()), name
 
 
 def test_pack_program_refuses_generic_family():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import pack_configs
 from conftest import GOLDEN_DIR, golden_cases
 from oracle.mpn_oracle import NumpyOracle, load_case
 
@@ -513,6 +514,18 @@ def test_device_pack_equals_host_pack(name):
     byte: BatchNorm fold in double, split-weight layouts, bf16 planes."""
     params, arch, sd, a = load_case(os.path.join(GOLDEN_DIR, name + ".npz"))
     m = build(params, arch, sd)
+    dev_blob = m._pack_weights_device(torch.device("cuda", torch.cuda.current_device()))
+    assert dev_blob is not None, "tuned family must pack on the GPU"
+    torch.cuda.synchronize()
+    assert torch.equal(dev_blob.cpu(), m.pack_weights_host()), name
+
+
+@pytest.mark.parametrize("name", pack_configs.NAMES)
+def test_device_pack_equals_host_pack_synthetic(name):
+    """The same byte-for-byte comparison on the branches of the pack program no golden case takes (tests/pack_configs.py): BatchNorm in
+    every MLP with non-trivial running statistics, 1- and 3-layer encoders, both reattach flags, edge_in 16, first-layer weights beyond
+    fp16's range and in its subnormal range.  One pack launch per case: no forward, no graph."""
+    m = pack_configs.build(name).cuda()
     dev_blob = m._pack_weights_device(torch.device("cuda", torch.cuda.current_device()))
     assert dev_blob is not None, "tuned family must pack on the GPU"
     torch.cuda.synchronize()
