@@ -3,7 +3,7 @@
 camera count) -> persistent track ids across frames and batches (gnn_cca_amd.tracking).  Everything stays on the GPU until the final
 print.  The reference has no counterpart of this stage: it scores single frames (inference.py:349-371).  Needs an MI355X.
 
-    python examples/track_frames.py [batches] [frames_per_batch] [cams] [persons] [--exclusive]
+    python examples/track_frames.py [batches] [frames_per_batch] [cams] [persons] [--exclusive] [--smooth]
 
 Persons walk on the ground plane; every camera sees every person, with noise on the position.  The model has random weights, so its
 clusters mean nothing: the ids are shown for the model's partition AND for the ground-truth partition of the same detections, where a
@@ -19,7 +19,10 @@ cover the time that really passed.  A TrackGallery (gnn_cca_amd.reentry) stands 
 hidden frame, so person 0 comes back as a new track, and the gallery gives that track the old identity back by appearance; its
 identities are scored like track ids.  With --exclusive one more linker runs the WAITING-FREE loop on a partition that is legal by
 construction: r.exclusive() (no cluster holds two detections of one camera, whatever the number of cameras; no wait for the host
-heuristics of final()) -> cluster_summaries -> FrameLinker, one extra line per batch.  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
+heuristics of final()) -> cluster_summaries -> FrameLinker, one extra line per batch.  With --smooth a TrackSmoother (gnn_cca_amd.smoothing)
+stands behind the linker with max_gap=1: a constant-velocity Kalman filter along every track turns the ids into trajectories -- filtered
+position, velocity, their variances, and how far a detection lay from where its track was expected; one extra line per batch (these
+persons wander without a heading, so the filtered velocity is small: DESIGN.md section 9 has straight walks).  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
 """
 import argparse
 import os
@@ -33,6 +36,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
 from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
 from gnn_cca_amd.reentry import TrackGallery  # noqa: E402
+from gnn_cca_amd.smoothing import TrackSmoother  # noqa: E402
 from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, Tracks, TrackScorer, cluster_summaries  # noqa: E402
 
 
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("cams", nargs="?", type=int, default=4)
     ap.add_argument("persons", nargs="?", type=int, default=6)
     ap.add_argument("--exclusive", action="store_true", help="also link the camera-exclusive clusters of r.exclusive(): the loop that never waits")
+    ap.add_argument("--smooth", action="store_true", help="also filter the tracks of the max_gap=1 linker: trajectories with velocities and variances")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     n_g = a.cams * a.persons
@@ -67,6 +72,8 @@ def main():
     by_truth_vel = FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity")   # a cluster is looked for where it is heading
     score_vel = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     gallery = TrackGallery(by_truth, max_cos=0.3)   # ended tracks, matched against newly born ones by appearance
+    # --smooth: the walk's step is 0.15 per axis and frame (the process noise), a detection's noise 0.05, and a cluster fuses `cams` of them
+    smooth = TrackSmoother(by_truth_gap, process_noise=0.15 ** 2, measurement_noise=0.05 ** 2, vel_var=0.15 ** 2, per_detection=True)
     score_back = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     blind, timed = (FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity") for _ in range(2))   # for the batches that lost a frame
     where = rng.uniform(-8, 8, size=(a.persons, 2))
@@ -96,6 +103,8 @@ def main():
         st = cluster_summaries(r.batch, truth)   # any partition of the batch's detections can be summarised
         tt = by_truth(st)
         tg = by_truth_gap(st)                    # tg.matched_gap: 1 where a cluster continues one that was last seen two frames ago
+        if a.smooth:
+            tj = smooth(st, tg)                  # Trajectories: pos / vel [N, 2], cov [N, 3], nis [N], age [N], rows as tg.cluster_track
         back = gallery(st, tt)                   # identities: a track born after an absence too long for the linker takes an ended track's
         score_back.add(r, Tracks(back.cluster_identity, back.node_identity, tt.matched_prev, tt.next_id, None))   # scored where tracks stood
         score.add(r, tt)                         # ids (batch.y), cameras and node tracks joined over time: nothing waits for the GPU
@@ -121,6 +130,11 @@ def main():
             print(f"  exclusive partition: {int(ex['n_clusters'].item())} clusters, every one with size == cameras: "
                   f"{bool((se.size == se.n_cams).all().item())} (model partition: {bool((s.size == s.n_cams).all().item())}); candidate pairs cut "
                   f"{int(ex['cut'].sum().item())}, tracks so far {int(te.next_id.item())}")
+        if a.smooth:
+            print(f"  last frame, true partition, smoothed: positions {[[round(v, 2) for v in p] for p in tj.pos[last][:k_truth].tolist()]}, "
+                  f"velocities {[[round(v, 2) for v in p] for p in tj.vel[last][:k_truth].tolist()]}, position sigma "
+                  f"{[round(v ** 0.5, 3) for v in tj.cov[last][:k_truth, 0].tolist()]}, links since birth {tj.age[last][:k_truth].tolist()}, "
+                  f"largest nis of the batch {float(tj.nis.max()):.2f}")
         if a.frames > 2:   # frame 1 never arrives: without time stamps the step over the hole passes for one period's
             sd, kept = without_frame(st, 1)
             tb = blind(sd)

@@ -31,7 +31,8 @@
 // A time stamp per frame (gnncca_link_frames_gap_timed in identities_assign.cuh, gnncca_link_frames_motion_timed in identities_motion.cuh)
 // is an argument of the same level and walk kernels, not a kernel of its own: link_common.cuh's level_dt.
 // The re-entry gallery (gnncca_reentry_update: a track born after a long absence gets an ended track's identity) is identities_reentry.cuh,
-// the last include: kernels of its own that share frame_range, usable_count, wave_number and wave_min_lex.
+// kernels of its own that share frame_range, usable_count, wave_number and wave_min_lex.  The track smoother (gnncca_track_smooth: a
+// constant-velocity Kalman filter along the links the linkers made) is identities_smooth.cuh, the last include: three kernels, chain-parallel.
 // Deterministic: every fp sum has a fixed order, integer counts go through LDS atomics, no fp64 atomics.  No host wait, no allocation:
 // capturable.  The file is compiled without fp contraction: the sums, the divisions and the cost are the documented operations one by one.
 #include <hip/hip_runtime.h>
@@ -454,3 +455,5 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
 #include "identities_motion.cuh"   // gnncca_link_frames_motion: the gap-tolerant linker with a velocity prediction (one walking workgroup)
 
 #include "identities_reentry.cuh"   // gnncca_reentry_update: the gallery that gives a returning person the old identity back
+
+#include "identities_smooth.cuh"   // gnncca_track_smooth: a constant-velocity Kalman filter along every track (chain-parallel)

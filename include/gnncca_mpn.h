@@ -1365,6 +1365,67 @@ GNNCCA_API int gnncca_reentry_update(const int32_t* node_ptr_dev, const int32_t*
                                      int64_t* node_identity, int64_t* reentered_from, void* workspace, size_t workspace_bytes,
                                      gnncca_stream_t stream);
 
+/* ---- Track smoother (csrc/identities_smooth.cuh, included by csrc/identities.hip) ------------------------------------------------------
+ * A stage behind gnncca_link_frames*: a constant-velocity Kalman filter along every track, so that a consumer gets trajectories --
+ * filtered position, velocity, their covariance, how far a detection lay from where its track was expected (nis) and the links since
+ * birth (age).  It filters after linking and gates nothing: matched_prev / matched_gap are the linker's outputs for the SAME summaries
+ * (matched_gap of gnncca_link_frames: 0 where matched_prev >= 0, else -1).  No counterpart in the reference.  The rule:
+ *   The two ground-plane axes are independent and share one 2 x 2 covariance (a, b, c) = (var pos, cov pos/vel, var vel).  q: process
+ *   noise intensity, finite and >= 0; r: measurement variance, finite and > 0; vel_var: initial velocity variance, finite and > 0;
+ *   per_detection (0 / 1): the measurement variance of a cluster is re = r / (double)size when 1 (a cluster fused from more detections
+ *   is trusted more), else re = r.  For cluster a of frame t with measurement z = pos(a):
+ *   Birth (matched_gap(a) == -1):  p = z, v = (0, 0), (a, b, c) = (re, 0, vel_var), age = 0, nis = 0.
+ *   Link to cluster m = matched_prev(a) of frame t - 1 - k, k = matched_gap(a):  dt = (double)(k + 1) without time stamps, with them
+ *   dt = T[t] - T[t - 1 - k] (frames counted among frames PRESENT, exactly as the linker counts them); start from that cluster's
+ *   filtered state (p, v, a, b, c, age).  Every line is one fp64 operation per operator as written, left to right, no FMA:
+ *     dt2 = dt*dt;  dt3 = dt2*dt
+ *     pp  = p + dt*v                               (per axis)
+ *     a_  = ((a + (2.0*dt)*b) + dt2*c) + (q*dt3)/3.0
+ *     b_  = (b + dt*c) + (q*dt2)/2.0
+ *     c_  = c + q*dt
+ *     s   = a_ + re
+ *     k1  = a_/s;  k2 = b_/s
+ *     i   = z - pp                                 (per axis)
+ *     p'  = pp + k1*i;  v' = v + k2*i              (per axis)
+ *     a'  = a_ - k1*a_;  b' = b_ - k1*b_;  c' = c_ - k2*b_
+ *     nis = (ix*ix + iy*iy)/s
+ *     age' = age + 1
+ *   Non-finite inputs propagate: there is no special case.  Rows at or beyond a frame's count, and every row of a refused frame, get
+ *   zeros in the fp64 outputs and age = -1.  The rule is causal along predecessor links only: the result does not depend on how a
+ *   sequence is cut into calls.  A link that points at nothing (a level outside 0 .. max_gap, a rank at or beyond its frame's count, a
+ *   frame before the carried history) is a birth; no linker of this library makes one.
+ * State (state_in is never written, state_out is overwritten), gnncca_track_smooth_state_bytes(capacity_rows, n_frames_kept) bytes: a
+ *   64-byte header (int32 n_frames, int32 count[9]: the usable cluster count per frame, zeros), then for a capacity of C rows fp64 [C][7]
+ *   (px, py, vx, vy, a, b, c), then int32 age [C] (-1: not a cluster) -- the 8-byte array before the 4-byte one.  The rows are aligned with
+ *   the linker's kept frames: the last max_gap + 1 frames, each with the row capacity the caller gives in state_*_frame_rows (host
+ *   arrays, as the state_*_frame_rows of gnncca_link_frames_gap: per frame its node count; state_out_frames = min(state_in_frames +
+ *   n_frames, max_gap + 1); a history frame that stays keeps its capacity).
+ * Outputs, row-aligned with cluster_track: out_pos, out_vel fp64 [N][2], out_cov fp64 [N][3], out_nis fp64 [N], out_age int32 [N].
+ * frame_time_dev: NULL (no time stamps), or the DEVICE array fp64 [state_in_frames + n_frames] the _timed linker entries take; max_dt is
+ *   then checked like theirs (finite and > 0) and gates nothing: whatever the linker linked is filtered.
+ * workspace: gnncca_track_smooth_workspace_bytes(n_nodes, n_frames, state_rows) bytes: a successor row int32 per combined row (the
+ *   state_rows history rows, then the batch rows), and the frame and the new-state row of every batch row.
+ * Three launches whatever max_gap and n_frames are, kernels only (no memset node: a captured call must replay): the workspace = -1,
+ * the successor rows (frame-parallel, plain stores: links are one-to-one), then a thread per combined row, where the head of every
+ * chain walks it, at most n_frames steps; every index taken from the workspace is checked against its own range.  Deterministic for one-to-one links, which is what every
+ * linker gives (of two clusters that name the same predecessor, which stays on the chain and which starts as a birth is not fixed); no
+ * host wait, no allocation, no cooperative launch: capturable.  n_frames = 0 launches nothing (the caller keeps its state); n_nodes = 0
+ * with n_frames > 0 still passes time: the walk launch moves the history rows that stay to their new slots.
+ * GNNCCA_ERR_INVALID_ARG before any launch: q, r, vel_var out of range, per_detection not 0 / 1, max_dt not finite and > 0 with
+ * frame_time_dev, max_gap outside [0, GNNCCA_TRACK_MAX_GAP], a frame above GNNCCA_TRACK_MAX_FRAME_NODES, inconsistent frame-row lists, a
+ * NULL array; GNNCCA_ERR_WORKSPACE: a short workspace (the status every entry of this library gives for one).
+ * Limits: constant velocity, one (q, r) for every track; it follows the linker's links only -- a track the re-entry gallery re-attaches
+ * starts a fresh filter. */
+GNNCCA_API size_t gnncca_track_smooth_state_bytes(int64_t capacity_rows, int32_t n_frames_kept);
+GNNCCA_API size_t gnncca_track_smooth_workspace_bytes(int64_t n_nodes, int64_t n_frames, int64_t state_rows);
+GNNCCA_API int gnncca_track_smooth(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* size, const double* pos,
+                                   const int32_t* matched_prev, const int32_t* matched_gap, int64_t n_nodes, int32_t n_frames,
+                                   int32_t max_frame_nodes, int32_t max_gap, double q, double r, double vel_var, int32_t per_detection,
+                                   const void* state_in, const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                                   const int32_t* state_out_frame_rows, int32_t state_out_frames, double* out_pos, double* out_vel,
+                                   double* out_cov, double* out_nis, int32_t* out_age, void* workspace, size_t workspace_bytes,
+                                   gnncca_stream_t stream, const double* frame_time_dev, double max_dt);
+
 /* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
  * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).
  * criterion: GNNCCA_LOSS_BCE, GNNCCA_LOSS_BCE_WEIGHTED (pos_weight > 0) or GNNCCA_LOSS_FOCAL (utils.FocalLoss_binary: focusing_param,
