@@ -3,7 +3,7 @@
 camera count) -> persistent track ids across frames and batches (gnn_cca_amd.tracking).  Everything stays on the GPU until the final
 print.  The reference has no counterpart of this stage: it scores single frames (inference.py:349-371).  Needs an MI355X.
 
-    python examples/track_frames.py [batches] [frames_per_batch] [cams] [persons] [--exclusive] [--smooth]
+    python examples/track_frames.py [batches] [frames_per_batch] [cams] [persons] [--exclusive] [--smooth] [--kalman]
 
 Persons walk on the ground plane; every camera sees every person, with noise on the position.  The model has random weights, so its
 clusters mean nothing: the ids are shown for the model's partition AND for the ground-truth partition of the same detections, where a
@@ -22,7 +22,10 @@ construction: r.exclusive() (no cluster holds two detections of one camera, what
 heuristics of final()) -> cluster_summaries -> FrameLinker, one extra line per batch.  With --smooth a TrackSmoother (gnn_cca_amd.smoothing)
 stands behind the linker with max_gap=1: a constant-velocity Kalman filter along every track turns the ids into trajectories -- filtered
 position, velocity, their variances, and how far a detection lay from where its track was expected; one extra line per batch (these
-persons wander without a heading, so the filtered velocity is small: DESIGN.md section 9 has straight walks).  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
+persons wander without a heading, so the filtered velocity is small: DESIGN.md section 9 has straight walks).  With --kalman a
+KalmanLinker (gnn_cca_amd.kalman) links the true partition with that filter INSIDE the linker: a track is looked for where its filtered
+state predicts it and a pair is gated by the variance of the prediction (max_nis); its tracks carry their trajectories, and it is scored
+like the others.  The scorers' result() is the last thing printed (synthetic walks and the ground-truth partition: what linking does to tracking quality with a trained model has not been measured).
 """
 import argparse
 import os
@@ -34,6 +37,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (model / GRAPH_NET_PARAMS builders)
+from gnn_cca_amd.kalman import KalmanLinker  # noqa: E402
 from gnn_cca_amd.pipeline import FramePipeline  # noqa: E402
 from gnn_cca_amd.reentry import TrackGallery  # noqa: E402
 from gnn_cca_amd.smoothing import TrackSmoother  # noqa: E402
@@ -58,6 +62,7 @@ def main():
     ap.add_argument("persons", nargs="?", type=int, default=6)
     ap.add_argument("--exclusive", action="store_true", help="also link the camera-exclusive clusters of r.exclusive(): the loop that never waits")
     ap.add_argument("--smooth", action="store_true", help="also filter the tracks of the max_gap=1 linker: trajectories with velocities and variances")
+    ap.add_argument("--kalman", action="store_true", help="also link the true partition by the filtered state, gated by its variance")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     n_g = a.cams * a.persons
@@ -74,6 +79,12 @@ def main():
     gallery = TrackGallery(by_truth, max_cos=0.3)   # ended tracks, matched against newly born ones by appearance
     # --smooth: the walk's step is 0.15 per axis and frame (the process noise), a detection's noise 0.05, and a cluster fuses `cams` of them
     smooth = TrackSmoother(by_truth_gap, process_noise=0.15 ** 2, measurement_noise=0.05 ** 2, vel_var=0.15 ** 2, per_detection=True)
+    # --kalman: the filter inside the linker.  These persons WANDER: a step of 0.15 per axis and frame without a heading is, to a
+    # constant-velocity model, noise around a velocity near zero, so it goes into the measurement variance beside the fused detection
+    # noise (with r = 0.05 ** 2 / cams alone the variance gate, 13.8 = chi-square(2) at one in a thousand, cuts tracks at ordinary steps)
+    by_truth_kal = KalmanLinker(max_step=1.0, process_noise=0.15 ** 2, measurement_noise=0.15 ** 2 + 0.05 ** 2 / a.cams, vel_var=0.15 ** 2,
+                                lam=1.0, max_gap=1, max_nis=13.8)
+    score_kal = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     score_back = TrackScorer(max_ids=a.persons, max_cams=a.cams)
     blind, timed = (FrameLinker(max_step=1.0, lam=1.0, max_gap=1, motion="velocity") for _ in range(2))   # for the batches that lost a frame
     where = rng.uniform(-8, 8, size=(a.persons, 2))
@@ -112,6 +123,9 @@ def main():
         score_opt.add(r, by_truth_opt(st))
         tv = by_truth_vel(st)                    # tv.velocity: float64 [N, 2], the displacement per frame since the predecessor
         score_vel.add(r, tv)
+        if a.kalman:
+            tk = by_truth_kal(st)                # KalmanTracks: a Tracks whose velocity is the filtered one, plus tk.trajectories
+            score_kal.add(r, tk)
         if a.exclusive:   # exclusive() -> cluster_summaries -> FrameLinker: device work only, legal clusters without final()'s wait
             ex = r.exclusive()
             se = cluster_summaries(r.batch, ex["labels"])
@@ -135,6 +149,12 @@ def main():
                   f"velocities {[[round(v, 2) for v in p] for p in tj.vel[last][:k_truth].tolist()]}, position sigma "
                   f"{[round(v ** 0.5, 3) for v in tj.cov[last][:k_truth, 0].tolist()]}, links since birth {tj.age[last][:k_truth].tolist()}, "
                   f"largest nis of the batch {float(tj.nis.max()):.2f}")
+        if a.kalman:
+            tj2 = tk.trajectories
+            print(f"  last frame, true partition, KalmanLinker: ids {tk.cluster_track[last][:k_truth].tolist()}, filtered velocities "
+                  f"{[[round(v, 2) for v in p] for p in tk.velocity[last][:k_truth].tolist()]}, position sigma "
+                  f"{[round(v ** 0.5, 3) for v in tj2.cov[last][:k_truth, 0].tolist()]}, links since birth {tj2.age[last][:k_truth].tolist()}, "
+                  f"largest nis of the batch {float(tj2.nis.max()):.2f} (gate 13.8)")
         if a.frames > 2:   # frame 1 never arrives: without time stamps the step over the hole passes for one period's
             sd, kept = without_frame(st, 1)
             tb = blind(sd)
@@ -152,7 +172,7 @@ def main():
                   f"{int(back.cluster_identity[after])} (re-entered from track {int(back.reentered_from[after])})")
     print("random weights: the model's clusters are meaningless, the plumbing is what is shown; on the true partition a person keeps its id")
     for name, sc in (("without max_gap", score), ("without max_gap, identities of the re-entry gallery", score_back), ("with max_gap=1", score_gap), ("with max_gap=1, matching='optimal'", score_opt),
-                     ("with max_gap=1, motion='velocity'", score_vel)):   # result(): the one synchronisation of a scorer
+                     ("with max_gap=1, motion='velocity'", score_vel)) + ((("with max_gap=1, KalmanLinker(max_nis=13.8)", score_kal),) if a.kalman else ()):   # result(): the one synchronisation of a scorer
         res = sc.result()
         print(f"true partition {name}: " + ", ".join(f"{q} {v:.3f}" if isinstance(v, float) else f"{q} {v}" for q, v in res.items()))
 

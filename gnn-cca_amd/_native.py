@@ -299,6 +299,14 @@ _SIGNATURES = {
                                                   C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                   C.c_void_p, C.c_double]),
+    "gnncca_link_kalman_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gnncca_link_kalman_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    # the motion entry's head, then q, r, vel_var, has_max_nis, max_nis; its tail with the five filter outputs; frame_time_dev (or NULL), max_dt
+    "gnncca_link_frames_kalman": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                            C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                            C.c_int32, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_double]),
     "gnncca_track_score_table_bytes": (C.c_size_t, [C.c_int64]),
     "gnncca_track_score_reset": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gnncca_track_score_rehash": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

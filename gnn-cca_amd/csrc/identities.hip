@@ -33,6 +33,8 @@
 // The re-entry gallery (gnncca_reentry_update: a track born after a long absence gets an ended track's identity) is identities_reentry.cuh,
 // kernels of its own that share frame_range, usable_count, wave_number and wave_min_lex.  The track smoother (gnncca_track_smooth: a
 // constant-velocity Kalman filter along the links the linkers made) is identities_smooth.cuh, the last include: three kernels, chain-parallel.
+// The Kalman linker (gnncca_link_frames_kalman: the motion walk that predicts with that filter, feeds it and can gate by its variance) is
+// identities_kalman.cuh, after identities_motion.cuh; the filter's arithmetic is link_common.cuh's, one definition for both.
 // Deterministic: every fp sum has a fixed order, integer counts go through LDS atomics, no fp64 atomics.  No host wait, no allocation:
 // capturable.  The file is compiled without fp contraction: the sums, the divisions and the cost are the documented operations one by one.
 #include <hip/hip_runtime.h>
@@ -453,6 +455,8 @@ int gnncca_link_frames(const int32_t* node_ptr_dev, const int32_t* count, const 
 #include "track_score.cuh"   // gnncca_track_score_*: identity-tracking scores over a sequence (its own kernels)
 
 #include "identities_motion.cuh"   // gnncca_link_frames_motion: the gap-tolerant linker with a velocity prediction (one walking workgroup)
+
+#include "identities_kalman.cuh"   // gnncca_link_frames_kalman: the same walk, predicting with and feeding a constant-velocity Kalman filter
 
 #include "identities_reentry.cuh"   // gnncca_reentry_update: the gallery that gives a returning person the old identity back
 

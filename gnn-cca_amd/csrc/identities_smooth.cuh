@@ -225,21 +225,7 @@ __global__ __launch_bounds__(256) void smooth_walk_kernel(SmoothIn si, const int
         // checks it all the same (registers only): no index below rests on what the workspace holds
         if (tn < 0 || tn >= G || k < 0 || k > si.max_gap || HN + tn - 1 - k < 0) return;
         const double dt = frame_time ? frame_time[HN + tn] - frame_time[HN + tn - 1 - k] : (double)(k + 1);
-        const double q = prm.q;
-        const double dt2 = dt * dt;
-        const double dt3 = dt2 * dt;
-        const double ppx = x[0] + dt * x[2];
-        const double ppy = x[1] + dt * x[3];
-        const double a_ = ((x[4] + (2.0 * dt) * x[5]) + dt2 * x[6]) + (q * dt3) / 3.0;
-        const double b_ = (x[5] + dt * x[6]) + (q * dt2) / 2.0;
-        const double c_ = x[6] + q * dt;
-        const double s = a_ + re;
-        const double k1 = a_ / s, k2 = b_ / s;
-        const double ix = zx - ppx, iy = zy - ppy;
-        x[0] = ppx + k1 * ix, x[1] = ppy + k1 * iy;
-        x[2] = x[2] + k2 * ix, x[3] = x[3] + k2 * iy;
-        x[4] = a_ - k1 * a_, x[5] = b_ - k1 * b_, x[6] = c_ - k2 * b_;
-        const double nis = (ix * ix + iy * iy) / s;
+        const double nis = cv_kalman_step(x, zx, zy, dt, prm.q, re);   // (the rule's lines: link_common.cuh)
         age = age + 1;
         smooth_write(so, row, orow, x, nis, age);
         cur = nxt;

@@ -6,7 +6,10 @@
 //   wave_min_lex    the lexicographic (value, index) minimum of a wave: ties to the smaller index;
 //   wave_number     the ballot scan that numbers the entries where a predicate holds, in ascending order;
 //   side_b          where a frame's partners of level k are: an earlier frame of the batch, or a frame of the carried history;
-//   StateView       the arrays of a carried history state (with or without velocities), write_slot one frame's rows into it;
+//   StateView       the arrays of a carried history state (without velocities, with them, or the Kalman linker's), write_slot one frame's
+//                   rows into it;
+//   cv_kalman_step  the constant-velocity Kalman filter's link rule (and cv_predicted_var, its predicted position variance): the
+//                   smoother's walk and the Kalman linker's commit and variance gate (VarianceGate, pair_rule's extra predicate) run it;
 //   level_dt        the time between the two frames of a (frame, level) table when the call has time stamps, and whether the table counts;
 //   write_node_tracks, link_init_kernel, and on the host plan_history: the checks and the numbers both history entries need.
 #pragma once
@@ -65,19 +68,40 @@ __device__ __forceinline__ double wave_cosine_distance(const float* er, const fl
     return (na == 0.0 || nb == 0.0) ? 1.0 : 1.0 - dot / (sqrt(na) * sqrt(nb));
 }
 
+// An extra admissibility predicate of the pair rule, asked with d^2 = dx*dx + dy*dy inside the distance gate: none.  (pair_rule is called
+// with d^2 alone, best_partner with the row and the column as well; an instantiation with AdmitAll compiles to the rule without one.)
+struct AdmitAll {
+    __device__ __forceinline__ bool operator()(double) const { return true; }
+    __device__ __forceinline__ bool operator()(double, int, int) const { return true; }
+};
+
+// The variance gate of the Kalman linker: d^2 / s <= max_nis, s the predicted innovation variance of the pair's cluster of side B -- the
+// search's row (BY_ROW) or its column -- which the caller has put into an LDS array, one per cluster of side B, before the search.  One fp64
+// division; a NaN is admissible with nobody.  has == 0: no variance gate was asked for, the array is not read.
+template <bool BY_ROW>
+struct VarianceGate {
+    const double* s;
+    double max_nis;
+    int has;
+    __device__ __forceinline__ bool operator()(double d2, int r, int c) const { return !has || d2 / s[BY_ROW ? r : c] <= max_nis; }
+};
+
 // One pass of 64 columns against a row at (rx, ry) with appearance row er: this lane's column stands at (cx, cy) if `on`, and ec_of(j) is
 // the appearance row of lane j's column.  use(cost) is called in the lanes whose pair is admissible (a NaN d is admissible with nobody):
-// the division and the caller's use of the cost stay under one branch, which a pass without admissible pairs skips.
-template <int LOADS, class EmbOf, class Use>
+// the division and the caller's use of the cost stay under one branch, which a pass without admissible pairs skips.  admit(d^2): one more
+// predicate a pair inside the distance gate has to pass (AdmitAll: none).
+template <int LOADS, class EmbOf, class Use, class Admit = AdmitAll>
 __device__ __forceinline__ void pair_rule(bool on, double rx, double ry, double cx, double cy, const float* er, EmbOf ec_of, int R,
-                                          const LinkRule& rule, Use use) {
+                                          const LinkRule& rule, Use use, Admit admit = Admit{}) {
     const int lane = threadIdx.x & 63;
     bool cand = false;
     double d = 0.0, dcos = 0.0;
     if (on) {
         const double dx = rx - cx, dy = ry - cy;
-        d = sqrt(dx * dx + dy * dy);
+        const double d2 = dx * dx + dy * dy;
+        d = sqrt(d2);
         cand = d <= rule.max_step;
+        if constexpr (!std::is_same_v<Admit, AdmitAll>) cand = cand && admit(d2);
     }
     if (rule.need_emb) {
         unsigned long long todo = __ballot(cand);   // (uniform) the pairs inside the gate: the whole wave computes each cosine
@@ -137,9 +161,10 @@ __device__ __forceinline__ Spot side_at(const LinkSide& s, int i, double steps) 
 
 // out[r] = the admissible free column of smallest cost for the free row r (ties: the smaller column), or -1.  A wave takes a row, its
 // lanes the columns.  The minimum is over ORIGINAL ranks, never over compacted positions.  dx is squared, so which side is predicted
-// does not change a bit of d.
-template <int BLOCK, int LOADS, bool MASKED>
-__device__ void best_partner(const LinkSide& rows, const LinkSide& cols, double steps, int R, const LinkRule& rule, int* out) {
+// does not change a bit of d.  admit(d^2, row, column): pair_rule's extra predicate for this search (AdmitAll: none).
+template <int BLOCK, int LOADS, bool MASKED, class Admit = AdmitAll>
+__device__ void best_partner(const LinkSide& rows, const LinkSide& cols, double steps, int R, const LinkRule& rule, int* out,
+                             Admit admit = Admit{}) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int r = wave; r < rows.n; r += BLOCK / 64) {
         const Spot row = side_at<MASKED>(rows, r, steps);
@@ -153,21 +178,28 @@ __device__ void best_partner(const LinkSide& rows, const LinkSide& cols, double 
             const int c = base + lane;
             Spot col{0.0, 0.0, false};
             if (c < cols.n) col = side_at<MASKED>(cols, c, steps);
-            pair_rule<LOADS>(col.free, row.x, row.y, col.x, col.y, rows.emb + (size_t)r * R,
-                             [&](int j) { return cols.emb + (size_t)(base + j) * R; }, R, rule, [&](double cost) {
-                                 if (cost < best) best = cost, bi = c;   // (a lane's columns ascend: the smaller one stays on a tie)
-                             });
+            const auto use = [&](double cost) {
+                if (cost < best) best = cost, bi = c;   // (a lane's columns ascend: the smaller one stays on a tie)
+            };
+            const auto emb_of = [&](int j) { return cols.emb + (size_t)(base + j) * R; };
+            if constexpr (std::is_same_v<Admit, AdmitAll>)
+                pair_rule<LOADS>(col.free, row.x, row.y, col.x, col.y, rows.emb + (size_t)r * R, emb_of, R, rule, use);
+            else
+                pair_rule<LOADS>(col.free, row.x, row.y, col.x, col.y, rows.emb + (size_t)r * R, emb_of, R, rule, use,
+                                 [&](double d2) { return admit(d2, r, c); });
         }
         const int b = wave_min_lex(best, bi).i;
         if (lane == 0) out[r] = b == INT_MAX ? -1 : b;
     }
 }
 
-// fwd[a] -> b and bwd[b] -> a for the two sides of a frame pair (the caller's barrier follows)
-template <int BLOCK, int LOADS, bool MASKED>
-__device__ __forceinline__ void mutual_best(const LinkSide& a, const LinkSide& b, double steps, int R, const LinkRule& rule, int* fwd, int* bwd) {
-    best_partner<BLOCK, LOADS, MASKED>(a, b, steps, R, rule, fwd);
-    best_partner<BLOCK, LOADS, MASKED>(b, a, steps, R, rule, bwd);
+// fwd[a] -> b and bwd[b] -> a for the two sides of a frame pair (the caller's barrier follows).  admit_ab / admit_ba: the extra predicate
+// of the two searches, the same pairs seen from either side (AdmitAll: none).
+template <int BLOCK, int LOADS, bool MASKED, class AdmitAB = AdmitAll, class AdmitBA = AdmitAll>
+__device__ __forceinline__ void mutual_best(const LinkSide& a, const LinkSide& b, double steps, int R, const LinkRule& rule, int* fwd, int* bwd,
+                                            AdmitAB admit_ab = AdmitAB{}, AdmitBA admit_ba = AdmitBA{}) {
+    best_partner<BLOCK, LOADS, MASKED>(a, b, steps, R, rule, fwd, admit_ab);
+    best_partner<BLOCK, LOADS, MASKED>(b, a, steps, R, rule, bwd, admit_ba);
 }
 
 // ---- numbering ----------------------------------------------------------------------------------------------------------------------------
@@ -229,10 +261,18 @@ struct GapFrames {
     int off[kGapMaxFrames + 1];
 };
 
-__host__ __device__ inline size_t hist_track_off(long long cap, bool has_vel) { return sizeof(GapHeader) + (size_t)cap * (has_vel ? 32 : 16); }
-__host__ __device__ inline size_t hist_emb_off(long long cap, bool has_vel) { return hist_track_off(cap, has_vel) + (size_t)cap * 8; }
-__host__ __device__ inline size_t hist_succ_off(long long cap, int R, bool has_vel) {
-    return hist_emb_off(cap, has_vel) + (size_t)cap * (size_t)R * sizeof(float);
+// The KIND of a history state, wherever a `kind` is passed below (false / true of the two older kinds convert to 0 / 1): without
+// velocities, with velocities, or the Kalman linker's -- the state with velocities whose pos and vel slots hold the FILTERED values, plus
+// cov fp64 [C][3] behind vel and age int32 [C] behind succ (still every 8-byte array before the 4-byte ones).  The layouts of the two older
+// kinds are as they were, byte for byte.
+enum : int { kStatePlain = 0, kStateVel = 1, kStateKalman = 2 };
+
+__host__ __device__ inline size_t hist_track_off(long long cap, int kind) {
+    return sizeof(GapHeader) + (size_t)cap * (kind == kStateKalman ? 56 : kind == kStateVel ? 32 : 16);
+}
+__host__ __device__ inline size_t hist_emb_off(long long cap, int kind) { return hist_track_off(cap, kind) + (size_t)cap * 8; }
+__host__ __device__ inline size_t hist_succ_off(long long cap, int R, int kind) {
+    return hist_emb_off(cap, kind) + (size_t)cap * (size_t)R * sizeof(float);
 }
 
 // the arrays of a state of `cap` rows (Byte = char: a state to write; const char: one to read)
@@ -242,14 +282,17 @@ struct StateView {
     using Ptr = std::conditional_t<std::is_const_v<Byte>, const T, T>*;
     Ptr<GapHeader> head;
     Ptr<double> pos, vel;   // vel: nullptr in a state without velocities
+    Ptr<double> cov;        // nullptr except in a Kalman state
     Ptr<long long> track;
     Ptr<float> emb;
     Ptr<int> succ;
-    __device__ StateView(Byte* base, long long cap, int R, bool has_vel)
+    Ptr<int> age;           // nullptr except in a Kalman state
+    __device__ StateView(Byte* base, long long cap, int R, int kind)
         : head(reinterpret_cast<Ptr<GapHeader>>(base)), pos(reinterpret_cast<Ptr<double>>(base + sizeof(GapHeader))),
-          vel(has_vel ? pos + 2 * (size_t)cap : nullptr), track(reinterpret_cast<Ptr<long long>>(base + hist_track_off(cap, has_vel))),
-          emb(reinterpret_cast<Ptr<float>>(base + hist_emb_off(cap, has_vel))),
-          succ(reinterpret_cast<Ptr<int>>(base + hist_succ_off(cap, R, has_vel))) {}
+          vel(kind != kStatePlain ? pos + 2 * (size_t)cap : nullptr), cov(kind == kStateKalman ? pos + 4 * (size_t)cap : nullptr),
+          track(reinterpret_cast<Ptr<long long>>(base + hist_track_off(cap, kind))),
+          emb(reinterpret_cast<Ptr<float>>(base + hist_emb_off(cap, kind))),
+          succ(reinterpret_cast<Ptr<int>>(base + hist_succ_off(cap, R, kind))), age(kind == kStateKalman ? succ + (size_t)cap : nullptr) {}
 };
 
 // cluster count of history frame f if the state holds one that fits its rows (0 otherwise: such a frame links to nothing)
@@ -263,7 +306,7 @@ __device__ __forceinline__ int hist_count(const char* state_in, int row0, int ro
 // count 0 if there is no such frame or it is not usable; row: the COMBINED row of its rank 0 (history row i is i, batch row v is S + v).
 __device__ __forceinline__ LinkSide side_b(int s, const int* __restrict__ node_ptr, int N_all, const int* __restrict__ count,
                                            const double* __restrict__ pos, const double* batch_vel, const float* __restrict__ emb, int R,
-                                           const char* state_in, int n_hist, const int* hist_off, int S, bool has_vel, int P_lds, int& row) {
+                                           const char* state_in, int n_hist, const int* hist_off, int S, int kind, int P_lds, int& row) {
     LinkSide b{nullptr, nullptr, nullptr, nullptr, 0, 0};
     row = 0;
     if (s >= 0) {
@@ -279,9 +322,9 @@ __device__ __forceinline__ LinkSide side_b(int s, const int* __restrict__ node_p
         const int f = n_hist + s;
         row = __builtin_amdgcn_readfirstlane(hist_off[f]);   // (the same in every lane)
         b.n = hist_count(state_in, row, __builtin_amdgcn_readfirstlane(hist_off[f + 1]), f, P_lds);
-        const StateView in(state_in, S, R, has_vel);
+        const StateView in(state_in, S, R, kind);
         b.pos = in.pos + 2 * (size_t)row;
-        b.vel = has_vel ? in.vel + 2 * (size_t)row : nullptr;
+        b.vel = kind != kStatePlain ? in.vel + 2 * (size_t)row : nullptr;
         b.emb = in.emb + (size_t)row * R;
     }
     return b;
@@ -296,10 +339,39 @@ __device__ __forceinline__ bool level_dt(const double* frame_time, int t, int s,
     return dt > 0.0 && dt <= max_dt;
 }
 
-// c rows of one frame -> slot j of the new state, whose rows start at orow: count, pos, vel (where the state has them), track, succ, emb
-template <int BLOCK>
+// ---- the constant-velocity Kalman filter's arithmetic, written once: the smoother (identities_smooth.cuh) and the Kalman linker
+// (identities_kalman.cuh) run these lines, one fp64 operation per operator as written, left to right, no FMA (fp contract is off) --------
+// the predicted position variance after dt, from the covariance (a, b, c) = (var pos, cov pos/vel, var vel) and the process noise q
+__device__ __forceinline__ double cv_predicted_var(double a, double b, double c, double dt, double q) {
+    const double dt2 = dt * dt;
+    const double dt3 = dt2 * dt;
+    return ((a + (2.0 * dt) * b) + dt2 * c) + (q * dt3) / 3.0;
+}
+
+// One link: x = (px, py, vx, vy, a, b, c) of the predecessor becomes the linked cluster's, given its measurement (zx, zy), the elapsed
+// time dt, the process noise q and the measurement variance re; -> nis.
+__device__ __forceinline__ double cv_kalman_step(double (&x)[7], double zx, double zy, double dt, double q, double re) {
+    const double dt2 = dt * dt;
+    const double ppx = x[0] + dt * x[2];
+    const double ppy = x[1] + dt * x[3];
+    const double a_ = cv_predicted_var(x[4], x[5], x[6], dt, q);
+    const double b_ = (x[5] + dt * x[6]) + (q * dt2) / 2.0;
+    const double c_ = x[6] + q * dt;
+    const double s = a_ + re;
+    const double k1 = a_ / s, k2 = b_ / s;
+    const double ix = zx - ppx, iy = zy - ppy;
+    x[0] = ppx + k1 * ix, x[1] = ppy + k1 * iy;
+    x[2] = x[2] + k2 * ix, x[3] = x[3] + k2 * iy;
+    x[4] = a_ - k1 * a_, x[5] = b_ - k1 * b_, x[6] = c_ - k2 * b_;
+    return (ix * ix + iy * iy) / s;
+}
+
+// c rows of one frame -> slot j of the new state, whose rows start at orow: count, pos, vel (where the state has them), track, succ, emb,
+// and in a Kalman state (KALMAN) cov and age
+template <int BLOCK, bool KALMAN = false>
 __device__ void write_slot(const StateView<char>& out, int j, int orow, int c, int R, const double* __restrict__ pos, const double* __restrict__ vel,
-                           const long long* track, const int* __restrict__ succ, const float* __restrict__ emb) {
+                           const long long* track, const int* __restrict__ succ, const float* __restrict__ emb,
+                           const double* __restrict__ cov = nullptr, const int* __restrict__ age = nullptr) {
     const int tid = threadIdx.x;
     if (tid == 0) out.head->count[j] = c;
     for (int i = tid; i < 2 * c; i += BLOCK) {
@@ -310,19 +382,24 @@ __device__ void write_slot(const StateView<char>& out, int j, int orow, int c, i
         out.track[orow + i] = track[i];
         out.succ[orow + i] = succ[i];
     }
+    if constexpr (KALMAN) {
+        for (int i = tid; i < 3 * c; i += BLOCK) out.cov[3 * (size_t)orow + i] = cov[i];
+        for (int i = tid; i < c; i += BLOCK) out.age[orow + i] = age[i];
+    }
     for (size_t i = tid; i < (size_t)c * R; i += BLOCK) out.emb[(size_t)orow * R + i] = emb[i];
 }
 
 // Slot j of the new state when it is frame f of the OLD one (a history frame that stays): its rows as they are, the flags from the workspace.
-template <int BLOCK>
+template <int BLOCK, bool KALMAN = false>
 __device__ void keep_slot(const StateView<char>& out, const GapFrames& of, int j, const char* state_in, const GapFrames& in, int f, int R,
-                          bool has_vel, const int* __restrict__ succ_ws, int P_lds) {
+                          int kind, const int* __restrict__ succ_ws, int P_lds) {
     const int orow = of.off[j], irow = in.off[f];
     int c = hist_count(state_in, irow, in.off[f + 1], f, P_lds);
     if (c > of.off[j + 1] - orow) c = 0;
-    const StateView old(state_in, in.off[in.n], R, has_vel);
-    write_slot<BLOCK>(out, j, orow, c, R, old.pos + 2 * (size_t)irow, has_vel ? old.vel + 2 * (size_t)irow : nullptr, old.track + irow,
-                      succ_ws + irow, old.emb + (size_t)irow * R);
+    const StateView old(state_in, in.off[in.n], R, kind);
+    write_slot<BLOCK, KALMAN>(out, j, orow, c, R, old.pos + 2 * (size_t)irow, kind != kStatePlain ? old.vel + 2 * (size_t)irow : nullptr,
+                              old.track + irow, succ_ws + irow, old.emb + (size_t)irow * R, KALMAN ? old.cov + 3 * (size_t)irow : nullptr,
+                              KALMAN ? old.age + irow : nullptr);
 }
 
 // ---- launch 1 of both history linkers: predecessor record (matched_prev, matched_gap) of the N batch rows = none, their velocity (if
@@ -430,9 +507,9 @@ static int plan_history(int64_t n_nodes, int32_t n_frames, int32_t reid_dim, int
 }
 
 // launch 1 of a history entry (velocity: nullptr for a linker without one)
-static void launch_link_init(hipStream_t st, const HistoryPlan& p, bool has_vel, int64_t n_nodes, int* succ_ws, int* matched_prev,
+static void launch_link_init(hipStream_t st, const HistoryPlan& p, int kind, int64_t n_nodes, int* succ_ws, int* matched_prev,
                              int* matched_gap, double* velocity) {
-    const int* in_succ = p.sin ? reinterpret_cast<const int*>(p.sin + hist_succ_off(p.S, p.R, has_vel)) : nullptr;
+    const int* in_succ = p.sin ? reinterpret_cast<const int*>(p.sin + hist_succ_off(p.S, p.R, kind)) : nullptr;
     hipLaunchKernelGGL(link_init_kernel, dim3(p.init_blocks), dim3(256), 0, st, in_succ, p.S, (int)n_nodes, succ_ws, matched_prev, matched_gap,
                        velocity);
 }

@@ -10,7 +10,8 @@ without a host wait.
 The tracking chain ends in ids; ClusterSummaries.pos is the raw fused position of one frame and Tracks.velocity (motion='velocity') one
 subtraction and one division.  The smoother filters AFTER linking: it consumes the links the linker made (matched_prev, matched_gap, the
 time stamps if any), decides nothing and gates nothing, and works behind every linker mode (with max_gap = 0, where Tracks.matched_gap is
-derived from matched_prev, too).  The reference has no counterpart.
+derived from matched_prev, too); kalman.KalmanLinker runs the same filter INSIDE the linker, where it predicts and gates.  The reference has
+no counterpart.
 
 The rule (include/gnncca_mpn.h has it word for word, tests/track_smooth_oracle.py as numpy loops).  The two ground-plane axes are
 independent and share one 2 x 2 covariance (a, b, c) = (var pos, cov pos/vel, var vel).  q = process_noise (finite, >= 0), r =

@@ -55,6 +55,7 @@ nobody.  vel(b) is known only when b's frame has been through all its levels, so
 is causal (the carried state holds the velocities of its M + 1 frames; it is a state of its own kind).  Tracks.velocity is float64 [N, 2].
 Limits: constant velocity from the LAST link only -- the prediction is wrong after a sharp turn, so a track can end there and restart;
 matching='optimal' has no motion yet (the combination is refused).  DESIGN.md section 9 has what it does to identity switches on synthetic crossing walks.
+kalman.KalmanLinker, a subclass with a mode of its own, predicts with a constant-velocity Kalman filter instead and can gate by its variance.
 Optimal matching (matching='optimal': csrc/identities_assign.cuh, the same M + 4 launches, also with max_gap = 0).  Mutual best leaves a
 cluster unlinked whenever its best partner prefers somebody else, even when a second admissible partner is free.  In this mode the levels,
 gates, masks and cost stay as above and only the choice of pairs inside a (level, frame pair) table changes: with A the clusters of frame t
@@ -339,8 +340,7 @@ class FrameLinker:
                 where = "the batch" if max_n > MAX_OPTIMAL_FRAME_NODES else "the carried history"
                 raise ValueError(f"a frame of {where} has {worst} detections; FrameLinker(matching='optimal') takes frames of at most "
                                  f"{MAX_OPTIMAL_FRAME_NODES} (reset() forgets the history)")
-        if self.motion not in nat.MOTION or (self.motion == "velocity" and self.matching == "optimal"):   # (changed after construction)
-            raise ValueError(f"motion={self.motion!r} with matching={self.matching!r} is not a linker this module has")
+        self._check_mode()
         if self._state is not None and self._state_motion != self.motion:
             raise ValueError(f"the carried state was written with motion={self._state_motion!r}, which motion={self.motion!r} cannot "
                              "continue (the states differ in kind): reset() it first")
@@ -358,11 +358,8 @@ class FrameLinker:
         lib = nat.lib()
         with _on(dev):
             if g == 0:   # nothing to link: the state stays
-                nid = self._state[:8].view(torch.int64) if self._state is not None else torch.zeros(1, dtype=torch.int64, device=dev)
-                e64, e32 = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
-                vel = torch.empty((0, 2), dtype=torch.float64, device=dev) if self.motion == "velocity" else None
-                return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone(), vel)
-            if timed or self.motion == "velocity" or self.max_gap > 0 or self.matching == "optimal":
+                return self._no_frames(dev)
+            if timed or self.motion != "none" or self.max_gap > 0 or self.matching == "optimal":
                 return self._link_history(lib, s, dev, sizes, g, n, max_n, r, times)
             cap = int(sizes[-1])
             state = torch.empty(lib.gnncca_link_state_bytes(cap, r), dtype=torch.uint8, device=dev)
@@ -381,6 +378,33 @@ class FrameLinker:
             # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
         self._state, self._cap, self._state_motion, self._state_timed = state, cap, self.motion, False
         return Tracks(tracks[0], tracks[1], matched, state[:8].view(torch.int64), state)
+
+    def _check_mode(self):
+        """ValueError unless the attributes that choose the kernels (they may have been changed after construction) name a linker this
+        class has.  A subclass with a mode of its own answers for it here."""
+        if self.motion not in nat.MOTION or (self.motion == "velocity" and self.matching == "optimal"):
+            raise ValueError(f"motion={self.motion!r} with matching={self.matching!r} is not a linker this module has")
+
+    def _no_frames(self, dev):
+        """What a call with a batch of no frames returns (inside _on(dev)): empty Tracks, the id counter as it stands; the state stays."""
+        nid = self._state[:8].view(torch.int64) if self._state is not None else torch.zeros(1, dtype=torch.int64, device=dev)
+        e64, e32 = torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+        vel = torch.empty((0, 2), dtype=torch.float64, device=dev) if self.motion != "none" else None
+        return Tracks(e64, e64.clone(), e32, nid, self._state, e32.clone(), vel)
+
+    def _stage_times(self, times, dev):
+        """The times of the carried frames, then the batch's checked `times` -> (the combined host list, its device copy: a fresh pinned
+        buffer and one non-blocking copy on the current stream)."""
+        all_times = self._frame_times + times.tolist()   # (one time per carried frame: _frame_times moves with _frame_rows)
+        staged = torch.empty(len(all_times), dtype=torch.float64, pin_memory=True)
+        staged.copy_(torch.from_numpy(np.asarray(all_times, dtype=np.float64)))
+        return all_times, staged.to(dev, non_blocking=True)
+
+    def _advance(self, state, out_rows, all_times):
+        """The history state moves on after a call that linked: the new device state, the node counts of the frames it holds and, from
+        a timed call (all_times not None), their times."""
+        self._state, self._frame_rows, self._state_motion, self._state_timed = state, out_rows, self.motion, all_times is not None
+        self._frame_times = all_times[-len(out_rows):] if all_times is not None else []
 
     def _link_history(self, lib, s, dev, sizes, g, n, max_n, r, times=None):
         """The call of every linker whose state is a history of frames (inside _on(dev), g > 0) -- max_gap > 0, matching='optimal',
@@ -408,11 +432,9 @@ class FrameLinker:
                 tracks[0].data_ptr() if n else None, tracks[1].data_ptr() if n else None, matched[0].data_ptr() if n else None,
                 matched[1].data_ptr() if n else None)
         end = (ws.data_ptr(), ws_bytes, _raw_stream(dev))
+        all_times = None
         if times is not None:
-            all_times = self._frame_times + times.tolist()   # (one time per carried frame: _frame_times moves with _frame_rows)
-            staged = torch.empty(len(all_times), dtype=torch.float64, pin_memory=True)
-            staged.copy_(torch.from_numpy(np.asarray(all_times, dtype=np.float64)))
-            times_dev = staged.to(dev, non_blocking=True)
+            all_times, times_dev = self._stage_times(times, dev)
             if moving:
                 name = "gnncca_link_frames_motion_timed"
                 st = lib.gnncca_link_frames_motion_timed(*head, nat.MOTION[self.motion], *tail, velocity.data_ptr() if n else None, *end,
@@ -434,8 +456,7 @@ class FrameLinker:
         if st:
             nat.check(st, name)
         # the previous state and the workspace are freed in stream order (allocated on this stream): the launches above still read them
-        self._state, self._frame_rows, self._state_motion, self._state_timed = state, out_rows, self.motion, times is not None
-        self._frame_times = all_times[-len(out_rows):] if times is not None else []
+        self._advance(state, out_rows, all_times)
         return Tracks(tracks[0], tracks[1], matched[0], state[:8].view(torch.int64), state, matched[1], velocity)
 
 

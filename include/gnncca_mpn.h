@@ -1426,6 +1426,61 @@ GNNCCA_API int gnncca_track_smooth(const int32_t* node_ptr_dev, const int32_t* c
                                    double* out_cov, double* out_nis, int32_t* out_age, void* workspace, size_t workspace_bytes,
                                    gnncca_stream_t stream, const double* frame_time_dev, double max_dt);
 
+/* ---- Linking by the filtered state (csrc/identities_kalman.cuh, included by csrc/identities.hip) ---------------------------------------
+ * gnncca_link_frames_kalman: gnncca_link_frames_motion whose motion model is the constant-velocity Kalman filter of gnncca_track_smooth,
+ * run INSIDE the linker: a track is looked for where its filtered state predicts it, every link feeds the filter, and a pair can be gated
+ * by the variance of that prediction, so that a newborn track (velocity unknown: variance vel_var) is looked for widely and an established
+ * one narrowly.  Mutual best only.  q, r, vel_var: the smoother's numbers (q finite and >= 0; r, vel_var finite and > 0; re = r for every
+ * cluster: there is no per_detection here).  max_nis (read iff has_max_nis = 1): finite and > 0.  The rule, in full:
+ *   Order.  Frames outside, levels k = 0 .. max_gap inside, exactly as in gnncca_link_frames_motion; the meaning of time, of n_frames = 0
+ *     and of the host arrays of frame capacities are gnncca_link_frames_gap's.  dt = (double)(k + 1); with time stamps (frame_time_dev
+ *     not NULL: the array of the _timed entries) dt = T[t] - T[t - 1 - k], one fp64 subtraction, and a table with !(dt > 0 && dt <= max_dt)
+ *     is skipped whole.
+ *   State.  Every cluster carries a filtered state x = (px, py, vx, vy, a, b, c), (a, b, c) = (var pos, cov pos/vel, var vel) shared by
+ *     the two axes, and an age.
+ *   Candidates and prediction.  At level k the clusters a of frame t without a predecessor meet the clusters b of frame t - 1 - k without
+ *     a successor.  b stands at  pred(b) = p(b) + dt * v(b)  per component, one multiplication and one addition (no FMA), from the
+ *     FILTERED position and velocity.
+ *   Pair rule.  The shared one:  dx = pos_x(a) - pred_x(b), dy likewise, with the RAW pos(a);  d = sqrt(dx*dx + dy*dy);  gate = max_step * dt
+ *     (one multiplication);  dcos and max_cos as in gnncca_link_frames;  cost = d / gate + lam * dcos;  admissible iff d <= gate (and
+ *     dcos <= max_cos) and, with has_max_nis, also  (dx*dx + dy*dy) / s <= max_nis  where
+ *       dt2 = dt*dt;  dt3 = dt2*dt;  a_ = ((a + (2.0*dt)*b) + dt2*c) + (q*dt3)/3.0;  s = a_ + r
+ *     from b's (a, b, c): the operations of the smoother's rule in its order, one fp64 operation per operator, no FMA.  A NaN is
+ *     admissible with nobody.
+ *   Matching.  fwd[a] = the admissible b of smallest cost, bwd[b] = the admissible a of smallest cost, ties to the smaller rank; a
+ *     continues b iff each is the other's best.  Levels go in order, so a shorter gap always wins.
+ *   Commit.  For a linked at level k to b:  x(a), nis(a), age(a) = step(x(b), age(b), z = pos(a), dt, q, re = r)  where step is the link
+ *     rule of gnncca_track_smooth verbatim (pp, a_, b_, c_, s, k1, k2, i, p', v', a', b', c', nis, age' = age + 1).
+ *   Births.  A cluster without a predecessor after all levels:  x = (z, 0, 0, r, 0, vel_var), age = 0, nis = 0, z = pos(a).
+ *   Ids.  A linked cluster takes its predecessor's id; the others get next_id, next_id + 1, ... in ascending (frame, rank) order.
+ *   Consequences.  The rule is causal: the result does not depend on how a sequence is cut into calls.  And gnncca_track_smooth with the
+ *     same (q, r, vel_var), per_detection = 0, fed this entry's matched_prev / matched_gap (and times) returns exactly out_pos .. out_age.
+ * Outputs: cluster_track, node_track, matched_prev, matched_gap as gnncca_link_frames_motion; out_pos, out_vel fp64 [N][2] (the filtered
+ * position and velocity: out_vel takes the place of that entry's velocity), out_cov fp64 [N][3], out_nis fp64 [N], out_age int32 [N], all
+ * row-aligned with cluster_track; rows at or beyond a frame's count, and every row of a refused frame, are zero with age = -1.
+ * The state is of its OWN kind: the 64-byte header of the gap state, then for C rows in all  pos fp64 [C][2], vel fp64 [C][2] (both
+ * FILTERED), cov fp64 [C][3], track int64 [C], emb fp32 [C][R], succ int32 [C], age int32 [C]  -- the 8-byte arrays first; 28 bytes per
+ * row more than the motion state.  state_out: gnncca_link_kalman_state_bytes(C, n_frames_kept, R) bytes;  workspace:
+ * gnncca_link_kalman_workspace_bytes(n_nodes, n_frames, state_rows).
+ * THREE launches whatever max_gap is: a frame-parallel clear, ONE workgroup of 1024 threads that walks the frames in order (with
+ * has_max_nis it computes s once per level into LDS, 8 bytes per cluster beside the 12 of the motion walk: 80 KiB at 4096 rows), a
+ * frame-parallel launch for node_track and the new state.  Deterministic, no host wait, no allocation: capturable.
+ * GNNCCA_ERR_INVALID_ARG before any launch: q, r, vel_var out of range, has_max_nis not 0 / 1, max_nis not finite and > 0 with it, max_dt
+ * not finite and > 0 with frame_time_dev, the checks of gnncca_link_frames_gap;  GNNCCA_ERR_WORKSPACE: a short workspace.
+ * Limits: constant velocity, one (q, r) for every track, no per_detection, no min-cost assignment; a track the re-entry gallery
+ * re-attaches starts a fresh filter. */
+GNNCCA_API size_t gnncca_link_kalman_state_bytes(int64_t capacity_rows, int32_t n_frames_kept, int32_t reid_dim);
+GNNCCA_API size_t gnncca_link_kalman_workspace_bytes(int64_t n_nodes, int64_t n_frames, int64_t state_rows);
+GNNCCA_API int gnncca_link_frames_kalman(const int32_t* node_ptr_dev, const int32_t* count, const int32_t* rank, const double* pos,
+                                         const float* emb, int32_t reid_dim, int64_t n_nodes, int32_t n_frames, int32_t max_frame_nodes,
+                                         double max_step, double lam, int32_t has_max_cos, double max_cos, int32_t max_gap, double q,
+                                         double r, double vel_var, int32_t has_max_nis, double max_nis, const void* state_in,
+                                         const int32_t* state_in_frame_rows, int32_t state_in_frames, void* state_out,
+                                         const int32_t* state_out_frame_rows, int32_t state_out_frames, int64_t* cluster_track,
+                                         int64_t* node_track, int32_t* matched_prev, int32_t* matched_gap, double* out_pos,
+                                         double* out_vel, double* out_cov, double* out_nis, int32_t* out_age, void* workspace,
+                                         size_t workspace_bytes, gnncca_stream_t stream, const double* frame_time_dev, double max_dt);
+
 /* ---- Training loss and its statistics (compute_loss_acc, train.py:51-208, and the mean probabilities of train.py:460-469) ---------
  * Inputs: logits fp32 [n_steps][n_edges] (step-major: the [S, E, 1] buffer of the MPN training forward), labels fp32 [n_edges] (0 / 1).
  * criterion: GNNCCA_LOSS_BCE, GNNCCA_LOSS_BCE_WEIGHTED (pos_weight > 0) or GNNCCA_LOSS_FOCAL (utils.FocalLoss_binary: focusing_param,

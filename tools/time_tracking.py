@@ -3,7 +3,8 @@
 (N = 2048, every person seen once per camera: 8 clusters of 4 per frame) with R = 2048 appearance columns.  Needs an MI355X.
 
     python tools/time_tracking.py [--frames 64] [--cams 4] [--per 8] [--reid 2048] [--reps 200] [--host-reps 3] [--max-gap 0] [--hide 0]
-                                  [--matching mutual|optimal] [--crowded] [--motion none|velocity] [--drift 0] [--times drop:P|jitter:S]
+                                  [--matching mutual|optimal] [--crowded] [--motion none|velocity|kalman] [--max-nis X] [--drift 0]
+                                  [--times drop:P|jitter:S]
 
 Two ways to the same result, timed in alternating rounds in one process (host clock around work that ends in a device synchronise):
   device   cluster summaries (2 launches) + FrameLinker (3 launches) on tensors that are already on the GPU, as a FramePipeline
@@ -22,6 +23,12 @@ alternating rounds, each compared with its oracle once.
 against tests/tracking_motion_oracle.py; the ids AND the velocities are compared once per run.  --drift V selects a batch whose people
 move: every person walks a straight line at V units per frame in a direction of its own (the default batch only jitters around a point,
 so its velocities are noise).
+--motion kalman times kalman.KalmanLinker (q = 0.001, r = 0.0025 = the batch's detection noise squared, vel_var = 0.25; --max-nis X adds the
+variance gate) against tests/tracking_kalman_oracle.py -- ids, links, the filtered velocity and the five trajectories arrays are compared
+once, bit for bit -- and, in the same alternating rounds, FrameLinker(motion='velocity') on the same batch (`velocity_ms`).  It then links
+the crossing walks of DESIGN.md section 9 (40 frames, 25 people, noise 0.10, people hiding for up to 2 frames, max_step 0.35, lam 0,
+max_gap 2, seeds 0 .. 3) with the velocity linker, the Kalman linker under the same gate, and the Kalman linker with max_nis = 13.8 under
+four times the gate, and prints IDSW / IDF1 of each (`walks`; scored by tests/track_score_oracle.py on the device's ids).
 --times times the call WITH time stamps (linker(s, times=...), the _timed entries; the adjacent linker then runs the gap path with
 M = 0) against tests/tracking_time_oracle.py: drop:P removes every frame but the first with probability P and stamps the survivors with
 their indices, jitter:S (S < 0.5) keeps every frame and perturbs its index by uniform +-S.  Every repetition continues the times of the
@@ -39,10 +46,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import tracking_assign_oracle as ta  # noqa: E402
+import track_score_oracle as tso  # noqa: E402
 import tracking_gap_oracle as tg  # noqa: E402
+import tracking_kalman_oracle as tk  # noqa: E402
 import tracking_motion_oracle as tm  # noqa: E402
 import tracking_oracle as to  # noqa: E402
 import tracking_time_oracle as tt  # noqa: E402
+from gnn_cca_amd.kalman import KalmanLinker  # noqa: E402
 from gnn_cca_amd.tracking import ClusterSummaries, FrameLinker, cluster_summaries_raw  # noqa: E402
 
 
@@ -100,6 +110,32 @@ def stamp(b, spec, n_g, seed=1):
     return out, np.flatnonzero(keep).astype(np.float64)
 
 
+KALMAN = dict(q=0.001, r=0.0025, vel_var=0.25)   # --motion kalman on the Terrace-shaped batch (detection noise 0.05)
+
+
+def crossing_walks():
+    """IDSW / IDF1 on the crossing walks of DESIGN.md section 9, linked on the device: velocity, Kalman under the same gate, Kalman with the
+    variance gate under four times the distance gate."""
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    rows = []
+    for seed in range(4):
+        summ = tm.cross_sequence(np.random.default_rng(seed), 40, 25, 8, noise=0.10, p_hide=0.1, max_hide=2)
+        n = len(summ["rank"])
+        ones = t(np.ones(n, np.int32))
+        s = ClusterSummaries(t(summ["count"]), t(summ["rank"]), ones, ones, t(summ["pos"]), t(summ["emb"]), summ["node_ptr"].tolist(),
+                             t(summ["node_ptr"].astype(np.int32)))
+        links = {"velocity": FrameLinker(0.35, lam=0.0, max_gap=2, motion="velocity"),
+                 "kalman": KalmanLinker(0.35, 0.001, 0.01, 0.25, lam=0.0, max_gap=2),
+                 "kalman_nis": KalmanLinker(1.4, 0.001, 0.01, 0.25, lam=0.0, max_gap=2, max_nis=13.8)}
+        row = {"seed": seed}
+        for name, link in links.items():
+            ids = link(s).node_track.cpu().numpy()
+            res = tso.score(summ["person"], np.zeros(n, np.int32), ids, summ["node_ptr"], 1024, 8)[2]
+            row[name] = {"IDSW": res["IDSW"], "IDF1": round(res["IDF1"], 4)}
+        rows.append(row)
+    return rows
+
+
 def crowded(a):
     """The linker's call alone on the crowded sequence, both matchings."""
     m = a.max_gap if a.max_gap > 0 else 1
@@ -146,14 +182,17 @@ def main():
     ap.add_argument("--hide", type=float, default=0.0)
     ap.add_argument("--matching", choices=("mutual", "optimal"), default="mutual")
     ap.add_argument("--crowded", action="store_true")
-    ap.add_argument("--motion", choices=("none", "velocity"), default="none")
+    ap.add_argument("--motion", choices=("none", "velocity", "kalman"), default="none")
+    ap.add_argument("--max-nis", type=float, default=None)
     ap.add_argument("--drift", type=float, default=0.0)
     ap.add_argument("--times", default=None, metavar="drop:P|jitter:S")
     a = ap.parse_args()
     if a.times and a.crowded:
         raise SystemExit("--times goes with the Terrace-shaped batch")
-    if a.motion == "velocity" and (a.matching == "optimal" or a.crowded):
-        raise SystemExit("--motion velocity goes with --matching mutual on the Terrace-shaped batch")
+    if a.motion != "none" and (a.matching == "optimal" or a.crowded):
+        raise SystemExit(f"--motion {a.motion} goes with --matching mutual on the Terrace-shaped batch")
+    if a.max_nis is not None and a.motion != "kalman":
+        raise SystemExit("--max-nis goes with --motion kalman")
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_tracking.py measures on the GPU; no device is visible")
     if a.crowded:
@@ -162,12 +201,17 @@ def main():
     times = None
     if a.times:
         b, times = stamp(b, a.times, a.cams * a.per)
-    calls = [0]   # timed: every call continues the times of the one before it, a.frames periods later
+    calls = [0, 0]   # timed: every call continues the times of the one before it, a.frames periods later
     dev = torch.device("cuda")
     d = {k: torch.from_numpy(b[k]).to(dev) for k in ("labels", "xw", "yw", "cam", "emb")}
     ptr_host = b["node_ptr"].tolist()
     max_step, lam = 1.0, 1.0
-    link = FrameLinker(max_step, lam=lam, max_gap=a.max_gap, matching=a.matching, motion=a.motion)
+    kalman = a.motion == "kalman"
+    if kalman:
+        link = KalmanLinker(max_step, KALMAN["q"], KALMAN["r"], KALMAN["vel_var"], lam=lam, max_gap=a.max_gap, max_nis=a.max_nis)
+        beside = FrameLinker(max_step, lam=lam, max_gap=a.max_gap, motion="velocity")   # timed in the same rounds
+    else:
+        link = FrameLinker(max_step, lam=lam, max_gap=a.max_gap, matching=a.matching, motion=a.motion)
 
     def device_once():
         s = cluster_summaries_raw(d["labels"], ptr_host, d["xw"], d["yw"], d["cam"], d["emb"])
@@ -176,6 +220,13 @@ def main():
         calls[0] += 1
         return s, link(s, times=times + float((calls[0] - 1) * a.frames))
 
+    def beside_once():
+        s = cluster_summaries_raw(d["labels"], ptr_host, d["xw"], d["yw"], d["cam"], d["emb"])
+        if times is None:
+            return beside(s)
+        calls[1] += 1   # (a running sequence of its own)
+        return beside(s, times=times + float((calls[1] - 1) * a.frames))
+
     def copy_once():
         out = [d[k].cpu() for k in ("labels", "xw", "yw", "cam", "emb")]   # (.cpu() of a device tensor synchronises)
         return [t.numpy() for t in out]
@@ -183,6 +234,9 @@ def main():
     def host_once(state):
         labels, xw, yw, cam, emb = copy_once()
         s = to.summaries(labels, b["node_ptr"], xw, yw, cam, emb)
+        if kalman:
+            return s, tk.link_kalman(s, b["node_ptr"], max_step, lam=lam, max_cos=None, max_gap=a.max_gap, max_nis=a.max_nis, times=times,
+                                     state=state, **KALMAN)
         if times is not None:
             return s, tt.link_timed(s, b["node_ptr"], times, max_step, lam, None, a.max_gap, state, matching=a.matching,
                                     motion=a.motion == "velocity")
@@ -201,20 +255,31 @@ def main():
     same = all(np.array_equal(getattr(s_dev, k).cpu().numpy(), s_host[k]) for k in ("count", "rank", "size", "n_cams", "pos", "emb"))
     same_ids = all(np.array_equal(getattr(t_dev, k).cpu().numpy(), t_host[k]) for k in ("cluster_track", "node_track", "matched_prev"))
     gaps = t_dev.matched_gap.cpu().numpy()
-    if a.max_gap > 0 or a.matching == "optimal" or a.motion == "velocity" or times is not None:
+    if a.max_gap > 0 or a.matching == "optimal" or a.motion != "none" or times is not None:
         same_ids = same_ids and np.array_equal(gaps, t_host["matched_gap"])
-    if a.motion == "velocity":
+    if a.motion != "none":
         same_ids = same_ids and np.array_equal(t_dev.velocity.cpu().numpy(), t_host["velocity"])
+    if kalman:   # the five trajectories arrays, bit for bit
+        same_ids = same_ids and all(np.array_equal(getattr(t_dev.trajectories, k).cpu().numpy().view(np.uint8), t_host[k].view(np.uint8))
+                                    for k in ("pos", "vel", "cov", "nis", "age"))
     for _ in range(10):   # warm-up: code objects, allocator
         device_once()
+        if kalman:
+            beside_once()
     torch.cuda.synchronize()
-    dev_ms, host_ms, copy_ms = [], [], []
+    dev_ms, host_ms, copy_ms, beside_ms = [], [], [], []
     for _ in range(a.rounds):
         t0 = time.perf_counter()
         for _ in range(a.reps):
             device_once()
         torch.cuda.synchronize()
         dev_ms.append((time.perf_counter() - t0) / a.reps * 1e3)
+        if kalman:
+            t0 = time.perf_counter()
+            for _ in range(a.reps):
+                beside_once()
+            torch.cuda.synchronize()
+            beside_ms.append((time.perf_counter() - t0) / a.reps * 1e3)
         t0 = time.perf_counter()
         for _ in range(a.reps):
             copy_once()
@@ -223,7 +288,11 @@ def main():
         for _ in range(a.host_reps):
             host_once(None)
         host_ms.append((time.perf_counter() - t0) / a.host_reps * 1e3)
-    print(json.dumps({"frames": a.frames, "cams": a.cams, "per_cam": a.per, "n_nodes": b["n"], "reid_dim": a.reid, "reps": a.reps,
+    more = {}
+    if kalman:
+        more = {"velocity_ms": [round(v, 4) for v in beside_ms], "max_nis": a.max_nis, "kalman": KALMAN,
+                "median_ratio_kalman_over_velocity": round(float(np.median(dev_ms) / np.median(beside_ms)), 3), "walks": crossing_walks()}
+    print(json.dumps({**more, "frames": a.frames, "cams": a.cams, "per_cam": a.per, "n_nodes": b["n"], "reid_dim": a.reid, "reps": a.reps,
                       "host_reps": a.host_reps, "device_ms": [round(v, 4) for v in dev_ms], "host_ms": [round(v, 2) for v in host_ms],
                       "copy_ms": [round(v, 4) for v in copy_ms], "summaries_equal": bool(same), "ids_equal": bool(same_ids),
                       "tracks": int(t_dev.next_id.item()), "max_gap": a.max_gap, "hide": a.hide, "matching": a.matching, "motion": a.motion, "drift": a.drift,
